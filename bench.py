@@ -15,9 +15,10 @@ contiguously over ranks (ladi_vton_amd.parallel.run_sharded), so results do not 
 
   python bench.py --gpus 1 --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
-  python bench.py --gpus N ...        (no launcher: bench.py re-executes itself under the torch.distributed.run line above, one rank per GPU)
+  python bench.py --gpus N ...        (no launcher: bench.py runs the torch.distributed.run line above as a child, one rank per GPU)
 `--gpus N` always means N ranks: fewer visible GPUs than N, or a launcher that started another WORLD_SIZE, is exit code 2 and no line.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; `ms_per_step` is the wall time of one timed step.
+  python bench.py ... --dump-outputs DIR   also writes what the last timed step returned as DIR/images.npy (see dump_outputs)
 """
 import argparse
 import ctypes
@@ -91,7 +92,13 @@ def parse():
     p.add_argument("--lanes", type=int, default=None,
                    help="sample-group lanes of the UNet forward inside the denoising loop (csrc/runtime.h UNetLanes); default: the library's "
                         "own choice (LADI_UNET_LANES, else 1: two concurrent half-batch forwards measured 3.5 % slower, DESIGN.md)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (the uint8 image batch, all ranks gathered) as "
+                        "DIR/images.npy in float32, at most 64 MB (a seeded sample of a larger batch); same arguments = same inputs")
+    a = p.parse_args()
+    if a.dump_outputs and (a.steps < 1 or a.roofline_only):
+        p.error("--dump-outputs needs at least one timed step (--steps >= 1, no --roofline-only)")
+    return a
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -389,6 +396,30 @@ def d2h_pil_tail(images_u8):
     return n
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: each array -> path/<name>.npy in float32 (float64 stays float64), so that two builds can be compared output for
+    output.  When the arrays exceed `budget` bytes together, each keeps a seeded, fixed sample of its flattened elements, an equal share
+    of the budget each: path/<name>.npy holds the sampled values, path/<name>_index.npy (float64) their flat indices."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = (t.double() if t.dtype == torch.float64 else t.float()).numpy()
+    share = budget // max(len(host), 1) - 4096                 # room for the .npy headers
+    sample = sum(x.nbytes for x in host.values()) > share * len(host)
+    for name, x in host.items():
+        if sample:
+            k = min(x.size, share // (x.itemsize + 8))
+            idx = np.sort(np.random.default_rng(seed).choice(x.size, size=k, replace=False))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
 def _free_port():
     import socket
     with socket.socket() as s_:
@@ -398,9 +429,10 @@ def _free_port():
 
 def launch_ranks(a, argv):
     """`--gpus N` is a promise about the number of ranks, not a label.  Called with --gpus N > 1 and no launcher around
-    it (no WORLD_SIZE in the environment), this process becomes the launcher: it replaces itself by `python -m torch.distributed.run
-    --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>` -- one rank per GPU -- after checking that the box has
-    N GPUs (exit code 2 and a message otherwise: one rank printing `n_gpus: 1` under a `--gpus 8` command line must not happen)."""
+    it (no WORLD_SIZE in the environment), this process becomes the launcher: it runs `python -m torch.distributed.run --nnodes=1
+    --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>` -- one rank per GPU -- as a fresh child process and exits with its
+    status, after checking that the box has N GPUs (exit code 2 and a message otherwise: one rank printing `n_gpus: 1` under a `--gpus 8`
+    command line must not happen).  A child, not exec(): the GPU count query has already initialised the GPU runtime in this process."""
     if not a.stub_step:
         have = torch.cuda.device_count() if torch.cuda.is_available() else 0
         if have < a.gpus:
@@ -411,7 +443,7 @@ def launch_ranks(a, argv):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.abspath(__file__)] + list(argv)
     sys.stdout.flush(); sys.stderr.flush()
-    os.execve(sys.executable, cmd, env)
+    sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
 def stub_run_local(inp):
@@ -428,7 +460,7 @@ def main():
         sys.stderr.write("bench.py: --gpus must be >= 1\n")
         sys.exit(2)
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
-        launch_ranks(a, sys.argv[1:])          # does not return
+        launch_ranks(a, sys.argv[1:])          # does not return (exits with the launcher's status)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -533,6 +565,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt.item())
     assert out.shape[0] == global_B and out.dtype == torch.uint8
+    if a.dump_outputs and rank == 0:     # the last TIMED step's result, before the tail leg below runs more steps
+        dump_outputs(a.dump_outputs, {"images": out})
     images_per_s = global_B * a.steps / dt if a.steps else 0.0
     # who took part in the collective (outside the timed region): the RCCL version and the number of DISTINCT ranks an all-gather of the rank ids
     # returned on rank 0 -- so that a SCALE_rNN.json line can be checked for "RCCL saw N ranks" 

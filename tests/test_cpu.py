@@ -629,6 +629,36 @@ def test_bench_refuses_to_run_fewer_ranks_than_gpus_flag():
     assert r.returncode == 2 and "WORLD_SIZE=1" in r.stderr and "{" not in r.stdout, (r.returncode, r.stdout, r.stderr)
 
 
+def test_bench_dump_outputs_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step returned (DIR/images.npy, float32) and the same arguments give the
+    same arrays; an output over the byte budget is reduced to a seeded sample with its flat indices, the same sample every time."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    got = []
+    for i, steps in enumerate((2, 3)):
+        d = tmp_path / ("run%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--stub-step", "--steps", str(steps), "--warmup", "1",
+                            "--batch", "3", "--height", "32", "--width", "24", "--dump-outputs", str(d)], capture_output=True, text=True,
+                           timeout=300, env=env)
+        assert r.returncode == 0, r.stdout + r.stderr
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == steps and line["ms_per_step"] is not None and line["ms_per_step"] >= 0
+        got.append(np.load(d / "images.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (3, 32, 24, 3) and np.array_equal(got[0], got[1])
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--stub-step", "--steps", "0",
+                        "--dump-outputs", str(tmp_path / "none")], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr
+    import bench
+    x = torch.arange(60000, dtype=torch.int32).reshape(6, 100, 100)
+    budget = 2 * 4096 + 60000
+    for d in ("s0", "s1"):
+        bench.dump_outputs(str(tmp_path / d), {"images": x}, budget=budget)
+    v, idx = np.load(tmp_path / "s0" / "images.npy"), np.load(tmp_path / "s0" / "images_index.npy")
+    assert v.dtype == np.float32 and idx.dtype == np.float64 and 0 < v.size < x.numel()
+    assert sum(os.path.getsize(tmp_path / "s0" / f) for f in os.listdir(tmp_path / "s0")) <= budget
+    assert np.array_equal(v, x.reshape(-1).numpy()[idx.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(idx, np.load(tmp_path / "s1" / "images_index.npy"))
+
+
 def test_dataset_preprocessing_matches_real_reference_classes(tmp_path):
     """ladi_vton_amd.dataset (host-side VITON-HD / DressCode readers: label-map algebra, PIL rasterisation, box dilation, pose heat-maps)
     vs fixtures produced by the REAL src/dataset/vitonhd.py / dresscode.py classes on the same synthetic trees (oracle/make_golden.py:
