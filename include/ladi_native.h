@@ -192,10 +192,34 @@ int ladi_tps_forward(ladi_tps* t, const void* input_a_dev, const void* input_b_d
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Scheduler — replaces diffusers DDIMScheduler / PNDMScheduler (skip_prk_steps) / LMSDiscreteScheduler set_timesteps +
- * scale_model_input + step (tryon_pipe.py:62,424,650-651,722,740).  kind: 0 = DDIM, 1 = PNDM, 2 = LMSDiscrete.
+ * scale_model_input + step (tryon_pipe.py:62,424,650-651,722,740), and the diffusers 0.14 DPMSolverMultistepScheduler
+ * (algorithm_type dpmsolver++), EulerDiscreteScheduler (s_churn 0) and EulerAncestralDiscreteScheduler, all with epsilon prediction.
+ * Scheduler code (the `kind` / `scheduler` argument): bits 0-3 the kind,
+ *   0 = DDIM, 1 = PNDM, 2 = LMSDiscrete, 3 = DPMSolverMultistep (dpmsolver++), 4 = EulerDiscrete, 5 = EulerAncestralDiscrete;
+ * bits 8-11 DPM-Solver++ options (kind 3 only; the code 3 alone is DPM-Solver++ 2M, midpoint, lower_order_final):
+ *   bits 8-9 solver_order (0 = 2, or 1..3), bit 10 solver_type heun (0 = midpoint), bit 11 lower_order_final off.
+ * Any other bit, an option bit on another kind or an unknown kind is an error.  The DPM / Euler formulas are restated from the published
+ * algorithms as diffusers 0.14 ships them, not pinned against diffusers itself (it is not installable here).
  * ------------------------------------------------------------------------------------------------------------- */
-/* host helper: writes the N (DDIM) or N+1 (PNDM) timesteps; returns their count, or negative on error */
+#define LADI_SCHED_DDIM 0
+#define LADI_SCHED_PNDM 1
+#define LADI_SCHED_LMS 2
+#define LADI_SCHED_DPMPP 3
+#define LADI_SCHED_EULER 4
+#define LADI_SCHED_EULER_ANCESTRAL 5
+#define LADI_SCHED_DPM_ORDER(o) ((o) << 8)     /* o in 1..3 */
+#define LADI_SCHED_DPM_HEUN (1 << 10)
+#define LADI_SCHED_DPM_NO_LOWER_ORDER_FINAL (1 << 11)
+/* host helper: writes the N (DDIM, DPMSolverMultistep) or N+1 (PNDM) integer timesteps; returns their count, or negative on error.
+ * LMSDiscrete / Euler / Euler-ancestral (fractional timesteps) are refused: use ladi_sched_lms, whose timesteps and sigmas all three share.
+ * DPMSolverMultistep refuses step counts whose rounded timesteps repeat (N = 1000), on which diffusers 0.14 fails. */
 int ladi_sched_timesteps(int kind, int num_inference_steps, int* timesteps_out, int cap);
+/* host helper (tests): the per-evaluation step table of any scheduler code, 10 floats per evaluation:
+ *   [c_x, c_e, w0, w1, w2, w3, p_x, p_e, c_n, in_scale_next]:  x' = c_x x + c_e sum_k w_k h_k + c_n noise, where h_0 is the guided eps
+ *   (DDIM / PNDM / LMS / Euler) or the data prediction p_x x + p_e eps (DPMSolverMultistep), and h_k (k > 0) the earlier ones;
+ *   in_scale_next = scale_model_input of the next evaluation.  timesteps_out[evals] (float64) and rows_out may be null.
+ * Returns the evaluation count (or negative on error; cap = capacity in evaluations). */
+int ladi_sched_table(int kind, int num_inference_steps, const float* alphas_cumprod_host, double* timesteps_out, float* rows_out, int cap);
 /* host helper, LMSDiscrete (order 4): timesteps_out[N] (fractional, float64 as diffusers holds them), sigmas_out[N + 1] (trailing 0;
  * init_noise_sigma = sigmas_out[0]), coeffs_out[N][4] = linear-multistep weights of evaluation i over its derivatives
  * [d_i, d_{i-1}, d_{i-2}, d_{i-3}] (zero beyond the order min(i + 1, 4)).  alphas_cumprod_host null = default.  Any output may be null. */
@@ -222,7 +246,8 @@ typedef struct {
     const float* noise_masked_dev;
     int num_inference_steps;
     float guidance_scale;
-    int scheduler;                     /* 0 DDIM, 1 PNDM, 2 LMSDiscrete */
+    int scheduler;                     /* scheduler code (see "Scheduler" above): 0 DDIM, 1 PNDM, 2 LMSDiscrete, 3 DPMSolverMultistep
+                                        * (+ option bits), 4 EulerDiscrete, 5 EulerAncestralDiscrete (needs ladi_tryon_set_step_noise) */
     int cloth_zero_from_eval;          /* first evaluation index i that sees zero cloth latents: the smallest i with
                                         * i >= num_inference_steps - (1 - cloth_cond_rate) * num_inference_steps, evaluated by the CALLER in
                                         * float64 exactly like tryon_pipe.py:654,718 (a float32 rate crossing the ABI shifts the cut-off by
@@ -244,6 +269,11 @@ int ladi_tryon_run_u8(ladi_tryon* t, const ladi_tryon_inputs* in, unsigned char*
  * and the updated latents of evaluation i to *_trace_dev[i] (fp32 [B, h*w, 4] each) for i < cap_evals; NULL pointers switch it off.
  * Buffers are caller-owned and must outlive the runs. */
 int ladi_tryon_set_trace(ladi_tryon* t, float* eps_trace_dev, float* latents_trace_dev, int cap_evals);
+/* per-step noise of EulerAncestralDiscrete (its randn draw in step(), one per evaluation): fp32 [steps][B][4][h][w] on the device.
+ * Each run copies the first `evaluations` steps on its stream into a runtime-owned buffer before the loop, so the captured graph never
+ * reads the caller's buffer (which, like the run's other inputs, must stay valid until the run's work on the stream has started); a run of
+ * kind 5 with no noise, or fewer steps than evaluations, fails.  Other kinds ignore it.  NULL = off. */
+int ladi_tryon_set_step_noise(ladi_tryon* t, const float* noise_dev, int steps);
 /* stage times (ms) of the last run: [0] preprocess + VAE encodes + EMASC, [1] denoising loop, [2] decode. Sync first. */
 int ladi_tryon_stage_ms(ladi_tryon* t, float* out3);
 /* fp16-range guard of the decode, examined WITHOUT a host round trip inside ladi_tryon_run (round 6): a run decodes once and queues the guard's flag
@@ -362,6 +392,9 @@ int ladi_op_nhwc_to_nchw(const void* src, int ld, int n, int C, int H, int W, vo
  * runs evaluations [0, evals) feeding eps_seq[i] ([2B or B][hw][4] fp16 NHWC per evaluation); latents fp32 [B][hw][4] in/out */
 int ladi_op_sched_run(int kind, int steps, const float* alphas_cumprod_host, const void* eps_seq_dev, int evals, int B, int hw,
                       int cfg, float guidance, float* latents_dev, void* stream);
+/* the same with per-evaluation step noise (EulerAncestralDiscrete): step_noise_dev fp32 [noise_steps][B][4][hw], noise_steps >= evals */
+int ladi_op_sched_run_noise(int kind, int steps, const float* alphas_cumprod_host, const void* eps_seq_dev, int evals, int B, int hw,
+                            int cfg, float guidance, float* latents_dev, const float* step_noise_dev, int noise_steps, void* stream);
 /* pipeline pre-processing kernels, one entry point per kernel so each can be checked on its own:
  * prepare_mask_and_masked_image (diffusers tensor branch; tryon_pipe.py:630): mask binarised at 0.5 -> mask_bin_dev fp16 [B,H,W];
  *   masked_image_dev NHWC fp16 [B,H,W,ld] (3 valid channels, the rest zero) = image * (mask < 0.5) */

@@ -8,7 +8,8 @@ from . import dataset  # noqa: F401  (host-side VITON-HD / DressCode readers)
 from ._lib import NativeError  # noqa: F401
 from .modules import (NativeEMASC, NativeInversionAdapter, NativeUNet, NativeVAE, mask_features)  # noqa: F401
 from .pipeline import StableDiffusionTryOnePipeline  # noqa: F401
-from .schedulers import DDIMScheduler, LMSDiscreteScheduler, PNDMScheduler  # noqa: F401
+from .schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler,  # noqa: F401
+                         LMSDiscreteScheduler, PNDMScheduler)
 from .text import NativeCLIPTextEncoder, encode_text_word_embedding  # noqa: F401
 from .vision import NativeCLIPVisionEncoder  # noqa: F401
 from .warp import NativeRefinementUNet, NativeTPS, clip_preprocess, grid_sample_border, resize_antialias, warp_cloth  # noqa: F401

@@ -123,6 +123,7 @@ SIGNATURES = {
     "ladi_text_encoder_forward_dev": (c_int, [_P, _P, c_int, c_int, _P, c_int, _P, _P, _P]),
     "ladi_sched_timesteps": (c_int, [c_int, c_int, POINTER(c_int), c_int]),
     "ladi_sched_lms": (c_int, [c_int, _P, _P, _P, _P]),
+    "ladi_sched_table": (c_int, [c_int, c_int, _P, _P, _P, c_int]),
     "ladi_sched_alphas_cumprod": (c_int, [POINTER(c_float)]),
     "ladi_tryon_create": (_P, [_P, _P, _P]),
     "ladi_tryon_destroy": (None, [_P]),
@@ -131,6 +132,7 @@ SIGNATURES = {
     "ladi_tryon_stage_ms": (c_int, [_P, POINTER(c_float)]),
     "ladi_tryon_poll_overflow": (c_int, [_P]),
     "ladi_tryon_set_trace": (c_int, [_P, _P, _P, c_int]),
+    "ladi_tryon_set_step_noise": (c_int, [_P, _P, c_int]),
     "ladi_tryon_set_lanes": (c_int, [_P, c_int]),
     "ladi_tryon_lanes": (c_int, [_P]),
     "ladi_vae_set_range_shift": (c_int, [_P, c_int]),
@@ -166,6 +168,7 @@ SIGNATURES = {
     "ladi_op_nchw_to_nhwc": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
     "ladi_op_nhwc_to_nchw": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
     "ladi_op_sched_run": (c_int, [c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P]),
+    "ladi_op_sched_run_noise": (c_int, [c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int, _P]),
     "ladi_op_prepare_mask": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
     "ladi_op_mask_down": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "ladi_op_pose_down8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),

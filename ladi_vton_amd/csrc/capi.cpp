@@ -499,7 +499,9 @@ int ladi_sched_timesteps(int kind, int steps, int* out, int cap) {
     return guarded("ladi_sched_timesteps", [&]() {
         if (steps < 2 || steps > 1000) throw std::runtime_error("num_inference_steps out of range");
         std::vector<float> ac; default_alphas_cumprod(ac);
-        if (kind == 2) throw std::runtime_error("LMSDiscrete timesteps are fractional: use ladi_sched_lms");
+        const int k = decode_sched_code(kind).kind;
+        if (k == SCHED_LMS || k == SCHED_EULER || k == SCHED_EULER_A)
+            throw std::runtime_error("LMSDiscrete / EulerDiscrete / EulerAncestralDiscrete timesteps are fractional: use ladi_sched_lms");
         std::vector<double> ts; std::vector<StepTable> tb;
         build_step_table(kind, steps, ac.data(), 1 << 30, ts, tb);
         if ((int)ts.size() > cap) throw std::runtime_error("timesteps buffer too small");
@@ -518,6 +520,22 @@ int ladi_sched_lms(int steps, const float* ac_host, double* timesteps_out, float
         if (sigmas_out) std::memcpy(sigmas_out, info.sigmas.data(), info.sigmas.size() * sizeof(float));
         if (coeffs_out) std::memcpy(coeffs_out, info.lms_coeffs.data(), info.lms_coeffs.size() * sizeof(float));
         return steps;
+    });
+}
+int ladi_sched_table(int code, int steps, const float* ac_host, double* timesteps_out, float* rows_out, int cap) {
+    return guarded("ladi_sched_table", [&]() {
+        std::vector<float> ac;
+        if (ac_host) ac.assign(ac_host, ac_host + 1000); else default_alphas_cumprod(ac);
+        std::vector<double> ts; std::vector<StepTable> tb;
+        build_step_table(code, steps, ac.data(), 1 << 30, ts, tb);
+        if ((int)tb.size() > cap) throw std::runtime_error("table buffer too small");
+        for (size_t i = 0; i < tb.size(); ++i) {
+            const StepTable& e = tb[i];
+            const float row[10] = {e.c_x, e.c_e, e.w[0], e.w[1], e.w[2], e.w[3], e.p_x, e.p_e, e.c_n, e.in_scale_next};
+            if (rows_out) std::memcpy(rows_out + 10 * i, row, sizeof(row));
+            if (timesteps_out) timesteps_out[i] = ts[i];
+        }
+        return (int)tb.size();
     });
 }
 int ladi_sched_alphas_cumprod(float* out) {
@@ -572,6 +590,11 @@ int ladi_tryon_set_lanes(ladi_tryon* t, int lanes) {
     return 0;
 }
 int ladi_tryon_lanes(ladi_tryon* t) { return t ? t->t.lanes.G : -1; }
+int ladi_tryon_set_step_noise(ladi_tryon* t, const float* noise_dev, int steps) {
+    if (!t || steps < 0) { set_error("ladi_tryon_set_step_noise: null handle or negative steps"); return -1; }
+    t->t.step_noise_src = noise_dev; t->t.step_noise_steps = noise_dev ? steps : 0;
+    return 0;
+}
 int ladi_tryon_set_trace(ladi_tryon* t, float* eps_trace, float* latents_trace, int cap_evals) {
     if (!t || cap_evals < 0) return -1;
     t->t.trace_eps = eps_trace; t->t.trace_lat = latents_trace; t->t.trace_cap = (eps_trace || latents_trace) ? cap_evals : 0;
@@ -797,15 +820,17 @@ int ladi_op_assemble_input(void* unet_in, int ld, int B, int hw, int cfg, const 
     return ladi_launch_assemble_static((h16*)unet_in, ld, B, hw, cfg, latents, (const h16*)mask_lat, masked_lat, (const h16*)pose, pose_ch,
                                        cloth_lat, cloth_lat ? 1 : 0, 1.0f, S(stream));
 }
-int ladi_op_sched_run(int kind, int steps, const float* ac_host, const void* eps_seq, int evals, int B, int hw, int cfg, float guidance,
-                      float* latents, void* stream) {
-    return guarded("ladi_op_sched_run", [&]() {
+static int sched_run_any(const char* name, int kind, int steps, const float* ac_host, const void* eps_seq, int evals, int B, int hw, int cfg,
+                         float guidance, float* latents, const float* step_noise, int noise_steps, void* stream) {
+    return guarded(name, [&]() {
         hipStream_t st = S(stream);
         std::vector<float> ac;
         if (ac_host) ac.assign(ac_host, ac_host + 1000); else default_alphas_cumprod(ac);
         std::vector<double> ts; std::vector<StepTable> tb;
         build_step_table(kind, steps, ac.data(), 1 << 30, ts, tb);
         if (evals > (int)tb.size()) throw std::runtime_error("evals exceeds scheduler length");
+        if (decode_sched_code(kind).kind == SCHED_EULER_A && (!step_noise || noise_steps < evals))
+            throw std::runtime_error("EulerAncestralDiscrete needs step noise for every evaluation run");
         char* buf = nullptr;
         const size_t plane = (size_t)B * hw * 4 * sizeof(float);
         const size_t tb_bytes = (tb.size() * sizeof(StepTable) + 255) & ~(size_t)255;
@@ -822,13 +847,22 @@ int ladi_op_sched_run(int kind, int steps, const float* ac_host, const void* eps
             StepArgs sa; std::memset(&sa, 0, sizeof(sa));
             sa.eps = reinterpret_cast<const h16*>(eps_seq) + (size_t)i * rows * 4; sa.ld_eps = 4;
             sa.B = B; sa.hw = hw; sa.cfg = cfg; sa.guidance = guidance; sa.latents = latents; sa.cur_sample = cur; sa.ets = ets;
-            sa.table = dt; sa.step_idx = dstep; sa.unet_in = nullptr;
+            sa.table = dt; sa.step_idx = dstep; sa.unet_in = nullptr; sa.step_noise = step_noise;
             rc = ladi_launch_sched_step(sa, st);
         }
         HIP_OK(hipStreamSynchronize(st));
         (void)hipFree(buf);
         return rc;
     });
+}
+int ladi_op_sched_run(int kind, int steps, const float* ac_host, const void* eps_seq, int evals, int B, int hw, int cfg, float guidance,
+                      float* latents, void* stream) {
+    return sched_run_any("ladi_op_sched_run", kind, steps, ac_host, eps_seq, evals, B, hw, cfg, guidance, latents, nullptr, 0, stream);
+}
+int ladi_op_sched_run_noise(int kind, int steps, const float* ac_host, const void* eps_seq, int evals, int B, int hw, int cfg, float guidance,
+                            float* latents, const float* step_noise, int noise_steps, void* stream) {
+    return sched_run_any("ladi_op_sched_run_noise", kind, steps, ac_host, eps_seq, evals, B, hw, cfg, guidance, latents, step_noise, noise_steps,
+                         stream);
 }
 
 }  // extern "C"

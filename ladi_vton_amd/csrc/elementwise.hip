@@ -141,14 +141,22 @@ __device__ __forceinline__ void sched_step_body(const StepArgs& a, const int idx
             for (int c = 0; c < 4; ++c) e[c] = (float)eu[c];
         }
     }
-    (void)b;
     const size_t plane = (size_t)total * 4;
     float4 x = reinterpret_cast<const float4*>(a.latents)[idx];
     if (T.save_cur) reinterpret_cast<float4*>(a.cur_sample)[idx] = x;
     if (T.mode == 1) x = reinterpret_cast<const float4*>(a.cur_sample)[idx];
+    // d: what the ring holds and w combines -- the guided eps (modes 0, 1) or, for DPM-Solver++ (mode 2), the data prediction
+    float d[4];
+    if (T.mode == 2) {
+        d[0] = T.p_x * x.x + T.p_e * e[0]; d[1] = T.p_x * x.y + T.p_e * e[1];
+        d[2] = T.p_x * x.z + T.p_e * e[2]; d[3] = T.p_x * x.w + T.p_e * e[3];
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) d[c] = e[c];
+    }
     float ec[4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) ec[c] = T.w[0] * e[c];
+    for (int c = 0; c < 4; ++c) ec[c] = T.w[0] * d[c];
     // history slots are encoded in the table through w[] order: slot ids packed in push field's upper bits
     const int s1 = (T.push >> 8) & 3, s2 = (T.push >> 10) & 3, s3 = (T.push >> 12) & 3, sp = (T.push >> 4) & 3;
     if (T.w[1] != 0.f) { const float4 h = reinterpret_cast<const float4*>(a.ets + s1 * plane)[idx];
@@ -157,10 +165,17 @@ __device__ __forceinline__ void sched_step_body(const StepArgs& a, const int idx
         ec[0] += T.w[2] * h.x; ec[1] += T.w[2] * h.y; ec[2] += T.w[2] * h.z; ec[3] += T.w[2] * h.w; }
     if (T.w[3] != 0.f) { const float4 h = reinterpret_cast<const float4*>(a.ets + s3 * plane)[idx];
         ec[0] += T.w[3] * h.x; ec[1] += T.w[3] * h.y; ec[2] += T.w[3] * h.z; ec[3] += T.w[3] * h.w; }
-    if (T.push & 1) reinterpret_cast<float4*>(a.ets + sp * plane)[idx] = make_float4(e[0], e[1], e[2], e[3]);
+    if (T.push & 1) reinterpret_cast<float4*>(a.ets + sp * plane)[idx] = make_float4(d[0], d[1], d[2], d[3]);
     float4 xn;
     xn.x = T.c_x * x.x + T.c_e * ec[0]; xn.y = T.c_x * x.y + T.c_e * ec[1];
     xn.z = T.c_x * x.z + T.c_e * ec[2]; xn.w = T.c_x * x.w + T.c_e * ec[3];
+    if (T.c_n != 0.f && a.step_noise) {
+        // Euler-ancestral: + sigma_up * noise[step], noise NCHW like posterior_sample_kernel's
+        const int p = idx - b * a.hw;
+        const float* nz = a.step_noise + ((size_t)step * total + (size_t)b * a.hw) * 4 + p;
+        xn.x += T.c_n * nz[0]; xn.y += T.c_n * nz[a.hw];
+        xn.z += T.c_n * nz[2 * (size_t)a.hw]; xn.w += T.c_n * nz[3 * (size_t)a.hw];
+    }
     reinterpret_cast<float4*>(a.latents)[idx] = xn;
     if (step < a.trace_cap) {
         if (a.trace_eps) reinterpret_cast<float4*>(a.trace_eps)[(size_t)step * total + idx] = make_float4(e[0], e[1], e[2], e[3]);

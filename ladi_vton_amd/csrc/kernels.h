@@ -129,13 +129,16 @@ struct StepTable {            // one entry per scheduler evaluation, device resi
     float c_x;                // multiplies current sample
     float c_e;                // multiplies the (possibly multistep-combined) epsilon
     float w[4];               // PLMS combination weights over [eps_now, ets[-1], ets[-2], ets[-3]]
-    int   mode;               // 0 plain (use w), 1 = PLMS 2nd evaluation (eps'=(eps+ets[-1])/2, sample=cur_sample, no push)
+    int   mode;               // 0 plain (use w), 1 = PLMS 2nd evaluation (eps'=(eps+ets[-1])/2, sample=cur_sample, no push),
+                              // 2 = DPM-Solver++: the ring holds data predictions m = p_x * sample + p_e * eps, and w combines those
     int   push;               // bit0: push eps_now into the ring; bits 4-5: slot to push into;
                               // bits 8-9 / 10-11 / 12-13: ring slots holding ets[-1] / ets[-2] / ets[-3] (before the push)
     int   save_cur;           // 1: save current sample as cur_sample before the update
     int   zero_cloth_next;    // 1: the NEXT evaluation must see zero cloth latents
     float in_scale_next;      // scheduler.scale_model_input of the NEXT evaluation: the UNet sees latents * in_scale_next (1 for DDIM / PNDM,
                               // 1 / sqrt(sigma^2 + 1) for LMS); the fp32 latents themselves stay unscaled
+    float p_x, p_e;           // mode 2: data prediction m = p_x * sample + p_e * eps (1 / alpha_s, -sigma_s / alpha_s)
+    float c_n;                // multiplies this evaluation's step noise (Euler-ancestral sigma_up; 0 = no noise term)
 };
 struct StepArgs {
     const h16* eps; int ld_eps;     // UNet output NHWC [2B or B][hw][ld_eps], channels 0..3 valid
@@ -150,6 +153,9 @@ struct StepArgs {
     // optional per-evaluation trace (parity tests): guided noise prediction and updated latents of evaluation i are written to
     // trace_*[i][B][hw][4] (fp32) for i < trace_cap; null = off
     float* trace_eps; float* trace_lat; int trace_cap;
+    // per-evaluation noise (Euler-ancestral): fp32 NCHW [evals][B][4][hw], indexed by the device step counter; read only where the
+    // table's c_n != 0 (null = none)
+    const float* step_noise;
 };
 int ladi_launch_sched_step(const StepArgs& a, hipStream_t st);
 

@@ -376,6 +376,10 @@ struct TryOn {
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool ev_valid = false;
     int last_evals = 0;
     float* trace_eps = nullptr; float* trace_lat = nullptr; int trace_cap = 0;   // caller-owned per-evaluation trace buffers (tests)
+    // Euler-ancestral step noise: the caller's fp32 [steps][B][4][h][w] (ladi_tryon_set_step_noise), copied by run() into the
+    // runtime-owned step_noise_buf that the captured graph reads
+    const float* step_noise_src = nullptr; int step_noise_steps = 0;
+    float* step_noise_buf = nullptr; size_t step_noise_cap = 0;
     // the legacy NULL stream (torch's default) cannot be captured: work then runs on this internal stream, fenced
     // against the caller's stream with events on entry and exit
     hipStream_t own_stream = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr;
@@ -387,16 +391,24 @@ struct TryOn {
 };
 
 // scheduler tables (host): builds timesteps + StepTable entries. kind 0 = DDIM, 1 = PNDM(PLMS, skip_prk_steps), 2 = LMSDiscrete
-// (fractional timesteps, sigma parameterisation: the latents start at noise * init_noise_sigma and the UNet sees them scaled)
+// (fractional timesteps, sigma parameterisation: the latents start at noise * init_noise_sigma and the UNet sees them scaled),
+// 3 = DPMSolverMultistep (dpmsolver++), 4 = EulerDiscrete, 5 = EulerAncestralDiscrete (LMS's timesteps and sigmas).
+// The scheduler code (ladi_tryon_inputs.scheduler, include/ladi_native.h) carries the kind in bits 0-3 and the DPM-Solver++ options in
+// bits 8-11: bits 8-9 solver_order (0 = the default 2, else 1..3), bit 10 solver_type heun (0 = midpoint), bit 11 lower_order_final off.
+// Any other bit, an option bit on another kind, or an unknown kind is rejected.
+enum { SCHED_DDIM = 0, SCHED_PNDM = 1, SCHED_LMS = 2, SCHED_DPMPP = 3, SCHED_EULER = 4, SCHED_EULER_A = 5 };
+struct SchedCode { int kind = 0, order = 2, heun = 0, lower_order_final = 1; };
+SchedCode decode_sched_code(int code);
 void default_alphas_cumprod(std::vector<float>& ac);
 struct SchedInfo {
     float init_noise_sigma = 1.f;    // prepare_latents: latents = noise * init_noise_sigma (tryon_pipe.py:424)
     float in_scale0 = 1.f;           // scale_model_input of evaluation 0 (later evaluations: StepTable::in_scale_next)
-    std::vector<float> sigmas;       // LMS only: steps + 1 values (trailing 0)
+    std::vector<float> sigmas;       // LMS / Euler / Euler-ancestral: steps + 1 values (trailing 0)
     std::vector<float> lms_coeffs;   // LMS only: [steps][4], c_ij over [d_i, d_{i-1}, d_{i-2}, d_{i-3}]
 };
-// cloth_zero_from: first evaluation index that must see zero cloth latents (tryon_pipe.py:718), computed by the caller in float64
-void build_step_table(int kind, int steps, const float* alphas_cumprod, int cloth_zero_from, std::vector<double>& timesteps,
+// cloth_zero_from: first evaluation index that must see zero cloth latents (tryon_pipe.py:718), computed by the caller in float64;
+// code: the scheduler code above
+void build_step_table(int code, int steps, const float* alphas_cumprod, int cloth_zero_from, std::vector<double>& timesteps,
                       std::vector<StepTable>& table, SchedInfo* info = nullptr);
 
 }  // namespace ladi

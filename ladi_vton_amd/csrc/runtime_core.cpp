@@ -366,31 +366,81 @@ static double lms_basis_integral(const double* s, int order, int j, double lo, d
     return acc * h;
 }
 
-void build_step_table(int kind, int steps, const float* ac, int cloth_zero_from, std::vector<double>& timesteps,
+SchedCode decode_sched_code(int code) {
+    SchedCode sc;
+    if (code < 0 || (code & ~0xF0F) != 0)
+        throw std::runtime_error("scheduler code " + std::to_string(code) + ": unknown bits (kind: bits 0-3, DPM-Solver++ options: bits 8-11)");
+    sc.kind = code & 15;
+    if (sc.kind > SCHED_EULER_A)
+        throw std::runtime_error("scheduler kind " + std::to_string(sc.kind) + " unknown: 0 DDIM, 1 PNDM, 2 LMSDiscrete, 3 DPMSolverMultistep, "
+                                 "4 EulerDiscrete, 5 EulerAncestralDiscrete");
+    const int opt = (code >> 8) & 15;
+    if (sc.kind != SCHED_DPMPP && opt) throw std::runtime_error("scheduler code " + std::to_string(code) + ": option bits 8-11 are DPM-Solver++ only");
+    if (sc.kind == SCHED_DPMPP) {
+        sc.order = (opt & 3) ? (opt & 3) : 2;
+        sc.heun = (opt >> 2) & 1;
+        sc.lower_order_final = !((opt >> 3) & 1);
+    }
+    return sc;
+}
+
+// diffusers 0.14 LMSDiscreteScheduler.set_timesteps (EulerDiscrete / EulerAncestralDiscrete use the same): timesteps = linspace(0, T-1, n)[::-1];
+// sigma = interp(t, arange(T), sqrt((1 - a) / a)) held in fp32, trailing 0
+static void lms_sigmas(int steps, const float* ac, std::vector<double>& timesteps, std::vector<float>& sig) {
+    const int T = 1000;
+    sig.assign((size_t)steps + 1, 0.f);
+    for (int i = 0; i < steps; ++i) {
+        // numpy.linspace: arange(n) * ((stop - start) / (n - 1)) + start, last element set to stop exactly
+        const int k = steps - 1 - i;
+        const double t = k == steps - 1 ? (double)(T - 1) : (double)k * ((double)(T - 1) / (double)(steps - 1));
+        timesteps.push_back(t);
+        const int lo = std::min((int)t, T - 1), hi = std::min(lo + 1, T - 1);
+        const double slo = (double)(float)std::sqrt((1.0 - (double)ac[lo]) / (double)ac[lo]);
+        const double shi = (double)(float)std::sqrt((1.0 - (double)ac[hi]) / (double)ac[hi]);
+        sig[i] = (float)(slo + (shi - slo) * (t - (double)lo));
+    }
+}
+
+// diffusers 0.14 DPMSolverMultistepScheduler.set_timesteps: linspace(0, T-1, n + 1).round()[::-1][:-1] (round half to even); the
+// duplicate timesteps some n give (n = 1000: 500 twice) make diffusers fail in step(), so they are refused here
+static std::vector<int> dpm_timesteps(int steps) {
+    const int T = 1000;
+    std::vector<int> ts;
+    for (int k = steps; k >= 1; --k) {
+        const double v = k == steps ? (double)(T - 1) : (double)k * ((double)(T - 1) / (double)steps);
+        ts.push_back((int)std::nearbyint(v));
+    }
+    for (int i = 1; i < steps; ++i)
+        if (ts[i] >= ts[i - 1])
+            throw std::runtime_error("DPMSolverMultistep: num_inference_steps = " + std::to_string(steps) + " gives the duplicate timestep " +
+                                     std::to_string(ts[i]) + " (diffusers 0.14 fails on it in step()); choose another step count");
+    return ts;
+}
+
+void build_step_table(int code, int steps, const float* ac, int cloth_zero_from, std::vector<double>& timesteps,
                       std::vector<StepTable>& table, SchedInfo* info) {
     const int T = 1000;
     if (steps < 2 || steps > T) throw std::runtime_error("num_inference_steps out of range [2, 1000]");   // ts[steps - 2] below
-    if (kind < 0 || kind > 2) throw std::runtime_error("scheduler kind must be 0 (DDIM), 1 (PNDM) or 2 (LMSDiscrete)");
+    const SchedCode sc = decode_sched_code(code);
+    const int kind = sc.kind;
     const int ratio = T / steps;
     const double final_ac = ac[0];  // set_alpha_to_one = False
     timesteps.clear(); table.clear();
     if (info) *info = SchedInfo();
-    if (kind == 2) {
-        // diffusers 0.14 LMSDiscreteScheduler.set_timesteps / step (order 4, epsilon prediction): timesteps = linspace(0, T-1, n)[::-1];
-        // sigma = interp(t, arange(T), sqrt((1 - a) / a)) held in fp32, trailing 0; derivative d_i = (x - (x - sigma_i eps)) / sigma_i = eps
-        std::vector<float> sig((size_t)steps + 1, 0.f);
-        for (int i = 0; i < steps; ++i) {
-            // numpy.linspace: arange(n) * ((stop - start) / (n - 1)) + start, last element set to stop exactly
-            const int k = steps - 1 - i;
-            const double t = k == steps - 1 ? (double)(T - 1) : (double)k * ((double)(T - 1) / (double)(steps - 1));
-            timesteps.push_back(t);
-            const int lo = std::min((int)t, T - 1), hi = std::min(lo + 1, T - 1);
-            const double slo = (double)(float)std::sqrt((1.0 - (double)ac[lo]) / (double)ac[lo]);
-            const double shi = (double)(float)std::sqrt((1.0 - (double)ac[hi]) / (double)ac[hi]);
-            sig[i] = (float)(slo + (shi - slo) * (t - (double)lo));
-        }
+    const bool sigma_kind = kind == SCHED_LMS || kind == SCHED_EULER || kind == SCHED_EULER_A;
+    std::vector<float> sig;
+    if (sigma_kind) {
+        lms_sigmas(steps, ac, timesteps, sig);
         float smax = 0.f;
         for (float s : sig) smax = std::max(smax, s);
+        if (info) {
+            info->init_noise_sigma = smax;
+            info->in_scale0 = (float)(1.0 / std::sqrt((double)sig[0] * (double)sig[0] + 1.0));
+            info->sigmas = sig;
+        }
+    }
+    if (kind == SCHED_LMS) {
+        // diffusers 0.14 LMSDiscreteScheduler.step (order 4, epsilon prediction): derivative d_i = (x - (x - sigma_i eps)) / sigma_i = eps
         std::vector<float> coeffs((size_t)steps * 4, 0.f);
         for (int i = 0; i < steps; ++i) {
             StepTable e; std::memset(&e, 0, sizeof(e));
@@ -407,10 +457,68 @@ void build_step_table(int kind, int steps, const float* ac, int cloth_zero_from,
             e.in_scale_next = i + 1 < steps ? (float)(1.0 / std::sqrt((double)sig[i + 1] * (double)sig[i + 1] + 1.0)) : 1.f;
             table.push_back(e);
         }
-        if (info) {
-            info->init_noise_sigma = smax;
-            info->in_scale0 = (float)(1.0 / std::sqrt((double)sig[0] * (double)sig[0] + 1.0));
-            info->sigmas = sig; info->lms_coeffs = coeffs;
+        if (info) info->lms_coeffs = coeffs;
+    } else if (kind == SCHED_EULER || kind == SCHED_EULER_A) {
+        // diffusers 0.14 EulerDiscreteScheduler.step (s_churn = 0): x + (sigma_{i+1} - sigma_i) * eps; EulerAncestralDiscreteScheduler.step:
+        // x + (sigma_down - sigma_i) * eps + sigma_up * noise_i, sigma_up = sqrt(s_to^2 (s_from^2 - s_to^2) / s_from^2),
+        // sigma_down = sqrt(s_to^2 - sigma_up^2)
+        for (int i = 0; i < steps; ++i) {
+            StepTable e; std::memset(&e, 0, sizeof(e));
+            const double s0 = sig[i], s1 = sig[i + 1];
+            e.c_x = 1.f; e.w[0] = 1.f;
+            if (kind == SCHED_EULER) e.c_e = (float)(s1 - s0);
+            else {
+                const double up = std::sqrt(s1 * s1 * (s0 * s0 - s1 * s1) / (s0 * s0));
+                const double down = std::sqrt(std::max(s1 * s1 - up * up, 0.0));
+                e.c_e = (float)(down - s0); e.c_n = (float)up;
+            }
+            e.in_scale_next = i + 1 < steps ? (float)(1.0 / std::sqrt(s1 * s1 + 1.0)) : 1.f;
+            table.push_back(e);
+        }
+    } else if (kind == SCHED_DPMPP) {
+        // diffusers 0.14 DPMSolverMultistepScheduler, algorithm_type dpmsolver++, epsilon prediction: alpha = sqrt(a), sigma = sqrt(1 - a),
+        // lambda = log(alpha) - log(sigma); data prediction m = (x - sigma_s eps) / alpha_s.  Every update is linear in x and the last
+        // (up to three) data predictions: x_t = (sigma_t / sigma_s0) x + sum_k W_k m_k, the ring holding m (mode 2).
+        const std::vector<int> ts = dpm_timesteps(steps);
+        auto alpha = [&](int t) { return std::sqrt((double)ac[t]); };
+        auto sigma = [&](int t) { return std::sqrt(1.0 - (double)ac[t]); };
+        auto lambda = [&](int t) { return std::log(alpha(t)) - std::log(sigma(t)); };
+        const bool lof = sc.lower_order_final && steps < 15;
+        for (int i = 0; i < steps; ++i) {
+            timesteps.push_back(ts[i]);
+            const int s0 = ts[i], t = i == steps - 1 ? 0 : ts[i + 1];
+            // warm-up: first order at step 0, at most second at step 1; lower_order_final: first order last, at most second before it
+            int order = std::min(sc.order, i + 1);
+            if (lof && i == steps - 1) order = 1;
+            if (lof && i == steps - 2) order = std::min(order, 2);
+            const double a_t = alpha(t), h = lambda(t) - lambda(s0);
+            const double em = std::expm1(-h);                         // e^-h - 1
+            const double A = -a_t * em;                               // coefficient of D0 = m0
+            const double Bc = a_t * (em / h + 1.0);                   // alpha_t ((e^-h - 1)/h + 1)
+            double W[3] = {A, 0.0, 0.0};
+            if (order == 2) {
+                const double r0 = (lambda(s0) - lambda(ts[i - 1])) / h;
+                const double cD1 = sc.heun ? Bc : 0.5 * A;            // midpoint: -0.5 alpha_t (e^-h - 1) D1; heun: + Bc D1
+                W[0] += cD1 / r0; W[1] -= cD1 / r0;                   // D1 = (m0 - m1) / r0
+            } else if (order == 3) {
+                const double r0 = (lambda(s0) - lambda(ts[i - 1])) / h, r1 = (lambda(ts[i - 1]) - lambda(ts[i - 2])) / h;
+                const double Cc = a_t * ((em + h) / (h * h) - 0.5);
+                const double d10[3] = {1.0 / r0, -1.0 / r0, 0.0}, d11[3] = {0.0, 1.0 / r1, -1.0 / r1};
+                for (int k = 0; k < 3; ++k) {
+                    const double diff = d10[k] - d11[k];
+                    const double D1 = d10[k] + r0 / (r0 + r1) * diff, D2 = diff / (r0 + r1);
+                    W[k] += Bc * D1 - Cc * D2;
+                }
+            }
+            StepTable e; std::memset(&e, 0, sizeof(e));
+            e.mode = 2;
+            e.c_x = (float)(sigma(t) / sigma(s0)); e.c_e = 1.f;
+            for (int k = 0; k < 3; ++k) e.w[k] = (float)W[k];
+            e.p_x = (float)(1.0 / alpha(s0)); e.p_e = (float)(-sigma(s0) / alpha(s0));
+            const int slot = i & 3, s1 = (i - 1) & 3, s2 = (i - 2) & 3, s3 = (i - 3) & 3;
+            e.push = 1 | (slot << 4) | (s1 << 8) | (s2 << 10) | (s3 << 12);
+            e.in_scale_next = 1.f;
+            table.push_back(e);
         }
     } else if (kind == 0) {
         for (int i = steps - 1; i >= 0; --i) timesteps.push_back(i * ratio + 1);
@@ -462,7 +570,7 @@ void build_step_table(int kind, int steps, const float* ac, int cloth_zero_from,
             table.push_back(e);
         }
     }
-    if (kind != 2) for (auto& e : table) e.in_scale_next = 1.f;
+    if (!sigma_kind) for (auto& e : table) e.in_scale_next = 1.f;
     // `if i >= num_inference_steps - cloth_conditioning_steps: cloth = 0` (tryon_pipe.py:718-719), evaluated at the
     // START of evaluation i -> mark entry i-1 so that the step kernel zeroes the cloth channels for evaluation i.
     for (int i = 1; i < (int)table.size(); ++i)

@@ -13,6 +13,7 @@ TryOn::~TryOn() {
     if (gexec) (void)hipGraphExecDestroy(gexec);
     if (graph) (void)hipGraphDestroy(graph);
     if (stats) (void)hipFree(stats);
+    if (step_noise_buf) (void)hipFree(step_noise_buf);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     if (ev_in) (void)hipEventDestroy(ev_in);
     if (ev_out) (void)hipEventDestroy(ev_out);
@@ -80,6 +81,24 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
     if (!sk_cnt) { sk_cnt = reinterpret_cast<int*>(pool.alloc(1024 * sizeof(int))); HIP_OK(hipMemset(sk_cnt, 0, 1024 * sizeof(int))); }
     if (evals > table_cap) { d_table = reinterpret_cast<StepTable*>(pool.alloc((size_t)evals * sizeof(StepTable))); table_cap = evals; }
     if (!ev[0]) for (auto& e : ev) HIP_OK(hipEventCreate(&e));
+    // Euler-ancestral: the caller's per-step noise is copied into a runtime-owned buffer (below, on the run's stream) so that the pointer the
+    // captured graph holds stays valid after the caller frees theirs
+    const bool use_step_noise = decode_sched_code(in.scheduler).kind == SCHED_EULER_A;
+    const size_t step_noise_bytes = use_step_noise ? (size_t)evals * B * 4 * hw * sizeof(float) : 0;
+    if (use_step_noise) {
+        if (!step_noise_src) { set_error("tryon: EulerAncestralDiscrete needs per-step noise (ladi_tryon_set_step_noise)"); return -7; }
+        if (step_noise_steps < evals) {
+            set_error("tryon: EulerAncestralDiscrete needs " + std::to_string(evals) + " steps of noise, ladi_tryon_set_step_noise gave " +
+                      std::to_string(step_noise_steps));
+            return -7;
+        }
+        if (step_noise_bytes > step_noise_cap) {
+            if (step_noise_buf) HIP_OK(hipFree(step_noise_buf));
+            step_noise_buf = nullptr; step_noise_cap = 0;
+            HIP_OK(hipMalloc(reinterpret_cast<void**>(&step_noise_buf), step_noise_bytes));
+            step_noise_cap = step_noise_bytes;
+        }
+    }
 
     try {
         lanes.configure(n, lanes_override > 0 && (n % lanes_override) == 0 ? lanes_override : 0);
@@ -90,6 +109,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
             if (pass == 1) {
                 HIP_OK(hipMemcpyAsync(d_table, table.data(), (size_t)evals * sizeof(StepTable), hipMemcpyHostToDevice, st));
                 HIP_OK(hipMemsetAsync(d_step, 0, 2 * sizeof(int), st));    // evaluation index + the step kernel's arrival ticket
+                if (use_step_noise) HIP_OK(hipMemcpyAsync(step_noise_buf, step_noise_src, step_noise_bytes, hipMemcpyDeviceToDevice, st));
                 std::vector<float> tsf(timesteps.begin(), timesteps.end());
                 if (unet->compute_temb(tsf.data(), evals, st)) return -5;
                 HIP_OK(hipEventRecord(ev[0], st));
@@ -173,6 +193,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
             sa.B = B; sa.hw = hw; sa.cfg = cfgf; sa.guidance = in.guidance; sa.latents = latents; sa.cur_sample = cur_sample; sa.ets = ets;
             sa.table = d_table; sa.step_idx = d_step; sa.unet_in = unet_in.p; sa.ld_in = 64; sa.cloth_ch0 = 9 + pose_ch;
             sa.trace_eps = trace_eps; sa.trace_lat = trace_lat; sa.trace_cap = trace_cap;
+            sa.step_noise = use_step_noise ? step_noise_buf : nullptr;
             // the UNet forward runs as lanes.G independent sample groups on as many streams (runtime.h UNetLanes); the lanes own their
             // arenas, the shared noise prediction lives in this one
             const int eps_ld = (unet->cfg.out_channels + 3) / 4 * 4;
@@ -196,6 +217,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 key = mix(key, (unsigned long long)pose_ch * 7 + has_cloth);
                 key = mix(key, (unsigned long long)(uintptr_t)trace_eps); key = mix(key, (unsigned long long)(uintptr_t)trace_lat);
                 key = mix(key, (unsigned long long)trace_cap);
+                key = mix(key, (unsigned long long)(uintptr_t)sa.step_noise);
                 key = mix(key, lanes.key());
                 if (!gexec || key != graph_key) {
                     if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }

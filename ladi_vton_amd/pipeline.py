@@ -16,7 +16,12 @@ import torch
 from . import _lib
 from ._lib import TryOnInputs, check, dtype_code, ptr, stream_ptr
 from .modules import NativeEMASC, NativeUNet, NativeVAE, mask_features
-from .schedulers import DDIMScheduler, LMSDiscreteScheduler, PNDMScheduler
+from .schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler,
+                         LMSDiscreteScheduler, PNDMScheduler)
+
+# the schedulers the fused native loop runs (ladi_tryon_run): the native step table of each is the mirror's arithmetic
+FUSED_SCHEDULERS = (DDIMScheduler, PNDMScheduler, LMSDiscreteScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler,
+                    EulerAncestralDiscreteScheduler)
 
 
 def numpy_to_pil(images):
@@ -160,12 +165,19 @@ class StableDiffusionTryOnePipeline:
         else:
             n_cloth, n_lat, n_mask = [t.to(device=device, dtype=torch.float32).contiguous() if t is not None else None for t in noise]
         native = isinstance(self.unet, NativeUNet) and isinstance(self.vae, NativeVAE) and (self.emasc is None or isinstance(self.emasc, NativeEMASC))
-        can_fuse = (fused and native and callback is None and isinstance(self.scheduler, (DDIMScheduler, PNDMScheduler, LMSDiscreteScheduler)) and eta == 0.0
+        can_fuse = (fused and native and callback is None and isinstance(self.scheduler, FUSED_SCHEDULERS) and eta == 0.0
                     and (not self.emasc or list(self.emasc_int_layers or []) == [1, 2, 3, 4, 5]))
         if can_fuse:
+            # Euler / Euler-ancestral step() draw one batch-shaped fp32 noise tensor per step after the three draws above: the fused path
+            # makes the same draws up front, in the same generator order (Euler's are unused, as in diffusers without churn)
+            step_noise = None
+            if isinstance(self.scheduler, (EulerDiscreteScheduler, EulerAncestralDiscreteScheduler)):
+                draws = [self._draw((B, 4, h, w), generator, torch.float32, device) for _ in range(int(num_inference_steps))]
+                if isinstance(self.scheduler, EulerAncestralDiscreteScheduler):
+                    step_noise = torch.stack(draws).contiguous()
             images = self._run_fused(image, mask_image, pose_map, warped_cloth if cloth_input_type == "warped" else None, pe, neg,
                                      n_cloth, n_lat, n_mask, height, width, num_inference_steps, guidance_scale, cloth_cond_rate,
-                                     no_pose, use_graph)
+                                     no_pose, use_graph, step_noise=step_noise)
             # prepare_mask_and_masked_image binarises the caller's mask in place; keep that side effect
             mask_image[mask_image < 0.5] = 0
             mask_image[mask_image >= 0.5] = 1
@@ -181,9 +193,10 @@ class StableDiffusionTryOnePipeline:
 
     # -------------------------------------------------------------------------------------------------------
     def _run_fused(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose,
-                   use_graph, return_device=False, out_uint8=False, lanes=None):
+                   use_graph, return_device=False, out_uint8=False, lanes=None, step_noise=None):
         """return_device: hand back the device tensor (no host copy); out_uint8: the batch as uint8 [B,H,W,3] = numpy_to_pil's
-        (images * 255).round() computed by the decode epilogue (ladi_tryon_run_u8); lanes: sample-group lanes of the UNet forward"""
+        (images * 255).round() computed by the decode epilogue (ladi_tryon_run_u8); lanes: sample-group lanes of the UNet forward;
+        step_noise: fp32 [steps, B, 4, h, w], the per-step noise of EulerAncestralDiscreteScheduler (ladi_tryon_set_step_noise)"""
         lib = _lib.load()
         if self._tryon is None:
             self._tryon = lib.ladi_tryon_create(self.unet.h, self.vae.h, self.emasc.h if self.emasc else None)
@@ -234,6 +247,13 @@ class StableDiffusionTryOnePipeline:
             check(lib.ladi_tryon_set_trace(self._tryon, ptr(tr[0]), ptr(tr[1]), self.trace_evals), "ladi_tryon_set_trace")
         else:
             check(lib.ladi_tryon_set_trace(self._tryon, None, None, 0), "ladi_tryon_set_trace")
+        if step_noise is not None:
+            if tuple(step_noise.shape[1:]) != (B, 4, h8, w8) or step_noise.shape[0] < int(steps):
+                raise ValueError("step noise has shape %s, expected (%d, %d, 4, %d, %d)" % (tuple(step_noise.shape), int(steps), B, h8, w8))
+            step_noise = step_noise.to(device=dev, dtype=torch.float32).contiguous()
+            check(lib.ladi_tryon_set_step_noise(self._tryon, ptr(step_noise), step_noise.shape[0]), "ladi_tryon_set_step_noise")
+        else:
+            check(lib.ladi_tryon_set_step_noise(self._tryon, None, 0), "ladi_tryon_set_step_noise")
         # the fused loop rewrites the UNet's cross-attention K/V cache behind the shim's back
         self.unet._ctx_key = None
         if lanes is not None or self.lanes is not None:

@@ -3,16 +3,23 @@ src/inference.py:123-124 instantiates —, PNDMScheduler with skip_prk_steps, wh
 describes, and LMSDiscreteScheduler).  They expose the attributes tryon_pipe.py touches
 (:74,88,331-346,424,650-651,711,722,740).
 
+Three more diffusers 0.14.0 schedulers work as the reference pipeline's `scheduler` because it only calls set_timesteps,
+scale_model_input, step, timesteps, init_noise_sigma and order: DPMSolverMultistepScheduler (dpmsolver++), EulerDiscreteScheduler and
+EulerAncestralDiscreteScheduler, mirrored here with the same SD2-inpainting config (scaled_linear 0.00085-0.012, 1000 training steps,
+epsilon prediction).  Their formulas are restated from the published algorithms as diffusers 0.14 ships them, from memory: diffusers is
+not installable here, so they are not pinned against it (like the other three).
+
 The fused native loop (ladi_tryon_run) does not call .step(): it consumes the same tables on the device.  .step() here serves
 the module-by-module drop-in path and operates on small [B,4,h,w] tensors.
 """
+import math
 from types import SimpleNamespace
 
 import torch
 
 from . import _lib
 
-DDIM, PNDM, LMS = 0, 1, 2
+DDIM, PNDM, LMS, DPMPP, EULER, EULER_ANCESTRAL = 0, 1, 2, 3, 4, 5
 
 
 def _alphas_cumprod():
@@ -49,6 +56,18 @@ class _SchedulerBase:
         return self.alphas_cumprod[t] if t >= 0 else self.final_alpha_cumprod
 
 
+def _step_noise(shape, dtype, generator, device):
+    """diffusers 0.14 randn_tensor(shape, generator, device, dtype) as the schedulers' step() calls it: drawn on the generator's device;
+    a LIST of generators draws one [1, ...] tensor per sample from that sample's generator"""
+    if isinstance(generator, (list, tuple)):
+        if len(generator) != shape[0]:
+            raise ValueError("You have passed a list of generators of length %d, but requested an effective batch size of %d."
+                             % (len(generator), shape[0]))
+        return torch.cat([torch.randn((1,) + shape[1:], generator=g_, device=g_.device, dtype=dtype).to(device) for g_ in generator], dim=0)
+    gdev = generator.device if generator is not None else device
+    return torch.randn(shape, generator=generator, device=gdev, dtype=dtype).to(device)
+
+
 class DDIMScheduler(_SchedulerBase):
     kind = DDIM
 
@@ -72,18 +91,8 @@ class DDIMScheduler(_SchedulerBase):
             raise NotImplementedError("use_clipped_model_output=True is not implemented (the try-on pipeline never sets it: tryon_pipe.py:740)")
         if eta > 0:
             if variance_noise is None:
-                # diffusers 0.14 randn_tensor(model_output.shape, generator, device, dtype=model_output.dtype): drawn on the generator's
-                # device; a LIST of generators draws one [1, ...] tensor per sample from that sample's generator
-                shape, dt = tuple(model_output.shape), model_output.dtype
-                if isinstance(generator, (list, tuple)):
-                    if len(generator) != shape[0]:
-                        raise ValueError("You have passed a list of generators of length %d, but requested an effective batch size of %d."
-                                         % (len(generator), shape[0]))
-                    variance_noise = torch.cat([torch.randn((1,) + shape[1:], generator=g_, device=g_.device, dtype=dt).to(sample.device)
-                                                for g_ in generator], dim=0)
-                else:
-                    gdev = generator.device if generator is not None else sample.device
-                    variance_noise = torch.randn(shape, generator=generator, device=gdev, dtype=dt).to(sample.device)
+                # randn_tensor(model_output.shape, generator, device, dtype=model_output.dtype)
+                variance_noise = _step_noise(tuple(model_output.shape), model_output.dtype, generator, sample.device)
             prev = prev + std * variance_noise.float()
         return SimpleNamespace(prev_sample=prev.to(sample.dtype))
 
@@ -124,18 +133,101 @@ class PNDMScheduler(_SchedulerBase):
         return SimpleNamespace(prev_sample=prev.to(sample.dtype))
 
 
-class LMSDiscreteScheduler(_SchedulerBase):
-    """diffusers 0.14 LMSDiscreteScheduler (order-4 linear multistep in the sigma parameterisation, epsilon prediction).  The
-    fractional timesteps, the sigmas and the multistep weights all come from the native table builder (ladi_sched_lms), i.e. they
-    are the very numbers the fused device loop uses."""
-    kind = LMS
+class DPMSolverMultistepScheduler(_SchedulerBase):
+    """diffusers 0.14 DPMSolverMultistepScheduler with algorithm_type="dpmsolver++" (DPM-Solver++ 2M by default), epsilon prediction.
+
+    Restated from memory (not pinned against diffusers): timesteps linspace(0, 999, n + 1).round()[::-1][:-1] (round half to even; the
+    native builder refuses n whose timesteps repeat, e.g. n = 1000, on which diffusers fails in step()); alpha = sqrt(a), sigma =
+    sqrt(1 - a), lambda = log(alpha) - log(sigma); data prediction m = (x - sigma_s eps) / alpha_s; prev_t = 0 at the last step; with
+    h = lambda_t - lambda_s0, r0 = h_0 / h, r1 = h_1 / h:
+      first order : x_t = (sigma_t / sigma_s) x - alpha_t (e^-h - 1) m0
+      second order: D1 = (m0 - m1) / r0; midpoint adds -0.5 alpha_t (e^-h - 1) D1, heun adds alpha_t ((e^-h - 1) / h + 1) D1
+      third order : D1_0 = (m0 - m1) / r0, D1_1 = (m1 - m2) / r1, D1 = D1_0 + r0 / (r0 + r1) (D1_0 - D1_1), D2 = (D1_0 - D1_1) / (r0 + r1);
+                    x_t = (sigma_t / sigma_s0) x - alpha_t (e^-h - 1) m0 + alpha_t ((e^-h - 1) / h + 1) D1 - alpha_t ((e^-h - 1 + h) / h^2 - 0.5) D2
+    Warm-up: first order at the first step, at most second at the second; lower_order_final (only if n < 15): first order at the last
+    step, at most second at the one before.  The fused device loop uses the native table (mode 2 of the step kernel: the history ring holds
+    the data predictions)."""
+
+    def __init__(self, solver_order=2, algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True, thresholding=False,
+                 prediction_type="epsilon"):
+        if solver_order not in (1, 2, 3):
+            raise ValueError("solver_order must be 1, 2 or 3, got %r" % (solver_order,))
+        if solver_type not in ("midpoint", "heun"):
+            raise ValueError("solver_type must be 'midpoint' or 'heun', got %r" % (solver_type,))
+        if algorithm_type != "dpmsolver++":
+            raise NotImplementedError("DPMSolverMultistepScheduler: only algorithm_type='dpmsolver++' is implemented, got %r" % (algorithm_type,))
+        if thresholding:
+            raise NotImplementedError("DPMSolverMultistepScheduler: thresholding=True is not implemented")
+        if prediction_type != "epsilon":
+            raise NotImplementedError("DPMSolverMultistepScheduler: only prediction_type='epsilon' is implemented, got %r" % (prediction_type,))
+        super().__init__()
+        self.config.solver_order, self.config.algorithm_type, self.config.solver_type = solver_order, algorithm_type, solver_type
+        self.config.lower_order_final, self.config.thresholding = bool(lower_order_final), False
+        # scheduler code (include/ladi_native.h): kind 3, bits 8-9 solver_order (0 = 2), bit 10 heun, bit 11 lower_order_final off
+        self.kind = (DPMPP | ((solver_order if solver_order != 2 else 0) << 8) | ((solver_type == "heun") << 10)
+                     | ((not lower_order_final) << 11))
+        ac = self.alphas_cumprod.double()
+        self.alpha_t, self.sigma_t = ac.sqrt(), (1 - ac).sqrt()
+        self.lambda_t = self.alpha_t.log() - self.sigma_t.log()
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        n = int(num_inference_steps)
+        self.num_inference_steps = n
+        self._ts = self._native_timesteps(n)
+        self.timesteps = torch.tensor(self._ts, dtype=torch.int64, device=device)
+        self.model_outputs = [None] * self.config.solver_order
+        self.lower_order_nums = 0
+
+    def _coef(self, t):
+        return float(self.alpha_t[t]), float(self.sigma_t[t]), float(self.lambda_t[t])
+
+    def step(self, model_output, timestep, sample, return_dict=True, **kw):
+        t_s = int(timestep)
+        ts, n, order = self._ts, len(self._ts), self.config.solver_order
+        i = ts.index(t_s) if t_s in ts else n - 1
+        prev_t = 0 if i == n - 1 else ts[i + 1]
+        lof = self.config.lower_order_final and n < 15
+        x, e = sample.float(), model_output.float()
+        a_s, s_s, l_s = self._coef(t_s)
+        m = (x - s_s * e) / a_s
+        self.model_outputs = self.model_outputs[1:] + [m]
+        a_t, s_t, l_t = self._coef(prev_t)
+        h = l_t - l_s
+        em = math.expm1(-h)
+        prev = (s_t / s_s) * x - a_t * em * m
+        if not (order == 1 or self.lower_order_nums < 1 or (lof and i == n - 1)):
+            m0, m1 = self.model_outputs[-1], self.model_outputs[-2]
+            r0 = (l_s - self._coef(ts[i - 1])[2]) / h
+            if order == 2 or self.lower_order_nums < 2 or (lof and i == n - 2):
+                d1 = (m0 - m1) / r0
+                if self.config.solver_type == "midpoint":
+                    prev = prev - 0.5 * a_t * em * d1
+                else:
+                    prev = prev + a_t * (em / h + 1.0) * d1
+            else:
+                m2 = self.model_outputs[-3]
+                r1 = (self._coef(ts[i - 1])[2] - self._coef(ts[i - 2])[2]) / h
+                d1_0, d1_1 = (m0 - m1) / r0, (m1 - m2) / r1
+                d1 = d1_0 + (r0 / (r0 + r1)) * (d1_0 - d1_1)
+                d2 = (d1_0 - d1_1) / (r0 + r1)
+                prev = prev + a_t * (em / h + 1.0) * d1 - a_t * ((em + h) / (h * h) - 0.5) * d2
+        if self.lower_order_nums < order:
+            self.lower_order_nums += 1
+        return SimpleNamespace(prev_sample=prev.to(sample.dtype))
+
+
+class _SigmaScheduler(_SchedulerBase):
+    """the sigma parameterisation LMSDiscrete, EulerDiscrete and EulerAncestralDiscrete share: fractional timesteps
+    linspace(0, 999, n)[::-1], sigmas interpolated from sqrt((1 - a) / a) in fp32 with a trailing 0, init_noise_sigma = max sigma,
+    scale_model_input = sample / sqrt(sigma^2 + 1).  The tables come from the native builder (ladi_sched_lms), i.e. they are the very
+    numbers the fused device loop uses."""
 
     def __init__(self):
         super().__init__()
         self.sigmas = None
         self.init_noise_sigma = float(((1 - self.alphas_cumprod) / self.alphas_cumprod).sqrt().max())   # as diffusers before set_timesteps
 
-    def set_timesteps(self, num_inference_steps, device=None):
+    def _set_sigma_tables(self, num_inference_steps, device):
         import ctypes
         n = int(num_inference_steps)
         ts = (ctypes.c_double * n)()
@@ -147,10 +239,9 @@ class LMSDiscreteScheduler(_SchedulerBase):
         self.num_inference_steps = n
         self.timesteps = torch.tensor(list(ts), dtype=torch.float64, device=device)
         self.sigmas = torch.tensor(list(sg), dtype=torch.float32)
-        self._coeffs = [list(cf[4 * i:4 * i + 4]) for i in range(n)]
         self._ts = list(ts)
         self.init_noise_sigma = float(self.sigmas.max())
-        self.derivatives = []
+        return cf
 
     def _index(self, timestep):
         t = float(timestep)
@@ -159,6 +250,59 @@ class LMSDiscreteScheduler(_SchedulerBase):
     def scale_model_input(self, sample, timestep=None):
         sigma = float(self.sigmas[self._index(timestep)])
         return sample / ((sigma * sigma + 1.0) ** 0.5)
+
+
+class EulerDiscreteScheduler(_SigmaScheduler):
+    """diffusers 0.14 EulerDiscreteScheduler, epsilon prediction, s_churn = 0 only: prev = x + (sigma_{i+1} - sigma_i) eps.  Like diffusers,
+    step() draws one noise tensor per call even without churn (it is unused), so a generator ends a run in the reference's state.
+    Restated from memory, not pinned against diffusers."""
+    kind = EULER
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        self._set_sigma_tables(num_inference_steps, device)
+
+    def step(self, model_output, timestep, sample, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, generator=None,
+             return_dict=True, **kw):
+        if s_churn != 0:
+            raise NotImplementedError("EulerDiscreteScheduler.step: only s_churn = 0 is implemented")
+        i = self._index(timestep)
+        x, e = sample.float(), model_output.float()
+        _step_noise(tuple(model_output.shape), torch.float32, generator, sample.device)
+        prev = x + (float(self.sigmas[i + 1]) - float(self.sigmas[i])) * e
+        return SimpleNamespace(prev_sample=prev.to(sample.dtype))
+
+
+class EulerAncestralDiscreteScheduler(_SigmaScheduler):
+    """diffusers 0.14 EulerAncestralDiscreteScheduler, epsilon prediction: sigma_up = sqrt(s_to^2 (s_from^2 - s_to^2) / s_from^2),
+    sigma_down = sqrt(s_to^2 - sigma_up^2), prev = x + (sigma_down - sigma) eps + sigma_up noise, one fp32 noise tensor drawn per step
+    (on the generator's device; a LIST of generators draws one [1, ...] tensor per sample).  The fused loop takes the same draws,
+    made up front in the same generator order (ladi_tryon_set_step_noise).  Restated from memory, not pinned against diffusers."""
+    kind = EULER_ANCESTRAL
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        self._set_sigma_tables(num_inference_steps, device)
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, **kw):
+        i = self._index(timestep)
+        s_from, s_to = float(self.sigmas[i]), float(self.sigmas[i + 1])
+        up = (s_to ** 2 * (s_from ** 2 - s_to ** 2) / s_from ** 2) ** 0.5
+        down = max(s_to ** 2 - up ** 2, 0.0) ** 0.5
+        x, e = sample.float(), model_output.float()
+        noise = _step_noise(tuple(model_output.shape), torch.float32, generator, sample.device)
+        prev = x + (down - s_from) * e + up * noise
+        return SimpleNamespace(prev_sample=prev.to(sample.dtype))
+
+
+class LMSDiscreteScheduler(_SigmaScheduler):
+    """diffusers 0.14 LMSDiscreteScheduler (order-4 linear multistep in the sigma parameterisation, epsilon prediction).  The
+    fractional timesteps, the sigmas and the multistep weights all come from the native table builder (ladi_sched_lms), i.e. they
+    are the very numbers the fused device loop uses."""
+    kind = LMS
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        cf = self._set_sigma_tables(num_inference_steps, device)
+        self._coeffs = [list(cf[4 * i:4 * i + 4]) for i in range(self.num_inference_steps)]
+        self.derivatives = []
 
     def step(self, model_output, timestep, sample, order=4, **kw):
         if order != 4:
