@@ -220,6 +220,11 @@ int ladi_sched_timesteps(int kind, int num_inference_steps, int* timesteps_out, 
  *   in_scale_next = scale_model_input of the next evaluation.  timesteps_out[evals] (float64) and rows_out may be null.
  * Returns the evaluation count (or negative on error; cap = capacity in evaluations). */
 int ladi_sched_table(int kind, int num_inference_steps, const float* alphas_cumprod_host, double* timesteps_out, float* rows_out, int cap);
+/* the same table for DDIMScheduler.step(eta = ...) (diffusers 0.14): std = eta sqrt(max((1 - a_p) / (1 - a_t) (1 - a_t / a_p), 0)), the eps
+ * direction sqrt(max(1 - a_p - std^2, 0)), c_n = std.  eta == 0 gives ladi_sched_table's rows bit for bit; eta < 0, a non-finite eta, or a
+ * non-zero eta with any kind but DDIM is an error (the other schedulers' step() takes no eta). */
+int ladi_sched_table_eta(int kind, int num_inference_steps, const float* alphas_cumprod_host, float eta, double* timesteps_out, float* rows_out,
+                         int cap);
 /* host helper, LMSDiscrete (order 4): timesteps_out[N] (fractional, float64 as diffusers holds them), sigmas_out[N + 1] (trailing 0;
  * init_noise_sigma = sigmas_out[0]), coeffs_out[N][4] = linear-multistep weights of evaluation i over its derivatives
  * [d_i, d_{i-1}, d_{i-2}, d_{i-3}] (zero beyond the order min(i + 1, 4)).  alphas_cumprod_host null = default.  Any output may be null. */
@@ -247,7 +252,8 @@ typedef struct {
     int num_inference_steps;
     float guidance_scale;
     int scheduler;                     /* scheduler code (see "Scheduler" above): 0 DDIM, 1 PNDM, 2 LMSDiscrete, 3 DPMSolverMultistep
-                                        * (+ option bits), 4 EulerDiscrete, 5 EulerAncestralDiscrete (needs ladi_tryon_set_step_noise) */
+                                        * (+ option bits), 4 EulerDiscrete, 5 EulerAncestralDiscrete (needs ladi_tryon_set_step_noise);
+                                        * DDIM's eta is set with ladi_tryon_set_eta */
     int cloth_zero_from_eval;          /* first evaluation index i that sees zero cloth latents: the smallest i with
                                         * i >= num_inference_steps - (1 - cloth_cond_rate) * num_inference_steps, evaluated by the CALLER in
                                         * float64 exactly like tryon_pipe.py:654,718 (a float32 rate crossing the ABI shifts the cut-off by
@@ -269,11 +275,23 @@ int ladi_tryon_run_u8(ladi_tryon* t, const ladi_tryon_inputs* in, unsigned char*
  * and the updated latents of evaluation i to *_trace_dev[i] (fp32 [B, h*w, 4] each) for i < cap_evals; NULL pointers switch it off.
  * Buffers are caller-owned and must outlive the runs. */
 int ladi_tryon_set_trace(ladi_tryon* t, float* eps_trace_dev, float* latents_trace_dev, int cap_evals);
-/* per-step noise of EulerAncestralDiscrete (its randn draw in step(), one per evaluation): fp32 [steps][B][4][h][w] on the device.
- * Each run copies the first `evaluations` steps on its stream into a runtime-owned buffer before the loop, so the captured graph never
- * reads the caller's buffer (which, like the run's other inputs, must stay valid until the run's work on the stream has started); a run of
- * kind 5 with no noise, or fewer steps than evaluations, fails.  Other kinds ignore it.  NULL = off. */
+/* per-step noise of EulerAncestralDiscrete and of DDIM with eta > 0 (the randn draw of their step(), one per evaluation): fp32
+ * [steps][B][4][h][w] on the device.  Each run copies the first `evaluations` steps on its stream into a runtime-owned buffer before the loop,
+ * so the captured graph never reads the caller's buffer (which, like the run's other inputs, must stay valid until the run's work on the stream
+ * has started); such a run with no noise, or fewer steps than evaluations, fails.  Runs without a stochastic term ignore it.  NULL = off. */
 int ladi_tryon_set_step_noise(ladi_tryon* t, const float* noise_dev, int steps);
+/* DDIMScheduler.step's eta for the following runs (sticky per handle, default 0): > 0 adds the stochastic term std * noise[i], which needs
+ * ladi_tryon_set_step_noise.  Only DDIM reads it: a run of any other scheduler with a non-zero eta fails.  eta < 0 or non-finite: error. */
+int ladi_tryon_set_eta(ladi_tryon* t, float eta);
+/* step callback (diffusers' callback / callback_steps): after evaluation i with i % every == 0, on the run's stream, the loop's latents are
+ * copied to latents_nchw_dev (caller-owned fp32 [B,4,h,w], what the modular path hands its callback), the stream is synchronised and
+ * fn(user, i) runs on the calling thread.  Afterwards work queued on the run's `stream` argument is waited for, and latents_nchw_dev is copied
+ * back into the loop (and into the next UNet input), so in-place edits take effect.  fn must not call back into this handle.  A non-zero
+ * return aborts the run: ladi_tryon_run returns LADI_TRYON_CALLBACK_ABORTED, nothing is decoded, and the handle stays usable.  The callback
+ * points sit between graph launches; with fn == NULL (off, the default) the loop runs exactly as without this call.  Sticky per handle. */
+typedef int (*ladi_step_callback)(void* user, int eval_index);
+#define LADI_TRYON_CALLBACK_ABORTED (-8)
+int ladi_tryon_set_step_callback(ladi_tryon* t, ladi_step_callback fn, void* user, int every, float* latents_nchw_dev);
 /* stage times (ms) of the last run: [0] preprocess + VAE encodes + EMASC, [1] denoising loop, [2] decode. Sync first. */
 int ladi_tryon_stage_ms(ladi_tryon* t, float* out3);
 /* fp16-range guard of the decode, examined WITHOUT a host round trip inside ladi_tryon_run (round 6): a run decodes once and queues the guard's flag
@@ -395,6 +413,9 @@ int ladi_op_sched_run(int kind, int steps, const float* alphas_cumprod_host, con
 /* the same with per-evaluation step noise (EulerAncestralDiscrete): step_noise_dev fp32 [noise_steps][B][4][hw], noise_steps >= evals */
 int ladi_op_sched_run_noise(int kind, int steps, const float* alphas_cumprod_host, const void* eps_seq_dev, int evals, int B, int hw,
                             int cfg, float guidance, float* latents_dev, const float* step_noise_dev, int noise_steps, void* stream);
+/* the same with DDIM's eta (ladi_sched_table_eta's table); eta > 0 needs step noise for every evaluation run */
+int ladi_op_sched_run_noise_eta(int kind, int steps, const float* alphas_cumprod_host, float eta, const void* eps_seq_dev, int evals, int B,
+                                int hw, int cfg, float guidance, float* latents_dev, const float* step_noise_dev, int noise_steps, void* stream);
 /* pipeline pre-processing kernels, one entry point per kernel so each can be checked on its own:
  * prepare_mask_and_masked_image (diffusers tensor branch; tryon_pipe.py:630): mask binarised at 0.5 -> mask_bin_dev fp16 [B,H,W];
  *   masked_image_dev NHWC fp16 [B,H,W,ld] (3 valid channels, the rest zero) = image * (mask < 0.5) */

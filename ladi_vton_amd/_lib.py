@@ -83,6 +83,10 @@ class IGemmDesc(Structure):
 
 # every symbol include/ladi_native.h declares: name -> (restype, argtypes)
 _P = c_void_p
+# ladi_step_callback: int (*)(void* user, int eval_index)
+STEP_CALLBACK = ctypes.CFUNCTYPE(c_int, c_void_p, c_int)
+NO_STEP_CALLBACK = STEP_CALLBACK()          # the NULL function pointer: switches the callback off
+TRYON_CALLBACK_ABORTED = -8
 SIGNATURES = {
     "ladi_last_error": (c_char_p, []),
     "ladi_version": (c_int, []),
@@ -124,6 +128,7 @@ SIGNATURES = {
     "ladi_sched_timesteps": (c_int, [c_int, c_int, POINTER(c_int), c_int]),
     "ladi_sched_lms": (c_int, [c_int, _P, _P, _P, _P]),
     "ladi_sched_table": (c_int, [c_int, c_int, _P, _P, _P, c_int]),
+    "ladi_sched_table_eta": (c_int, [c_int, c_int, _P, c_float, _P, _P, c_int]),
     "ladi_sched_alphas_cumprod": (c_int, [POINTER(c_float)]),
     "ladi_tryon_create": (_P, [_P, _P, _P]),
     "ladi_tryon_destroy": (None, [_P]),
@@ -133,6 +138,8 @@ SIGNATURES = {
     "ladi_tryon_poll_overflow": (c_int, [_P]),
     "ladi_tryon_set_trace": (c_int, [_P, _P, _P, c_int]),
     "ladi_tryon_set_step_noise": (c_int, [_P, _P, c_int]),
+    "ladi_tryon_set_eta": (c_int, [_P, c_float]),
+    "ladi_tryon_set_step_callback": (c_int, [_P, STEP_CALLBACK, _P, c_int, _P]),
     "ladi_tryon_set_lanes": (c_int, [_P, c_int]),
     "ladi_tryon_lanes": (c_int, [_P]),
     "ladi_vae_set_range_shift": (c_int, [_P, c_int]),
@@ -169,6 +176,7 @@ SIGNATURES = {
     "ladi_op_nhwc_to_nchw": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
     "ladi_op_sched_run": (c_int, [c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P]),
     "ladi_op_sched_run_noise": (c_int, [c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int, _P]),
+    "ladi_op_sched_run_noise_eta": (c_int, [c_int, c_int, _P, c_float, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int, _P]),
     "ladi_op_prepare_mask": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
     "ladi_op_mask_down": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "ladi_op_pose_down8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),

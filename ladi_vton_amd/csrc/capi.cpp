@@ -21,6 +21,7 @@ struct ladi_vision_encoder { VisionEncoder v; };
 struct ladi_refine { Refine r; };
 struct ladi_tps { Tps t; };
 struct ladi_tryon { TryOn t; };
+static_assert(TRYON_CALLBACK_ABORT == LADI_TRYON_CALLBACK_ABORTED, "callback abort code");
 
 static_assert(sizeof(ladi_igemm_desc) == sizeof(IGemmArgs), "public igemm descriptor must mirror IGemmArgs");
 
@@ -522,12 +523,13 @@ int ladi_sched_lms(int steps, const float* ac_host, double* timesteps_out, float
         return steps;
     });
 }
-int ladi_sched_table(int code, int steps, const float* ac_host, double* timesteps_out, float* rows_out, int cap) {
-    return guarded("ladi_sched_table", [&]() {
+static int sched_table_any(const char* name, int code, int steps, const float* ac_host, double* timesteps_out, float* rows_out, int cap,
+                           float eta) {
+    return guarded(name, [&]() {
         std::vector<float> ac;
         if (ac_host) ac.assign(ac_host, ac_host + 1000); else default_alphas_cumprod(ac);
         std::vector<double> ts; std::vector<StepTable> tb;
-        build_step_table(code, steps, ac.data(), 1 << 30, ts, tb);
+        build_step_table(code, steps, ac.data(), 1 << 30, ts, tb, nullptr, eta);
         if ((int)tb.size() > cap) throw std::runtime_error("table buffer too small");
         for (size_t i = 0; i < tb.size(); ++i) {
             const StepTable& e = tb[i];
@@ -537,6 +539,12 @@ int ladi_sched_table(int code, int steps, const float* ac_host, double* timestep
         }
         return (int)tb.size();
     });
+}
+int ladi_sched_table(int code, int steps, const float* ac_host, double* timesteps_out, float* rows_out, int cap) {
+    return sched_table_any("ladi_sched_table", code, steps, ac_host, timesteps_out, rows_out, cap, 0.f);
+}
+int ladi_sched_table_eta(int code, int steps, const float* ac_host, float eta, double* timesteps_out, float* rows_out, int cap) {
+    return sched_table_any("ladi_sched_table_eta", code, steps, ac_host, timesteps_out, rows_out, cap, eta);
 }
 int ladi_sched_alphas_cumprod(float* out) {
     std::vector<float> ac; default_alphas_cumprod(ac);
@@ -593,6 +601,17 @@ int ladi_tryon_lanes(ladi_tryon* t) { return t ? t->t.lanes.G : -1; }
 int ladi_tryon_set_step_noise(ladi_tryon* t, const float* noise_dev, int steps) {
     if (!t || steps < 0) { set_error("ladi_tryon_set_step_noise: null handle or negative steps"); return -1; }
     t->t.step_noise_src = noise_dev; t->t.step_noise_steps = noise_dev ? steps : 0;
+    return 0;
+}
+int ladi_tryon_set_eta(ladi_tryon* t, float eta) {
+    if (!t || !(eta >= 0.f) || !std::isfinite(eta)) { set_error("ladi_tryon_set_eta: null handle, or eta not finite and >= 0"); return -1; }
+    t->t.eta = eta;
+    return 0;
+}
+int ladi_tryon_set_step_callback(ladi_tryon* t, ladi_step_callback fn, void* user, int every, float* latents_nchw_dev) {
+    if (!t) { set_error("ladi_tryon_set_step_callback: null handle"); return -1; }
+    if (fn && (every < 1 || !latents_nchw_dev)) { set_error("ladi_tryon_set_step_callback: every must be >= 1 and the latents buffer set"); return -1; }
+    t->t.cb_fn = fn; t->t.cb_user = fn ? user : nullptr; t->t.cb_every = fn ? every : 1; t->t.cb_latents = fn ? latents_nchw_dev : nullptr;
     return 0;
 }
 int ladi_tryon_set_trace(ladi_tryon* t, float* eps_trace, float* latents_trace, int cap_evals) {
@@ -821,16 +840,16 @@ int ladi_op_assemble_input(void* unet_in, int ld, int B, int hw, int cfg, const 
                                        cloth_lat, cloth_lat ? 1 : 0, 1.0f, S(stream));
 }
 static int sched_run_any(const char* name, int kind, int steps, const float* ac_host, const void* eps_seq, int evals, int B, int hw, int cfg,
-                         float guidance, float* latents, const float* step_noise, int noise_steps, void* stream) {
+                         float guidance, float* latents, const float* step_noise, int noise_steps, float eta, void* stream) {
     return guarded(name, [&]() {
         hipStream_t st = S(stream);
         std::vector<float> ac;
         if (ac_host) ac.assign(ac_host, ac_host + 1000); else default_alphas_cumprod(ac);
         std::vector<double> ts; std::vector<StepTable> tb;
-        build_step_table(kind, steps, ac.data(), 1 << 30, ts, tb);
+        build_step_table(kind, steps, ac.data(), 1 << 30, ts, tb, nullptr, eta);
         if (evals > (int)tb.size()) throw std::runtime_error("evals exceeds scheduler length");
-        if (decode_sched_code(kind).kind == SCHED_EULER_A && (!step_noise || noise_steps < evals))
-            throw std::runtime_error("EulerAncestralDiscrete needs step noise for every evaluation run");
+        if (table_needs_step_noise(tb) && (!step_noise || noise_steps < evals))
+            throw std::runtime_error("EulerAncestralDiscrete / DDIM with eta > 0 need step noise for every evaluation run");
         char* buf = nullptr;
         const size_t plane = (size_t)B * hw * 4 * sizeof(float);
         const size_t tb_bytes = (tb.size() * sizeof(StepTable) + 255) & ~(size_t)255;
@@ -857,12 +876,17 @@ static int sched_run_any(const char* name, int kind, int steps, const float* ac_
 }
 int ladi_op_sched_run(int kind, int steps, const float* ac_host, const void* eps_seq, int evals, int B, int hw, int cfg, float guidance,
                       float* latents, void* stream) {
-    return sched_run_any("ladi_op_sched_run", kind, steps, ac_host, eps_seq, evals, B, hw, cfg, guidance, latents, nullptr, 0, stream);
+    return sched_run_any("ladi_op_sched_run", kind, steps, ac_host, eps_seq, evals, B, hw, cfg, guidance, latents, nullptr, 0, 0.f, stream);
 }
 int ladi_op_sched_run_noise(int kind, int steps, const float* ac_host, const void* eps_seq, int evals, int B, int hw, int cfg, float guidance,
                             float* latents, const float* step_noise, int noise_steps, void* stream) {
     return sched_run_any("ladi_op_sched_run_noise", kind, steps, ac_host, eps_seq, evals, B, hw, cfg, guidance, latents, step_noise, noise_steps,
-                         stream);
+                         0.f, stream);
+}
+int ladi_op_sched_run_noise_eta(int kind, int steps, const float* ac_host, float eta, const void* eps_seq, int evals, int B, int hw, int cfg,
+                                float guidance, float* latents, const float* step_noise, int noise_steps, void* stream) {
+    return sched_run_any("ladi_op_sched_run_noise_eta", kind, steps, ac_host, eps_seq, evals, B, hw, cfg, guidance, latents, step_noise,
+                         noise_steps, eta, stream);
 }
 
 }  // extern "C"

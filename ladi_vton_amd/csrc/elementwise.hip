@@ -170,7 +170,7 @@ __device__ __forceinline__ void sched_step_body(const StepArgs& a, const int idx
     xn.x = T.c_x * x.x + T.c_e * ec[0]; xn.y = T.c_x * x.y + T.c_e * ec[1];
     xn.z = T.c_x * x.z + T.c_e * ec[2]; xn.w = T.c_x * x.w + T.c_e * ec[3];
     if (T.c_n != 0.f && a.step_noise) {
-        // Euler-ancestral: + sigma_up * noise[step], noise NCHW like posterior_sample_kernel's
+        // the stochastic term, + c_n * noise[step] (Euler-ancestral sigma_up, DDIM-eta std), noise NCHW like posterior_sample_kernel's
         const int p = idx - b * a.hw;
         const float* nz = a.step_noise + ((size_t)step * total + (size_t)b * a.hw) * 4 + p;
         xn.x += T.c_n * nz[0]; xn.y += T.c_n * nz[a.hw];
@@ -352,6 +352,22 @@ __global__ void lat_pix_to_nchw_kernel(const float* __restrict__ src, int B, int
     const int b = idx / hw, p = idx - b * hw;
 #pragma unroll
     for (int c = 0; c < 4; ++c) dst[((size_t)b * 4 + c) * hw + p] = src[(size_t)idx * 4 + c];
+}
+
+// step-callback import: the (possibly edited) NCHW latents back into the loop, and the next evaluation's UNet input refreshed from them exactly
+// as sched_step_body refreshes it (same scale, same fp16 rounding, uncond and cond rows), so an untouched round trip changes no bit
+__global__ __launch_bounds__(256) void latents_import_kernel(const float* __restrict__ src, int B, int hw, float* __restrict__ latents,
+                                                             h16* __restrict__ unet_in, int ld_in, int cfg, float is) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int total = B * hw;
+    if (idx >= total) return;
+    const int b = idx / hw, p = idx - b * hw;
+    const float* s = src + (size_t)b * 4 * hw + p;
+    const float4 x = make_float4(s[0], s[hw], s[2 * (size_t)hw], s[3 * (size_t)hw]);
+    reinterpret_cast<float4*>(latents)[idx] = x;
+    h16x4 o; o[0] = (h16)(x.x * is); o[1] = (h16)(x.y * is); o[2] = (h16)(x.z * is); o[3] = (h16)(x.w * is);
+    *reinterpret_cast<h16x4*>(unet_in + (size_t)idx * ld_in) = o;
+    if (cfg) *reinterpret_cast<h16x4*>(unet_in + ((size_t)idx + total) * ld_in) = o;
 }
 
 inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -11; }
@@ -700,6 +716,11 @@ int ladi_launch_lat_nchw_to_pix(const float* src, int B, int hw, float scale, fl
 }
 int ladi_launch_lat_pix_to_nchw(const float* src, int B, int hw, float* dst, hipStream_t st) {
     hipLaunchKernelGGL(lat_pix_to_nchw_kernel, dim3((B * hw + 255) / 256), dim3(256), 0, st, src, B, hw, dst);
+    return ok();
+}
+int ladi_launch_latents_import(const float* src, int B, int hw, float* latents, h16* unet_in, int ld_in, int cfg, float in_scale, hipStream_t st) {
+    if (ld_in < 4 || ld_in % 4) return -1;      // 8-byte stores of channels 0-3 of every row
+    hipLaunchKernelGGL(latents_import_kernel, dim3((B * hw + 255) / 256), dim3(256), 0, st, src, B, hw, latents, unet_in, ld_in, cfg, in_scale);
     return ok();
 }
 

@@ -138,7 +138,7 @@ struct StepTable {            // one entry per scheduler evaluation, device resi
     float in_scale_next;      // scheduler.scale_model_input of the NEXT evaluation: the UNet sees latents * in_scale_next (1 for DDIM / PNDM,
                               // 1 / sqrt(sigma^2 + 1) for LMS); the fp32 latents themselves stay unscaled
     float p_x, p_e;           // mode 2: data prediction m = p_x * sample + p_e * eps (1 / alpha_s, -sigma_s / alpha_s)
-    float c_n;                // multiplies this evaluation's step noise (Euler-ancestral sigma_up; 0 = no noise term)
+    float c_n;                // multiplies this evaluation's step noise (Euler-ancestral sigma_up, DDIM-eta std; 0 = no noise term)
 };
 struct StepArgs {
     const h16* eps; int ld_eps;     // UNet output NHWC [2B or B][hw][ld_eps], channels 0..3 valid
@@ -153,7 +153,7 @@ struct StepArgs {
     // optional per-evaluation trace (parity tests): guided noise prediction and updated latents of evaluation i are written to
     // trace_*[i][B][hw][4] (fp32) for i < trace_cap; null = off
     float* trace_eps; float* trace_lat; int trace_cap;
-    // per-evaluation noise (Euler-ancestral): fp32 NCHW [evals][B][4][hw], indexed by the device step counter; read only where the
+    // per-evaluation noise (Euler-ancestral, DDIM with eta > 0): fp32 NCHW [evals][B][4][hw], indexed by the device step counter; read only where the
     // table's c_n != 0 (null = none)
     const float* step_noise;
 };
@@ -211,6 +211,9 @@ int ladi_launch_gather_rows(const h16* src, const int* rows, int n, int H, h16* 
 int ladi_launch_post_quant(const float* lat, const float* pq, float inv_sf, int n, h16* dst, int ld, hipStream_t st);
 int ladi_launch_lat_nchw_to_pix(const float* src, int B, int hw, float scale, float* dst, hipStream_t st);
 int ladi_launch_lat_pix_to_nchw(const float* src, int B, int hw, float* dst, hipStream_t st);
+// step-callback import: fp32 NCHW [B][4][hw] src -> the loop's latents [B][hw][4], and the latent channels 0-3 of the next UNet input
+// (rows [B] or, with cfg, [2B], ld_in halves per row) rewritten as fp16(x * in_scale) -- what sched_step_kernel wrote from the unedited x
+int ladi_launch_latents_import(const float* src, int B, int hw, float* latents, h16* unet_in, int ld_in, int cfg, float in_scale, hipStream_t st);
 
 // ---- f32path.hip: fp32 kernels of the warping module (fp32 NHWC activations, fp32 weights, v_mfma_f32_32x32x2_f32)
 struct ConvF32Args {

@@ -365,6 +365,7 @@ struct TryOnInputs {
     int steps; float guidance; int scheduler; int cloth_zero_from; int no_pose; int use_graph;
     const float* alphas_cumprod;  // optional [1000] host
 };
+enum { TRYON_CALLBACK_ABORT = -8 };   // TryOn::run: the step callback returned non-zero (LADI_TRYON_CALLBACK_ABORTED, include/ladi_native.h)
 struct TryOn {
     UNet* unet = nullptr; VAE* vae = nullptr; EMASC* emasc = nullptr;
     Arena arena; float* stats = nullptr; size_t stats_cap = 0;
@@ -376,10 +377,14 @@ struct TryOn {
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool ev_valid = false;
     int last_evals = 0;
     float* trace_eps = nullptr; float* trace_lat = nullptr; int trace_cap = 0;   // caller-owned per-evaluation trace buffers (tests)
-    // Euler-ancestral step noise: the caller's fp32 [steps][B][4][h][w] (ladi_tryon_set_step_noise), copied by run() into the
+    // step noise (Euler-ancestral, DDIM with eta > 0): the caller's fp32 [steps][B][4][h][w] (ladi_tryon_set_step_noise), copied by run() into the
     // runtime-owned step_noise_buf that the captured graph reads
     const float* step_noise_src = nullptr; int step_noise_steps = 0;
     float* step_noise_buf = nullptr; size_t step_noise_cap = 0;
+    float eta = 0.f;   // DDIM's eta (ladi_tryon_set_eta), sticky; other kinds refuse a non-zero one
+    // step callback (ladi_tryon_set_step_callback): after evaluation i with i % cb_every == 0 the latents go to the caller's fp32 NCHW
+    // cb_latents, cb_fn(cb_user, i) runs on the host, and cb_latents comes back (edits included); fn == null = off
+    int (*cb_fn)(void*, int) = nullptr; void* cb_user = nullptr; int cb_every = 1; float* cb_latents = nullptr;
     // the legacy NULL stream (torch's default) cannot be captured: work then runs on this internal stream, fenced
     // against the caller's stream with events on entry and exit
     hipStream_t own_stream = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr;
@@ -407,8 +412,10 @@ struct SchedInfo {
     std::vector<float> lms_coeffs;   // LMS only: [steps][4], c_ij over [d_i, d_{i-1}, d_{i-2}, d_{i-3}]
 };
 // cloth_zero_from: first evaluation index that must see zero cloth latents (tryon_pipe.py:718), computed by the caller in float64;
-// code: the scheduler code above
+// code: the scheduler code above; eta: DDIMScheduler.step's eta (DDIM only, >= 0; > 0 puts the stochastic term into c_n)
 void build_step_table(int code, int steps, const float* alphas_cumprod, int cloth_zero_from, std::vector<double>& timesteps,
-                      std::vector<StepTable>& table, SchedInfo* info = nullptr);
+                      std::vector<StepTable>& table, SchedInfo* info = nullptr, double eta = 0.0);
+// true if the table has a stochastic term (some c_n != 0: Euler-ancestral, DDIM with eta > 0), i.e. a run of it needs step noise
+bool table_needs_step_noise(const std::vector<StepTable>& table);
 
 }  // namespace ladi

@@ -418,11 +418,14 @@ static std::vector<int> dpm_timesteps(int steps) {
 }
 
 void build_step_table(int code, int steps, const float* ac, int cloth_zero_from, std::vector<double>& timesteps,
-                      std::vector<StepTable>& table, SchedInfo* info) {
+                      std::vector<StepTable>& table, SchedInfo* info, double eta) {
     const int T = 1000;
     if (steps < 2 || steps > T) throw std::runtime_error("num_inference_steps out of range [2, 1000]");   // ts[steps - 2] below
     const SchedCode sc = decode_sched_code(code);
     const int kind = sc.kind;
+    if (!(eta >= 0.0) || !std::isfinite(eta)) throw std::runtime_error("eta must be finite and >= 0, got " + std::to_string(eta));
+    // only DDIMScheduler.step takes eta; the other schedulers ignore it, and a table that silently did the same would diverge from the caller's intent
+    if (eta != 0.0 && kind != SCHED_DDIM) throw std::runtime_error("eta > 0 is DDIM only (scheduler kind " + std::to_string(kind) + ")");
     const int ratio = T / steps;
     const double final_ac = ac[0];  // set_alpha_to_one = False
     timesteps.clear(); table.clear();
@@ -527,7 +530,14 @@ void build_step_table(int code, int steps, const float* ac, int cloth_zero_from,
             const double a_t = ac[t], a_p = tp >= 0 ? (double)ac[tp] : final_ac;
             StepTable e; std::memset(&e, 0, sizeof(e));
             e.c_x = (float)std::sqrt(a_p / a_t);
-            e.c_e = (float)(std::sqrt(1.0 - a_p) - std::sqrt(a_p) * std::sqrt(1.0 - a_t) / std::sqrt(a_t));
+            if (eta == 0.0) e.c_e = (float)(std::sqrt(1.0 - a_p) - std::sqrt(a_p) * std::sqrt(1.0 - a_t) / std::sqrt(a_t));
+            else {
+                // diffusers 0.14 DDIMScheduler.step with eta: std = eta sqrt((1 - a_p) / (1 - a_t) (1 - a_t / a_p)), the eps direction
+                // sqrt(1 - a_p - std^2), and + std * variance_noise (the step noise)
+                const double std_ = eta * std::sqrt(std::max((1.0 - a_p) / (1.0 - a_t) * (1.0 - a_t / a_p), 0.0));
+                e.c_e = (float)(std::sqrt(std::max(1.0 - a_p - std_ * std_, 0.0)) - std::sqrt(a_p) * std::sqrt(1.0 - a_t) / std::sqrt(a_t));
+                e.c_n = (float)std_;
+            }
             e.w[0] = 1.f;
             table.push_back(e);
         }
@@ -575,6 +585,12 @@ void build_step_table(int code, int steps, const float* ac, int cloth_zero_from,
     // START of evaluation i -> mark entry i-1 so that the step kernel zeroes the cloth channels for evaluation i.
     for (int i = 1; i < (int)table.size(); ++i)
         if (i >= cloth_zero_from) table[i - 1].zero_cloth_next = 1;
+}
+
+bool table_needs_step_noise(const std::vector<StepTable>& table) {
+    for (const StepTable& e : table)
+        if (e.c_n != 0.f) return true;
+    return false;
 }
 
 }  // namespace ladi

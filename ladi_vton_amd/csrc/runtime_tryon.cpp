@@ -72,7 +72,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
     std::vector<float> ac;
     if (in.alphas_cumprod) ac.assign(in.alphas_cumprod, in.alphas_cumprod + 1000); else default_alphas_cumprod(ac);
     std::vector<double> timesteps; std::vector<StepTable> table; SchedInfo sinfo;
-    build_step_table(in.scheduler, in.steps, ac.data(), in.cloth_zero_from, timesteps, table, &sinfo);
+    build_step_table(in.scheduler, in.steps, ac.data(), in.cloth_zero_from, timesteps, table, &sinfo, eta);
     const int evals = (int)timesteps.size();
     const bool cloth_zero_from_start = has_cloth && in.cloth_zero_from <= 0;
     last_evals = evals;
@@ -81,14 +81,15 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
     if (!sk_cnt) { sk_cnt = reinterpret_cast<int*>(pool.alloc(1024 * sizeof(int))); HIP_OK(hipMemset(sk_cnt, 0, 1024 * sizeof(int))); }
     if (evals > table_cap) { d_table = reinterpret_cast<StepTable*>(pool.alloc((size_t)evals * sizeof(StepTable))); table_cap = evals; }
     if (!ev[0]) for (auto& e : ev) HIP_OK(hipEventCreate(&e));
-    // Euler-ancestral: the caller's per-step noise is copied into a runtime-owned buffer (below, on the run's stream) so that the pointer the
-    // captured graph holds stays valid after the caller frees theirs
-    const bool use_step_noise = decode_sched_code(in.scheduler).kind == SCHED_EULER_A;
+    // a table with a stochastic term (Euler-ancestral, DDIM with eta > 0): the caller's per-step noise is copied into a runtime-owned buffer
+    // (below, on the run's stream) so that the pointer the captured graph holds stays valid after the caller frees theirs
+    const bool use_step_noise = table_needs_step_noise(table);
     const size_t step_noise_bytes = use_step_noise ? (size_t)evals * B * 4 * hw * sizeof(float) : 0;
+    const char* noisy = decode_sched_code(in.scheduler).kind == SCHED_EULER_A ? "EulerAncestralDiscrete" : "DDIM with eta > 0";
     if (use_step_noise) {
-        if (!step_noise_src) { set_error("tryon: EulerAncestralDiscrete needs per-step noise (ladi_tryon_set_step_noise)"); return -7; }
+        if (!step_noise_src) { set_error(std::string("tryon: ") + noisy + " needs per-step noise (ladi_tryon_set_step_noise)"); return -7; }
         if (step_noise_steps < evals) {
-            set_error("tryon: EulerAncestralDiscrete needs " + std::to_string(evals) + " steps of noise, ladi_tryon_set_step_noise gave " +
+            set_error(std::string("tryon: ") + noisy + " needs " + std::to_string(evals) + " steps of noise, ladi_tryon_set_step_noise gave " +
                       std::to_string(step_noise_steps));
             return -7;
         }
@@ -204,10 +205,26 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 lanes.forward(*unet, st, c.dry(), concurrent, unet_in, eps, unet->temb_table, d_step);
                 if (!c.dry()) { sa.eps = eps.p; sa.ld_eps = eps.ld; c.check(ladi_launch_sched_step(sa, st), "sched_step"); }
             };
+            // step callback after evaluation i (between launches, never inside a capture): latents out to the caller's NCHW buffer, the host
+            // call, the buffer back into the loop and the next UNet input.  Work the callback queued on the caller's stream comes first.
+            // A non-zero return of the callback lands in cb_rc and ends the loop (the run is then aborted).  No callback set: nothing is
+            // launched and nothing waits.
+            int cb_rc = 0, cb_eval = -1;
+            auto callback_point = [&](int i) {
+                if (!cb_fn || i % cb_every) return;
+                c.check(ladi_launch_lat_pix_to_nchw(latents, B, hw, cb_latents, st), "callback export");
+                HIP_OK(hipStreamSynchronize(st));
+                cb_eval = i;
+                if ((cb_rc = cb_fn(cb_user, i)) != 0) return;
+                HIP_OK(hipEventRecord(ev_in, user_st));
+                HIP_OK(hipStreamWaitEvent(st, ev_in, 0));
+                c.check(ladi_launch_latents_import(cb_latents, B, hw, latents, unet_in.p, 64, cfgf, table[i].in_scale_next, st), "callback import");
+            };
             if (c.dry()) one_step(false);
-            else if (!in.use_graph || evals < 3) { for (int i = 0; i < evals; ++i) one_step(i > 0); }
+            else if (!in.use_graph || evals < 3) { for (int i = 0; i < evals && !cb_rc; ++i) { one_step(i > 0); callback_point(i); } }
             else {
                 one_step(false);  // eager first evaluation, lanes one after the other (one-time function attribute setup, per-shape tile measurement)
+                callback_point(0);
                 unsigned long long key = 0x1234;
                 key = mix(key, (unsigned long long)(uintptr_t)arena.base); key = mix(key, (unsigned long long)B * 1000003ULL + H * 4099ULL + W);
                 key = mix(key, (unsigned long long)cfgf); key = mix(key, (unsigned long long)L);
@@ -219,7 +236,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 key = mix(key, (unsigned long long)trace_cap);
                 key = mix(key, (unsigned long long)(uintptr_t)sa.step_noise);
                 key = mix(key, lanes.key());
-                if (!gexec || key != graph_key) {
+                if (!cb_rc && (!gexec || key != graph_key)) {
                     if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
                     if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
                     HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
@@ -228,9 +245,18 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                     HIP_OK(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
                     graph_key = key;
                 }
-                for (int i = 1; i < evals; ++i) HIP_OK(hipGraphLaunch(gexec, st));
+                for (int i = 1; i < evals && !cb_rc; ++i) { HIP_OK(hipGraphLaunch(gexec, st)); callback_point(i); }
             }
             arena.release(mk_loop);
+            if (cb_rc) {
+                // the handle stays usable: the next run re-arms the step counter and the arrival ticket (hipMemsetAsync above)
+                set_error("tryon: the step callback returned " + std::to_string(cb_rc) + " after evaluation " + std::to_string(cb_eval) +
+                          ": run aborted");
+                ev_valid = false;
+                HIP_OK(hipEventRecord(ev_out, st));
+                HIP_OK(hipStreamWaitEvent(user_st, ev_out, 0));
+                return TRYON_CALLBACK_ABORT;
+            }
             if (!c.dry()) HIP_OK(hipEventRecord(ev[2], st));
             // ---------------- 11. decode (tryon_pipe.py:349-359)
             {

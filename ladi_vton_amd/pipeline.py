@@ -165,19 +165,24 @@ class StableDiffusionTryOnePipeline:
         else:
             n_cloth, n_lat, n_mask = [t.to(device=device, dtype=torch.float32).contiguous() if t is not None else None for t in noise]
         native = isinstance(self.unet, NativeUNet) and isinstance(self.vae, NativeVAE) and (self.emasc is None or isinstance(self.emasc, NativeEMASC))
-        can_fuse = (fused and native and callback is None and isinstance(self.scheduler, FUSED_SCHEDULERS) and eta == 0.0
+        # only DDIMScheduler.step takes eta (the modular path passes it to no other scheduler); a negative one stays on the modular path
+        ddim_eta = float(eta) if isinstance(self.scheduler, DDIMScheduler) else 0.0
+        can_fuse = (fused and native and isinstance(self.scheduler, FUSED_SCHEDULERS) and ddim_eta >= 0.0
                     and (not self.emasc or list(self.emasc_int_layers or []) == [1, 2, 3, 4, 5]))
         if can_fuse:
-            # Euler / Euler-ancestral step() draw one batch-shaped fp32 noise tensor per step after the three draws above: the fused path
-            # makes the same draws up front, in the same generator order (Euler's are unused, as in diffusers without churn)
+            # Euler / Euler-ancestral / DDIM with eta > 0 step() draw one batch-shaped fp32 noise tensor per step after the three draws above:
+            # the fused path makes the same draws up front, in the same generator order (Euler's are unused, as in diffusers without churn)
             step_noise = None
-            if isinstance(self.scheduler, (EulerDiscreteScheduler, EulerAncestralDiscreteScheduler)):
+            if isinstance(self.scheduler, (EulerDiscreteScheduler, EulerAncestralDiscreteScheduler)) or ddim_eta > 0.0:
                 draws = [self._draw((B, 4, h, w), generator, torch.float32, device) for _ in range(int(num_inference_steps))]
-                if isinstance(self.scheduler, EulerAncestralDiscreteScheduler):
+                if not isinstance(self.scheduler, EulerDiscreteScheduler):
                     step_noise = torch.stack(draws).contiguous()
+            if callback is not None:
+                self.scheduler.set_timesteps(num_inference_steps, device=device)    # the callback's t, as on the modular path
             images = self._run_fused(image, mask_image, pose_map, warped_cloth if cloth_input_type == "warped" else None, pe, neg,
                                      n_cloth, n_lat, n_mask, height, width, num_inference_steps, guidance_scale, cloth_cond_rate,
-                                     no_pose, use_graph, step_noise=step_noise)
+                                     no_pose, use_graph, step_noise=step_noise, eta=ddim_eta, callback=callback,
+                                     callback_steps=callback_steps)
             # prepare_mask_and_masked_image binarises the caller's mask in place; keep that side effect
             mask_image[mask_image < 0.5] = 0
             mask_image[mask_image >= 0.5] = 1
@@ -193,10 +198,15 @@ class StableDiffusionTryOnePipeline:
 
     # -------------------------------------------------------------------------------------------------------
     def _run_fused(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose,
-                   use_graph, return_device=False, out_uint8=False, lanes=None, step_noise=None):
+                   use_graph, return_device=False, out_uint8=False, lanes=None, step_noise=None, eta=0.0, callback=None, callback_steps=1):
         """return_device: hand back the device tensor (no host copy); out_uint8: the batch as uint8 [B,H,W,3] = numpy_to_pil's
         (images * 255).round() computed by the decode epilogue (ladi_tryon_run_u8); lanes: sample-group lanes of the UNet forward;
-        step_noise: fp32 [steps, B, 4, h, w], the per-step noise of EulerAncestralDiscreteScheduler (ladi_tryon_set_step_noise)"""
+        step_noise: fp32 [steps, B, 4, h, w], the per-step noise of EulerAncestralDiscreteScheduler and of DDIM with eta > 0
+        (ladi_tryon_set_step_noise); eta: DDIM's eta (ladi_tryon_set_eta, DDIM only);
+        callback / callback_steps: called as callback(i, self.scheduler.timesteps[i], latents) after every evaluation i with
+        i % callback_steps == 0, latents an fp32 [B, 4, h, w] device tensor whose in-place edits the loop takes over
+        (ladi_tryon_set_step_callback).  An exception in the callback aborts the run and is re-raised here.  When the decode's fp16-range
+        guard re-runs the batch (below), the whole loop runs again and the callback sees every step a second time."""
         lib = _lib.load()
         if self._tryon is None:
             self._tryon = lib.ladi_tryon_create(self.unet.h, self.vae.h, self.emasc.h if self.emasc else None)
@@ -254,27 +264,54 @@ class StableDiffusionTryOnePipeline:
             check(lib.ladi_tryon_set_step_noise(self._tryon, ptr(step_noise), step_noise.shape[0]), "ladi_tryon_set_step_noise")
         else:
             check(lib.ladi_tryon_set_step_noise(self._tryon, None, 0), "ladi_tryon_set_step_noise")
+        check(lib.ladi_tryon_set_eta(self._tryon, float(eta)), "ladi_tryon_set_eta")
+        cb_error = []
+        cb_latents = trampoline = None
+        if callback is not None:
+            cb_latents = torch.empty((B, 4, h8, w8), dtype=torch.float32, device=dev)
+            timesteps = self.scheduler.timesteps
+
+            def _step(_user, i):
+                try:
+                    callback(i, timesteps[i], cb_latents)
+                    return 0
+                except BaseException as e:     # noqa: B902  (re-raised after the native call returns)
+                    cb_error.append(e)
+                    return 1
+            trampoline = _lib.STEP_CALLBACK(_step)     # referenced until the callback is switched off below
+            check(lib.ladi_tryon_set_step_callback(self._tryon, trampoline, None, int(callback_steps), ptr(cb_latents)),
+                  "ladi_tryon_set_step_callback")
         # the fused loop rewrites the UNet's cross-attention K/V cache behind the shim's back
         self.unet._ctx_key = None
         if lanes is not None or self.lanes is not None:
             check(lib.ladi_tryon_set_lanes(self._tryon, int(lanes if lanes is not None else self.lanes)), "ladi_tryon_set_lanes")
-        run = lib.ladi_tryon_run_u8 if out_uint8 else lib.ladi_tryon_run
-        check(run(self._tryon, ctypes.byref(inp), ptr(images), ptr(self.last_latents), stream_ptr()), "ladi_tryon_run")
-        if not return_device:
-            # results go to the host: this is the synchronisation point anyway, so the decode's fp16-range guard is asked now (a run decodes
-            # once and queues its flag; no host round trip inside the run).  An overflow raised the automatic range shift: run the batch again.
-            # With return_device the flag is examined by the next call instead (or by check_overflow()), which fails loudly rather than hand out
-            # a bad batch silently.
-            for _ in range(2):
-                po = lib.ladi_tryon_poll_overflow(self._tryon)
-                if po == 0:
-                    break
-                if po < 0:
-                    raise _lib.NativeError("ladi_tryon_poll_overflow: " + _lib.last_error())
-                check(run(self._tryon, ctypes.byref(inp), ptr(images), ptr(self.last_latents), stream_ptr()), "ladi_tryon_run (re-run at a larger range shift)")
-            else:
-                if lib.ladi_tryon_poll_overflow(self._tryon) != 0:
-                    raise _lib.NativeError("VAE decode: activations exceed the fp16 range even at range shift 8")
+        native_run = lib.ladi_tryon_run_u8 if out_uint8 else lib.ladi_tryon_run
+
+        def run(what):
+            rc = native_run(self._tryon, ctypes.byref(inp), ptr(images), ptr(self.last_latents), stream_ptr())
+            if cb_error:
+                raise cb_error[0]
+            check(rc, what)
+        try:
+            run("ladi_tryon_run")
+            if not return_device:
+                # results go to the host: this is the synchronisation point anyway, so the decode's fp16-range guard is asked now (a run
+                # decodes once and queues its flag; no host round trip inside the run).  An overflow raised the automatic range shift: run the
+                # batch again (a step callback then sees every step a second time).  With return_device the flag is examined by the next call
+                # instead (or by check_overflow()), which fails loudly rather than hand out a bad batch silently.
+                for _ in range(2):
+                    po = lib.ladi_tryon_poll_overflow(self._tryon)
+                    if po == 0:
+                        break
+                    if po < 0:
+                        raise _lib.NativeError("ladi_tryon_poll_overflow: " + _lib.last_error())
+                    run("ladi_tryon_run (re-run at a larger range shift)")
+                else:
+                    if lib.ladi_tryon_poll_overflow(self._tryon) != 0:
+                        raise _lib.NativeError("VAE decode: activations exceed the fp16 range even at range shift 8")
+        finally:
+            if trampoline is not None:
+                check(lib.ladi_tryon_set_step_callback(self._tryon, _lib.NO_STEP_CALLBACK, None, 1, None), "ladi_tryon_set_step_callback")
         if tr is not None:   # [evals, B, 4, h, w] like the reference's noise_pred / latents (tryon_pipe.py:732-740)
             nchw = tr.view(2, self.trace_evals, B, h8, w8, 4).permute(0, 1, 2, 5, 3, 4)
             self.last_trace = dict(noise_pred=nchw[0].contiguous(), latents=nchw[1].contiguous())
