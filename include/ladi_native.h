@@ -59,7 +59,10 @@ ladi_unet* ladi_unet_create(const ladi_unet_config* cfg, const ladi_weights* ws)
 void ladi_unet_destroy(ladi_unet* u);
 /* encoder_hidden_states [n, L, cross_attention_dim] fp16 dense; precomputes the cross-attention K/V of all blocks */
 int ladi_unet_set_context(ladi_unet* u, const void* ehs_dev, int n, int L, void* stream);
-/* sample [n, in_channels, h, w] NCHW (dtype), scalar timestep, out [n, out_channels, h, w] NCHW (out_dtype) */
+/* sample [n, in_channels, h, w] NCHW (dtype), scalar timestep, out [n, out_channels, h, w] NCHW (out_dtype).
+ * Size contract: any h, w (images of any side divisible by 8; the tests run latents from 3x3 to 128x96).  As diffusers' UNet2DConditionModel: the stride-2 downsamplers give
+ * ceil(side / 2), and when h or w is not a multiple of 8 every upsampler stretches to the size of the skip it is concatenated with
+ * (`forward_upsample_size`, nearest as F.interpolate(size=...)); multiples of 8 double at every level, as before. */
 int ladi_unet_forward(ladi_unet* u, const void* sample_dev, int dtype, int n, int h, int w, float timestep, void* out_dev,
                       int out_dtype, void* stream);
 
@@ -266,7 +269,8 @@ typedef struct ladi_tryon ladi_tryon;
 /* emasc may be NULL (pipeline without EMASC); handles stay owned by the caller */
 ladi_tryon* ladi_tryon_create(ladi_unet* unet, ladi_vae* vae, ladi_emasc* emasc);
 void ladi_tryon_destroy(ladi_tryon* t);
-/* images_dev: fp32 [B,H,W,3] in [0,1] (decode_latents layout, tryon_pipe.py:356-358); latents_dev: optional fp32 [B,4,h,w] */
+/* images_dev: fp32 [B,H,W,3] in [0,1] (decode_latents layout, tryon_pipe.py:356-358); latents_dev: optional fp32 [B,4,h,w].
+ * H and W: any multiple of 8 (ladi_unet_forward's size contract for the latent h = H / 8, w = W / 8). */
 int ladi_tryon_run(ladi_tryon* t, const ladi_tryon_inputs* in, float* images_dev, float* latents_dev, void* stream);
 /* the same call with the batch in the dtype numpy_to_pil produces (tryon_pipe.py:357-360): uint8 [B,H,W,3] = round(image * 255),
  * round-half-to-even like numpy -- what the RCCL all-gather of the sharded path and the JPEG encoder consume */
@@ -338,6 +342,10 @@ const char* ladi_igemm_cfg_symbol_name(int cfg);
  * Op-level entry points (kernel parity tests; NHWC fp16 device tensors)
  * ------------------------------------------------------------------------------------------------------------- */
 typedef struct {
+    /* ups = 1: nearest upsample folded into the gather, stride 1 only.  The Hs x Ws source is stretched to the logical
+     * (Ho + ksize - 1 - 2 pad) x (Wo + ksize - 1 - 2 pad) image -- Ho x Wo for a 3x3 pad-1 conv.  Twice the source is nearest-2x (the
+     * meaning of every descriptor with Ho == 2 Hs); any other size maps output index d to min(floor(d * (in / out)), in - 1) in fp32, as
+     * F.interpolate(size=..., mode="nearest").  Only the generic tile forms take non-2x sizes; the halo forms refuse them. */
     const void* src0; const void* src1; int C0, C1, ld0, ld1, Hs, Ws, Ho, Wo, P, ksize, stride, pad, ups;
     const void* W; int Q, K, ldw; long long bs_src0, bs_w, bs_out, bs_res;
     const void* bias; int bias_per_pixel; const float* rowadd; const int* rowadd_idx; int rowadd_stride; int act; float out_scale;
@@ -374,7 +382,7 @@ int ladi_op_attention_generic(const void* q, const void* k, const void* v, void*
                               long long sk, long long sv, long long so, int n, int heads, int head_dim, int Nq, int Nk, float scale,
                               void* stream);
 /* ONE wide head (head_dim 128 / 256 / 512) — the VAE mid-block AttentionBlock (diffusers 0.14; src/models/vae.py:66-75 builds it through
- * UNetMidBlock2D): flash-style, scores never materialised.  q, k: [n][N][ld]; vt = V TRANSPOSED [n][head_dim][ldvt >= Nk]; Nk % 4 == 0 */
+ * UNetMidBlock2D): flash-style, scores never materialised.  q, k: [n][N][ld]; vt = V TRANSPOSED [n][head_dim][ldvt >= Nk]; ldvt % 4 == 0, any Nk */
 int ladi_op_attention_wide(const void* q, const void* k, const void* vt, void* o, int ldq, int ldk, int ldvt, int ldo, long long sq,
                            long long sk, long long svt, long long so, int n, int head_dim, int Nq, int Nk, float scale, void* stream);
 /* glue between the TPS network and the refinement UNet (src/inference.py:242-260), NCHW planes, dtype 0 fp32 / 1 fp16 in and out:

@@ -535,7 +535,13 @@ __global__ __launch_bounds__(256) void flash_attn_wide_kernel(const AttnArgs a) 
                 const h16* vrow = vt + (size_t)(d * 32 + l31) * a.ldv + kofs;
                 h16x4 lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
                 if (kofs + 3 < a.Nk) lo = *reinterpret_cast<const h16x4*>(vrow);
+                else                                   // the last, partial 4-key segment of a ragged Nk: element by element
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) if (kofs + e < a.Nk) lo[e] = vrow[e];
                 if (kofs + 11 < a.Nk) hi = *reinterpret_cast<const h16x4*>(vrow + 8);
+                else
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) if (kofs + 8 + e < a.Nk) hi[e] = vrow[8 + e];
                 h16x8 vf;
                 vf[0] = lo[0]; vf[1] = lo[1]; vf[2] = lo[2]; vf[3] = lo[3];
                 vf[4] = hi[0]; vf[5] = hi[1]; vf[6] = hi[2]; vf[7] = hi[3];
@@ -641,8 +647,8 @@ int ladi_launch_attn_generic(const AttnArgs& a, int head_dim, hipStream_t st) {
 }
 
 int ladi_launch_attn_wide(const AttnArgs& a, int head_dim, hipStream_t st) {
-    // Nk % 4 == 0 keeps the 8-byte V^T row segments whole (masked per segment); heads == 1
-    if ((a.ldq & 7) || (a.ldk & 7) || (a.ldv & 3) || (a.ldo & 3) || a.Nk <= 0 || (a.Nk & 3) || a.Nq <= 0 || a.heads != 1 || a.causal) return -1;
+    // ldv % 4 == 0 keeps the 8-byte V^T row segments aligned; any Nk (a ragged last segment is read element by element); heads == 1
+    if ((a.ldq & 7) || (a.ldk & 7) || (a.ldv & 3) || (a.ldo & 3) || a.Nk <= 0 || a.Nq <= 0 || a.heads != 1 || a.causal) return -1;
     dim3 grid((unsigned)((a.Nq + 31) / 32), (unsigned)a.n);
     switch (head_dim) {
         case 128: hipLaunchKernelGGL(flash_attn_wide_kernel<128>, grid, dim3(256), 0, st, a); break;

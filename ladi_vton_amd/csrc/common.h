@@ -109,7 +109,9 @@ struct IGemmArgs {
     int ksize;           // 1 or 3
     int stride;          // 1 or 2
     int pad;             // leading pad (top/left); trailing pad is implied by bounds check
-    int ups;             // 1: nearest-2x upsample folded into the gather (source is Hs x Ws, logical 2Hs x 2Ws)
+    int ups;             // 1: nearest upsample folded into the gather (stride 1 only): the Hs x Ws source is stretched to the logical
+                         // Lh x Lw = (Ho + ksize - 1 - 2 pad) x (Wo + ...), i.e. Ho x Wo for a 3x3 pad-1 conv -- 2Hs x 2Ws is nearest-2x,
+                         // any other size maps like F.interpolate(size=(Lh, Lw), mode="nearest") (diffusers' `upsample_size`)
     // "weight" operand: [Q][K] fp16 row-major, K = ksize*ksize*(C0+C1), tap-major / channel-minor
     const h16* W;
     int Q;               // output channels (rows of W)

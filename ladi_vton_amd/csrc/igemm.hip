@@ -506,6 +506,7 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
     if (a.K != a.ksize * a.ksize * (a.C0 + a.C1)) return -3;
     if ((a.ld0 % 8) || (a.C1 && (a.ld1 % 8)) || (a.K % 8) || (a.ldw % 8)) return -4;
     if (a.P <= 0 || a.Q <= 0) return -5;
+    if (a.ups && (a.stride != 1 || a.Ho + a.ksize - 1 - 2 * a.pad < 1 || a.Wo + a.ksize - 1 - 2 * a.pad < 1)) return -1;   // folded upsample: stride 1, non-empty logical image
     const bool geglu = a.act == LADI_ACT_GEGLU;
     if (geglu && (a.Q % 64)) return -6;
     // ---- measured tile-shape selection ("measure, don't guess"): the first time a problem shape is seen outside a stream

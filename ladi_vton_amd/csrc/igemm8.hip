@@ -82,8 +82,9 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const IGemmArgs a) {
     const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<h16*>(a.W + (a.splitk > 1 ? 0 : (size_t)z * a.bs_w)), 0, 0x7FFFFFFF, 0x00020000);
 
-    const int Hlog = a.ups ? 2 * a.Hs : a.Hs;
-    const int Wlog = a.ups ? 2 * a.Ws : a.Ws;
+    const int Hlog = a.ups ? a.Ho + a.ksize - 1 - 2 * a.pad : a.Hs;     // folded upsample: logical size from the output (igemm_kernel.h)
+    const int Wlog = a.ups ? a.Wo + a.ksize - 1 - 2 * a.pad : a.Ws;
+    const float ups_sy = (float)a.Hs / (float)Hlog, ups_sx = (float)a.Ws / (float)Wlog;
     int nb[NB], iy0[NB], ix0[NB];          // folded-upsample path only
     unsigned vox0[NB], vox1[NB], vmask[NB];
 #pragma unroll
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const IGemmArgs a) {
             } else {
                 int iy = iy0[i] + tdy, ix = ix0[i] + tdx;
                 const bool ok = st_valid && ((unsigned)iy < (unsigned)Hlog) && ((unsigned)ix < (unsigned)Wlog);
-                iy >>= 1; ix >>= 1;
+                iy = ups_src_idx(iy, a.Hs, Hlog, ups_sy); ix = ups_src_idx(ix, a.Ws, Wlog, ups_sx);
                 const unsigned vo = ok ? (unsigned)(((nb[i] + iy * a.Ws + ix) * ld + csub + clog * 8) * 2) : OOB;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(buf + BQ * BK * 2 + i * 8192 + wave * 1024), 16, vo, 0, 0, 0);
             }

@@ -16,6 +16,13 @@ __device__ __forceinline__ int swz(int row, int chunk) {
     else return row * 32 + ((chunk ^ ((row >> 2) & 3)) << 3);
 }
 
+// Folded nearest upsample (IGemmArgs::ups): source row / column of logical coordinate d (0 <= d < out) when `in` source pixels are
+// stretched to `out`.  PyTorch's rule for F.interpolate(size=out, mode="nearest") (aten nearest_idx): an exact doubling halves, anything
+// else scales in fp32 by in / out and clamps.  `scale` = (float)in / out, computed once by the caller.
+__device__ __forceinline__ int ups_src_idx(int d, int in, int out, float scale) {
+    return out == 2 * in ? d >> 1 : min((int)floorf((float)d * scale), in - 1);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Epilogue shared by the implicit-GEMM kernels.  On entry every wave holds acc[TQ][TP] (32x32 MFMA accumulators) of its
 // (TQ*32 channels) x (TP*32 pixels) sub-tile at channel offset q0 + wq*TQ*32, pixel offset p0 + wp*TP*32; the staging ring is dead

@@ -91,8 +91,11 @@ __global__ __launch_bounds__(64 * WQ * WP, OCC) void igemm_kernel(const IGemmArg
     const int HoWo = a.Ho * a.Wo;
     const int HsWs = a.Hs * a.Ws;
     const int n_first = p0 / HoWo;
-    const int Hlog = a.ups ? 2 * a.Hs : a.Hs;
-    const int Wlog = a.ups ? 2 * a.Ws : a.Ws;
+    // folded upsample: the logical (upsampled) image is the one a stride-1 convolution with this padding maps onto Ho x Wo -- 2Hs x 2Ws for
+    // every descriptor of the nearest-2x form, the skip's size for the size-mapped form of diffusers' `upsample_size`
+    const int Hlog = a.ups ? a.Ho + a.ksize - 1 - 2 * a.pad : a.Hs;
+    const int Wlog = a.ups ? a.Wo + a.ksize - 1 - 2 * a.pad : a.Ws;
+    const float ups_sy = (float)a.Hs / (float)Hlog, ups_sx = (float)a.Ws / (float)Wlog;
     const int ntap = a.ksize * a.ksize;
     const int Ct = a.C0 + a.C1;
     const int ldw = a.ldw ? a.ldw : a.K;
@@ -188,7 +191,7 @@ __global__ __launch_bounds__(64 * WQ * WP, OCC) void igemm_kernel(const IGemmArg
                 if (RQ + j >= i0 && RQ + j < i1) {
                     int iy = iy0[j] + tdy, ix = ix0[j] + tdx;
                     const bool ok = ((unsigned)iy < (unsigned)Hlog) && ((unsigned)ix < (unsigned)Wlog);
-                    iy >>= 1; ix >>= 1;
+                    iy = ups_src_idx(iy, a.Hs, Hlog, ups_sy); ix = ups_src_idx(ix, a.Ws, Wlog, ups_sx);
                     const unsigned vo = ok ? (unsigned)(((nb[j] + iy * a.Ws + ix) * ld + c) * 2) : OOB;
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(sbase + (BQ * BK * 2) + j * (RPP * BK * 2)), 16, vo, 0, 0, 0);
                 }

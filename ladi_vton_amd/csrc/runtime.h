@@ -84,6 +84,8 @@ struct DNorm { h16* g = nullptr; h16* b = nullptr; int c = 0; };
 
 struct ConvOpt {
     int stride = 1, pad = -1 /* -1: k/2 */, ups = 0, act = LADI_ACT_NONE;
+    int pad_end = -1;        // trailing (bottom / right) pad of a strided conv, -1: = pad (the VAE's F.pad(0, 1, 0, 1) downsamplers: 1 with pad 0)
+    int ups_h = 0, ups_w = 0;   // ups: size the source is stretched to (nearest, diffusers' `upsample_size`); 0: twice the source
     const float* rowadd = nullptr; const int* rowadd_idx = nullptr; int rowadd_stride = 0;
     const Act* res0 = nullptr; const Act* res1 = nullptr;
     const h16* mask = nullptr;

@@ -206,10 +206,14 @@ void launch_conv_into(Ctx& c, IGemmArgs& a, Act& out, int cfg) {
 
 Act conv2d(Ctx& c, const DConv& cv, const Act& x, const Act* x2, const ConvOpt& o) {
     const int pad = o.pad >= 0 ? o.pad : cv.k / 2;
-    const int Hlog = o.ups ? 2 * x.h : x.h, Wlog = o.ups ? 2 * x.w : x.w;
-    int Ho, Wo;
-    if (o.stride == 1) { Ho = Hlog; Wo = Wlog; }
-    else { Ho = Hlog / 2; Wo = Wlog / 2; }
+    if (o.ups && (o.stride != 1 || 2 * pad != cv.k - 1)) throw std::runtime_error("conv2d: the folded upsample needs a stride-1 'same' convolution");
+    const int Hlog = o.ups ? (o.ups_h ? o.ups_h : 2 * x.h) : x.h, Wlog = o.ups ? (o.ups_w ? o.ups_w : 2 * x.w) : x.w;
+    // the real output size, (H + pad + pad_end - k) / stride + 1.  For every stride-2 conv of the library's models at latent / image sides
+    // that are multiples of 8 this is H / 2: the UNet's k3 p1 downsamplers, the TPS network's k4 p1 convs and the VAE's k3 pad (0, 1)
+    // downsamplers, which see only even sides then (image side % 8 == 0).  At other latent sides the UNet's downsamplers give ceil(H / 2),
+    // as torch's Conv2d does.
+    const int pad_end = o.pad_end >= 0 ? o.pad_end : pad;
+    const int Ho = (Hlog + pad + pad_end - cv.k) / o.stride + 1, Wo = (Wlog + pad + pad_end - cv.k) / o.stride + 1;
     const int C0 = x.c, C1 = x2 ? x2->c : 0;
     if (C0 + C1 != cv.cin_pad) throw std::runtime_error("conv2d: channel mismatch (" + std::to_string(C0 + C1) + " vs " + std::to_string(cv.cin_pad) + ")");
     const bool geglu = o.act == LADI_ACT_GEGLU;

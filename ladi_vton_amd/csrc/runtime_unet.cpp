@@ -307,6 +307,9 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
     h = f.res(mid_res[0], h, nullptr);
     h = f.xf(mid_xf, h);
     h = f.res(mid_res[1], h, nullptr);
+    // diffusers' `forward_upsample_size`: when a latent side is not a multiple of 2^3 (three upsamplers), the down path rounded a level up
+    // (ceil(H / 2)) and every upsampler stretches to the size of the skip it is concatenated with; else each one doubles
+    const bool ups_to_skip = (x.h % 8) || (x.w % 8);
     ri = 0; xi = 0;
     for (int i = 0; i < 4; ++i) {
         for (int j = 0; j < L + 1; ++j) {
@@ -316,6 +319,7 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
         }
         if (i < 3) {
             ConvOpt ou; ou.ups = 1; ou.stats = true;
+            if (ups_to_skip) { ou.ups_h = skips.back().h; ou.ups_w = skips.back().w; }
             h = conv2d(c, up_samp[i], h, nullptr, ou);
         }
     }

@@ -155,14 +155,15 @@ struct VF {
     // the wide head, scores never leave the chip (flash_attn_wide_kernel); other widths: materialised scores through batched GEMMs.
     Act attn(const VAEAttn& at, const Act& x) {
         const int n = x.n, T = x.h * x.w, C = at.C;
-        const bool flash = (C == 128 || C == 256 || C == 512) && (T % 4 == 0);
+        const bool flash = C == 128 || C == 256 || C == 512;
+        const int ldv = (T + 3) / 4 * 4;                              // V^T row stride: 8-byte aligned rows for the flash kernel (= T when T % 4 == 0)
         Act out = new_act_with_stats(c, x.n, x.h, x.w, C);
         const size_t mk = c.ar->mark();
         Act g = group_norm(c, at.gn, x, nullptr, v.cfg.groups, eps_s(), 0);
         Act tok = g; tok.h = T; tok.w = 1;
         ConvOpt op;
         Act qk = conv2d(c, at.qk, tok, nullptr, op);                 // [n*T][2C]
-        h16* vt = c.alloc_h16((size_t)n * C * T);                    // V^T [n][C][T]
+        h16* vt = c.alloc_h16((size_t)n * C * ldv);                  // V^T [n][C][T], rows ldv apart
         float* S = flash ? nullptr : c.alloc_f32((size_t)n * T * T);
         h16* P = flash ? nullptr : c.alloc_h16((size_t)n * T * T);
         Act o = c.new_act(n, T, 1, C);
@@ -173,13 +174,13 @@ struct VF {
             std::memset(&a, 0, sizeof(a));
             a.src0 = at.v.w; a.C0 = at.v.cin_pad; a.ld0 = at.v.cin_pad; a.Hs = C; a.Ws = 1; a.Ho = C; a.Wo = 1; a.P = C;
             a.ksize = 1; a.stride = 1; a.W = g.p; a.Q = T; a.K = C; a.ldw = g.ld; a.bs_w = (long long)T * g.ld;
-            a.bias = at.v.b; a.bias_per_pixel = 1; a.out_scale = 1.f; a.out = vt; a.ldo = T; a.bs_out = (long long)C * T;
+            a.bias = at.v.b; a.bias_per_pixel = 1; a.out_scale = 1.f; a.out = vt; a.ldo = ldv; a.bs_out = (long long)C * ldv;
             c.check(ladi_launch_igemm(a, n, 0, c.st), "igemm(vT)");
             if (flash) {
                 AttnArgs fa;
                 fa.q = qk.p; fa.k = qk.p + C; fa.v = vt; fa.o = o.p;
-                fa.ldq = 2 * C; fa.ldk = 2 * C; fa.ldv = T; fa.ldo = C;
-                fa.sq = (long long)T * 2 * C; fa.sk = fa.sq; fa.sv = (long long)C * T; fa.so = (long long)T * C;
+                fa.ldq = 2 * C; fa.ldk = 2 * C; fa.ldv = ldv; fa.ldo = C;
+                fa.sq = (long long)T * 2 * C; fa.sk = fa.sq; fa.sv = (long long)C * ldv; fa.so = (long long)T * C;
                 fa.n = n; fa.heads = 1; fa.Nq = T; fa.Nk = T; fa.scale = 1.f / std::sqrt((float)C);
                 c.check(ladi_launch_attn_wide(fa, C, c.st), "attn_wide");
             } else {
@@ -193,7 +194,7 @@ struct VF {
             // O[b] = P[b] V[b]
             std::memset(&a, 0, sizeof(a));
             a.src0 = P; a.C0 = T; a.ld0 = T; a.bs_src0 = (long long)T * T; a.Hs = T; a.Ws = 1; a.Ho = T; a.Wo = 1; a.P = T;
-            a.ksize = 1; a.stride = 1; a.W = vt; a.Q = C; a.K = T; a.ldw = T; a.bs_w = (long long)C * T;
+            a.ksize = 1; a.stride = 1; a.W = vt; a.Q = C; a.K = T; a.ldw = ldv; a.bs_w = (long long)C * ldv;
             a.out_scale = 1.f; a.out = o.p; a.ldo = C; a.bs_out = (long long)T * C;
             c.check(ladi_launch_igemm(a, n, 0, c.st), "igemm(PV)");
             }
@@ -223,7 +224,7 @@ Act VAE::encode(Ctx& c, const Act& x, Act feats[5]) {
         if (i > 0) feats[i + 1] = h;  // input of down block i
         for (int j = 0; j < L; ++j) h = f.res(e_res[ri++], h, nullptr);
         if (i < 3) {
-            ConvOpt od; od.stats = true; od.stride = 2; od.pad = 0;  // F.pad(0,1,0,1) + stride-2 conv, pad 0: trailing zeros via bounds check
+            ConvOpt od; od.stats = true; od.stride = 2; od.pad = 0; od.pad_end = 1;  // F.pad(0,1,0,1) + stride-2 conv, pad 0: trailing zeros via bounds check
             h = conv2d(c, e_down[i], h, nullptr, od);
         }
     }

@@ -137,6 +137,8 @@ class StableDiffusionTryOnePipeline:
                  negative_prompt_embeds=None, generator=None, latents=None, output_type="pil", return_dict=True, callback=None,
                  callback_steps=1, cloth_cond_rate=1.0, no_pose=False, cloth_input_type="warped", fused=True, noise=None,
                  use_graph=True):
+        """tryon_pipe.py's __call__.  `height` / `width`: any multiple of 8, as the reference's check_inputs.  Latent sides that are not
+        multiples of 8 (e.g. 640x480 -> 80x60) run diffusers' `forward_upsample_size` arithmetic on both the fused and the modular path."""
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
