@@ -13,12 +13,19 @@ Synthetic inputs with the datasets' shapes / value ranges and a deterministic ra
 (no weights or datasets are reachable offline).  Global-batch row g depends only on g (per-row generators), rows are sharded
 contiguously over ranks (ladi_vton_amd.parallel.run_sharded), so results do not depend on the world size.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W            the plain run: set up, warm up, time K steps, print the line -- nothing else
+  python bench.py --gpus 1 --steps K --warmup W --full     the same timed steps, then every other leg (see below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
   python bench.py --gpus N ...        (no launcher: bench.py runs the torch.distributed.run line above as a child, one rank per GPU)
 `--gpus N` always means N ranks: fewer visible GPUs than N, or a launcher that started another WORLD_SIZE, is exit code 2 and no line.
 Prints ONE JSON line on rank 0; `ms_per_step` is the wall time of one timed step.
   python bench.py ... --dump-outputs DIR   also writes what the last timed step returned as DIR/images.npy (see dump_outputs)
+
+A plain run does only what `value` / `ms_per_step` need; the keys of the other legs are in its line with the value null.  `--full` adds, AFTER
+the timed steps (which are the same with and without it): the step with the reference's D2H + PIL + JPEG tail (`d2h_pil_tail`), the
+dominant-kernel / roofline leg (`roofline`: stand-alone CFG UNet forwards, shader-clock probe, committed or measured HBM traffic, the vendor
+GEMM calibration) and the fp32 CPU baseline (`cpu_baseline`).  `--no-tail`, `--no-roofline` and `--no-cpu-baseline` drop single legs of a
+`--full` run; `--roofline-only` and `--measure-traffic` are roofline runs of their own and need `--full`.
 """
 import argparse
 import ctypes
@@ -73,9 +80,12 @@ def parse():
     p.add_argument("--height", type=int, default=None)
     p.add_argument("--width", type=int, default=None)
     p.add_argument("--size", default="full", choices=["full", "tiny"])
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every other leg: the D2H + PIL tail, the roofline leg and the CPU baseline (off by "
+                        "default: a plain run sets up, warms up, times the steps and prints the line)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
     p.add_argument("--cpu-runs", type=int, default=3, help="end-to-end runs of config #0 on the host cores, median reported (BASELINE.md §3 protocol: 3)")
-    p.add_argument("--no-roofline", action="store_true")
+    p.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
     p.add_argument("--no-graph", action="store_true")
     p.add_argument("--measure-traffic", action="store_true",
                    help="collect FETCH_SIZE / WRITE_SIZE of the dominant kernel NOW (two rocprofv3 --pmc child runs of --roofline-only) "
@@ -84,7 +94,7 @@ def parse():
                    help="only the dominant-kernel measurement: CFG UNet forwards at the bench batch (the command the rocprofv3 "
                         "summaries under profiles/ are taken from)")
     p.add_argument("--roofline-iters", type=int, default=4)
-    p.add_argument("--no-tail", action="store_true", help="skip the D2H + PIL leg (with_d2h_pil_images_per_s)")
+    p.add_argument("--no-tail", action="store_true", help="with --full: skip the D2H + PIL leg (with_d2h_pil_images_per_s)")
     p.add_argument("--stub-step", action="store_true",
                    help="rehearsal of the launch / sharding / collective / timing / reporting code WITHOUT the native pipeline: the step's compute is "
                         "a per-row CPU function, the collective backend is gloo (tests/test_cpu.py drives `bench.py --gpus 2 --stub-step`); the printed "
@@ -98,6 +108,10 @@ def parse():
     a = p.parse_args()
     if a.dump_outputs and (a.steps < 1 or a.roofline_only):
         p.error("--dump-outputs needs at least one timed step (--steps >= 1, no --roofline-only)")
+    if not a.full:
+        if a.roofline_only or a.measure_traffic:
+            p.error("--roofline-only and --measure-traffic are legs of the full benchmark: add --full")
+        a.no_cpu_baseline = a.no_roofline = a.no_tail = True    # the plain run: the timed steps and the line, nothing else
     return a
 
 
@@ -172,12 +186,12 @@ def _pmc_avg_kib(db_path, symbol):
 
 
 def traffic_measured(symbol, extra_args):
-    """two separate rocprofv3 --pmc child runs of `bench.py --roofline-only` (FETCH_SIZE and WRITE_SIZE cannot share a pass:
+    """two separate rocprofv3 --pmc child runs of `bench.py --full --roofline-only` (FETCH_SIZE and WRITE_SIZE cannot share a pass:
     MI355X_MICROARCH.md §rocprofv3 PMC slots); FETCH_SIZE doubled (gfx950 reports 64 B per 128-B request, §HBM)"""
     vals = {}
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="ladi_pmc_", dir="/tmp")
-        cmd = ["rocprofv3", "--pmc", ctr, "--kernel-trace", "-d", d, "--", sys.executable, os.path.join(ROOT, "bench.py"), "--roofline-only",
+        cmd = ["rocprofv3", "--pmc", ctr, "--kernel-trace", "-d", d, "--", sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--roofline-only",
                "--no-cpu-baseline"] + extra_args
         env = dict(os.environ, TMPDIR="/tmp")
         r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=900)

@@ -629,6 +629,26 @@ def test_bench_refuses_to_run_fewer_ranks_than_gpus_flag():
     assert r.returncode == 2 and "WORLD_SIZE=1" in r.stderr and "{" not in r.stdout, (r.returncode, r.stdout, r.stderr)
 
 
+def test_bench_full_option_gates_the_extra_legs(monkeypatch):
+    """a plain `bench.py` run carries no leg beyond its timed steps: parse() switches the tail, roofline and CPU-baseline legs off
+    unless --full is given, --full keeps the --no-* switches working, and the roofline runs of their own are refused without --full"""
+    import bench
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + list(argv))
+        return bench.parse()
+    a = parse("--gpus", "1", "--steps", "3", "--warmup", "2")
+    assert not a.full and a.no_tail and a.no_roofline and a.no_cpu_baseline and (a.steps, a.warmup) == (3, 2)
+    a = parse("--gpus", "1", "--steps", "3", "--warmup", "2", "--full")
+    assert a.full and not (a.no_tail or a.no_roofline or a.no_cpu_baseline) and (a.steps, a.warmup) == (3, 2)
+    a = parse("--full", "--no-cpu-baseline", "--roofline-only")
+    assert a.no_cpu_baseline and a.roofline_only and not a.no_roofline
+    for flag in ("--roofline-only", "--measure-traffic"):
+        with pytest.raises(SystemExit) as e:
+            parse(flag)
+        assert e.value.code == 2
+
+
 def test_bench_dump_outputs_last_timed_step(tmp_path):
     """`bench.py --dump-outputs DIR` writes what the last timed step returned (DIR/images.npy, float32) and the same arguments give the
     same arrays; an output over the byte budget is reduced to a seeded sample with its flat indices, the same sample every time."""

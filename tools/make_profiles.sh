@@ -15,7 +15,7 @@ export LADI_TUNE_NO_SHIPPED=1
 export LADI_TUNE_CACHE=$O/r06_tune.txt
 rm -f $LADI_TUNE_CACHE
 timeout 600 python bench.py --no-cpu-baseline --no-roofline --no-tail --steps 1 --warmup 1 > /dev/null 2>&1
-timeout 300 python bench.py --roofline-only --no-cpu-baseline > /dev/null 2>&1
+timeout 300 python bench.py --full --roofline-only --no-cpu-baseline > /dev/null 2>&1
 timeout 400 python bench.py --config 2 --no-cpu-baseline --no-roofline --no-tail --steps 1 --warmup 1 > /dev/null 2>&1
 timeout 400 python bench.py --config 4 --no-cpu-baseline --no-roofline --no-tail --steps 1 --warmup 0 > /dev/null 2>&1
 unset LADI_TUNE_NO_SHIPPED; unset LADI_TUNE_CACHE
@@ -24,11 +24,11 @@ fi
 wc -l ladi_vton_amd/tune_gfx950.txt
 # ---- 2. kernel traces and PMC passes of the roofline command (each counter set in its own run)
 cd /tmp; export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt -- python $R/bench.py --roofline-only --no-cpu-baseline > /dev/null 2>&1
-timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_f -- python $R/bench.py --roofline-only --no-cpu-baseline > /dev/null 2>&1
-timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_w -- python $R/bench.py --roofline-only --no-cpu-baseline > /dev/null 2>&1
-timeout 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $O/pmc_m -- python $R/bench.py --roofline-only --no-cpu-baseline > /dev/null 2>&1
-timeout 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_MFMA GRBM_GUI_ACTIVE --kernel-trace -d $O/pmc_w8 -- python $R/bench.py --roofline-only --no-cpu-baseline > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt -- python $R/bench.py --full --roofline-only --no-cpu-baseline > /dev/null 2>&1
+timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_f -- python $R/bench.py --full --roofline-only --no-cpu-baseline > /dev/null 2>&1
+timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_w -- python $R/bench.py --full --roofline-only --no-cpu-baseline > /dev/null 2>&1
+timeout 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $O/pmc_m -- python $R/bench.py --full --roofline-only --no-cpu-baseline > /dev/null 2>&1
+timeout 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_MFMA GRBM_GUI_ACTIVE --kernel-trace -d $O/pmc_w8 -- python $R/bench.py --full --roofline-only --no-cpu-baseline > /dev/null 2>&1
 timeout 300 python $R/tools/bench_vae.py > $O/r06_vae_stages.txt 2>/dev/null
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/ktv -- python $R/tools/bench_vae.py --iters 1 > /dev/null 2>&1
 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fv -- python $R/tools/bench_vae.py --iters 1 > /dev/null 2>&1
@@ -45,14 +45,14 @@ python tools/rocpd_pmc.py $(find $O/pmc_wv -name "*.db" | head -1) $O/r06_vae_pm
 rm -rf $O/kt $O/pmc_f $O/pmc_w $O/pmc_m $O/pmc_w8 $O/ktv $O/pmc_fv $O/pmc_wv
 cp $O/r06_unet_forward_kernel_stats.txt $O/r06_pmc_fetch_size.txt $O/r06_pmc_write_size.txt $O/r06_vae_kernel_stats.txt $O/r06_vae_pmc_fetch_size.txt $O/r06_vae_pmc_write_size.txt profiles/
 # ---- 3. bench lines (shipped table, committed PMC files of this binary)
-timeout 1200 python bench.py --steps 10 --warmup 3 > $O/r06_bench_default.json 2> $O/r06_bench_default.err
-timeout 300 python bench.py --config 2 --no-cpu-baseline --no-roofline --steps 2 --warmup 1 > $O/r06_bench_config2.json 2>/dev/null
-timeout 300 python bench.py --scheduler ddim --no-cpu-baseline --no-roofline --steps 3 --warmup 1 > $O/r06_bench_ddim.json 2>/dev/null
-[ -z "${LADI_PROFILE_QUICK:-}" ] && timeout 300 python bench.py --scheduler lms --no-cpu-baseline --no-roofline --steps 3 --warmup 1 > $O/r06_bench_lms.json 2>/dev/null
-timeout 400 python bench.py --config 4 --no-cpu-baseline --no-roofline --steps 1 --warmup 1 > $O/r06_bench_config4.json 2>/dev/null
-timeout 300 python bench.py --roofline-only --no-cpu-baseline > $O/r06_bench_roofline_only.json 2>/dev/null
-[ -z "${LADI_PROFILE_QUICK:-}" ] && timeout 400 python bench.py --config 2 --roofline-only --no-cpu-baseline > $O/r06_bench_config2_roofline_only.json 2>/dev/null
-[ -z "${LADI_PROFILE_QUICK:-}" ] && timeout 400 python bench.py --config 4 --roofline-only --no-cpu-baseline > $O/r06_bench_config4_roofline_only.json 2>/dev/null
+timeout 1200 python bench.py --full --steps 10 --warmup 3 > $O/r06_bench_default.json 2> $O/r06_bench_default.err
+timeout 300 python bench.py --full --config 2 --no-cpu-baseline --no-roofline --steps 2 --warmup 1 > $O/r06_bench_config2.json 2>/dev/null
+timeout 300 python bench.py --full --scheduler ddim --no-cpu-baseline --no-roofline --steps 3 --warmup 1 > $O/r06_bench_ddim.json 2>/dev/null
+[ -z "${LADI_PROFILE_QUICK:-}" ] && timeout 300 python bench.py --full --scheduler lms --no-cpu-baseline --no-roofline --steps 3 --warmup 1 > $O/r06_bench_lms.json 2>/dev/null
+timeout 400 python bench.py --full --config 4 --no-cpu-baseline --no-roofline --steps 1 --warmup 1 > $O/r06_bench_config4.json 2>/dev/null
+timeout 300 python bench.py --full --roofline-only --no-cpu-baseline > $O/r06_bench_roofline_only.json 2>/dev/null
+[ -z "${LADI_PROFILE_QUICK:-}" ] && timeout 400 python bench.py --full --config 2 --roofline-only --no-cpu-baseline > $O/r06_bench_config2_roofline_only.json 2>/dev/null
+[ -z "${LADI_PROFILE_QUICK:-}" ] && timeout 400 python bench.py --full --config 4 --roofline-only --no-cpu-baseline > $O/r06_bench_config4_roofline_only.json 2>/dev/null
 cd /tmp
 timeout 400 rocprofv3 --kernel-trace --stats -d $O/ktb -- python $R/bench.py --no-cpu-baseline --no-roofline --no-tail --steps 1 --warmup 1 > /dev/null 2>&1
 cd $R
