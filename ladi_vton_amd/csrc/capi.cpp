@@ -39,26 +39,26 @@ static void require_gpu() {
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw std::runtime_error("no HIP device: libladi_native has no CPU fallback");
 }
 
-// two-pass (plan, run) execution of a module graph on its own arena
-template <typename Body>
-static void run_planned(Arena& arena, float*& stats, size_t& stats_cap, hipStream_t st, Body&& body) {
-    for (int pass = 0; pass < 2; ++pass) {
-        arena.dry = (pass == 0);
-        arena.off = 0;
-        Ctx c; c.st = st; c.ar = &arena; c.stats = stats; c.stats_cap = stats_cap;
-        if (pass == 1 && stats_cap) HIP_OK(hipMemsetAsync(stats, 0, stats_cap * sizeof(float), st));
-        body(c);
-        if (pass == 0) {
-            arena.reserve(arena.peak + 4096);
-            if (c.stats_peak > stats_cap) {
-                if (stats) (void)hipFree(stats);
-                stats = nullptr;
-                HIP_OK(hipMalloc(reinterpret_cast<void**>(&stats), c.stats_peak * sizeof(float)));
-                stats_cap = c.stats_peak;
-            }
-        }
-    }
+namespace {
+// Arena of the op-level GroupNorm: one grow-only arena per (device, stream), never freed while the process lives, so a steady-state call
+// neither allocates nor synchronises (growing goes through Arena::reserve, whose hipFree waits for the work still reading the old buffer).
+// Calls are serialised: the planning state of an arena is not shareable.
+struct OpArena { int dev; hipStream_t st; Arena* ar; };
+std::mutex g_op_mu;
+Arena& op_arena(hipStream_t st) {
+    static std::vector<OpArena> pool;
+    int dev = 0;
+    HIP_OK(hipGetDevice(&dev));
+    for (auto& e : pool)
+        if (e.dev == dev && e.st == st) return *e.ar;
+    pool.push_back(OpArena{dev, st, new Arena()});
+    return *pool.back().ar;
 }
+Act op_view(const void* p, int n, int HW, int C) {
+    Act a; a.p = reinterpret_cast<h16*>(const_cast<void*>(p)); a.n = n; a.h = HW; a.w = 1; a.c = C; a.ld = C;
+    return a;
+}
+}  // namespace
 
 extern "C" {
 
@@ -115,12 +115,12 @@ int ladi_unet_forward(ladi_unet* u, const void* sample, int dtype, int n, int h,
         UNet& U = u->u;
         hipStream_t st = S(stream);
         if (U.compute_temb(&timestep, 1, st)) return -1;
-        run_planned(U.arena, U.stats, U.stats_cap, st, [&](Ctx& c) {
+        run_planned(U.arena, st, [&](Ctx& c) {
             Act x = c.new_act(n, h, w, 64);
             if (!c.dry()) c.check(ladi_launch_nchw_to_nhwc(sample, dtype == LADI_F32, n, U.cfg.in_channels, h, w, x.p, 64, st), "nchw_to_nhwc");
             Act eps = U.forward(c, x, U.temb_table, nullptr);
             if (!c.dry()) c.check(ladi_launch_nhwc_to_nchw(eps.p, eps.ld, n, U.cfg.out_channels, h, w, out, out_dtype == LADI_F32, st), "nhwc_to_nchw");
-        });
+        }, &U.stats, &U.stats_cap);
         return 0;
     });
 }
@@ -133,7 +133,7 @@ int ladi_unet_time_forward(ladi_unet* u, int n, int h, int w, int iters, float* 
         if (U.compute_temb(&t0, 1, st)) return -1;
         hipEvent_t e0, e1;
         HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
-        run_planned(U.arena, U.stats, U.stats_cap, st, [&](Ctx& c) {
+        run_planned(U.arena, st, [&](Ctx& c) {
             Act x = c.new_act(n, h, w, 64);
             if (!c.dry()) HIP_OK(hipMemsetAsync(x.p, 0, x.pixels() * 64 * sizeof(h16), st));
             const size_t mk = c.ar->mark();
@@ -147,7 +147,7 @@ int ladi_unet_time_forward(ladi_unet* u, int n, int h, int w, int iters, float* 
                 c.ar->release(mk);
             }
             if (!c.dry()) HIP_OK(hipEventRecord(e1, st));
-        });
+        }, &U.stats, &U.stats_cap);
         HIP_OK(hipEventSynchronize(e1));
         float ms = 0.f;
         HIP_OK(hipEventElapsedTime(&ms, e0, e1));
@@ -183,13 +183,11 @@ int ladi_unet_time_forward_lanes(ladi_unet* u, int n, int h, int w, int iters, i
             const int eps_ld = (U.cfg.out_channels + 3) / 4 * 4;
             Arena& io = u->io;
             Act x, eps;
-            for (int pass = 0; pass < 2; ++pass) {
-                io.dry = (pass == 0); io.off = 0;
-                Ctx c; c.st = st; c.ar = &io;
+            run_planned(io, st, [&](Ctx& c) {
                 x = c.new_act(n, h, w, 64);
                 eps = c.new_act(n, h, w, U.cfg.out_channels, eps_ld);
-                if (pass == 0) { LN.forward(U, st, true, false, x, eps, U.temb_table, nullptr); LN.commit_plan(); io.reserve(io.peak + 4096); }
-            }
+                if (c.dry()) { LN.forward(U, st, true, false, x, eps, U.temb_table, nullptr); LN.commit_plan(); }
+            });
             HIP_OK(hipMemsetAsync(x.p, 0, x.pixels() * 64 * sizeof(h16), st));
             LN.forward(U, st, false, false, x, eps, U.temb_table, nullptr);      // warm-up, lanes in sequence (tile measurement)
             if (use_graph) {
@@ -241,7 +239,7 @@ int ladi_vae_encode(ladi_vae* v, const void* x, int dtype, int B, int H, int W, 
         VAE& V = v->v;
         hipStream_t st = S(stream);
         if (H % 8 || W % 8) throw std::runtime_error("H and W must be divisible by 8");
-        run_planned(V.arena, V.stats, V.stats_cap, st, [&](Ctx& c) {
+        run_planned(V.arena, st, [&](Ctx& c) {
             Act xi = c.new_act(B, H, W, 64);
             if (!c.dry()) c.check(ladi_launch_nchw_to_nhwc(x, dtype == LADI_F32, B, 3, H, W, xi.p, 64, st), "nchw_to_nhwc");
             Act feats[5];
@@ -253,7 +251,7 @@ int ladi_vae_encode(ladi_vae* v, const void* x, int dtype, int B, int H, int W, 
             if (feats_out)
                 for (int i = 0; i < 5; ++i)
                     if (feats_out[i]) HIP_OK(hipMemcpyAsync(feats_out[i], feats[i].p, feats[i].pixels() * feats[i].c * sizeof(h16), hipMemcpyDeviceToDevice, st));
-        });
+        }, &V.stats, &V.stats_cap);
         // the encoder's intermediate features feed EMASC at their true scale, so there is no scaled form to fall back to: report instead
         if (V.overflowed(st)) throw std::runtime_error("VAE encode: activations exceed the fp16 range (non-finite GroupNorm statistics)");
         return 0;
@@ -266,7 +264,7 @@ int ladi_vae_decode(ladi_vae* v, const float* z, int B, int h, int w, const void
         VAE& V = v->v;
         hipStream_t st = S(stream);
         (void)V.decode_guarded(st, [&](int shift) {
-        run_planned(V.arena, V.stats, V.stats_cap, st, [&](Ctx& c) {
+        run_planned(V.arena, st, [&](Ctx& c) {
             float* zp = c.alloc_f32((size_t)B * h * w * 4);
             Act zi = c.new_act(B, h, w, 64);
             Act skips[5];
@@ -286,7 +284,7 @@ int ladi_vae_decode(ladi_vae* v, const float* z, int B, int h, int w, const void
             }
             Act img = V.decode(c, zi, skips_dev ? skips : nullptr, shift);
             if (!c.dry()) c.check(ladi_launch_nhwc_to_nchw(img.p, img.ld, B, 3, 8 * h, 8 * w, sample, out_dtype == LADI_F32, st), "sample");
-        });
+        }, &V.stats, &V.stats_cap);
         });
         return 0;
     });
@@ -322,8 +320,7 @@ int ladi_emasc_forward(ladi_emasc* e, const void* const* feats_dev, const int* h
     return guarded("ladi_emasc_forward", [&]() {
         EMASC& E = e->e;
         hipStream_t st = S(stream);
-        float* nostats = nullptr; size_t nocap = 0;
-        run_planned(E.arena, nostats, nocap, st, [&](Ctx& c) {
+        run_planned(E.arena, st, [&](Ctx& c) {
             Act feats[8], outs[8];
             const h16* masks[8];
             for (int i = 0; i < E.cfg.n; ++i) {
@@ -638,70 +635,17 @@ int ladi_op_igemm(const ladi_igemm_desc* d, int batch, int tile_cfg, void* strea
         return rc;
     });
 }
-namespace {
-// Scratch of the op-level entry points: one grow-only buffer per (device, stream), never freed while the process lives.  Round 5's
-// ladi_op_group_norm did hipMalloc + hipStreamSynchronize + hipFree on EVERY call -- 0.27 ms for a 15 us kernel, which is what
-// profiles/r05_attn_bench.txt's "group_norm 0.17-0.86 TB/s" lines measured: every external caller of the C ABI paid it.
-struct OpScratch { int dev; hipStream_t st; float* p; size_t bytes; };
-float* op_scratch(hipStream_t st, size_t bytes) {
-    static std::vector<OpScratch> pool;
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    int dev = 0;
-    HIP_OK(hipGetDevice(&dev));
-    for (auto& e : pool)
-        if (e.dev == dev && e.st == st) {
-            if (e.bytes >= bytes) return e.p;
-            HIP_OK(hipStreamSynchronize(st));                  // growing: the old buffer may still be read by work queued on this stream
-            (void)hipFree(e.p);
-            e.p = nullptr; e.bytes = 0;
-            HIP_OK(hipMalloc(reinterpret_cast<void**>(&e.p), bytes));
-            e.bytes = bytes;
-            return e.p;
-        }
-    OpScratch e{dev, st, nullptr, bytes};
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&e.p), bytes));
-    pool.push_back(e);
-    return e.p;
-}
-}  // namespace
-
+// the runtime's group_norm() (runtime_core.cpp) on views of the caller's dense tensors: the form every model runs for the same operands
 int ladi_op_group_norm(const void* src0, int C0, const void* src1, int C1, int n, int HW, int groups, const void* gamma, const void* beta,
                        float eps, int silu, const void* add, void* out, float* stats, void* stream) {
     return guarded("ladi_op_group_norm", [&]() {
         hipStream_t st = S(stream);
-        (void)stats;  // legacy scratch argument (unused: statistics are atomics-free partial rows in a per-stream scratch now)
-        const int r0 = ladi_gn_partial_rows(n, HW, C0), r1 = C1 ? ladi_gn_partial_rows(n, HW, C1) : 0;
-        const size_t f0 = (size_t)n * r0 * C0 * 2, f1 = (size_t)n * r1 * C1 * 2, fs = (size_t)n * (C0 + C1) * 2;
-        const size_t g0 = (size_t)n * ladi_gn_reduce_rows() * C0 * 2, g1 = (size_t)n * ladi_gn_reduce_rows() * C1 * 2;
-        float* buf = op_scratch(st, (f0 + f1 + fs + g0 + g1) * sizeof(float));     // asynchronous: no allocation, no synchronisation per call
-        int rc = 0;
-        const bool direct = ladi_gn_norm_direct(HW) && ladi_gn_norm_eligible(C0, 0, C1, 0, groups, HW);
-        if (!direct) {
-            rc = ladi_launch_gn_partial((const h16*)src0, C0, C0, n, HW, buf, st);
-            if (!rc && C1) rc = ladi_launch_gn_partial((const h16*)src1, C1, C1, n, HW, buf + f0, st);
-        }
-        // the forms the runtime takes for the same operands (runtime_core.cpp group_norm): statistics from the data (tiny samples), partial rows
-        // folded first (many rows), one-pass; the three-stage form only where the one-pass kernel is not eligible
-        const float* p0 = buf; const float* p1 = buf + f0; int q0 = r0, q1 = r1;
-        const bool shape_ok = ladi_gn_norm_eligible(C0, 1, C1, C1 ? 1 : 0, groups, HW);
-        if (!rc && !direct && shape_ok) {
-            if (ladi_gn_reduce_eligible(C0, r0)) { rc = ladi_launch_gn_reduce(p0, C0, r0, n, buf + f0 + f1 + fs, st); p0 = buf + f0 + f1 + fs; q0 = ladi_gn_reduce_rows(); }
-            if (!rc && C1 && ladi_gn_reduce_eligible(C1, r1)) { rc = ladi_launch_gn_reduce(p1, C1, r1, n, buf + f0 + f1 + fs + g0, st); p1 = buf + f0 + f1 + fs + g0; q1 = ladi_gn_reduce_rows(); }
-        }
-        if (rc) return rc;
-        if (direct) {
-            rc = ladi_launch_gn_norm((const h16*)src0, C0, C0, nullptr, 0, (const h16*)src1, C1, C1, nullptr, 0, n, HW, groups, (const h16*)gamma,
-                                     (const h16*)beta, eps, silu, (const h16*)add, (h16*)out, st);
-        } else if (ladi_gn_norm_eligible(C0, q0, C1, q1, groups, HW)) {
-            rc = ladi_launch_gn_norm((const h16*)src0, C0, C0, p0, q0, (const h16*)src1, C1, C1, C1 ? p1 : nullptr, q1, n, HW, groups, (const h16*)gamma,
-                                     (const h16*)beta, eps, silu, (const h16*)add, (h16*)out, st);
-        } else {
-            rc = ladi_launch_gn_finalize(buf, C0, r0, buf + f0, C1, r1, n, HW, groups, (const h16*)gamma, (const h16*)beta, eps, buf + f0 + f1, st);
-            if (!rc) rc = ladi_launch_gn_apply((const h16*)src0, C0, C0, (const h16*)src1, C1, C1, n, HW, buf + f0 + f1, silu, (const h16*)add,
-                                               (h16*)out, st);
-        }
-        return rc;
+        (void)stats;  // legacy scratch argument (unused: statistics are atomics-free partial rows in a per-stream arena now)
+        const Act x = op_view(src0, n, HW, C0), x2 = op_view(src1, n, HW, C1), ad = op_view(add, n, HW, C0 + C1), o = op_view(out, n, HW, C0 + C1);
+        DNorm nm; nm.g = reinterpret_cast<h16*>(const_cast<void*>(gamma)); nm.b = reinterpret_cast<h16*>(const_cast<void*>(beta)); nm.c = C0 + C1;
+        std::lock_guard<std::mutex> lk(g_op_mu);
+        run_planned(op_arena(st), st, [&](Ctx& c) { (void)group_norm(c, nm, x, C1 ? &x2 : nullptr, groups, eps, silu, add ? &ad : nullptr, &o); });
+        return 0;
     });
 }
 // fused transformer sub-blocks of the C = 320 level from plain operands: the packings the kernels read are built here, per call (op-level

@@ -63,7 +63,6 @@ struct Ctx {
     Arena* ar = nullptr;
     float* stats = nullptr;  // GroupNorm statistics arena (floats), zeroed at forward start
     size_t stats_off = 0, stats_cap = 0, stats_peak = 0;
-    int err = 0;
     int* bad = nullptr;      // optional device flag: set by a GroupNorm whose input statistics are not finite (fp16 overflow upstream)
     int* sk_cnt = nullptr;   // arrival counters of the in-launch split-K combine for THIS stream (1024 ints, zeroed once; kernels.h); null: process-wide
     bool dry() const { return ar->dry; }
@@ -73,6 +72,26 @@ struct Ctx {
     Act new_act(int n, int h, int w, int c, int ld = 0);
     void check(int rc, const char* what);
 };
+
+// Two-pass (plan, run) execution of a module graph on its arena: `body(Ctx&)` runs once dry (addresses are fake, nothing is launched; it
+// only records the arena / statistics peaks), the plan is committed, and it runs again for real.  Both passes must allocate identically.
+// A body reports failure by throwing std::runtime_error (Ctx::check does).
+// commit_plan: reserve the arena (peak + 4096 bytes) and grow the GroupNorm-statistics buffer to `stats_peak` floats (stats may be null)
+void commit_plan(Arena& arena, size_t stats_peak, float** stats, size_t* stats_cap);
+// stats / stats_cap: the owner's statistics buffer (grown here, zeroed at the start of the real pass) or null; sk_cnt: see Ctx::sk_cnt
+template <typename Body>
+void run_planned(Arena& arena, hipStream_t st, Body&& body, float** stats = nullptr, size_t* stats_cap = nullptr, int* sk_cnt = nullptr) {
+    for (int pass = 0; pass < 2; ++pass) {
+        arena.dry = (pass == 0);
+        arena.off = 0;
+        Ctx c; c.st = st; c.ar = &arena; c.sk_cnt = sk_cnt;
+        if (stats) { c.stats = *stats; c.stats_cap = *stats_cap; }
+        if (pass == 1 && c.stats_cap && hipMemsetAsync(c.stats, 0, c.stats_cap * sizeof(float), st) != hipSuccess)
+            throw std::runtime_error("run_planned: zeroing the GroupNorm statistics failed");
+        body(c);
+        if (pass == 0) commit_plan(arena, c.stats_peak, stats, stats_cap);
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 struct DConv {  // conv3x3 / conv1x1 / linear weights in igemm layout [cout][k*k][cin_pad]
@@ -94,6 +113,8 @@ struct ConvOpt {
     int out_ld = 0;          // 0 -> cout (GEGLU: cout/2)
     int cfg = 0;             // igemm tile config override
     bool stats = false;      // also produce per-channel partial statistics of the output (for a consuming GroupNorm)
+    Act* dst = nullptr;      // caller-owned output view of the computed size: nothing is allocated for the output (out_ld and stats are the
+                             // view's: ld, st_part); its st_part / st_px are updated like the returned Act's
     const DNorm* ln = nullptr; float ln_eps = 1e-5f;   // LayerNorm applied to the input first: fused into the kernel when it can be, else a launch
     const float* gn_ss = nullptr;                      // GroupNorm affine of the input ([n][C][2] scale / shift from gn_scale_shift) applied
                                                        // in the X-stationary kernel's prologue (see gn_fusable)
@@ -107,9 +128,9 @@ DNorm load_norm(DevPool& pool, const WeightStore& ws, const std::string& prefix)
 Act conv2d(Ctx& c, const DConv& cv, const Act& x, const Act* x2, const ConvOpt& o);
 // output tensor + worst-case partial-statistics buffer (rows of 32 pixels) allocated together (stack discipline)
 Act new_act_with_stats(Ctx& c, int n, int h, int w, int cc);
-// launch an igemm whose output is `out` (pre-allocated), filling out.st_part / out.st_px when out.st_part != nullptr
-void launch_conv_into(Ctx& c, IGemmArgs& a, Act& out, int cfg = 0);
-Act group_norm(Ctx& c, const DNorm& nm, const Act& x, const Act* x2, int groups, float eps, int silu, const Act* add = nullptr);
+// dst: caller-owned dense output view [n, h, w, C0 + C1] (null: allocated from the arena)
+Act group_norm(Ctx& c, const DNorm& nm, const Act& x, const Act* x2, int groups, float eps, int silu, const Act* add = nullptr,
+               const Act* dst = nullptr);
 // statistics + finalize only: per-(sample, channel) scale / shift of GroupNorm(x | x2) as [n][C0 + C1][2] floats (what group_norm applies)
 float* gn_scale_shift(Ctx& c, const DNorm& nm, const Act& x, const Act* x2, int groups, float eps);
 // can a following 1x1 projection apply that affine in its own prologue instead of a gn_apply pass?  (X-stationary kernel: K = 320 / 640,
@@ -277,7 +298,11 @@ struct Adapter {
 
 // CLIP text encoder + pseudo-word splice (reference src/utils/encode_text_word_embedding.py:6-72)
 struct TextCfg { int vocab = 49408, hidden = 1024, heads = 16, mlp = 4096, layers = 23, max_pos = 77, vstar_id = 259; float ln_eps = 1e-5f; };
-struct TextLayer { DNorm ln1, ln2; DConv qkv, o, fc1, fc2; };
+struct TextLayer { DNorm ln1, ln2; DConv qkv, o, fc1, fc2; };   // one pre-LN CLIP encoder layer (text and vision towers)
+std::vector<TextLayer> load_clip_layers(DevPool& pool, const WeightStore& ws, const std::string& prefix, int n);   // prefix + "<i>.layer_norm1" ...
+// dst = cur + attn(LN1(cur)) -> + fc2(gelu(fc1(LN2(.)))) over tokens cur [B, T, 1, hidden]; head dim 64: flash kernel (causal or not), else the
+// generic-head-dim kernel (non-causal); softmax scale 1 / sqrt(head dim).  dst: caller-owned view of cur's shape, not cur itself
+void clip_layer(Ctx& c, const TextLayer& L, const Act& cur, Act& dst, int heads, bool causal, float eps);
 struct TextEncoder {
     TextCfg cfg; DevPool pool;
     h16* tok = nullptr; h16* pos = nullptr;   // [vocab][hidden], [max_pos][hidden]

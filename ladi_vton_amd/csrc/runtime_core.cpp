@@ -77,6 +77,15 @@ void Arena::reserve(size_t bytes) {
 }
 Arena::~Arena() { if (base) (void)hipFree(base); }
 
+void commit_plan(Arena& arena, size_t stats_peak, float** stats, size_t* stats_cap) {
+    arena.reserve(arena.peak + 4096);
+    if (!stats || stats_peak <= *stats_cap) return;
+    if (*stats) (void)hipFree(*stats);
+    *stats = nullptr; *stats_cap = 0;
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(stats), stats_peak * sizeof(float)));
+    *stats_cap = stats_peak;
+}
+
 float* Ctx::alloc_stats(size_t floats) {
     size_t o = stats_off;
     stats_off += floats;
@@ -191,19 +200,6 @@ Act new_act_with_stats(Ctx& c, int n, int h, int w, int cc) {
     return a;
 }
 
-void launch_conv_into(Ctx& c, IGemmArgs& a, Act& out, int cfg) {
-    a.out = out.p; a.ldo = out.ld;
-    a.stats = (out.st_part && out.ld == out.c) ? out.st_part : nullptr;
-    int px = 0;
-    // split-K slab from this handle's planned arena (stack discipline: it lives until the enclosing block releases its mark), so a
-    // captured graph only ever references memory covered by the graph key (arena base)
-    const size_t wsb = ladi_igemm_splitk_ws_bytes(a, 1);
-    float* ws = wsb ? c.alloc_f32(wsb / sizeof(float)) : nullptr;
-    if (!c.dry()) c.check(ladi_launch_igemm(a, 1, cfg, c.st, &px, ws, wsb, c.sk_cnt), "igemm");
-    out.st_px = px;
-    if (!c.dry() && px == 0) out.st_part = nullptr;
-}
-
 Act conv2d(Ctx& c, const DConv& cv, const Act& x, const Act* x2, const ConvOpt& o) {
     const int pad = o.pad >= 0 ? o.pad : cv.k / 2;
     if (o.ups && (o.stride != 1 || 2 * pad != cv.k - 1)) throw std::runtime_error("conv2d: the folded upsample needs a stride-1 'same' convolution");
@@ -218,8 +214,17 @@ Act conv2d(Ctx& c, const DConv& cv, const Act& x, const Act* x2, const ConvOpt& 
     if (C0 + C1 != cv.cin_pad) throw std::runtime_error("conv2d: channel mismatch (" + std::to_string(C0 + C1) + " vs " + std::to_string(cv.cin_pad) + ")");
     const bool geglu = o.act == LADI_ACT_GEGLU;
     const int cout = geglu ? cv.cout / 2 : cv.cout;
-    Act out = c.new_act(x.n, Ho, Wo, cout, o.out_ld);
-    if (o.stats && !geglu) out.st_part = alloc_part(c, out);
+    Act out;
+    if (o.dst) {
+        out = *o.dst;
+        if (out.n != x.n || out.h != Ho || out.w != Wo || out.c != cout)
+            throw std::runtime_error("conv2d: the caller's output view is [" + std::to_string(out.n) + ", " + std::to_string(out.h) + ", " + std::to_string(out.w) +
+                                     ", " + std::to_string(out.c) + "], computed [" + std::to_string(x.n) + ", " + std::to_string(Ho) + ", " +
+                                     std::to_string(Wo) + ", " + std::to_string(cout) + "]");
+    } else {
+        out = c.new_act(x.n, Ho, Wo, cout, o.out_ld);
+        if (o.stats && !geglu) out.st_part = alloc_part(c, out);
+    }
     IGemmArgs a;
     std::memset(&a, 0, sizeof(a));
     a.src0 = x.p; a.C0 = C0; a.ld0 = x.ld;
@@ -244,7 +249,17 @@ Act conv2d(Ctx& c, const DConv& cv, const Act& x, const Act* x2, const ConvOpt& 
         // scratch is reserved unconditionally (the planning pass and the real pass allocate identically)
         a.ln_scratch = c.new_act(x.n, x.h, x.w, C0).p;
     }
-    launch_conv_into(c, a, out, o.cfg);
+    a.out = out.p; a.ldo = out.ld;
+    a.stats = (out.st_part && out.ld == out.c) ? out.st_part : nullptr;
+    int px = 0;
+    // split-K slab from this handle's planned arena (stack discipline: it lives until the enclosing block releases its mark), so a
+    // captured graph only ever references memory covered by the graph key (arena base)
+    const size_t wsb = ladi_igemm_splitk_ws_bytes(a, 1);
+    float* ws = wsb ? c.alloc_f32(wsb / sizeof(float)) : nullptr;
+    if (!c.dry()) c.check(ladi_launch_igemm(a, 1, o.cfg, c.st, &px, ws, wsb, c.sk_cnt), "igemm");
+    out.st_px = px;
+    if (!c.dry() && px == 0) out.st_part = nullptr;
+    if (o.dst) { o.dst->st_part = out.st_part; o.dst->st_px = out.st_px; }
     return out;
 }
 
@@ -286,11 +301,13 @@ float* gn_scale_shift(Ctx& c, const DNorm& nm, const Act& x, const Act* x2, int 
     return ss;
 }
 
-Act group_norm(Ctx& c, const DNorm& nm, const Act& x, const Act* x2, int groups, float eps, int silu, const Act* add) {
+Act group_norm(Ctx& c, const DNorm& nm, const Act& x, const Act* x2, int groups, float eps, int silu, const Act* add, const Act* dst) {
     const int C0 = x.c, C1 = x2 ? x2->c : 0;
     if (C0 + C1 != nm.c) throw std::runtime_error("group_norm: channel mismatch");
     const int HW = x.h * x.w;
-    Act out = c.new_act(x.n, x.h, x.w, C0 + C1);
+    if (dst && (dst->n != x.n || dst->h * dst->w != HW || dst->c != C0 + C1 || dst->ld != dst->c))
+        throw std::runtime_error("group_norm: the caller's output view must be dense [n, h, w, C0 + C1]");
+    Act out = dst ? *dst : c.new_act(x.n, x.h, x.w, C0 + C1);
     // (the scale / shift table is reserved whichever form runs: the arena plan does not depend on LADI_GN_ONEPASS)
     float* ss = c.alloc_f32((size_t)x.n * (C0 + C1) * 2);
     // (direct statistics only when the one-pass form will take the launch: group size and the other source's rows decide that)

@@ -89,11 +89,7 @@ static ActF up2_f32(Ctx& c, const ActF& x) {
 }
 
 int Refine::forward_f32(const void* x, int B, int H, int W, void* out, int out_f32, hipStream_t st) {
-    for (int pass = 0; pass < 2; ++pass) {
-        arena.dry = (pass == 0);
-        if (pass == 1) arena.reserve(arena.peak);
-        arena.off = 0;
-        Ctx c; c.st = st; c.ar = &arena;
+    run_planned(arena, st, [&](Ctx& c) {
         ActF x0 = new_act_f32(c, B, H, W, incf.c1.cin_pad);
         if (!c.dry()) c.check(ladi_launch_nchw_to_nhwc_f32(x, 1, B, cfg.in_ch, H, W, x0.p, x0.ld, st), "nchw_to_nhwc_f32");
         ActF x1 = double_conv_f32(c, incf, x0, nullptr);
@@ -107,18 +103,14 @@ int Refine::forward_f32(const void* x, int B, int H, int W, void* out, int out_f
         ActF u4 = up2_f32(c, y); y = double_conv_f32(c, upf[3], x1, &u4);
         ActF lg = conv2d_f32(c, outcf, y, nullptr, 1, 0, LADI_ACT_NONE);
         if (!c.dry()) c.check(ladi_launch_nhwc_to_nchw_f32(lg.p, lg.ld, B, cfg.out_ch, H, W, out, out_f32, st), "nhwc_to_nchw_f32");
-    }
+    });
     return 0;
 }
 
 // ------------------------------------------------------------------------------------------------ TPS matching network
 int Tps::forward_f32(const void* a, const void* b, int B, float* grid, float* coor, hipStream_t st) {
     const int H = cfg.height, W = cfg.width, fh = H / 16, fw = W / 16, hw = fh * fw, N = cfg.grid * cfg.grid;
-    for (int pass = 0; pass < 2; ++pass) {
-        arena.dry = (pass == 0);
-        if (pass == 1) arena.reserve(arena.peak);
-        arena.off = 0;
-        Ctx c; c.st = st; c.ar = &arena;
+    run_planned(arena, st, [&](Ctx& c) {
         auto extract = [&](const TpsExtractF& e, const TpsExtract& e16, const void* src, int cin) -> ActF {
             ActF x = new_act_f32(c, B, H, W, e.conv[0].cin_pad);
             if (!c.dry()) c.check(ladi_launch_nchw_to_nhwc_f32(src, 1, B, cin, H, W, x.p, x.ld, st), "nchw_to_nhwc_f32");
@@ -159,7 +151,7 @@ int Tps::forward_f32(const void* a, const void* b, int B, float* grid, float* co
             c.check(ladi_launch_linear_f32(x.p, feat, linf_w, linf_b, B, 2 * N, feat, LADI_ACT_TANH, co, 2 * N, st), "regression linear f32");
             c.check(ladi_launch_tps_grid(co, d_inv, d_ctrl, N, B, H, W, grid, st), "tps grid");
         }
-    }
+    });
     return 0;
 }
 

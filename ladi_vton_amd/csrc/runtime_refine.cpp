@@ -83,14 +83,10 @@ void Refine::load(const RefineCfg& c, const WeightStore& ws) {
 int Refine::forward(const void* x, int in_f32, int B, int H, int W, void* out, int out_f32, hipStream_t st) {
     if (B <= 0 || H <= 0 || W <= 0 || (H % 16) || (W % 16)) { set_error("refinement UNet: H and W must be positive multiples of 16"); return -1; }
     if (in_f32) return forward_f32(x, B, H, W, out, out_f32, st);      // fp32 caller (inference.py:264): fp32 network (runtime_f32.cpp)
-    for (int pass = 0; pass < 2; ++pass) {
-        arena.dry = (pass == 0);
-        if (pass == 1) arena.reserve(arena.peak);
-        arena.off = 0;
-        Ctx c; c.st = st; c.ar = &arena;
+    run_planned(arena, st, [&](Ctx& c) {
         Act x0 = c.new_act(B, H, W, inc.c1.cin_pad);
         if (!c.dry()) {
-            if (hipMemsetAsync(x0.p, 0, x0.pixels() * (size_t)x0.ld * sizeof(h16), st) != hipSuccess) { set_error("refinement UNet: memset"); return -1; }
+            if (hipMemsetAsync(x0.p, 0, x0.pixels() * (size_t)x0.ld * sizeof(h16), st) != hipSuccess) throw std::runtime_error("refinement UNet: memset");
             c.check(ladi_launch_nchw_to_nhwc(x, in_f32, B, cfg.in_ch, H, W, x0.p, x0.ld, st), "nchw_to_nhwc");
         }
         Act x1 = double_conv(c, inc, x0, nullptr);
@@ -106,7 +102,7 @@ int Refine::forward(const void* x, int in_f32, int B, int H, int W, void* out, i
         ConvOpt oc; oc.out_ld = 8;
         Act lg = conv2d(c, outc, y, nullptr, oc);
         if (!c.dry()) c.check(ladi_launch_nhwc_to_nchw(lg.p, lg.ld, B, cfg.out_ch, H, W, out, out_f32, st), "nhwc_to_nchw");
-    }
+    });
     return 0;
 }
 

@@ -11,6 +11,48 @@
 
 namespace ladi {
 
+std::vector<TextLayer> load_clip_layers(DevPool& pool, const WeightStore& ws, const std::string& prefix, int n) {
+    std::vector<TextLayer> layers(n);
+    for (int i = 0; i < n; ++i) {
+        const std::string e = prefix + std::to_string(i);
+        TextLayer& L = layers[i];
+        L.ln1 = load_norm(pool, ws, e + ".layer_norm1");
+        L.ln2 = load_norm(pool, ws, e + ".layer_norm2");
+        L.qkv = load_linear_cat(pool, ws, {e + ".self_attn.q_proj", e + ".self_attn.k_proj", e + ".self_attn.v_proj"}, true);
+        L.o = load_conv(pool, ws, e + ".self_attn.out_proj");
+        L.fc1 = load_conv(pool, ws, e + ".mlp.fc1");
+        L.fc2 = load_conv(pool, ws, e + ".mlp.fc2");
+    }
+    return layers;
+}
+
+void clip_layer(Ctx& c, const TextLayer& L, const Act& cur, Act& dst, int heads, bool causal, float eps) {
+    const int B = cur.n, T = cur.h, H = cur.c, d = H / heads;
+    if (causal && d != 64) throw std::runtime_error("clip_layer: the causal mask needs head dim 64");
+    const size_t mk = c.ar->mark();
+    Act a = layer_norm(c, L.ln1, cur, eps);
+    ConvOpt op;
+    Act qkv = conv2d(c, L.qkv, a, nullptr, op);            // [B*T][3H], bias fused
+    Act ao = c.new_act(B, T, 1, H);
+    if (!c.dry()) {
+        AttnArgs aa;
+        aa.q = qkv.p; aa.k = qkv.p + H; aa.v = qkv.p + 2 * H; aa.o = ao.p;
+        aa.ldq = aa.ldk = aa.ldv = qkv.ld; aa.ldo = ao.ld;
+        aa.sq = aa.sk = aa.sv = (long long)T * qkv.ld; aa.so = (long long)T * ao.ld;
+        aa.n = B; aa.heads = heads; aa.Nq = T; aa.Nk = T; aa.scale = 1.f / std::sqrt((float)d); aa.causal = causal ? 1 : 0;
+        if (d == 64) c.check(ladi_launch_flash_attn64(aa, c.st), "clip attention");
+        else c.check(ladi_launch_attn_generic(aa, d, c.st), "clip attention");
+    }
+    ConvOpt oo; oo.res0 = &cur;
+    Act h1 = conv2d(c, L.o, ao, nullptr, oo);              // x + out_proj(attn)
+    Act a2 = layer_norm(c, L.ln2, h1, eps);
+    ConvOpt o1; o1.act = LADI_ACT_GELU;
+    Act m = conv2d(c, L.fc1, a2, nullptr, o1);
+    ConvOpt o2; o2.res0 = &h1; o2.dst = &dst;              // dst = h1 + fc2(m)
+    (void)conv2d(c, L.fc2, m, nullptr, o2);
+    c.ar->release(mk);
+}
+
 void TextEncoder::load(const TextCfg& c, const WeightStore& ws) {
     cfg = c;
     if (c.hidden % 64 || c.hidden / c.heads != 64) throw std::runtime_error("text encoder: head dim must be 64");
@@ -22,17 +64,7 @@ void TextEncoder::load(const TextCfg& c, const WeightStore& ws) {
     if (pe.shape.size() != 2 || pe.shape[0] != c.max_pos || pe.shape[1] != c.hidden) throw std::runtime_error("text encoder: position_embedding shape");
     tok = pool.upload_h16(te.data);
     pos = pool.upload_h16(pe.data);
-    layers.resize(c.layers);
-    for (int i = 0; i < c.layers; ++i) {
-        const std::string e = pre + "encoder.layers." + std::to_string(i);
-        TextLayer& L = layers[i];
-        L.ln1 = load_norm(pool, ws, e + ".layer_norm1");
-        L.ln2 = load_norm(pool, ws, e + ".layer_norm2");
-        L.qkv = load_linear_cat(pool, ws, {e + ".self_attn.q_proj", e + ".self_attn.k_proj", e + ".self_attn.v_proj"}, true);
-        L.o = load_conv(pool, ws, e + ".self_attn.out_proj");
-        L.fc1 = load_conv(pool, ws, e + ".mlp.fc1");
-        L.fc2 = load_conv(pool, ws, e + ".mlp.fc2");
-    }
+    layers = load_clip_layers(pool, ws, pre + "encoder.layers.", c.layers);
     final_ln = load_norm(pool, ws, pre + "final_layer_norm");
 }
 
@@ -92,53 +124,18 @@ int TextEncoder::forward(const int* ids, int ids_on_device, int B, int T, const 
     const int* d_first = d_ids + (size_t)B * T;
     const int* d_eot = d_first + B;
 
-    for (int pass = 0; pass < 2; ++pass) {
-        arena.dry = (pass == 0);
-        if (pass == 1) arena.reserve(arena.peak);
-        arena.off = 0;
-        Ctx c; c.st = st; c.ar = &arena;
+    run_planned(arena, st, [&](Ctx& c) {
         Act xa = c.new_act(B, T, 1, H), xb = c.new_act(B, T, 1, H);   // residual stream, ping-pong
         Act* cur = &xa; Act* nxt = &xb;
         if (!c.dry()) c.check(ladi_launch_text_embed(d_ids, d_first, nv, tok, pos, word_emb, B, T, H, cfg.vocab, cur->p, st), "text_embed");
         for (const TextLayer& L : layers) {
-            const size_t mk = c.ar->mark();
-            Act a = layer_norm(c, L.ln1, *cur, cfg.ln_eps);
-            ConvOpt op;
-            Act qkv = conv2d(c, L.qkv, a, nullptr, op);            // [B*T][3H], bias fused
-            Act ao = c.new_act(B, T, 1, H);
-            if (!c.dry()) {
-                AttnArgs aa;
-                aa.q = qkv.p; aa.k = qkv.p + H; aa.v = qkv.p + 2 * H; aa.o = ao.p;
-                aa.ldq = aa.ldk = aa.ldv = qkv.ld; aa.ldo = ao.ld;
-                aa.sq = aa.sk = aa.sv = (long long)T * qkv.ld; aa.so = (long long)T * ao.ld;
-                aa.n = B; aa.heads = cfg.heads; aa.Nq = T; aa.Nk = T; aa.scale = 0.125f; aa.causal = 1;   // q * 64^-0.5, causal mask
-                c.check(ladi_launch_flash_attn64(aa, st), "text attention");
-            }
-            ConvOpt oo; oo.res0 = cur;
-            Act h1 = conv2d(c, L.o, ao, nullptr, oo);              // x + out_proj(attn)
-            Act a2 = layer_norm(c, L.ln2, h1, cfg.ln_eps);
-            ConvOpt o1; o1.act = LADI_ACT_GELU;
-            Act m = conv2d(c, L.fc1, a2, nullptr, o1);
-            {   // nxt = h1 + fc2(m), written into the other residual buffer
-                IGemmArgs g;
-                std::memset(&g, 0, sizeof(g));
-                g.src0 = m.p; g.C0 = m.c; g.ld0 = m.ld; g.Hs = T; g.Ws = 1; g.Ho = T; g.Wo = 1; g.P = B * T;
-                g.ksize = 1; g.stride = 1; g.pad = 0; g.W = L.fc2.w; g.Q = L.fc2.cout; g.K = L.fc2.K(); g.bias = L.fc2.b;
-                g.act = LADI_ACT_NONE; g.out_scale = 1.f; g.res0 = h1.p; g.ldr0 = h1.ld;
-                if (m.c != L.fc2.cin_pad) throw std::runtime_error("text encoder: fc2 channel mismatch");
-                launch_conv_into(c, g, *nxt);
-            }
-            c.ar->release(mk);
+            clip_layer(c, L, *cur, *nxt, cfg.heads, true, cfg.ln_eps);     // q * 64^-0.5, causal mask
             std::swap(cur, nxt);
         }
-        const Act& x = *cur;
-        Act y; y.p = out_hidden; y.n = B; y.h = T; y.w = 1; y.c = H; y.ld = H;
-        if (!c.dry()) {
-            c.check(ladi_launch_layernorm(x.p, x.ld, final_ln.g, final_ln.b, cfg.ln_eps, B * T, H, y.p, y.ld, st), "text final LN");
-            if (out_pooled) c.check(ladi_launch_gather_rows(out_hidden, d_eot, B, H, out_pooled, st), "text pooled");
-        }
-        if (c.err) { set_error("text encoder forward launch failure"); return -1; }
-    }
+        if (c.dry()) return;
+        c.check(ladi_launch_layernorm(cur->p, cur->ld, final_ln.g, final_ln.b, cfg.ln_eps, B * T, H, out_hidden, H, st), "text final LN");
+        if (out_pooled) c.check(ladi_launch_gather_rows(out_hidden, d_eot, B, H, out_pooled, st), "text pooled");
+    });
     return 0;
 }
 

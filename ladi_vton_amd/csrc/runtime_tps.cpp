@@ -150,11 +150,7 @@ int Tps::forward(const void* a, const void* b, int in_f32, int B, float* grid, f
     }
     // fp32 tensors from the caller (what src/inference.py:253 passes): the whole network runs in fp32 (runtime_f32.cpp)
     if (in_f32) return forward_f32(a, b, B, grid, coor, st);
-    for (int pass = 0; pass < 2; ++pass) {
-        arena.dry = (pass == 0);
-        if (pass == 1) arena.reserve(arena.peak);
-        arena.off = 0;
-        Ctx c; c.st = st; c.ar = &arena;
+    run_planned(arena, st, [&](Ctx& c) {
         auto extract = [&](const TpsExtract& e, const void* src, int cin) -> Act {
             Act x = c.new_act(B, H, W, e.conv[0].cin_pad);
             if (!c.dry()) {
@@ -201,7 +197,7 @@ int Tps::forward(const void* a, const void* b, int in_f32, int B, float* grid, f
             c.check(ladi_launch_small_linear(x.p, 0, feat, lin.w, lin.b, nullptr, 0, B, lin.cout, lin.cin, LADI_ACT_TANH, 0, co, 1, lin.cout, st), "regression linear");
             c.check(ladi_launch_tps_grid(co, d_inv, d_ctrl, N, B, H, W, grid, st), "tps grid");
         }
-    }
+    });
     return 0;
 }
 

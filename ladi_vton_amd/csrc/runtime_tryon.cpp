@@ -101,6 +101,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
         }
     }
 
+    int rc = 0;      // -5 / -6: time embedding / context failed in the real pass (the error is set; the streams are joined like on success)
     try {
         lanes.configure(n, lanes_override > 0 && (n % lanes_override) == 0 ? lanes_override : 0);
         for (int pass = 0; pass < 2; ++pass) {
@@ -112,7 +113,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 HIP_OK(hipMemsetAsync(d_step, 0, 2 * sizeof(int), st));    // evaluation index + the step kernel's arrival ticket
                 if (use_step_noise) HIP_OK(hipMemcpyAsync(step_noise_buf, step_noise_src, step_noise_bytes, hipMemcpyDeviceToDevice, st));
                 std::vector<float> tsf(timesteps.begin(), timesteps.end());
-                if (unet->compute_temb(tsf.data(), evals, st)) return -5;
+                if (unet->compute_temb(tsf.data(), evals, st)) { rc = -5; break; }
                 HIP_OK(hipEventRecord(ev[0], st));
             }
             // ---------------- persistent buffers for this call
@@ -144,7 +145,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                     HIP_OK(hipMemcpyAsync(ehs, in.negative_prompt_embeds, pe, hipMemcpyDeviceToDevice, st));
                     HIP_OK(hipMemcpyAsync(ehs + (size_t)B * L * D, in.prompt_embeds, pe, hipMemcpyDeviceToDevice, st));
                 } else HIP_OK(hipMemcpyAsync(ehs, in.prompt_embeds, pe, hipMemcpyDeviceToDevice, st));
-                if (unet->set_context(ehs, n, L, st)) return -6;
+                if (unet->set_context(ehs, n, L, st)) { rc = -6; break; }
             }
             // ---------------- 4. mask / masked image / pose (tryon_pipe.py:630-636)
             Act masked_img = c.new_act(B, H, W, 64);
@@ -290,13 +291,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
             }
             if (pass == 0) {
                 lanes.commit_plan();
-                arena.reserve(arena.peak + 4096);
-                if (c.stats_peak > stats_cap) {
-                    if (stats) (void)hipFree(stats);
-                    stats = nullptr;
-                    HIP_OK(hipMalloc(reinterpret_cast<void**>(&stats), c.stats_peak * sizeof(float)));
-                    stats_cap = c.stats_peak;
-                }
+                commit_plan(arena, c.stats_peak, &stats, &stats_cap);
             }
         }
         HIP_OK(hipEventRecord(ev_out, st));
@@ -307,7 +302,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
         (void)hipStreamWaitEvent(user_st, ev_out, 0);
         return -100;
     }
-    return 0;
+    return rc;
 }
 
 }  // namespace ladi

@@ -179,22 +179,9 @@ struct Fwd {
         const Act* resid = &x;
         if (r.has_sc) { ConvOpt os; sc = conv2d(c, r.sc, x, x2, os); resid = &sc; }
         else if (x2) throw std::runtime_error("resnet: concat input requires conv_shortcut");
-        ConvOpt o2; o2.res0 = resid;
-        Act y = conv2d_into(r.c2, s2, o2, out);
+        ConvOpt o2; o2.res0 = resid; o2.dst = &out;
+        (void)conv2d(c, r.c2, s2, nullptr, o2);
         c.ar->release(mk);
-        return y;
-    }
-    // conv writing into a pre-allocated output
-    Act conv2d_into(const DConv& cv, const Act& x, ConvOpt o, Act out) {
-        IGemmArgs a; std::memset(&a, 0, sizeof(a));
-        a.src0 = x.p; a.C0 = x.c; a.ld0 = x.ld;
-        a.Hs = x.h; a.Ws = x.w; a.Ho = out.h; a.Wo = out.w; a.P = out.n * out.h * out.w;
-        a.ksize = cv.k; a.stride = 1; a.pad = cv.k / 2; a.ups = 0;
-        a.W = cv.w; a.Q = cv.cout; a.K = cv.K();
-        a.bias = cv.b; a.act = o.act; a.out_scale = 1.f;
-        if (o.res0) { a.res0 = o.res0->p; a.ldr0 = o.res0->ld; }
-        if (o.res1) { a.res1 = o.res1->p; a.ldr1 = o.res1->ld; }
-        launch_conv_into(c, a, out);
         return out;
     }
     Act attn(const h16* q, int ldq, long long sq, const h16* k, const h16* v, int ldkv, long long skv, int n, int T, int Nk,
@@ -273,8 +260,8 @@ struct Fwd {
         }
         Act xin = x; xin.h = T; xin.w = 1;
         Act outv = out; outv.h = T; outv.w = 1;
-        ConvOpt oo; oo.res0 = &xin;
-        outv = conv2d_into(b.proj_out, t3, oo, outv);
+        ConvOpt oo; oo.res0 = &xin; oo.dst = &outv;
+        (void)conv2d(c, b.proj_out, t3, nullptr, oo);
         out.st_part = outv.st_part; out.st_px = outv.st_px;
         c.ar->release(mk);
         return out;
@@ -326,7 +313,8 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
     Act g = group_norm(c, norm_out, h, nullptr, cfg.groups, cfg.eps, 1);
     ConvOpt oc; oc.out_ld = 4;
     if (cfg.out_channels > 4) oc.out_ld = (cfg.out_channels + 3) / 4 * 4;
-    if (eps_out) return f.conv2d_into(conv_out, g, oc, *eps_out);     // a sample-group lane writes its rows of the shared output
+    Act eps;
+    if (eps_out) { eps = *eps_out; oc.dst = &eps; }     // a sample-group lane writes its rows of the shared output
     return conv2d(c, conv_out, g, nullptr, oc);
 }
 

@@ -138,16 +138,8 @@ struct VF {
         Act s2 = group_norm(c, r.n2, h1, nullptr, v.cfg.groups, v.cfg.eps, 1);
         Act sc; const Act* resid = &x;
         if (r.has_sc) { ConvOpt os; os.bias_mul = s; sc = conv2d(c, r.sc, x, nullptr, os); resid = &sc; }
-        {
-            IGemmArgs a; std::memset(&a, 0, sizeof(a));
-            a.src0 = s2.p; a.C0 = s2.c; a.ld0 = s2.ld;
-            a.Hs = x.h; a.Ws = x.w; a.Ho = x.h; a.Wo = x.w; a.P = (int)x.pixels();
-            a.ksize = 3; a.stride = 1; a.pad = 1;
-            a.W = r.c2.w; a.Q = r.c2.cout; a.K = r.c2.K(); a.bias = r.c2.b; a.out_scale = s;
-            a.res0 = resid->p; a.ldr0 = resid->ld;
-            if (extra) { a.res1 = extra->p; a.ldr1 = extra->ld; }
-            launch_conv_into(c, a, out);
-        }
+        ConvOpt o2; o2.out_scale = s; o2.res0 = resid; o2.res1 = extra; o2.dst = &out;
+        (void)conv2d(c, r.c2, s2, nullptr, o2);
         c.ar->release(mk);
         return out;
     }
@@ -198,13 +190,13 @@ struct VF {
             a.out_scale = 1.f; a.out = o.p; a.ldo = C; a.bs_out = (long long)T * C;
             c.check(ladi_launch_igemm(a, n, 0, c.st), "igemm(PV)");
             }
-            // proj_attn + residual
-            std::memset(&a, 0, sizeof(a));
-            a.src0 = o.p; a.C0 = C; a.ld0 = C; a.Hs = n * T; a.Ws = 1; a.Ho = n * T; a.Wo = 1; a.P = n * T;
-            a.ksize = 1; a.stride = 1; a.W = at.proj.w; a.Q = C; a.K = at.proj.K(); a.bias = at.proj.b; a.out_scale = s;
-            a.res0 = x.p; a.ldr0 = x.ld;
-            launch_conv_into(c, a, out);
         }
+        // proj_attn + residual, over the n * T tokens as one sequence
+        Act ov = o; ov.n = 1; ov.h = n * T;
+        Act outv = out; outv.n = 1; outv.h = n * T; outv.w = 1;
+        ConvOpt opj; opj.out_scale = s; opj.res0 = &x; opj.dst = &outv;
+        (void)conv2d(c, at.proj, ov, nullptr, opj);
+        out.st_part = outv.st_part; out.st_px = outv.st_px;
         c.ar->release(mk);
         return out;
     }
@@ -302,14 +294,9 @@ void EMASC::forward(Ctx& c, const Act* feats, const h16* const* masks, Act* outs
         const size_t mk = c.ar->mark();
         ConvOpt oa; oa.act = LADI_ACT_SILU;
         Act t = conv2d(c, a[i], feats[i], nullptr, oa);
-        if (!c.dry()) {
-            IGemmArgs g; std::memset(&g, 0, sizeof(g));
-            g.src0 = t.p; g.C0 = t.c; g.ld0 = t.ld; g.Hs = t.h; g.Ws = t.w; g.Ho = t.h; g.Wo = t.w; g.P = (int)t.pixels();
-            g.ksize = 3; g.stride = 1; g.pad = 1; g.W = b[i].w; g.Q = b[i].cout; g.K = b[i].K(); g.bias = b[i].b; g.out_scale = 1.f;
-            g.mask = masks ? masks[i] : nullptr;  // mask_features fused: out *= (1 - mask)
-            g.out = outs[i].p; g.ldo = outs[i].ld;
-            c.check(ladi_launch_igemm(g, 1, 0, c.st), "igemm(emasc)");
-        }
+        ConvOpt ob; ob.mask = masks ? masks[i] : nullptr;  // mask_features fused: out *= (1 - mask)
+        ob.dst = &outs[i];
+        (void)conv2d(c, b[i], t, nullptr, ob);
         c.ar->release(mk);
     }
 }
@@ -335,11 +322,7 @@ int Adapter::forward(const h16* x, int B, int T, h16* out, hipStream_t st) {
     // Only the CLS row of the encoder layer output is consumed (inversion_adapter.py:26): K/V need all T tokens,
     // everything downstream of the scores only row 0.
     const int H = cfg.hidden, d = H / cfg.heads;
-    for (int pass = 0; pass < 2; ++pass) {
-        arena.dry = (pass == 0);
-        if (pass == 1) arena.reserve(arena.peak);
-        arena.off = 0;
-        Ctx c; c.st = st; c.ar = &arena;
+    run_planned(arena, st, [&](Ctx& c) {
         Act xin; xin.p = const_cast<h16*>(x); xin.n = B; xin.h = T; xin.w = 1; xin.c = H; xin.ld = H;
         Act a1 = layer_norm(c, ln1, xin, cfg.ln_eps);                         // [B][T][H]
         ConvOpt op;
@@ -353,7 +336,7 @@ int Adapter::forward(const h16* x, int B, int T, h16* out, hipStream_t st) {
         h16* n3 = c.alloc_h16((size_t)B * H);
         h16* g1 = c.alloc_h16((size_t)B * cfg.head_hidden);
         h16* g2 = c.alloc_h16((size_t)B * cfg.head_hidden);
-        if (c.dry()) continue;
+        if (c.dry()) return;
         const int ldrow = T * H;  // CLS rows of [B][T][H]
         int rc = 0;
         // q = q_proj(LN1(x))[CLS]  (HF CLIPAttention scales q by d^-0.5 -> applied as the softmax scale)
@@ -369,8 +352,8 @@ int Adapter::forward(const h16* x, int B, int T, h16* out, hipStream_t st) {
         rc |= ladi_launch_small_linear(n3, 0, H, l0.w, l0.b, nullptr, 0, B, cfg.head_hidden, l0.cin_pad, LADI_ACT_GELU, 0, g1, 0, cfg.head_hidden, st);
         rc |= ladi_launch_small_linear(g1, 0, cfg.head_hidden, l3.w, l3.b, nullptr, 0, B, cfg.head_hidden, l3.cin_pad, LADI_ACT_GELU, 0, g2, 0, cfg.head_hidden, st);
         rc |= ladi_launch_small_linear(g2, 0, cfg.head_hidden, l6.w, l6.b, nullptr, 0, B, cfg.out_dim, l6.cin_pad, LADI_ACT_NONE, 0, out, 0, cfg.out_dim, st);
-        if (rc) { set_error("adapter forward launch failure"); return -1; }
-    }
+        if (rc) throw std::runtime_error("adapter forward launch failure");
+    });
     return 0;
 }
 

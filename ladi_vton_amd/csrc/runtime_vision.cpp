@@ -29,27 +29,13 @@ void VisionEncoder::load(const VisionCfg& c, const WeightStore& ws) {
     posc = pool.upload_h16(pc);
     pre_ln = load_norm(pool, ws, pre + "pre_layrnorm");      // (sic: the key is misspelled upstream)
     post_ln = load_norm(pool, ws, pre + "post_layernorm");
-    layers.resize(c.layers);
-    for (int i = 0; i < c.layers; ++i) {
-        const std::string e = pre + "encoder.layers." + std::to_string(i);
-        TextLayer& L = layers[i];
-        L.ln1 = load_norm(pool, ws, e + ".layer_norm1");
-        L.ln2 = load_norm(pool, ws, e + ".layer_norm2");
-        L.qkv = load_linear_cat(pool, ws, {e + ".self_attn.q_proj", e + ".self_attn.k_proj", e + ".self_attn.v_proj"}, true);
-        L.o = load_conv(pool, ws, e + ".self_attn.out_proj");
-        L.fc1 = load_conv(pool, ws, e + ".mlp.fc1");
-        L.fc2 = load_conv(pool, ws, e + ".mlp.fc2");
-    }
+    layers = load_clip_layers(pool, ws, pre + "encoder.layers.", c.layers);
 }
 
 int VisionEncoder::forward(const void* pixels, int in_f32, int B, h16* out_hidden, h16* out_pooled, hipStream_t st) {
     if (B <= 0) { set_error("vision encoder: bad batch"); return -1; }
-    const int H = cfg.hidden, T = tokens(), d = H / cfg.heads;
-    for (int pass = 0; pass < 2; ++pass) {
-        arena.dry = (pass == 0);
-        if (pass == 1) arena.reserve(arena.peak);
-        arena.off = 0;
-        Ctx c; c.st = st; c.ar = &arena;
+    const int H = cfg.hidden, T = tokens();
+    run_planned(arena, st, [&](Ctx& c) {
         Act xa = c.new_act(B, T, 1, H), xb = c.new_act(B, T, 1, H);   // residual stream, ping-pong
         Act* cur = &xa; Act* nxt = &xb;
         {   // embeddings: patch rows -> GEMM (+ position / class embeddings as the residual, shared by every image) -> pre_layrnorm
@@ -69,44 +55,14 @@ int VisionEncoder::forward(const void* pixels, int in_f32, int B, h16* out_hidde
             }
             c.ar->release(mk);
         }
+        Act last = xa; last.p = out_hidden; last.ld = H;      // the last block writes straight into the caller's buffer
         for (const TextLayer& L : layers) {
-            const size_t mk = c.ar->mark();
-            Act a = layer_norm(c, L.ln1, *cur, cfg.ln_eps);
-            ConvOpt op;
-            Act qkv = conv2d(c, L.qkv, a, nullptr, op);            // [B*T][3H], bias fused
-            Act ao = c.new_act(B, T, 1, H);
-            if (!c.dry()) {
-                AttnArgs aa;
-                aa.q = qkv.p; aa.k = qkv.p + H; aa.v = qkv.p + 2 * H; aa.o = ao.p;
-                aa.ldq = aa.ldk = aa.ldv = qkv.ld; aa.ldo = ao.ld;
-                aa.sq = aa.sk = aa.sv = (long long)T * qkv.ld; aa.so = (long long)T * ao.ld;
-                aa.n = B; aa.heads = cfg.heads; aa.Nq = T; aa.Nk = T; aa.scale = 1.f / std::sqrt((float)d);
-                if (d == 64) c.check(ladi_launch_flash_attn64(aa, st), "vision attention");
-                else c.check(ladi_launch_attn_generic(aa, d, st), "vision attention");
-            }
-            ConvOpt oo; oo.res0 = cur;
-            Act h1 = conv2d(c, L.o, ao, nullptr, oo);              // x + out_proj(attn)
-            Act a2 = layer_norm(c, L.ln2, h1, cfg.ln_eps);
-            ConvOpt o1; o1.act = LADI_ACT_GELU;
-            Act m = conv2d(c, L.fc1, a2, nullptr, o1);
-            {
-                IGemmArgs g;
-                std::memset(&g, 0, sizeof(g));
-                g.src0 = m.p; g.C0 = m.c; g.ld0 = m.ld; g.Hs = T; g.Ws = 1; g.Ho = T; g.Wo = 1; g.P = B * T;
-                g.ksize = 1; g.stride = 1; g.pad = 0; g.W = L.fc2.w; g.Q = L.fc2.cout; g.K = L.fc2.K(); g.bias = L.fc2.b;
-                g.act = LADI_ACT_NONE; g.out_scale = 1.f; g.res0 = h1.p; g.ldr0 = h1.ld;
-                if (m.c != L.fc2.cin_pad) throw std::runtime_error("vision encoder: fc2 channel mismatch");
-                // the last block writes straight into the caller's buffer
-                Act dst = *nxt;
-                if (&L == &layers.back()) { dst.p = out_hidden; dst.ld = H; }
-                launch_conv_into(c, g, dst);
-            }
-            c.ar->release(mk);
+            clip_layer(c, L, *cur, &L == &layers.back() ? last : *nxt, cfg.heads, false, cfg.ln_eps);
             std::swap(cur, nxt);
         }
         if (!c.dry() && out_pooled)
             c.check(ladi_launch_layernorm(out_hidden, T * H, post_ln.g, post_ln.b, cfg.ln_eps, B, H, out_pooled, H, st), "post_layernorm");
-    }
+    });
     return 0;
 }
 
