@@ -336,6 +336,12 @@ int ladi_profile_igemm_symbols(char* buf, int n);
 /* number of tile configurations (valid ids 1..count) and the kernel symbol configuration `cfg` launches, as rocprofv3 names it
  * (split-K variants share the symbol of their base tile); "" for an unknown id.  The string is owned by the library. */
 int ladi_igemm_cfg_count(void);
+/* what the LAST implicit-GEMM launch of this process did, as recorded by the launcher that computed its grid (not a restatement of the rule):
+ * out[0] kernel family (1 ring, 2 igemm8, 3 loader / consumer, 4 halo, 5 X-stationary linear), out[1] tile_map as the kernel received it
+ * (0 plain, 1 pixel tiles over the XCDs, 2 channel tiles over the XCDs, 3 | G << 4 weight-slice-major with groups of G pixel tiles),
+ * out[2] split-K factor (1 = none), out[3] workgroups per grid plane (0 for family 5).  A launch with tile_cfg = 0 that tunes first reports
+ * the launch that produced the output (the last one).  Not thread-safe, like the handles. */
+int ladi_igemm_last_launch(int out[4]);
 const char* ladi_igemm_cfg_symbol_name(int cfg);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -362,6 +368,9 @@ int ladi_op_igemm(const ladi_igemm_desc* d, int batch, int tile_cfg, void* strea
 int ladi_op_group_norm(const void* src0, int C0, const void* src1, int C1, int n, int HW, int groups, const void* gamma,
                        const void* beta, float eps, int silu, const void* add, void* out, float* stats_scratch, void* stream);
 int ladi_op_layer_norm(const void* x, const void* gamma, const void* beta, float eps, int rows, int C, void* out, void* stream);
+/* the same on strided rows: x [rows][ldx], out [rows][ldo] (ldx, ldo >= C, multiples of 8; columns [C, ld) are neither read nor written) */
+int ladi_op_layer_norm_ld(const void* x, int ldx, const void* gamma, const void* beta, float eps, int rows, int C, void* out, int ldo,
+                          void* stream);
 /* Fused sub-blocks of diffusers' BasicTransformerBlock on the 320-channel level (5 heads of 64), fp16 operands in torch layout:
  *   xattn: out = x + to_out(softmax(to_q(LayerNorm(x)) K^T / 8) V) with kv = [n][L][640] rows (K | V of the context, L <= 96), x / out [n*T][320],
  *          T % 128 == 0 (norm2 / attn2 of the block: tryon_pipe.py:732 -> UNet2DConditionModel -> Transformer2DModel);

@@ -150,10 +150,12 @@ SIGNATURES = {
     "ladi_profile_igemm_collect": (c_int, [POINTER(ctypes.c_double), c_int]),
     "ladi_profile_igemm_symbols": (c_int, [ctypes.c_char_p, c_int]),
     "ladi_igemm_cfg_count": (c_int, []),
+    "ladi_igemm_last_launch": (c_int, [POINTER(c_int)]),
     "ladi_igemm_cfg_symbol_name": (ctypes.c_char_p, [c_int]),
     "ladi_op_igemm": (c_int, [POINTER(IGemmDesc), c_int, c_int, _P]),
     "ladi_op_group_norm": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, c_float, c_int, _P, _P, _P, _P]),
     "ladi_op_layer_norm": (c_int, [_P, _P, _P, c_float, c_int, c_int, _P, _P]),
+    "ladi_op_layer_norm_ld": (c_int, [_P, c_int, _P, _P, c_float, c_int, c_int, _P, c_int, _P]),
     "ladi_op_xattn_block": (c_int, [_P, _P, _P, c_float, _P, _P, c_int, _P, _P, c_int, c_int, _P, _P]),
     "ladi_op_ff_block": (c_int, [_P, _P, _P, c_float, _P, _P, _P, _P, c_int, _P, _P]),
     "ladi_op_attention": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_longlong,

@@ -623,6 +623,11 @@ void ladi_profile_igemm_enable(int on) { ladi_igemm_profile_enable(on); }
 int ladi_profile_igemm_collect(double* out, int n_out) { return ladi_igemm_profile_collect(out, n_out); }
 int ladi_profile_igemm_symbols(char* buf, int n) { return ladi_igemm_profile_symbols(buf, n); }
 int ladi_igemm_cfg_count(void) { return ladi_igemm_num_cfgs(); }
+int ladi_igemm_last_launch(int out[4]) {
+    if (!out) return -1;
+    ladi_igemm_last_launch_info(out);
+    return 0;
+}
 const char* ladi_igemm_cfg_symbol_name(int cfg) { return ladi_igemm_cfg_symbol(cfg); }
 
 // ------------------------------------------------------------------------------------------------ op level
@@ -690,6 +695,9 @@ int ladi_op_ff_block(const void* x, const void* ln_gamma, const void* ln_beta, f
 }
 int ladi_op_layer_norm(const void* x, const void* gamma, const void* beta, float eps, int rows, int C, void* out, void* stream) {
     return ladi_launch_layernorm((const h16*)x, C, (const h16*)gamma, (const h16*)beta, eps, rows, C, (h16*)out, C, S(stream));
+}
+int ladi_op_layer_norm_ld(const void* x, int ldx, const void* gamma, const void* beta, float eps, int rows, int C, void* out, int ldo, void* stream) {
+    return ladi_launch_layernorm((const h16*)x, ldx, (const h16*)gamma, (const h16*)beta, eps, rows, C, (h16*)out, ldo, S(stream));
 }
 int ladi_op_attention(const void* q, const void* k, const void* v, void* o, int ldq, int ldk, int ldv, int ldo, long long sq, long long sk,
                       long long sv, long long so, int n, int heads, int Nq, int Nk, float scale, void* stream) {

@@ -442,6 +442,12 @@ void tune_cache_append(const TuneKey& k, int cfg) {
 }  // namespace
 
 int ladi_igemm_num_cfgs() { return NCFG; }
+
+static int g_last_launch[4] = {0, 0, 0, 0};     // {family, tile_map, split factor, blocks} of the last launch (igemm_common.h)
+void ladi_igemm_note_launch(int family, int tile_map, int splitk, int blocks) {
+    g_last_launch[0] = family; g_last_launch[1] = tile_map; g_last_launch[2] = splitk; g_last_launch[3] = blocks;
+}
+void ladi_igemm_last_launch_info(int out[4]) { for (int i = 0; i < 4; ++i) out[i] = g_last_launch[i]; }
 // kernel symbol (as rocprofv3 prints it, without the "void " / argument list) a tile configuration launches; "" for an unknown id
 const char* ladi_igemm_cfg_symbol(int cfg) {
     static std::string names[NCFG + 1];
@@ -649,6 +655,7 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
     } else a.splitk = 1;
     const int batch_l = lbatch;
     int rc;
+    ladi_igemm_note_launch(is_xs(kCfg[cfg].base) ? 5 : 0, 0, 1, 0);   // the tiled launchers overwrite it where they compute their grid
     rc = launch_base(cfg, a, batch_l, st);
     if (rc == 0 && split > 1 && !sk_inline) {
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((full.P + 31) / 32), (unsigned)((full.Q + 63) / 64)), dim3(256), 0, st, ws, split, full);

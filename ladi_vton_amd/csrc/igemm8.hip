@@ -279,6 +279,7 @@ int launch_cfg8(IGemmArgs a, int batch, hipStream_t st) {
         if (np >= 16) { a.tile_map = 1; blocks = 8 * ((np + 7) / 8) * nq; }
         else if (nq >= 16) { a.tile_map = 2; blocks = 8 * ((nq + 7) / 8) * np; }
     }
+    ladi_igemm_note_launch(2, a.tile_map, a.splitk > 1 ? a.splitk : 1, blocks);
     dim3 grid((unsigned)blocks, 1, (unsigned)batch);
     hipLaunchKernelGGL(kfn, grid, dim3(512), SMEM, st, a);
     return hipGetLastError() == hipSuccess ? 0 : -11;

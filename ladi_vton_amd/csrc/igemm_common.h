@@ -2,6 +2,11 @@
 #pragma once
 #include "common.h"
 
+// what the last implicit-GEMM launch of this process did (igemm.hip; tests query it through ladi_igemm_last_launch): every launcher records
+// it where it computes its grid.  family: 1 ring (igemm_kernel.h), 2 igemm8, 3 loader / consumer, 4 halo, 5 X-stationary linear (recorded by
+// ladi_launch_igemm: that kernel has no tile map); tile_map as the kernel receives it (map 3 carries G in bits 4 and up)
+void ladi_igemm_note_launch(int family, int tile_map, int splitk, int blocks);
+
 namespace {
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;

@@ -414,6 +414,7 @@ int launch_halo(IGemmArgs a, int batch, hipStream_t st) {
             if (G <= 255 && units >= 8) { a.tile_map = 3 | (G << 4); blocks = 8 * ((units + 7) / 8) * G; gz = 1; }
         }
     }
+    ladi_igemm_note_launch(4, a.tile_map, a.splitk > 1 ? a.splitk : 1, blocks);
     dim3 grid((unsigned)blocks, 1, (unsigned)gz);
     hipLaunchKernelGGL(kfn, grid, dim3(128 * WPN), SMEM, st, a);
     return hipGetLastError() == hipSuccess ? 0 : -11;

@@ -242,6 +242,8 @@ void ladi_igemm_autotune(int on);   // measured tile-shape selection on first us
 void ladi_igemm_splitk_two_pass(int on);   // 1: split-K launches use the separate reduce pass (A/B switch; default: in-launch combine)
 int ladi_igemm_tuned_count();
 int ladi_igemm_num_cfgs();
+// {kernel family, tile_map, split factor, blocks} of the last implicit-GEMM launch (igemm_common.h ladi_igemm_note_launch)
+void ladi_igemm_last_launch_info(int out[4]);
 const char* ladi_igemm_cfg_symbol(int cfg);
 int ladi_igemm_profile_collect(double* out, int n_out);
 // the same records grouped by kernel SYMBOL (exact rocprofv3 name): lines "symbol\tms\tflop\tlaunches\n" into buf (truncated at n); does

@@ -142,3 +142,325 @@ def record_parity(key, value, name=None):
         json.dump(blob, open(path, "w"), indent=1, sort_keys=True)
     except OSError:
         pass
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------------
+# Strided, offset views with poisoned surroundings (tests/test_gpu_views.py, tests/test_cpu_views.py)
+#
+# The product hands every kernel views into a bump arena: q / k / v are column slices of the fused QKV buffer, convolutions write into
+# out_ld 4 / 8 buffers and into caller views, LayerNorm runs on x.ld.  guarded() reproduces that placement for one operand and fills
+# everything the contract (include/ladi_native.h) says the kernel does not use with NaN, assert_untouched() checks that a launch left every
+# such element bit-identical, and check_elem() judges the result element by element against a float64 reference.
+# ----------------------------------------------------------------------------------------------------------------------------------------
+POISON16 = 0x7E5A                   # an fp16 quiet NaN with a payload no arithmetic produces
+POISON32 = 0x7FC5A5A5               # the same for fp32
+
+
+class Guarded:
+    """one operand inside its poisoned allocation: .buf the whole 1-D device buffer, .view the [rows, C] strided device view of the operand
+    (row stride .ld elements), .ptr its address, .pre / .post the poison rows before / after it"""
+
+    def __init__(self, buf, rows, C, ld, pre, post):
+        self.buf, self.rows, self.C, self.ld, self.pre, self.post = buf, rows, C, ld, pre, post
+        self.view = buf.as_strided((rows, C), (ld, 1), pre * ld)
+        self.ptr = self.view.data_ptr()
+
+    def col(self, c0):
+        """address of column c0 of the view's first row (q / k / v slices of a fused buffer)"""
+        return self.ptr + c0 * self.buf.element_size()
+
+    def cpu(self):
+        return self.view.cpu()
+
+    def _bits(self):
+        return self.buf.view(torch.int16 if self.buf.dtype == torch.float16 else torch.int32).cpu()
+
+    def poison_mask(self):
+        """bool [pre + rows + post, ld]: True where the allocation holds poison (outside the view)"""
+        m = torch.ones((self.pre + self.rows + self.post, self.ld), dtype=torch.bool)
+        m[self.pre:self.pre + self.rows, :self.C] = False
+        return m
+
+
+def _poison_word(dtype):
+    # the int16 / int32 value with the poison's bit pattern (two's complement for the sign-less patterns above: both are < 2^15 / 2^31)
+    return (torch.int16, POISON16) if dtype == torch.float16 else (torch.int32, POISON32)
+
+
+def guarded(t, ld=None, pre_rows=2, post_rows=2, device=None):
+    """Place an fp16 / fp32 operand t ([rows, C], or NHWC [N, H, W, C] flattened to pixel rows; CPU or GPU) inside a larger device buffer of
+    NaN: pre_rows rows of poison, then the rows of t at row stride ld (default C: dense), columns [C, ld) of every row poison, then post_rows
+    rows of poison.  ld % 8 == 0 (ld % 4 == 0 is accepted for the two strides the ABI itself defines that way: out_ld = 4 of the UNet's output
+    layer and the V^T rows of the wide attention) and pre_rows rounded up to the next count that puts the view on a 16-byte boundary of the
+    torch allocator's 256-byte aligned block, as every launcher requires.
+    What t itself holds is the caller's business: channel padding the contract defines as ZERO (nhwc16's padding to 64, packed-weight padding)
+    is part of t and stays zero.  device: default the GPU ("cpu" for the harness's own CPU test).  Returns a Guarded."""
+    assert t.dtype in (torch.float16, torch.float32)
+    t2 = t.reshape(-1, t.shape[-1])
+    rows, C = t2.shape
+    ld = C if ld is None else ld
+    assert ld >= C and ld % 4 == 0, (C, ld)
+    while (pre_rows * ld * t.element_size()) % 16:
+        pre_rows += 1
+    it, word = _poison_word(t.dtype)
+    device = dev() if device is None else torch.device(device)
+    buf = torch.full(((pre_rows + rows + post_rows) * ld,), word, dtype=it, device=device).view(t.dtype)
+    g = Guarded(buf, rows, C, ld, pre_rows, post_rows)
+    g.view.copy_(t2.to(device))
+    assert g.ptr % 16 == 0
+    return g
+
+
+def guarded_out(rows, C, ld=None, pre_rows=2, post_rows=2, dtype=torch.float16, device=None):
+    """an OUTPUT placed like guarded(): the view itself starts as NaN too, so an element the kernel never wrote fails check_elem"""
+    return guarded(torch.full((rows, C), float("nan"), dtype=dtype), ld, pre_rows, post_rows, device)
+
+
+def assert_untouched(g, what=""):
+    """every poison element of g's allocation is still bit-identical (raw 16 / 32-bit patterns: NaN != NaN)"""
+    _, word = _poison_word(g.buf.dtype)
+    bits = g._bits().reshape(g.pre + g.rows + g.post, g.ld)
+    bad = (bits != word) & g.poison_mask()
+    if bool(bad.any()):
+        r, c = (int(v) for v in bad.nonzero()[0])
+        raise AssertionError("%s: %d poison elements were overwritten; first at allocation row %d (view row %d of %d), column %d (C = %d, ld = %d): "
+                             "bits 0x%X" % (what, int(bad.sum()), r, r - g.pre, g.rows, c, g.C, g.ld, int(bits[r, c]) & (0xFFFF if g.buf.dtype == torch.float16 else 0xFFFFFFFF)))
+
+
+U16 = 2.0 ** -11       # unit roundoff of fp16 (round to nearest): |fp16(x) - x| <= U16 |x| for normal x
+U32 = 2.0 ** -24       # unit roundoff of fp32
+
+
+def ulp16(x):
+    """spacing of fp16 numbers at |x| (float64 tensor): 2^(floor(log2 |x|) - 10), 2^-24 in the subnormal range.  Rounding a real to fp16
+    moves it by at most half of this; check_elem grants one whole spacing so that a reference a hair below a binade boundary does not halve
+    the allowance of a result a hair above it."""
+    a = x.double().abs().clamp_min(2.0 ** -14)
+    return torch.exp2(torch.floor(torch.log2(a)) - 10.0)
+
+
+def check_elem(got, ref, bound, what, locate=None):
+    """Per-element check |got - ref| <= ulp16(ref) + bound.  got: the kernel's output (any float dtype, CPU), ref: float64 reference,
+    bound: float64 tensor (or scalar) >= 0 derived from the reference alone (the *_bound helpers below) for everything between the exact
+    result and the value that is finally rounded to fp16.  A non-finite output element fails by itself.  locate(flat_index) -> str names
+    the failing element for the message (pixel, channel, tile).  Returns the worst err / (ulp16(ref) + bound), the margin the tests record."""
+    got, ref = got.double(), ref.double()
+    assert got.shape == ref.shape, (what, tuple(got.shape), tuple(ref.shape))
+    bound = torch.as_tensor(bound, dtype=torch.float64).expand_as(ref)
+    assert bool(torch.isfinite(ref).all()) and bool((bound >= 0).all()), what
+    fin = torch.isfinite(got)
+    if not bool(fin.all()):
+        i = int((~fin).reshape(-1).nonzero()[0])
+        raise AssertionError("%s: %d non-finite output elements; first at flat index %d %s: got %r, ref %.6g"
+                             % (what, int((~fin).sum()), i, locate(i) if locate else "", float(got.reshape(-1)[i]), float(ref.reshape(-1)[i])))
+    err = (got - ref).abs()
+    lim = ulp16(ref) + bound
+    ratio = err / lim
+    bad = err > lim
+    if bool(bad.any()):
+        i = int(torch.where(bad.reshape(-1), ratio.reshape(-1), torch.zeros(())).argmax())
+        f = int(bad.reshape(-1).nonzero()[0])
+        raise AssertionError("%s: %d of %d elements outside ulp16(ref) + bound; first at flat index %d %s; worst at %d %s: got %.6g, ref %.6g, "
+                             "err %.3g, limit %.3g (ulp16 %.3g + bound %.3g)"
+                             % (what, int(bad.sum()), bad.numel(), f, locate(f) if locate else "", i, locate(i) if locate else "",
+                                float(got.reshape(-1)[i]), float(ref.reshape(-1)[i]), float(err.reshape(-1)[i]), float(lim.reshape(-1)[i]),
+                                float(ulp16(ref).reshape(-1)[i]), float(bound.reshape(-1)[i])))
+    return float(ratio.max())
+
+
+# Lipschitz constants of the epilogue's activations (sup |f'|): SiLU 1.0999 at x = 2.3994, exact GELU 1.1290 at x = sqrt(2), ReLU / none 1
+ACT_LIP = dict(none=1.0, relu=1.0, silu=1.1, gelu=1.13)
+# fp32 evaluation of an activation with the hardware's fast exp / reciprocal (v_exp_f32 and v_rcp_f32 are specified to 1 ulp, the erf / tanh
+# polynomial a few more): 16 fp32 ulps of the result, a documented allowance, not a measurement
+ACT_EVAL = 16.0 * U32
+GELU_ERF_ABS = 1.5e-7               # |error| of the erf approximation the library's gelu_f uses (Abramowitz & Stegun 7.1.26, csrc/common.h): an
+                                    # ABSOLUTE error of erf, so gelu(x) = x (1 + erf(x / sqrt 2)) / 2 carries |x| GELU_ERF_ABS / 2 on top
+
+
+def _act_eval_err(x, t, act):
+    """error of evaluating t = act(x) in fp32 (x exact)"""
+    if act == "none":
+        return torch.zeros_like(t)
+    e = ACT_EVAL * t.abs()
+    return e + 0.5 * GELU_ERF_ABS * x.abs() if act == "gelu" else e
+
+
+def _act64(x, act):
+    import torch.nn.functional as F
+    return dict(none=lambda v: v, relu=F.relu, silu=F.silu, gelu=F.gelu)[act](x)
+
+
+def conv_ref_bound(x, w, bias=None, rowadd=None, act="none", res=None, mask=None, stride=1, padding=1, x_err=None):
+    """float64 reference and the derived error bound of ladi_op_igemm's convolution / linear epilogue
+        out = fp16( fp16( act(conv(x, w) + bias + rowadd) ) + res ) * (1 - mask)
+    x [N, C, H, W] (already padded / upsampled as the case needs), w [Q, C, k, k], all values fp16-representable.
+
+    Derivation (u = 2^-24, the fp32 unit roundoff).  The kernels accumulate the K = C k k products in fp32; products of two fp16 values are
+    exact in fp32, so the only error of s = conv(x, w) is the summation's.  For ANY order of an fp32 sum of K terms the running-error bound is
+        |fl(s) - s| <= K u (|w| (*) |x|)                                  (Higham, Accuracy and Stability, eq. 4.4 with gamma_K ~ K u),
+    where |w| (*) |x| is the same convolution applied to absolute values -- computed here by the same float64 code.  bias and rowadd are
+    added in fp32: two more roundings of a value no larger than A = |w| (*) |x| + |bias| + |rowadd|, so e_pre = (K + 2) u A.
+    An operand the kernel first normalises and rounds to fp16 (fused LayerNorm / GroupNorm affine) enters with a per-element perturbation
+    x_err >= 0 (same shape as x); it reaches the sum as |w| (*) x_err, added to e_pre.
+    The activation f propagates e_pre by its Lipschitz constant (ACT_LIP) and is itself evaluated in fp32 with fast intrinsics:
+    e_act = L e_pre + ACT_EVAL |f|.  Without a residual that is the whole bound: the one fp16 rounding left is check_elem's ulp16(ref).
+    With a residual the epilogue rounds t = f(...) to fp16 BEFORE the residual is added in fp32 (the rounding point of every epilogue of the
+    library: igemm_common.h step (1) / (2)), so the bound gains half an ulp16 for that rounding -- evaluated at |t| + e_act so that
+    the binade of the computed t is covered -- plus one fp32 rounding of the sum, u |ref|.  The mask multiplies by exactly 0 or 1.
+    Returns (ref, bound), float64 [N, Q, Ho, Wo]."""
+    import torch.nn.functional as F
+    x, w = x.double(), w.double()
+    K = w.shape[1] * w.shape[2] * w.shape[3]
+    s = F.conv2d(x, w, stride=stride, padding=padding)
+    e = torch.zeros_like(s)
+    xa = x.abs()
+    if x_err is not None:
+        e = e + F.conv2d(x_err.double(), w.abs(), stride=stride, padding=padding)
+        xa = xa + x_err.double()                      # the summation bound is over the operand the kernel actually multiplies
+    A = F.conv2d(xa, w.abs(), stride=stride, padding=padding)
+    for v in (bias, rowadd):
+        if v is not None:
+            s = s + v.double()[None, :, None, None]
+            A = A + v.double().abs()[None, :, None, None]
+    e = e + (K + 2) * U32 * A
+    t = _act64(s, act)
+    e = ACT_LIP[act] * e + _act_eval_err(s, t, act)
+    ref = t
+    if res is not None:
+        ref = t + res.double()
+        e = e + 0.5 * ulp16(t.abs() + e) + U32 * ref.abs()
+    if mask is not None:
+        ref = ref * (1.0 - mask.double())
+        e = e * (1.0 - mask.double())
+    return ref, e
+
+
+def geglu_ref_bound(x, w, b, x_err=None):
+    """out = (u + bu) * gelu(g + bg) with (u | g) = x w^T, x [T, C], w [2 Qh, C] (torch order: value rows, then gate rows), float64.
+    Both halves carry the summation bound of conv_ref_bound, e = (K + 2) u (|w| |x| + |b|) (+ |w| x_err); the product rule gives
+        |d(u gelu(g))| <= |gelu(g)| e_u + |u| d_g + e_u d_g,  d_g = L e_g + (evaluation error of gelu),  and one fp32 rounding of the product, u |ref|."""
+    import torch.nn.functional as F
+    x, w, b = x.double(), w.double(), b.double()
+    K = x.shape[1]
+    s = x @ w.t() + b
+    e = (K + 2) * U32 * (x.abs() @ w.abs().t() + b.abs())
+    if x_err is not None:
+        e = e + x_err.double() @ w.abs().t()
+    (u, g), (eu, eg) = s.chunk(2, -1), e.chunk(2, -1)
+    gl = F.gelu(g)
+    dg = ACT_LIP["gelu"] * eg + _act_eval_err(g, gl, "gelu")
+    ref = u * gl
+    return ref, gl.abs() * eu + u.abs() * dg + eu * dg + U32 * ref.abs()
+
+
+def layer_norm_ref_bound(x, gamma, beta, eps):
+    """float64 LayerNorm over the last dimension and the bound of an fp32 implementation (any summation order).
+    With C terms: mean m = sum(x) / C carries e_m = (C + 1) u mean|x|; the variance is computed either as mean((x - m)^2) or as
+    mean(x^2) - m^2 -- the second form is the worse one and is what is bounded: e_v = (C + 3) u mean(x^2) + 2 |m| e_m  (the inputs of the
+    tests have mean 1 and sigma 3, which keeps mean(x^2) / var at 10 / 9 and this term harmless).  r = rsqrt(v + eps):
+    |dr| <= r e_v / (2 (v + eps)) + 2 u r (v_rsq_f32 is specified to 1 ulp).  y = (x - m) r gamma + beta:
+        |dy| <= |gamma| (e_m r + |x - m| |dr|) + 4 u (|(x - m) r gamma| + |beta|)      (four fp32 roundings: subtract, two products, add)
+    The single fp16 rounding of y is check_elem's ulp16(ref)."""
+    x, gamma, beta = x.double(), gamma.double(), beta.double()
+    C = x.shape[-1]
+    m = x.mean(-1, keepdim=True)
+    v = ((x - m) ** 2).mean(-1, keepdim=True)
+    e_m = (C + 1) * U32 * x.abs().mean(-1, keepdim=True)
+    e_v = (C + 3) * U32 * (x * x).mean(-1, keepdim=True) + 2 * m.abs() * e_m
+    r = torch.rsqrt(v + eps)
+    dr = r * e_v / (2 * (v + eps)) + 2 * U32 * r
+    core = (x - m) * r * gamma
+    ref = core + beta
+    bound = gamma.abs() * (e_m * r + (x - m).abs() * dr) + 4 * U32 * (core.abs() + beta.abs())
+    return ref, bound
+
+
+def group_norm_ref_bound(x, groups, gamma, beta, eps, silu=False, add=None):
+    """float64 GroupNorm (+ SiLU) (+ add) of x [N, C, H, W] and the bound of the library's form: per-channel partial sums in fp32, group
+    statistics from them, the affine y = x scale + shift with scale = r gamma, shift = beta - m r gamma in fp32, SiLU, `add` in fp32 (one more
+    fp32 rounding, u |ref|), ONE rounding to fp16 (norm.hip gn_apply_kernel / gn_norm_kernel).  n = pixels x channels of a group; statistics as in
+    layer_norm_ref_bound with C -> n (E[x^2] - m^2 form); the shift's cancellation is covered by bounding |x scale| and |shift| separately:
+        |dy| <= |x| |dscale| + |dshift| + 2 u (|x scale| + |shift|),  dscale = |gamma| |dr| + u |scale|,
+        dshift = |gamma| (e_m r + |m| |dr|) + 3 u (|m r gamma| + |beta|)."""
+    import torch.nn.functional as F
+    x, gamma, beta = x.double(), gamma.double(), beta.double()
+    N, C, H, W = x.shape
+    xg = x.reshape(N, groups, -1)
+    n = xg.shape[-1]
+    m = xg.mean(-1, keepdim=True)
+    v = ((xg - m) ** 2).mean(-1, keepdim=True)
+    e_m = (n + 1) * U32 * xg.abs().mean(-1, keepdim=True)
+    e_v = (n + 3) * U32 * (xg * xg).mean(-1, keepdim=True) + 2 * m.abs() * e_m
+    r = torch.rsqrt(v + eps)
+    dr = r * e_v / (2 * (v + eps)) + 2 * U32 * r
+    per_ch = lambda t: t.expand(N, groups, C // groups).reshape(N, C, 1, 1)
+    m, r, e_m, dr = per_ch(m), per_ch(r), per_ch(e_m), per_ch(dr)
+    g4, b4 = gamma.reshape(1, C, 1, 1), beta.reshape(1, C, 1, 1)
+    scale, shift = r * g4, b4 - m * r * g4
+    y = x * scale + shift
+    dscale = g4.abs() * dr + U32 * scale.abs()
+    dshift = g4.abs() * (e_m * r + m.abs() * dr) + 3 * U32 * ((m * r * g4).abs() + b4.abs())
+    e = x.abs() * dscale + dshift + 2 * U32 * ((x * scale).abs() + shift.abs())
+    if silu:
+        t = F.silu(y)
+        e = ACT_LIP["silu"] * e + ACT_EVAL * t.abs()
+        y = t
+    if add is not None:
+        ref = y + add.double()
+        e = e + U32 * ref.abs()
+        y = ref
+    return y, e
+
+
+def attention_ref_bound(q, k, v, scale, causal=False):
+    """float64 softmax(scale q k^T) v for q [.., Nq, d], k, v [.., Nk, d] (leading dims = samples x heads) and the bound of the library's
+    flash kernels (attention.hip), whose arithmetic is: q' = fp16(q scale log2 e) -- ONE rounding of the pre-scaled query, relative 2^-11
+    per element --, scores q' k in fp32 (d terms), p~ = exp2(s - m_run) in fp32 with m_run within a few units of the row maximum, p~ rounded
+    to fp16 for the second product, the denominator summed in fp32 from the unrounded p~, o = (sum p~ v) / l in fp32 (Nk terms), one
+    rounding to fp16 (check_elem's ulp16(ref)).
+      score error (natural units), per query i and key j:  D_ij = (2^-11 + (d + 2) u) scale sum_c |q_ic| |k_jc|  (the fp16 query + the fp32 sum)
+      softmax:  p'_j = p_j e^(d_j) / sum_i p_i e^(d_i) with |d_j| <= D_ij; by Jensen sum_i p_i e^(-D_i) >= e^(-Dbar), Dbar = sum_i p_i D_i, so
+                |p'_j - p_j| <= p_j (e^(D_ij + Dbar_i) - 1): a key with a large score error but no weight does not loosen the bound
+      fp16 p~:  relative 2^-11 while p~ is normal; below 2^-14 the absolute error is 2^-25, against a denominator l >= 1/2 (the row maximum has
+                p~ > 1/2 after the last rescale) -- an absolute 2^-24 per key
+      sums:     (Nk + 2) u relative on numerator and denominator each, exp2 to 2 fp32 ulps
+        |do_c| <= sum_j p_j (e^(D_ij + Dbar_i) - 1) |v_jc| + (2^-11 + (2 Nk + 8) u) sum_j p_j |v_jc| + 2^-24 sum_j |v_jc|"""
+    if q.dim() == 4 and q.shape[0] > 1:             # sample by sample: the float64 score matrices of a large case stay small
+        parts = [attention_ref_bound(q[i:i + 1], k[i:i + 1], v[i:i + 1], scale, causal) for i in range(q.shape[0])]
+        return torch.cat([r for r, _ in parts]), torch.cat([b for _, b in parts])
+    q, k, v = q.double(), k.double(), v.double()
+    d, Nk = q.shape[-1], k.shape[-2]
+    s = (q @ k.transpose(-1, -2)) * scale
+    sa = (q.abs() @ k.abs().transpose(-1, -2)) * scale
+    if causal:
+        keep = torch.ones(s.shape[-2:], dtype=torch.bool).tril()
+        s = s.masked_fill(~keep, float("-inf"))
+        sa = sa.masked_fill(~keep, 0.0)
+    p = torch.softmax(s, -1)
+    D = (U16 + (d + 2) * U32) * sa
+    Dbar = (p * D).sum(-1, keepdim=True)
+    va = v.abs()
+    vsum = va.sum(-2, keepdim=True) if not causal else torch.cumsum(va, -2)
+    bound = (p * torch.expm1(D + Dbar)) @ va + (U16 + (2 * Nk + 8) * U32) * (p @ va) + 2.0 ** -24 * vsum
+    return p @ v, bound
+
+
+def softmax_rows_ref_bound(s, scale):
+    """float64 softmax(scale s) of fp32 scores [rows, cols] and the bound of an fp32 implementation: the argument scale s - max carries three
+    fp32 roundings of values up to |scale s| + |max| (D = 3 u 2 max|scale s|), exp2 two ulps, the sum (cols + 2) u, the division one:
+        |dp| <= (e^(2 D) - 1 + (cols + 6) u) p"""
+    s = s.double() * scale
+    p = torch.softmax(s, -1)
+    D = 6 * U32 * s.abs().amax(-1, keepdim=True)
+    return p, (torch.expm1(2 * D) + (s.shape[-1] + 6) * U32) * p
+
+
+def pixel_locator(N, H, W, C, bq=None, bp=None):
+    """flat index of an NHWC [N, H, W, C] tensor -> "(n, y, x, c) [pixel tile, channel tile]" for check_elem's messages"""
+    def loc(i):
+        p, c = divmod(i, C)
+        n, r = divmod(p, H * W)
+        y, x = divmod(r, W)
+        tile = " pixel %d = tile %d of %d, channel tile %d of %d" % (p, p // bp, bp, c // bq, bq) if bq and bp else " pixel %d" % p
+        return "(n, y, x, c) = (%d, %d, %d, %d)%s" % (n, y, x, c, tile)
+    return loc
