@@ -451,6 +451,41 @@ int ladi_op_posterior_sample(const void* moments_dev, int ldm, const float* nois
 int ladi_op_assemble_input(void* unet_in_dev, int ld, int B, int hw, int cfg, const float* latents_dev, const void* mask_lat_dev,
                            const float* masked_lat_dev, const void* pose_dev, int pose_channels, const float* cloth_lat_dev, void* stream);
 
+/* ---- fp16 range probe (opt-in; with no probe attached nothing changes: same launches, same captured graph, same bits) ----
+ * A probe records, for every named activation of the modules it is attached to, the largest finite |x| and the number of inf / NaN
+ * elements the fp16 tensor held (one extra read of the tensor per point; values accumulate -- max / sum -- until ladi_probe_reset).
+ * Points are named by the diffusers key prefix of the module that produced the tensor:
+ *   UNet:    conv_in, down_blocks.I.resnets.J, down_blocks.I.attentions.J, down_blocks.I.downsamplers.0, mid_block.resnets.0,
+ *            mid_block.attentions.0, mid_block.resnets.1, up_blocks.I.resnets.J, up_blocks.I.attentions.J, up_blocks.I.upsamplers.0, conv_out
+ *   VAE:     encoder.conv_in, encoder.down_blocks.I, encoder.mid_block, quant_conv (the moments); post_quant_conv, decoder.mid_block,
+ *            decoder.up_blocks.I, decoder.conv_out -- the decoder's stream points are what the stream holds (an EMASC skip that the
+ *            producing kernel folds in included) and are reported at their TRUE scale under a range shift
+ *   EMASC:   emasc.I
+ * A name gets its slot the first time a run meets it, so slot order is execution order.  One probe may be attached to several modules
+ * (a second UNet on the same probe would share the first one's names).  A probe must outlive its attachments: detach (attach NULL)
+ * or destroy the modules before ladi_probe_destroy, which otherwise destroys nothing and leaves a message for ladi_last_error.  Inside
+ * ladi_tryon_run the attached probes are zeroed at the start of the run and the UNet slots accumulate over all evaluations. */
+typedef struct ladi_probe ladi_probe;
+ladi_probe* ladi_probe_create(int max_points);
+void ladi_probe_destroy(ladi_probe* p);
+int ladi_unet_attach_probe(ladi_unet* u, ladi_probe* p);     /* NULL detaches; same for vae / emasc */
+int ladi_vae_attach_probe(ladi_vae* v, ladi_probe* p);
+int ladi_emasc_attach_probe(ladi_emasc* e, ladi_probe* p);
+int ladi_probe_count(const ladi_probe* p);                   /* registered points, -1 on a null handle */
+const char* ladi_probe_name(const ladi_probe* p, int i);     /* NULL when out of range; valid until the probe is destroyed */
+/* absmax_out[i] / nonfinite_out[i] (host; either may be NULL) of the first min(count, cap) points; returns the point count, < 0 on error.
+ * Synchronises `stream`. */
+int ladi_probe_read(ladi_probe* p, float* absmax_out, unsigned* nonfinite_out, int cap, void* stream);
+/* rank_out[i] (host) = the rank in TIME (1, 2, ...) at which point i first held an inf / NaN since the last reset, 0 = never.  Point
+ * order is the order of one forward; inside the denoising loop a NaN of one evaluation comes back into the first points of the next, so
+ * "which layer left the range first" is the point of rank 1.  Returns the point count, < 0 on error.  Synchronises `stream`. */
+int ladi_probe_read_rank(ladi_probe* p, unsigned* rank_out, int cap, void* stream);
+int ladi_probe_reset(ladi_probe* p, void* stream);           /* zero every slot and rank, asynchronous on `stream` */
+/* the probe kernel on its own: over the C valid lanes of each of `rows` rows of an fp16 view (row stride ld >= C halves; lanes C..ld-1 are
+ * never read; any C, ld and 2-byte alignment): *absmax_dev = max(*absmax_dev, max |x| over finite x) and *nonfinite_dev += #(inf / NaN).
+ * Both words are device memory the caller zeroes; *absmax_dev must be a non-negative float. */
+int ladi_op_absmax(const void* x, int rows, int C, int ld, float* absmax_dev, unsigned* nonfinite_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,17 @@ SIGNATURES = {
     "ladi_tryon_lanes": (c_int, [_P]),
     "ladi_vae_set_range_shift": (c_int, [_P, c_int]),
     "ladi_vae_last_range_shift": (c_int, [_P]),
+    "ladi_probe_create": (_P, [c_int]),
+    "ladi_probe_destroy": (None, [_P]),
+    "ladi_unet_attach_probe": (c_int, [_P, _P]),
+    "ladi_vae_attach_probe": (c_int, [_P, _P]),
+    "ladi_emasc_attach_probe": (c_int, [_P, _P]),
+    "ladi_probe_count": (c_int, [_P]),
+    "ladi_probe_name": (c_char_p, [_P, c_int]),
+    "ladi_probe_read": (c_int, [_P, POINTER(c_float), POINTER(ctypes.c_uint), c_int, _P]),
+    "ladi_probe_read_rank": (c_int, [_P, POINTER(ctypes.c_uint), c_int, _P]),
+    "ladi_probe_reset": (c_int, [_P, _P]),
+    "ladi_op_absmax": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     "ladi_igemm_set_autotune": (None, [c_int]),
     "ladi_igemm_set_splitk_two_pass": (None, [c_int]),
     "ladi_profile_igemm_enable": (None, [c_int]),

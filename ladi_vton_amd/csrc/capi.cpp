@@ -21,6 +21,17 @@ struct ladi_vision_encoder { VisionEncoder v; };
 struct ladi_refine { Refine r; };
 struct ladi_tps { Tps t; };
 struct ladi_tryon { TryOn t; };
+struct ladi_probe { Probe p; explicit ladi_probe(int n) : p(n) {} };
+// how many modules point at each probe: ladi_probe_destroy refuses while the count is not zero; attaching, detaching and destroying a module
+// keep it (set_module_probe)
+static std::mutex g_probe_mu;
+static std::unordered_map<const Probe*, int> g_probe_refs;
+static void set_module_probe(Probe*& slot, ladi_probe* p) {
+    std::lock_guard<std::mutex> lk(g_probe_mu);
+    if (slot) --g_probe_refs[slot];
+    slot = p ? &p->p : nullptr;
+    if (slot) ++g_probe_refs[slot];
+}
 static_assert(TRYON_CALLBACK_ABORT == LADI_TRYON_CALLBACK_ABORTED, "callback abort code");
 
 static_assert(sizeof(ladi_igemm_desc) == sizeof(IGemmArgs), "public igemm descriptor must mirror IGemmArgs");
@@ -103,7 +114,7 @@ ladi_unet* ladi_unet_create(const ladi_unet_config* cfg, const ladi_weights* ws)
     if (rc) { delete h; return nullptr; }
     return h;
 }
-void ladi_unet_destroy(ladi_unet* u) { delete u; }
+void ladi_unet_destroy(ladi_unet* u) { if (u) set_module_probe(u->u.probe, nullptr); delete u; }
 
 int ladi_unet_set_context(ladi_unet* u, const void* ehs, int n, int L, void* stream) {
     return guarded("ladi_unet_set_context", [&]() { return u->u.set_context(reinterpret_cast<const h16*>(ehs), n, L, S(stream)); });
@@ -232,7 +243,7 @@ ladi_vae* ladi_vae_create(const ladi_vae_config* cfg, const ladi_weights* ws) {
     if (rc) { delete h; return nullptr; }
     return h;
 }
-void ladi_vae_destroy(ladi_vae* v) { delete v; }
+void ladi_vae_destroy(ladi_vae* v) { if (v) set_module_probe(v->v.probe, nullptr); delete v; }
 
 int ladi_vae_encode(ladi_vae* v, const void* x, int dtype, int B, int H, int W, float* moments, void* const* feats_out, void* stream) {
     return guarded("ladi_vae_encode", [&]() {
@@ -313,7 +324,7 @@ ladi_emasc* ladi_emasc_create(const ladi_emasc_config* cfg, const ladi_weights* 
     if (rc) { delete h; return nullptr; }
     return h;
 }
-void ladi_emasc_destroy(ladi_emasc* e) { delete e; }
+void ladi_emasc_destroy(ladi_emasc* e) { if (e) set_module_probe(e->e.probe, nullptr); delete e; }
 
 int ladi_emasc_forward(ladi_emasc* e, const void* const* feats_dev, const int* hs, const int* wss, int B, const void* mask_dev, int Hm,
                        int Wm, void* const* outs_dev, void* stream) {
@@ -615,6 +626,72 @@ int ladi_tryon_set_trace(ladi_tryon* t, float* eps_trace, float* latents_trace, 
     if (!t || cap_evals < 0) return -1;
     t->t.trace_eps = eps_trace; t->t.trace_lat = latents_trace; t->t.trace_cap = (eps_trace || latents_trace) ? cap_evals : 0;
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ range probe
+ladi_probe* ladi_probe_create(int max_points) {
+    ladi_probe* h = nullptr;
+    int rc = guarded("ladi_probe_create", [&]() { require_gpu(); h = new ladi_probe(max_points); return 0; });
+    return rc ? nullptr : h;
+}
+void ladi_probe_destroy(ladi_probe* p) {
+    if (!p) return;
+    {
+        std::lock_guard<std::mutex> lk(g_probe_mu);
+        auto it = g_probe_refs.find(&p->p);
+        if (it != g_probe_refs.end() && it->second > 0) {
+            // a module would go on launching into the freed slots: keep the probe (a leak, not a dangling pointer) and say so
+            set_error("ladi_probe_destroy: the probe is still attached to " + std::to_string(it->second) + " module(s); nothing was destroyed -- detach (attach NULL) or destroy the modules first");
+            return;
+        }
+        g_probe_refs.erase(&p->p);
+    }
+    delete p;
+}
+int ladi_unet_attach_probe(ladi_unet* u, ladi_probe* p) {
+    if (!u) { set_error("ladi_unet_attach_probe: null handle"); return -1; }
+    set_module_probe(u->u.probe, p);
+    return 0;
+}
+int ladi_vae_attach_probe(ladi_vae* v, ladi_probe* p) {
+    if (!v) { set_error("ladi_vae_attach_probe: null handle"); return -1; }
+    set_module_probe(v->v.probe, p);
+    return 0;
+}
+int ladi_emasc_attach_probe(ladi_emasc* e, ladi_probe* p) {
+    if (!e) { set_error("ladi_emasc_attach_probe: null handle"); return -1; }
+    set_module_probe(e->e.probe, p);
+    return 0;
+}
+int ladi_probe_count(const ladi_probe* p) { return p ? (int)p->p.names.size() : -1; }
+const char* ladi_probe_name(const ladi_probe* p, int i) { return (p && i >= 0 && i < (int)p->p.names.size()) ? p->p.names[i].c_str() : nullptr; }
+int ladi_probe_read(ladi_probe* p, float* absmax_out, unsigned* nonfinite_out, int cap, void* stream) {
+    return guarded("ladi_probe_read", [&]() {
+        if (!p || cap < 0) throw std::runtime_error("null handle or negative cap");
+        p->p.read(absmax_out, nonfinite_out, cap, S(stream));
+        return (int)p->p.names.size();
+    });
+}
+int ladi_probe_read_rank(ladi_probe* p, unsigned* rank_out, int cap, void* stream) {
+    return guarded("ladi_probe_read_rank", [&]() {
+        if (!p || !rank_out || cap < 0) throw std::runtime_error("null argument or negative cap");
+        p->p.read_rank(rank_out, cap, S(stream));
+        return (int)p->p.names.size();
+    });
+}
+int ladi_probe_reset(ladi_probe* p, void* stream) {
+    return guarded("ladi_probe_reset", [&]() {
+        if (!p) throw std::runtime_error("null handle");
+        p->p.reset(S(stream));
+        return 0;
+    });
+}
+int ladi_op_absmax(const void* x, int rows, int C, int ld, float* absmax_dev, unsigned* nonfinite_dev, void* stream) {
+    return guarded("ladi_op_absmax", [&]() {
+        int rc = ladi_launch_absmax_probe(reinterpret_cast<const h16*>(x), rows, C, ld, reinterpret_cast<unsigned*>(absmax_dev), nonfinite_dev, S(stream));
+        if (rc) set_error("ladi_op_absmax: bad arguments (rows >= 0, C >= 1, ld >= C, non-null pointers) rc=" + std::to_string(rc));
+        return rc;
+    });
 }
 
 void ladi_igemm_set_autotune(int on) { ladi_igemm_autotune(on); }

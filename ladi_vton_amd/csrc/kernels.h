@@ -236,6 +236,14 @@ int ladi_launch_maxpool2_f32(const float* src, int lds_, int n, int H, int W, in
 int ladi_launch_upsample2x_bilinear_ac_f32(const float* src, int lds_, int n, int H, int W, int C, float* dst, int ldd, hipStream_t st);
 int ladi_launch_linear_f32(const float* x, int ldx, const float* W, const float* b, int M, int N, int K, int act, float* out, int ldo, hipStream_t st);
 
+// ---- probe.hip: fp16 range probe.  Over the C valid lanes of each of `rows` rows (ld >= C halves apart; lanes C..ld-1 are never read):
+// *absmax_bits = max(*absmax_bits, bits of max |x| over finite x) (atomicMax on the bits of a non-negative float), *nonfinite += number of
+// inf / NaN elements.  Any C, ld and 2-byte alignment (16-byte loads when C % 8 == 0, ld % 8 == 0 and p is 16-byte aligned).
+// seq / first_rank (both or neither): when this launch takes *nonfinite from zero, *first_rank = ++*seq -- the rank in time at which the
+// slot first held an inf / NaN among the slots sharing `seq`
+int ladi_launch_absmax_probe(const h16* p, long long rows, int C, int ld, unsigned* absmax_bits, unsigned* nonfinite, hipStream_t st,
+                             unsigned* seq = nullptr, unsigned* first_rank = nullptr);
+
 // ---- igemm per-launch timing hooks (HIP events on the launch stream); see igemm.hip
 void ladi_igemm_profile_enable(int on);
 void ladi_igemm_autotune(int on);   // measured tile-shape selection on first use of a problem shape (default on)

@@ -58,6 +58,38 @@ struct Act {  // NHWC fp16 activation view
     size_t pixels() const { return (size_t)n * h * w; }
 };
 
+// Opt-in fp16 range probe (probe.hip): one device slot {bits of the largest finite |x|, number of inf / NaN elements} per NAMED activation
+// of the modules it is attached to (UNet / VAE / EMASC ::probe).  A name gets its slot the first time a planning (dry) pass meets it, so
+// slot order is call order; the real pass only looks names up and launches the kernel on the pass's stream -- no allocation, no
+// synchronisation, capturable.  Slots accumulate (max / sum) until reset().  Names are the diffusers key prefix of the producing module.
+struct ProbeSlot { unsigned absmax_bits; unsigned nonfinite; };
+struct Probe {
+    int cap = 0;
+    // never reused within the process: what a captured graph that holds this probe's launches is keyed on (a later Probe can get the same
+    // device addresses back from the allocator with another name <-> slot order or a smaller cap)
+    unsigned long long id = 0;
+    ProbeSlot* d_slots = nullptr;            // device [cap]
+    ProbeSlot* h_slots = nullptr;            // pinned host mirror [cap] (read())
+    // d_rank[0]: how many slots have gone non-finite since the last reset; d_rank[1 + i]: the rank in time (1-based) at which slot i first held
+    // an inf / NaN, 0 = never.  Slot order is the order of one forward; inside the denoising loop a NaN of evaluation k comes back into the
+    // earlier slots at evaluation k + 1, so "which layer overflowed first" needs the time order
+    unsigned* d_rank = nullptr; unsigned* h_rank = nullptr;
+    std::vector<std::string> names;          // slot i <-> names[i]
+    std::vector<float> scale;                // factor by which slot i's tensor is stored relative to its true value (last call's)
+    std::unordered_map<std::string, int> index;
+    explicit Probe(int max_points);
+    ~Probe();
+    void release();                          // frees the device / pinned buffers (destructor, failed construction)
+    Probe(const Probe&) = delete;
+    Probe& operator=(const Probe&) = delete;
+    int slot(const std::string& name, bool add);                       // index of `name` (registered when add), -1: unknown
+    void reset(hipStream_t st);                                        // zero every slot, asynchronous on st
+    void reset_prefix(const char* prefix, hipStream_t st);             // zero the slots whose name starts with prefix
+    // true-scale absmax (stored absmax / scale) and counts of the first min(count, cap_out) slots; synchronises st
+    void read(float* absmax_out, unsigned* nonfinite_out, int cap_out, hipStream_t st);
+    void read_rank(unsigned* rank_out, int cap_out, hipStream_t st);   // d_rank[1 + i] of the first min(count, cap_out) slots; synchronises st
+};
+
 struct Ctx {
     hipStream_t st = nullptr;
     Arena* ar = nullptr;
@@ -71,6 +103,16 @@ struct Ctx {
     float* alloc_stats(size_t floats);
     Act new_act(int n, int h, int w, int c, int ld = 0);
     void check(int rc, const char* what);
+    // range probe of the module being run (set from the module's `probe` for the span of its forward; null = off: probe_point returns at
+    // once and nothing is launched).  scale: the factor by which `a` is stored relative to its true value
+    Probe* probe = nullptr;
+    void probe_point(const char* name, const Act& a, float scale = 1.f);
+};
+// sets Ctx::probe for the span of one module's forward and puts the caller's back
+struct ProbeScope {
+    Ctx& c; Probe* saved;
+    ProbeScope(Ctx& c_, Probe* p) : c(c_), saved(c_.probe) { c.probe = p; }
+    ~ProbeScope() { c.probe = saved; }
 };
 
 // Two-pass (plan, run) execution of a module graph on its arena: `body(Ctx&)` runs once dry (addresses are fake, nothing is launched; it
@@ -177,6 +219,7 @@ struct UNet {
     // own arena for the stand-alone forward entry
     Arena arena; float* stats = nullptr; size_t stats_cap = 0;
     h16* in_buf = nullptr; size_t in_cap = 0;
+    Probe* probe = nullptr;                 // attached range probe (not owned): conv_in, every resnet / transformer / sampler output, conv_out
 
     void load(const UNetCfg& c, const WeightStore& ws);
     int set_context(const h16* ehs, int n, int L, hipStream_t st);
@@ -239,6 +282,10 @@ struct VAE {
     // feeds the stream is scaled in its producer's epilogue, so the result is the same function with 2^shift more head-room.
     // range_shift < 0 = automatic: run at shift 0, and if a GroupNorm saw non-finite statistics (d_bad) re-run at 4, then 8.
     int range_shift = -1; int last_shift = 0; int* d_bad = nullptr;
+    // attached range probe (not owned): encoder.conv_in / down_blocks.i / mid_block, quant_conv (moments), post_quant_conv,
+    // decoder.mid_block / up_blocks.i / conv_out.  Decoder stream points are reported at their true scale (stored value x 2^shift) and
+    // are what the stream holds, i.e. with the EMASC skip that the producing epilogue folds in
+    Probe* probe = nullptr;
 
     void load(const VAECfg& c, const WeightStore& ws);
     // x: [n,H,W,64] padded NHWC image. Returns moments Act [n,h,w,8]; feats[0..4] = encoder features idx1..5 (views)
@@ -272,6 +319,7 @@ int VAE::decode_guarded(hipStream_t st, Body&& body) {
         last_shift = sh;
         if (!overflowed(st)) return sh;
         if (fixed >= 0) break;
+        if (probe) { probe->reset_prefix("decoder.", st); probe->reset_prefix("post_quant_conv", st); }   // the retry reports its own values
     }
     throw std::runtime_error("VAE decode: activations exceed the fp16 range (non-finite GroupNorm statistics) at range shift " +
                              std::to_string(last_shift));
@@ -281,6 +329,7 @@ struct EMASCCfg { int n = 5; int in_ch[8] = {128, 128, 128, 256, 512}; int out_c
 struct EMASC {
     EMASCCfg cfg; DevPool pool; DConv a[8], b[8];
     Arena arena;
+    Probe* probe = nullptr;                 // attached range probe (not owned): emasc.i = output i (after the mask)
     void load(const EMASCCfg& c, const WeightStore& ws);
     // out[i] = conv_b(silu(conv_a(feat[i]))) * (1 - mask[i])   (mask[i] may be null)
     void forward(Ctx& c, const Act* feats, const h16* const* masks, Act* outs, bool outs_preallocated = false);

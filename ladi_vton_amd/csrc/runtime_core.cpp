@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cmath>
 #include <cstdlib>
+#include <atomic>
 
 namespace ladi {
 
@@ -101,6 +102,79 @@ Act Ctx::new_act(int n, int h, int w, int cc, int ld) {
 }
 void Ctx::check(int rc, const char* what) {
     if (rc != 0) throw std::runtime_error(std::string(what) + " failed rc=" + std::to_string(rc));
+}
+
+// ------------------------------------------------------------------------------------------------
+// fp16 range probe (runtime.h Probe)
+// ------------------------------------------------------------------------------------------------
+Probe::Probe(int max_points) {
+    if (max_points < 1 || max_points > (1 << 16)) throw std::runtime_error("probe: max_points must be in [1, 65536]");
+    cap = max_points;
+    static std::atomic<unsigned long long> next_id{1};
+    id = next_id.fetch_add(1);
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(&d_slots), (size_t)cap * sizeof(ProbeSlot)));
+    if (hipMemset(d_slots, 0, (size_t)cap * sizeof(ProbeSlot)) != hipSuccess ||   // (d_slots itself: HIP_OK above throws before anything is held)
+        hipHostMalloc(reinterpret_cast<void**>(&h_slots), (size_t)cap * sizeof(ProbeSlot)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&d_rank), (size_t)(cap + 1) * sizeof(unsigned)) != hipSuccess ||
+        hipMemset(d_rank, 0, (size_t)(cap + 1) * sizeof(unsigned)) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&h_rank), (size_t)(cap + 1) * sizeof(unsigned)) != hipSuccess) {
+        release();
+        throw std::runtime_error("probe: allocating the slots failed");
+    }
+}
+Probe::~Probe() { release(); }
+void Probe::release() {
+    if (d_slots) (void)hipFree(d_slots);
+    if (h_slots) (void)hipHostFree(h_slots);
+    if (d_rank) (void)hipFree(d_rank);
+    if (h_rank) (void)hipHostFree(h_rank);
+    d_slots = h_slots = nullptr; d_rank = h_rank = nullptr;
+}
+int Probe::slot(const std::string& name, bool add) {
+    auto it = index.find(name);
+    if (it != index.end()) return it->second;
+    if (!add) return -1;
+    if ((int)names.size() >= cap) throw std::runtime_error("probe: more than max_points = " + std::to_string(cap) + " probe points (at " + name + ")");
+    const int i = (int)names.size();
+    names.push_back(name); scale.push_back(1.f); index.emplace(name, i);
+    return i;
+}
+void Probe::reset(hipStream_t st) {
+    HIP_OK(hipMemsetAsync(d_slots, 0, (size_t)cap * sizeof(ProbeSlot), st));
+    HIP_OK(hipMemsetAsync(d_rank, 0, (size_t)(cap + 1) * sizeof(unsigned), st));
+}
+void Probe::read_rank(unsigned* rank_out, int cap_out, hipStream_t st) {
+    const int n = std::min((int)names.size(), cap_out);
+    if (n > 0) HIP_OK(hipMemcpyAsync(h_rank, d_rank, (size_t)(n + 1) * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i) rank_out[i] = h_rank[1 + i];
+}
+void Probe::reset_prefix(const char* prefix, hipStream_t st) {
+    for (size_t i = 0; i < names.size(); ++i)
+        if (names[i].compare(0, std::strlen(prefix), prefix) == 0) {
+            HIP_OK(hipMemsetAsync(d_slots + i, 0, sizeof(ProbeSlot), st));
+            HIP_OK(hipMemsetAsync(d_rank + 1 + i, 0, sizeof(unsigned), st));
+        }
+}
+void Probe::read(float* absmax_out, unsigned* nonfinite_out, int cap_out, hipStream_t st) {
+    const int n = std::min((int)names.size(), cap_out);
+    if (n > 0) HIP_OK(hipMemcpyAsync(h_slots, d_slots, (size_t)n * sizeof(ProbeSlot), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i) {
+        float m; std::memcpy(&m, &h_slots[i].absmax_bits, sizeof(m));
+        if (absmax_out) absmax_out[i] = m / scale[i];
+        if (nonfinite_out) nonfinite_out[i] = h_slots[i].nonfinite;
+    }
+}
+
+void Ctx::probe_point(const char* name, const Act& a, float scale) {
+    if (!probe) return;
+    const int i = probe->slot(name, dry());
+    if (dry()) return;
+    if (i < 0) throw std::runtime_error(std::string("probe: point ") + name + " was not met by the planning pass");
+    probe->scale[i] = scale;
+    check(ladi_launch_absmax_probe(a.p, (long long)a.pixels(), a.c, a.ld, &probe->d_slots[i].absmax_bits, &probe->d_slots[i].nonfinite, st,
+                                   probe->d_rank, probe->d_rank + 1 + i), "absmax_probe");
 }
 
 // ------------------------------------------------------------------------------------------------

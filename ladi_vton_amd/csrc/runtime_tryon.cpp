@@ -109,6 +109,11 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
             arena.off = 0;
             Ctx c; c.st = st; c.ar = &arena; c.stats = stats; c.stats_cap = stats_cap; c.sk_cnt = sk_cnt;
             if (pass == 1) {
+                // attached range probes start the run from zero (here, never inside the replayed graph): UNet slots then accumulate
+                // over all evaluations of this run
+                Probe* pr[3] = {unet->probe, vae->probe, emasc ? emasc->probe : nullptr};
+                for (int i = 0; i < 3; ++i)
+                    if (pr[i] && !(i > 0 && pr[i] == pr[0]) && !(i > 1 && pr[i] == pr[1])) pr[i]->reset(st);
                 HIP_OK(hipMemcpyAsync(d_table, table.data(), (size_t)evals * sizeof(StepTable), hipMemcpyHostToDevice, st));
                 HIP_OK(hipMemsetAsync(d_step, 0, 2 * sizeof(int), st));    // evaluation index + the step kernel's arrival ticket
                 if (use_step_noise) HIP_OK(hipMemcpyAsync(step_noise_buf, step_noise_src, step_noise_bytes, hipMemcpyDeviceToDevice, st));
@@ -237,6 +242,9 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 key = mix(key, (unsigned long long)trace_cap);
                 key = mix(key, (unsigned long long)(uintptr_t)sa.step_noise);
                 key = mix(key, lanes.key());
+                // a graph captured without the probe launches is never replayed with it, nor one that holds another probe's slots: the id is
+                // unique per Probe (0 = none), and within one Probe a name keeps its slot
+                key = mix(key, unet->probe ? unet->probe->id : 0ULL);
                 if (!cb_rc && (!gexec || key != graph_key)) {
                     if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
                     if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <new>
 #include <cstdlib>
+#include <cstdio>
 
 namespace ladi {
 
@@ -273,27 +274,41 @@ struct Fwd {
 Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_idx, const Act* eps_out, int sample0) {
     if ((eps_out ? sample0 + x.n > ctx_n : ctx_n != x.n) && !c.dry()) throw std::runtime_error("UNet::forward: set_context batch mismatch");
     Fwd f{c, *this, temb_row, temb_idx, sample0};
+    ProbeScope probe_scope(c, probe);
+    // range probe points, named by the diffusers key prefix of the module that produced the tensor (off: one pointer test each)
+    auto pp = [&](const Act& a, const char* fmt, int i = 0, int j = 0) {
+        if (!c.probe) return;
+        char name[64];
+        std::snprintf(name, sizeof(name), fmt, i, j);
+        c.probe_point(name, a);
+    };
     const int L = cfg.layers_per_block;
     std::vector<Act> skips;
     ConvOpt o; o.stats = true;
     Act h = conv2d(c, conv_in, x, nullptr, o);
+    pp(h, "conv_in");
     skips.push_back(h);
     int ri = 0, xi = 0;
     for (int i = 0; i < 4; ++i) {
         for (int j = 0; j < L; ++j) {
             h = f.res(down_res[ri++], h, nullptr);
-            if (i < 3) h = f.xf(down_xf[xi++], h);
+            pp(h, "down_blocks.%d.resnets.%d", i, j);
+            if (i < 3) { h = f.xf(down_xf[xi++], h); pp(h, "down_blocks.%d.attentions.%d", i, j); }
             skips.push_back(h);
         }
         if (i < 3) {
             ConvOpt od; od.stride = 2; od.pad = 1; od.stats = true;
             h = conv2d(c, down_samp[i], h, nullptr, od);
+            pp(h, "down_blocks.%d.downsamplers.0", i);
             skips.push_back(h);
         }
     }
     h = f.res(mid_res[0], h, nullptr);
+    pp(h, "mid_block.resnets.0");
     h = f.xf(mid_xf, h);
+    pp(h, "mid_block.attentions.0");
     h = f.res(mid_res[1], h, nullptr);
+    pp(h, "mid_block.resnets.1");
     // diffusers' `forward_upsample_size`: when a latent side is not a multiple of 2^3 (three upsamplers), the down path rounded a level up
     // (ceil(H / 2)) and every upsampler stretches to the size of the skip it is concatenated with; else each one doubles
     const bool ups_to_skip = (x.h % 8) || (x.w % 8);
@@ -302,12 +317,14 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
         for (int j = 0; j < L + 1; ++j) {
             Act sk = skips.back(); skips.pop_back();
             h = f.res(up_res[ri++], h, &sk);
-            if (i > 0) h = f.xf(up_xf[xi++], h);
+            pp(h, "up_blocks.%d.resnets.%d", i, j);
+            if (i > 0) { h = f.xf(up_xf[xi++], h); pp(h, "up_blocks.%d.attentions.%d", i, j); }
         }
         if (i < 3) {
             ConvOpt ou; ou.ups = 1; ou.stats = true;
             if (ups_to_skip) { ou.ups_h = skips.back().h; ou.ups_w = skips.back().w; }
             h = conv2d(c, up_samp[i], h, nullptr, ou);
+            pp(h, "up_blocks.%d.upsamplers.0", i);
         }
     }
     Act g = group_norm(c, norm_out, h, nullptr, cfg.groups, cfg.eps, 1);
@@ -315,7 +332,9 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
     if (cfg.out_channels > 4) oc.out_ld = (cfg.out_channels + 3) / 4 * 4;
     Act eps;
     if (eps_out) { eps = *eps_out; oc.dst = &eps; }     // a sample-group lane writes its rows of the shared output
-    return conv2d(c, conv_out, g, nullptr, oc);
+    Act out = conv2d(c, conv_out, g, nullptr, oc);
+    pp(out, "conv_out");
+    return out;
 }
 
 // ------------------------------------------------------------------------------------------------

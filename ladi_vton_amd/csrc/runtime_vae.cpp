@@ -6,6 +6,7 @@
 #include <stdexcept>
 #include <cstring>
 #include <cmath>
+#include <cstdio>
 
 namespace ladi {
 
@@ -204,11 +205,21 @@ struct VF {
 
 }  // namespace
 
+// range probe point "<fmt % i>" (off: one pointer test)
+static void vae_probe(Ctx& c, const Act& a, float scale, const char* fmt, int i = 0) {
+    if (!c.probe) return;
+    char name[64];
+    std::snprintf(name, sizeof(name), fmt, i);
+    c.probe_point(name, a, scale);
+}
+
 Act VAE::encode(Ctx& c, const Act& x, Act feats[5]) {
     VF f{c, *this};
+    ProbeScope probe_scope(c, probe);
     const int L = cfg.layers_per_block;
     ConvOpt o; o.stats = true;
     Act h = conv2d(c, e_conv_in, x, nullptr, o);
+    vae_probe(c, h, 1.f, "encoder.conv_in");
     feats[0] = h;  // idx1 (conv_in output)
     feats[1] = h;  // idx2 (input of down block 0) - same tensor (vae.py:104-109)
     int ri = 0;
@@ -219,19 +230,25 @@ Act VAE::encode(Ctx& c, const Act& x, Act feats[5]) {
             ConvOpt od; od.stats = true; od.stride = 2; od.pad = 0; od.pad_end = 1;  // F.pad(0,1,0,1) + stride-2 conv, pad 0: trailing zeros via bounds check
             h = conv2d(c, e_down[i], h, nullptr, od);
         }
+        vae_probe(c, h, 1.f, "encoder.down_blocks.%d", i);
     }
     h = f.res(e_mid[0], h, nullptr);
     h = f.attn(e_attn, h);
     h = f.res(e_mid[1], h, nullptr);
+    vae_probe(c, h, 1.f, "encoder.mid_block");
     Act g = group_norm(c, e_norm_out, h, nullptr, cfg.groups, cfg.eps, 1);
     ConvOpt oc; oc.out_ld = 8;
-    return conv2d(c, e_conv_out, g, nullptr, oc);  // moments (quant_conv folded)
+    Act mom = conv2d(c, e_conv_out, g, nullptr, oc);  // moments (quant_conv folded)
+    vae_probe(c, mom, 1.f, "quant_conv");
+    return mom;
 }
 
 Act VAE::decode(Ctx& c, const Act& z, const Act* skips, int shift) {
     VF f{c, *this};
+    ProbeScope probe_scope(c, probe);
     f.s = std::ldexp(1.f, -shift);
     c.bad = d_bad;
+    { Act zv = z; zv.c = cfg.latent_channels; vae_probe(c, zv, 1.f, "post_quant_conv"); }   // z: latent_channels valid lanes of a padded row
     const int L = cfg.layers_per_block;
     // slot i = EMASC output for encoder feature idx i+1; a slot without a tensor is an int_layers selection that omits it (vae.py:190-205).
     // Skips that are added INTO the stream (slots 1..4) must carry the stream's scale: scaled copies under the range guard
@@ -251,6 +268,7 @@ Act VAE::decode(Ctx& c, const Act& z, const Act* skips, int shift) {
     h = f.attn(d_attn, h);
     // vae.py:191-194: sample += reversed(feats)[i] before up_block i  -> folded into the producing epilogue
     h = f.res(d_mid[1], h, sk(4));
+    vae_probe(c, h, f.s, "decoder.mid_block");
     int ri = 0;
     for (int i = 0; i < 4; ++i) {
         for (int j = 0; j < L + 1; ++j) h = f.res(d_res[ri++], h, nullptr);
@@ -259,12 +277,15 @@ Act VAE::decode(Ctx& c, const Act& z, const Act* skips, int shift) {
             ou.res0 = sk(3 - i);
             h = conv2d(c, d_up[i], h, nullptr, ou);
         }
+        vae_probe(c, h, f.s, "decoder.up_blocks.%d", i);
     }
     // vae.py:200-205: conv_norm_out -> SiLU -> (+ feats for int layer 1, true scale: it is added behind the norm) -> conv_out
     Act g = group_norm(c, d_norm_out, h, nullptr, cfg.groups, f.eps_s(), 1, sk(0));
     ConvOpt oc; oc.out_ld = 4;
     c.bad = nullptr;
-    return conv2d(c, d_conv_out, g, nullptr, oc);
+    Act img = conv2d(c, d_conv_out, g, nullptr, oc);
+    vae_probe(c, img, 1.f, "decoder.conv_out");
+    return img;
 }
 
 bool VAE::overflowed(hipStream_t st) {
@@ -287,6 +308,7 @@ void EMASC::load(const EMASCCfg& c, const WeightStore& ws) {
 }
 
 void EMASC::forward(Ctx& c, const Act* feats, const h16* const* masks, Act* outs, bool outs_preallocated) {
+    ProbeScope probe_scope(c, probe);
     for (int i = 0; i < cfg.n; ++i) {
         if (!outs_preallocated) outs[i] = c.new_act(feats[i].n, feats[i].h, feats[i].w, b[i].cout);
     }
@@ -297,6 +319,7 @@ void EMASC::forward(Ctx& c, const Act* feats, const h16* const* masks, Act* outs
         ConvOpt ob; ob.mask = masks ? masks[i] : nullptr;  // mask_features fused: out *= (1 - mask)
         ob.dst = &outs[i];
         (void)conv2d(c, b[i], t, nullptr, ob);
+        vae_probe(c, outs[i], 1.f, "emasc.%d", i);
         c.ar->release(mk);
     }
 }

@@ -46,6 +46,37 @@ class StableDiffusionTryOnePipeline:
         self.last_stage_ms = None
         self.trace_evals = 0          # > 0: the next fused runs record per-evaluation noise_pred / latents into self.last_trace
         self.lanes = None             # sample-group lanes of the fused loop's UNet forward (None: library default, LADI_UNET_LANES or 1)
+        self._range_probe = None
+
+    @property
+    def range_probe(self):
+        """a ladi_vton_amd.RangeProbe (default None = off: nothing is launched for it).  When set it is attached to unet, vae and emasc, for
+        the fused and the modular path alike, and holds after every call the per-layer fp16 magnitudes / non-finite counts of that call
+        (probe.report()).  The attachment follows the pipeline's modules: every call attaches it to the unet / vae / emasc the pipeline
+        holds then, and takes it off a module that was replaced since.  With probe.raise_on_nonfinite = True a call that hands results to the host raises
+        NativeError("fp16 range exceeded first at <name> ...") when a UNet / encoder / EMASC activation held an inf or NaN (a decoder
+        overflow is left to the VAE's range-shift guard, which re-runs the batch)."""
+        return self._range_probe
+
+    @range_probe.setter
+    def range_probe(self, probe):
+        if self._range_probe is not None and self._range_probe is not probe:
+            self._range_probe.detach()
+        self._range_probe = probe
+        if probe is not None:
+            probe.attach_only(self.unet, self.vae, self.emasc)
+
+    def _check_range_probe(self):
+        """-> the name of the first UNet / encoder / EMASC point that left the fp16 range when the probe asks for an error, else None"""
+        p = self._range_probe
+        if p is None or not p.raise_on_nonfinite:
+            return None
+        name = p.first_nonfinite()
+        return None if name is None or name.startswith(("decoder.", "post_quant_conv")) else name
+
+    @staticmethod
+    def _range_error(name):
+        return _lib.NativeError("fp16 range exceeded first at %s (RangeProbe: inf / NaN in that activation; probe.report() has every layer)" % name)
 
     def to(self, *a, **k):
         return self
@@ -166,6 +197,9 @@ class StableDiffusionTryOnePipeline:
             n_mask = self._draw((B, 4, h, w), generator, pe.dtype, device)
         else:
             n_cloth, n_lat, n_mask = [t.to(device=device, dtype=torch.float32).contiguous() if t is not None else None for t in noise]
+        if self._range_probe is not None:
+            self._range_probe.attach_only(self.unet, self.vae, self.emasc)     # the modules of THIS call (one may have been replaced)
+            self._range_probe.reset()
         native = isinstance(self.unet, NativeUNet) and isinstance(self.vae, NativeVAE) and (self.emasc is None or isinstance(self.emasc, NativeEMASC))
         # only DDIMScheduler.step takes eta (the modular path passes it to no other scheduler); a negative one stays on the modular path
         ddim_eta = float(eta) if isinstance(self.scheduler, DDIMScheduler) else 0.0
@@ -296,6 +330,12 @@ class StableDiffusionTryOnePipeline:
             check(rc, what)
         try:
             run("ladi_tryon_run")
+            bad = None if return_device else self._check_range_probe()
+            if bad is not None:
+                # NaN latents also trip the decoder's guard: take its flag so that the next run is not refused for this one (the automatic
+                # range shift it raises stays; it only adds decoder head-room)
+                lib.ladi_tryon_poll_overflow(self._tryon)
+                raise self._range_error(bad)
             if not return_device:
                 # results go to the host: this is the synchronisation point anyway, so the decode's fp16-range guard is asked now (a run
                 # decodes once and queues its flag; no host round trip inside the run).  An overflow raised the automatic range shift: run the
@@ -401,4 +441,8 @@ class StableDiffusionTryOnePipeline:
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, latents)
         self.last_latents = latents
-        return self.decode_latents(latents, inter)
+        images = self.decode_latents(latents, inter)
+        bad = self._check_range_probe()
+        if bad is not None:
+            raise self._range_error(bad)
+        return images
