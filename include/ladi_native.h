@@ -363,6 +363,11 @@ typedef struct {
                                       (multiple of 32); K = 320 / 640 projections without residual / GEGLU only */
     /* optional LayerNorm of the pixel operand (single source, 1x1): fused into the X-stationary linear kernel where the tuner finds that
        faster, else run as its own kernel into ln_scratch ([P][C0] fp16, caller-provided; null = only the fused form is admissible) */
+    /* The epilogue: t = act(acc + bias * bias_mul + rowadd), out = fp16(fp16(t * out_scale) + res0 + res1) * (1 - mask); bias is indexed by
+       output channel, or by pixel when bias_per_pixel.  batch > 1 runs `batch` problems whose src0 / W / out / res0 and res1 lie bs_src0 / bs_w /
+       bs_out / bs_res elements apart (0 = shared).  Two combinations are refused, for every tile_cfg (0 included):
+         rc -18: batch > 1 with a second source (src1 / C1): there is no batch stride for it;
+         rc -19: out_f32 with an activation, rowadd, res0, res1 or mask: the fp32 store is (acc + bias * bias_mul) * out_scale only. */
 } ladi_igemm_desc;
 int ladi_op_igemm(const ladi_igemm_desc* d, int batch, int tile_cfg, void* stream);
 int ladi_op_group_norm(const void* src0, int C0, const void* src1, int C1, int n, int HW, int groups, const void* gamma,

@@ -117,7 +117,8 @@ struct IGemmArgs {
     int Q;               // output channels (rows of W)
     int K;
     int ldw;             // row stride of W in elements (0 -> K)
-    // batching over grid.z (element strides); 0 = shared
+    // batching over grid.z (element strides); 0 = shared.  bs_res moves res0 AND res1.  There is no stride for src1: a batched launch
+    // (batch > 1) with a second source is refused (ladi_launch_igemm: -18)
     long long bs_src0, bs_w, bs_out, bs_res;
     // epilogue
     const h16* bias;     // [Q] or null (GEGLU: interleaved like W rows)
@@ -130,7 +131,8 @@ struct IGemmArgs {
     int ldr0, ldr1;
     const h16* mask;     // [P] fp16; out *= (1 - mask[p]) or null
     void* out; int ldo;  // [P][ldo]
-    int out_f32;         // 1: store fp32
+    int out_f32;         // 1: store fp32 = (acc + bias * bias_mul) * out_scale and nothing else: with an activation, rowadd, res0 / res1 or
+                         // mask the launch is refused (ladi_launch_igemm: -19)
     float* stats;        // optional per-channel partial statistics of the OUTPUT: rows of [Q][2] (sum, sumsq), see kernels.h
     int stats_groups;    // unused
     int splitk;          // set by the launcher: > 1 = grid.z slices K, fp32 partials to `out` (+ z*bs_out), reduced by a 2nd kernel

@@ -515,6 +515,11 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
     if (a.ups && (a.stride != 1 || a.Ho + a.ksize - 1 - 2 * a.pad < 1 || a.Wo + a.ksize - 1 - 2 * a.pad < 1)) return -1;   // folded upsample: stride 1, non-empty logical image
     const bool geglu = a.act == LADI_ACT_GEGLU;
     if (geglu && (a.Q % 64)) return -6;
+    // refused, never mis-computed (both hold for every configuration, cfg 0 included):
+    // a batched launch offsets src0 / W / out / the residuals by the batch element; a second source has no batch stride (every element would
+    // read element 0's), and the fp32 store (igemm_epilogue_generic) applies bias and out_scale only
+    if (batch > 1 && (a.src1 || a.C1)) return -18;
+    if (a.out_f32 && (a.act != LADI_ACT_NONE || a.rowadd || a.res0 || a.res1 || a.mask)) return -19;
     // ---- measured tile-shape selection ("measure, don't guess"): the first time a problem shape is seen outside a stream
     //      capture, every admissible configuration is timed with HIP events on the launch stream and the fastest is cached.
     //      Re-running a launch is idempotent (outputs never alias inputs in this library).

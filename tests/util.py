@@ -211,6 +211,52 @@ def guarded(t, ld=None, pre_rows=2, post_rows=2, device=None):
     return g
 
 
+class GuardedBatch(Guarded):
+    """B operands of a batched launch in ONE poisoned allocation: element b is the [erows, C] view .views[b] at row stride ld, .bs elements
+    (erows + gap rows) behind element b - 1 -- the rows between two elements are poison like the rows before the first and after the last, so
+    a wrong batch stride reads NaN or overwrites a poison pattern.  .ptr is element 0's address, .rows the span from element 0's first row to
+    the last element's last row (what assert_untouched walks)."""
+
+    def __init__(self, buf, B, erows, C, ld, gap, pre, post):
+        self.B, self.erows, self.gap, self.bs = B, erows, gap, (erows + gap) * ld
+        super().__init__(buf, B * erows + (B - 1) * gap, C, ld, pre, post)
+        self.views = [buf.as_strided((erows, C), (ld, 1), pre * ld + b * self.bs) for b in range(B)]
+        self.view = None
+
+    def cpu(self):
+        return torch.stack([v.cpu() for v in self.views])
+
+    def poison_mask(self):
+        m = torch.ones((self.pre + self.rows + self.post, self.ld), dtype=torch.bool)
+        for b in range(self.B):
+            r0 = self.pre + b * (self.erows + self.gap)
+            m[r0:r0 + self.erows, :self.C] = False
+        return m
+
+
+def guarded_batch(ts, ld=None, gap_rows=3, pre_rows=2, post_rows=2, device=None):
+    """guarded() for the B same-shaped [rows, C] operands ts of a batched launch (see GuardedBatch).  gap_rows is rounded up to the next count
+    that keeps the batch stride a multiple of 8 elements (16 bytes of fp16), as the product's strides are."""
+    t0 = ts[0]
+    assert t0.dtype in (torch.float16, torch.float32) and all(t.shape == t0.shape and t.dtype == t0.dtype for t in ts)
+    erows, C = t0.shape
+    ld = C if ld is None else ld
+    assert ld >= C and ld % 4 == 0 and gap_rows >= 1, (C, ld)
+    while ((erows + gap_rows) * ld) % 8:
+        gap_rows += 1
+    while (pre_rows * ld * t0.element_size()) % 16:
+        pre_rows += 1
+    it, word = _poison_word(t0.dtype)
+    device = dev() if device is None else torch.device(device)
+    B = len(ts)
+    buf = torch.full(((pre_rows + B * erows + (B - 1) * gap_rows + post_rows) * ld,), word, dtype=it, device=device).view(t0.dtype)
+    g = GuardedBatch(buf, B, erows, C, ld, gap_rows, pre_rows, post_rows)
+    for v, t in zip(g.views, ts):
+        v.copy_(t.to(device))
+    assert g.ptr % 16 == 0
+    return g
+
+
 def guarded_out(rows, C, ld=None, pre_rows=2, post_rows=2, dtype=torch.float16, device=None):
     """an OUTPUT placed like guarded(): the view itself starts as NaN too, so an element the kernel never wrote fails check_elem"""
     return guarded(torch.full((rows, C), float("nan"), dtype=dtype), ld, pre_rows, post_rows, device)
@@ -239,11 +285,13 @@ def ulp16(x):
     return torch.exp2(torch.floor(torch.log2(a)) - 10.0)
 
 
-def check_elem(got, ref, bound, what, locate=None):
+def check_elem(got, ref, bound, what, locate=None, out_f32=False):
     """Per-element check |got - ref| <= ulp16(ref) + bound.  got: the kernel's output (any float dtype, CPU), ref: float64 reference,
     bound: float64 tensor (or scalar) >= 0 derived from the reference alone (the *_bound helpers below) for everything between the exact
     result and the value that is finally rounded to fp16.  A non-finite output element fails by itself.  locate(flat_index) -> str names
-    the failing element for the message (pixel, channel, tile).  Returns the worst err / (ulp16(ref) + bound), the margin the tests record."""
+    the failing element for the message (pixel, channel, tile).  Returns the worst err / (ulp16(ref) + bound), the margin the tests record.
+    out_f32: the kernel stores fp32 -- the final rounding is an fp32 one, so U32 |ref| takes the place of ulp16(ref) (the messages keep
+    calling that term "ulp16")."""
     got, ref = got.double(), ref.double()
     assert got.shape == ref.shape, (what, tuple(got.shape), tuple(ref.shape))
     bound = torch.as_tensor(bound, dtype=torch.float64).expand_as(ref)
@@ -254,7 +302,8 @@ def check_elem(got, ref, bound, what, locate=None):
         raise AssertionError("%s: %d non-finite output elements; first at flat index %d %s: got %r, ref %.6g"
                              % (what, int((~fin).sum()), i, locate(i) if locate else "", float(got.reshape(-1)[i]), float(ref.reshape(-1)[i])))
     err = (got - ref).abs()
-    lim = ulp16(ref) + bound
+    last = U32 * ref.abs() if out_f32 else ulp16(ref)
+    lim = last + bound
     ratio = err / lim
     bad = err > lim
     if bool(bad.any()):
@@ -264,7 +313,7 @@ def check_elem(got, ref, bound, what, locate=None):
                              "err %.3g, limit %.3g (ulp16 %.3g + bound %.3g)"
                              % (what, int(bad.sum()), bad.numel(), f, locate(f) if locate else "", i, locate(i) if locate else "",
                                 float(got.reshape(-1)[i]), float(ref.reshape(-1)[i]), float(err.reshape(-1)[i]), float(lim.reshape(-1)[i]),
-                                float(ulp16(ref).reshape(-1)[i]), float(bound.reshape(-1)[i])))
+                                float(last.reshape(-1)[i]), float(bound.reshape(-1)[i])))
     return float(ratio.max())
 
 
@@ -290,9 +339,11 @@ def _act64(x, act):
     return dict(none=lambda v: v, relu=F.relu, silu=F.silu, gelu=F.gelu)[act](x)
 
 
-def conv_ref_bound(x, w, bias=None, rowadd=None, act="none", res=None, mask=None, stride=1, padding=1, x_err=None):
+def conv_ref_bound(x, w, bias=None, rowadd=None, act="none", res=None, mask=None, stride=1, padding=1, x_err=None,
+                   bias_mul=1.0, out_scale=1.0, res1=None, bias_per_pixel=False):
     """float64 reference and the derived error bound of ladi_op_igemm's convolution / linear epilogue
-        out = fp16( fp16( act(conv(x, w) + bias + rowadd) ) + res ) * (1 - mask)
+        t   = act(conv(x, w) + bias * bias_mul + rowadd)          (bias [Q] by channel, or [N, 1, Ho, Wo] by pixel when bias_per_pixel)
+        out = fp16( fp16(t * out_scale) + res + res1 ) * (1 - mask)
     x [N, C, H, W] (already padded / upsampled as the case needs), w [Q, C, k, k], all values fp16-representable.
 
     Derivation (u = 2^-24, the fp32 unit roundoff).  The kernels accumulate the K = C k k products in fp32; products of two fp16 values are
@@ -307,6 +358,15 @@ def conv_ref_bound(x, w, bias=None, rowadd=None, act="none", res=None, mask=None
     With a residual the epilogue rounds t = f(...) to fp16 BEFORE the residual is added in fp32 (the rounding point of every epilogue of the
     library: igemm_common.h step (1) / (2)), so the bound gains half an ulp16 for that rounding -- evaluated at |t| + e_act so that
     the binade of the computed t is covered -- plus one fp32 rounding of the sum, u |ref|.  The mask multiplies by exactly 0 or 1.
+
+    The VAE's range-guard fields (each term vanishes at the field's neutral value, where the operation is exact in fp32):
+      bias_mul   the product bias * bias_mul is formed in fp32 before it is added: one more rounding, u |bias bias_mul|; the sum and its
+                 magnitude A carry the product
+      out_scale  t * out_scale is one fp32 product, rounded to fp16 at once: the error of t is scaled by |out_scale| and the product adds
+                 u |t out_scale| (zero when out_scale is a power of two -- the general term is kept); the half-ulp16 of the pre-residual
+                 rounding is taken at |t out_scale| + e
+      res1       a second residual is one further fp32 add: u |t out_scale + res| for the first sum as before, u (|ref| + e) for the second,
+                 whose left operand is the computed first sum
     Returns (ref, bound), float64 [N, Q, Ho, Wo]."""
     import torch.nn.functional as F
     x, w = x.double(), w.double()
@@ -318,17 +378,30 @@ def conv_ref_bound(x, w, bias=None, rowadd=None, act="none", res=None, mask=None
         e = e + F.conv2d(x_err.double(), w.abs(), stride=stride, padding=padding)
         xa = xa + x_err.double()                      # the summation bound is over the operand the kernel actually multiplies
     A = F.conv2d(xa, w.abs(), stride=stride, padding=padding)
-    for v in (bias, rowadd):
-        if v is not None:
-            s = s + v.double()[None, :, None, None]
-            A = A + v.double().abs()[None, :, None, None]
+    if bias is not None:
+        b = bias.double() * float(bias_mul)
+        b = b.reshape(s.shape[0], 1, s.shape[2], s.shape[3]) if bias_per_pixel else b[None, :, None, None]
+        s, A = s + b, A + b.abs()
+        if float(bias_mul) != 1.0:
+            e = e + U32 * b.abs()
+    if rowadd is not None:
+        s = s + rowadd.double()[None, :, None, None]
+        A = A + rowadd.double().abs()[None, :, None, None]
     e = e + (K + 2) * U32 * A
     t = _act64(s, act)
     e = ACT_LIP[act] * e + _act_eval_err(s, t, act)
+    if float(out_scale) != 1.0:
+        t = t * float(out_scale)
+        e = abs(float(out_scale)) * e + U32 * t.abs()
     ref = t
-    if res is not None:
-        ref = t + res.double()
-        e = e + 0.5 * ulp16(t.abs() + e) + U32 * ref.abs()
+    if res is not None or res1 is not None:
+        e = e + 0.5 * ulp16(t.abs() + e)
+        if res is not None:
+            ref = ref + res.double()
+            e = e + U32 * ref.abs()
+        if res1 is not None:
+            ref = ref + res1.double()
+            e = e + U32 * (ref.abs() + e)
     if mask is not None:
         ref = ref * (1.0 - mask.double())
         e = e * (1.0 - mask.double())
@@ -351,6 +424,29 @@ def geglu_ref_bound(x, w, b, x_err=None):
     dg = ACT_LIP["gelu"] * eg + _act_eval_err(g, gl, "gelu")
     ref = u * gl
     return ref, gl.abs() * eu + u.abs() * dg + eu * dg + U32 * ref.abs()
+
+
+def gemm_batched_ref_bound(x, w, bias=None, bias_per_pixel=False, res=None, out_f32=False):
+    """float64 reference and bound of a batched launch of the linear form (ladi_op_igemm with batch = B, ksize 1):
+        out[b] = x[b] w[b]^T + bias (+ res[b]),   x[b] [P, K] (the pixel operand), w[b] [Q, K], out[b] [P, Q]
+    x / w / res are lists of B tensors, or of ONE tensor for an operand every element shares (its batch stride is 0); bias is [Q], or [P] when
+    bias_per_pixel, and always shared.  Every element is conv_ref_bound's 1 x 1 case: the same (K + 2) u (|w| |x| + |bias|) summation bound
+    and, with a residual, the same pre-residual rounding.  out_f32: the launch stores the fp32 sum itself -- there is no fp16 rounding, the
+    bound is the summation's alone and check_elem(out_f32=True) grants U32 |ref| for the stored value in place of ulp16(ref).
+    Returns (ref, bound), float64 [B, P, Q]."""
+    B = max(len(x), len(w), len(res) if res is not None else 1)
+    assert all(len(v) in (1, B) for v in (x, w) + ((res,) if res is not None else ())) and not (out_f32 and res is not None)
+    refs, bounds = [], []
+    for b in range(B):
+        xb, wb = x[b % len(x)], w[b % len(w)]
+        P, K = xb.shape
+        Q = wb.shape[0]
+        rb = res[b % len(res)].t().reshape(1, Q, P, 1) if res is not None else None
+        bb = bias.reshape(1, 1, P, 1) if (bias is not None and bias_per_pixel) else bias
+        r, e = conv_ref_bound(xb.t().reshape(1, K, P, 1), wb.reshape(Q, K, 1, 1), bias=bb, bias_per_pixel=bias_per_pixel, res=rb, padding=0)
+        refs.append(r.reshape(Q, P).t())
+        bounds.append(e.reshape(Q, P).t())
+    return torch.stack(refs), torch.stack(bounds)
 
 
 def layer_norm_ref_bound(x, gamma, beta, eps):
