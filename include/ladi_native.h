@@ -287,6 +287,19 @@ int ladi_tryon_set_step_noise(ladi_tryon* t, const float* noise_dev, int steps);
 /* DDIMScheduler.step's eta for the following runs (sticky per handle, default 0): > 0 adds the stochastic term std * noise[i], which needs
  * ladi_tryon_set_step_noise.  Only DDIM reads it: a run of any other scheduler with a non-zero eta fails.  eta < 0 or non-finite: error. */
 int ladi_tryon_set_eta(ladi_tryon* t, float eta);
+/* per-evaluation guidance scale for the following runs (sticky per handle; copied): scales_host[i] is the scale of evaluation i and
+ * in->guidance_scale is ignored while a schedule is set.  NULL or count 0 switches it off.  A run whose evaluation count is not `count`
+ * fails before anything is launched (PNDM has num_inference_steps + 1 evaluations); negative or non-finite entries are an error.  The run is
+ * CFG-shaped (2B samples, negative_prompt_embeds_dev required) if any entry is > 1; inside such a run an evaluation whose entry is <= 1 is
+ * cond-only: the UNet runs over the B conditional samples alone and their prediction is the eps (the rule the reference applies to a whole
+ * run, do_classifier_free_guidance = guidance_scale > 1).  With use_graph the loop replays two graphs, one per kind of evaluation. */
+int ladi_tryon_set_guidance_schedule(ladi_tryon* t, const float* scales_host, int count);
+/* guidance rescale (rescale_noise_cfg of later diffusers releases) for the following runs (sticky per handle, default 0): on every CFG
+ * evaluation the guided prediction of sample b is multiplied by phi * std(cond_b) / std(guided_b) + (1 - phi), unbiased standard deviations
+ * over the sample's 4 * h * w elements, no epsilon.  Cond-only evaluations and runs without CFG are not touched.  phi outside [0, 1]: error. */
+int ladi_tryon_set_guidance_rescale(ladi_tryon* t, float phi);
+/* how many evaluations of the last run ran cond-only, i.e. over B samples (all of them for a run without CFG) */
+int ladi_tryon_cond_only_evals(ladi_tryon* t);
 /* step callback (diffusers' callback / callback_steps): after evaluation i with i % every == 0, on the run's stream, the loop's latents are
  * copied to latents_nchw_dev (caller-owned fp32 [B,4,h,w], what the modular path hands its callback), the stream is synchronised and
  * fn(user, i) runs on the calling thread.  Afterwards work queued on the run's `stream` argument is waited for, and latents_nchw_dev is copied
@@ -438,6 +451,15 @@ int ladi_op_sched_run_noise(int kind, int steps, const float* alphas_cumprod_hos
 /* the same with DDIM's eta (ladi_sched_table_eta's table); eta > 0 needs step noise for every evaluation run */
 int ladi_op_sched_run_noise_eta(int kind, int steps, const float* alphas_cumprod_host, float eta, const void* eps_seq_dev, int evals, int B,
                                 int hw, int cfg, float guidance, float* latents_dev, const float* step_noise_dev, int noise_steps, void* stream);
+/* ladi_op_sched_run_noise_eta with a per-evaluation guidance table, guidance rescale phi and a row stride: eps_seq_dev holds, per evaluation,
+ * 2B rows [uncond ; cond] of hw pixels, ld_eps halves apart (a multiple of 4; lanes 4.. are never read).  An evaluation whose
+ * guidance_tab_host[i] is <= 1 is cond-only and reads rows B..2B-1 alone.  phi in [0, 1] acts on the other evaluations (ladi_op_cfg_stats). */
+int ladi_op_sched_run_guided(int kind, int steps, const float* alphas_cumprod_host, float eta, const void* eps_seq_dev, int ld_eps, int evals,
+                             int B, int hw, const float* guidance_tab_host, float phi, float* latents_dev, const float* step_noise_dev,
+                             int noise_steps, void* stream);
+/* the guidance-rescale statistics kernel on its own: eps_dev [2B][hw] rows of 4 fp16 channels, ld_eps halves apart, uncond half first ->
+ * factor_dev[b] = phi * std(cond_b) / std(u_b + guidance (c_b - u_b)) + (1 - phi), fp32 [B].  Bit-reproducible from call to call. */
+int ladi_op_cfg_stats(const void* eps_dev, int ld_eps, int B, int hw, float guidance, float phi, float* factor_dev, void* stream);
 /* pipeline pre-processing kernels, one entry point per kernel so each can be checked on its own:
  * prepare_mask_and_masked_image (diffusers tensor branch; tryon_pipe.py:630): mask binarised at 0.5 -> mask_bin_dev fp16 [B,H,W];
  *   masked_image_dev NHWC fp16 [B,H,W,ld] (3 valid channels, the rest zero) = image * (mask < 0.5) */

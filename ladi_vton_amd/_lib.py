@@ -139,6 +139,9 @@ SIGNATURES = {
     "ladi_tryon_set_trace": (c_int, [_P, _P, _P, c_int]),
     "ladi_tryon_set_step_noise": (c_int, [_P, _P, c_int]),
     "ladi_tryon_set_eta": (c_int, [_P, c_float]),
+    "ladi_tryon_set_guidance_schedule": (c_int, [_P, POINTER(c_float), c_int]),
+    "ladi_tryon_set_guidance_rescale": (c_int, [_P, c_float]),
+    "ladi_tryon_cond_only_evals": (c_int, [_P]),
     "ladi_tryon_set_step_callback": (c_int, [_P, STEP_CALLBACK, _P, c_int, _P]),
     "ladi_tryon_set_lanes": (c_int, [_P, c_int]),
     "ladi_tryon_lanes": (c_int, [_P]),
@@ -190,6 +193,8 @@ SIGNATURES = {
     "ladi_op_sched_run": (c_int, [c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P]),
     "ladi_op_sched_run_noise": (c_int, [c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int, _P]),
     "ladi_op_sched_run_noise_eta": (c_int, [c_int, c_int, _P, c_float, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int, _P]),
+    "ladi_op_sched_run_guided": (c_int, [c_int, c_int, _P, c_float, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_float, _P, _P, c_int, _P]),
+    "ladi_op_cfg_stats": (c_int, [_P, c_int, c_int, c_int, c_float, c_float, _P, _P]),
     "ladi_op_prepare_mask": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
     "ladi_op_mask_down": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "ladi_op_pose_down8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),

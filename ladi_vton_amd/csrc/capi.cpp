@@ -616,6 +616,22 @@ int ladi_tryon_set_eta(ladi_tryon* t, float eta) {
     t->t.eta = eta;
     return 0;
 }
+int ladi_tryon_set_guidance_schedule(ladi_tryon* t, const float* scales_host, int count) {
+    if (!t || count < 0) { set_error("ladi_tryon_set_guidance_schedule: null handle or negative count"); return -1; }
+    if (!scales_host || count == 0) { t->t.g_sched.clear(); return 0; }
+    for (int i = 0; i < count; ++i)
+        if (!std::isfinite(scales_host[i]) || scales_host[i] < 0.f) {
+            set_error("ladi_tryon_set_guidance_schedule: entry " + std::to_string(i) + " is negative or not finite");
+            return -1;
+        }
+    return guarded("ladi_tryon_set_guidance_schedule", [&]() { t->t.g_sched.assign(scales_host, scales_host + count); return 0; });
+}
+int ladi_tryon_set_guidance_rescale(ladi_tryon* t, float phi) {
+    if (!t || !(phi >= 0.f && phi <= 1.f)) { set_error("ladi_tryon_set_guidance_rescale: null handle, or phi outside [0, 1]"); return -1; }
+    t->t.phi = phi;
+    return 0;
+}
+int ladi_tryon_cond_only_evals(ladi_tryon* t) { return t ? t->t.last_cond_only : -1; }
 int ladi_tryon_set_step_callback(ladi_tryon* t, ladi_step_callback fn, void* user, int every, float* latents_nchw_dev) {
     if (!t) { set_error("ladi_tryon_set_step_callback: null handle"); return -1; }
     if (fn && (every < 1 || !latents_nchw_dev)) { set_error("ladi_tryon_set_step_callback: every must be >= 1 and the latents buffer set"); return -1; }
@@ -916,6 +932,63 @@ int ladi_op_sched_run_noise_eta(int kind, int steps, const float* ac_host, float
                                 float guidance, float* latents, const float* step_noise, int noise_steps, void* stream) {
     return sched_run_any("ladi_op_sched_run_noise_eta", kind, steps, ac_host, eps_seq, evals, B, hw, cfg, guidance, latents, step_noise,
                          noise_steps, eta, stream);
+}
+int ladi_op_cfg_stats(const void* eps, int ld_eps, int B, int hw, float guidance, float phi, float* factor, void* stream) {
+    return guarded("ladi_op_cfg_stats", [&]() {
+        if (!eps || !factor || B <= 0 || hw <= 0) throw std::runtime_error("null argument or empty shape");
+        if (ld_eps < 4 || (ld_eps & 3) || ((uintptr_t)eps & 7)) throw std::runtime_error("ld_eps must be a multiple of 4 (>= 4) and eps 8-byte aligned");
+        if (!(phi >= 0.f && phi <= 1.f)) throw std::runtime_error("phi outside [0, 1]");
+        return ladi_launch_cfg_stats(reinterpret_cast<const h16*>(eps), ld_eps, B, hw, nullptr, nullptr, guidance, phi, factor, S(stream));
+    });
+}
+int ladi_op_sched_run_guided(int kind, int steps, const float* ac_host, float eta, const void* eps_seq, int ld_eps, int evals, int B, int hw,
+                             const float* guidance_tab_host, float phi, float* latents, const float* step_noise, int noise_steps, void* stream) {
+    return guarded("ladi_op_sched_run_guided", [&]() {
+        hipStream_t st = S(stream);
+        if (!eps_seq || !latents || !guidance_tab_host || evals <= 0 || B <= 0 || hw <= 0) throw std::runtime_error("null argument or empty shape");
+        if (ld_eps < 4 || (ld_eps & 3) || ((uintptr_t)eps_seq & 7)) throw std::runtime_error("ld_eps must be a multiple of 4 (>= 4) and eps_seq 8-byte aligned");
+        if (!(phi >= 0.f && phi <= 1.f)) throw std::runtime_error("phi outside [0, 1]");
+        for (int i = 0; i < evals; ++i)
+            if (!std::isfinite(guidance_tab_host[i]) || guidance_tab_host[i] < 0.f) throw std::runtime_error("guidance table entry negative or not finite");
+        std::vector<float> ac;
+        if (ac_host) ac.assign(ac_host, ac_host + 1000); else default_alphas_cumprod(ac);
+        std::vector<double> ts; std::vector<StepTable> tb;
+        build_step_table(kind, steps, ac.data(), 1 << 30, ts, tb, nullptr, eta);
+        if (evals > (int)tb.size()) throw std::runtime_error("evals exceeds scheduler length");
+        if (table_needs_step_noise(tb) && (!step_noise || noise_steps < evals))
+            throw std::runtime_error("EulerAncestralDiscrete / DDIM with eta > 0 need step noise for every evaluation run");
+        char* buf = nullptr;
+        const size_t plane = (size_t)B * hw * 4 * sizeof(float);
+        const size_t tb_bytes = (tb.size() * sizeof(StepTable) + 255) & ~(size_t)255;
+        const size_t gt_bytes = ((size_t)evals * sizeof(float) + 255) & ~(size_t)255;
+        const size_t fc_bytes = ((size_t)B * sizeof(float) + 255) & ~(size_t)255;
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&buf), tb_bytes + 256 + gt_bytes + fc_bytes + 5 * plane));
+        StepTable* dt = reinterpret_cast<StepTable*>(buf);
+        int* dstep = reinterpret_cast<int*>(buf + tb_bytes);
+        float* dgt = reinterpret_cast<float*>(buf + tb_bytes + 256);
+        float* dfc = reinterpret_cast<float*>(buf + tb_bytes + 256 + gt_bytes);
+        float* cur = reinterpret_cast<float*>(buf + tb_bytes + 256 + gt_bytes + fc_bytes);
+        float* ets = cur + (size_t)B * hw * 4;
+        int rc = 0;
+        try {
+            HIP_OK(hipMemcpyAsync(dt, tb.data(), tb.size() * sizeof(StepTable), hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemcpyAsync(dgt, guidance_tab_host, (size_t)evals * sizeof(float), hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemsetAsync(dstep, 0, 8, st));       // evaluation index + the step kernel's arrival ticket
+            const size_t per_eval = (size_t)2 * B * hw * ld_eps;
+            for (int i = 0; i < evals && !rc; ++i) {
+                StepArgs sa; std::memset(&sa, 0, sizeof(sa));
+                sa.eps = reinterpret_cast<const h16*>(eps_seq) + (size_t)i * per_eval; sa.ld_eps = ld_eps;
+                sa.B = B; sa.hw = hw; sa.cfg = 1; sa.latents = latents; sa.cur_sample = cur; sa.ets = ets;
+                sa.table = dt; sa.step_idx = dstep; sa.unet_in = nullptr; sa.step_noise = step_noise;
+                sa.guidance_tab = dgt; sa.factor = phi > 0.f ? dfc : nullptr;
+                if (phi > 0.f && guidance_tab_host[i] > 1.0f) rc = ladi_launch_cfg_stats(sa.eps, ld_eps, B, hw, dgt, dstep, 0.f, phi, dfc, st);
+                if (!rc) rc = ladi_launch_sched_step(sa, st);
+            }
+            HIP_OK(hipStreamSynchronize(st));
+        } catch (...) { (void)hipFree(buf); throw; }
+        (void)hipFree(buf);
+        return rc;
+    });
 }
 
 }  // extern "C"

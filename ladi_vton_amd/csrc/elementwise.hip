@@ -130,12 +130,23 @@ __device__ __forceinline__ void sched_step_body(const StepArgs& a, const int idx
     const size_t row_u = (size_t)idx;                       // uncond (or only) row
     const size_t row_c = (size_t)idx + (size_t)total;       // cond row when cfg
     float e[4];
-    {
+    // guidance table: this evaluation's scale; a scale <= 1 makes it a cond-only evaluation (e = the conditional row, the uncond row is not read)
+    const float g = a.guidance_tab ? a.guidance_tab[step] : a.guidance;
+    if (a.cfg && a.guidance_tab && !(g > 1.0f)) {
+        const h16x4 ec = *reinterpret_cast<const h16x4*>(a.eps + row_c * a.ld_eps);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) e[c] = (float)ec[c];
+    } else {
         const h16x4 eu = *reinterpret_cast<const h16x4*>(a.eps + row_u * a.ld_eps);
         if (a.cfg) {
             const h16x4 ec = *reinterpret_cast<const h16x4*>(a.eps + row_c * a.ld_eps);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) { float u = (float)eu[c]; e[c] = u + a.guidance * ((float)ec[c] - u); }
+            for (int c = 0; c < 4; ++c) { float u = (float)eu[c]; e[c] = u + g * ((float)ec[c] - u); }
+            if (a.factor) {      // guidance rescale: the per-sample factor cfg_stats_kernel wrote for this evaluation
+                const float f = a.factor[b];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) e[c] *= f;
+            }
         } else {
 #pragma unroll
             for (int c = 0; c < 4; ++c) e[c] = (float)eu[c];
@@ -206,6 +217,57 @@ __global__ __launch_bounds__(256) void sched_step_kernel(const StepArgs a) {
     if (threadIdx.x == 0) {
         __threadfence();
         if (atomicAdd(a.step_idx + 1, 1) == (int)gridDim.x - 1) { a.step_idx[1] = 0; a.step_idx[0] = step + 1; }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// guidance rescale (rescale_noise_cfg): per sample b, the unbiased standard deviations over all 4 * hw elements of the conditional
+// prediction c and of the guided one u + g (c - u), factor[b] = phi * std_c / std_g + (1 - phi).  One workgroup per sample, two passes
+// (means, then squared deviations) over rows that stay in L2; every sum is taken in a fixed order (a thread's pixels in index order, the
+// xor butterfly of wave_sum, the four waves in index order), so the result is the same bits on every launch, eager or replayed.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void block_sum2(float& x, float& y, float (*red)[4]) {
+    x = wave_sum(x); y = wave_sum(y);
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();                         // the previous round's readers are done with red
+    if ((threadIdx.x & 63) == 0) { red[0][wave] = x; red[1][wave] = y; }
+    __syncthreads();
+    x = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+    y = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+}
+__global__ __launch_bounds__(256) void cfg_stats_kernel(const h16* __restrict__ eps, int ld_eps, int B, int hw,
+                                                        const float* __restrict__ guidance_tab, const int* __restrict__ step_idx,
+                                                        float guidance, float phi, float* __restrict__ factor) {
+    __shared__ float red[2][4];
+    const int b = blockIdx.x;
+    const float g = guidance_tab ? guidance_tab[*step_idx] : guidance;
+    const h16* pu = eps + (size_t)b * hw * ld_eps;               // uncond rows of sample b
+    const h16* pc = eps + ((size_t)B + b) * hw * ld_eps;         // cond rows
+    float sc = 0.f, sg = 0.f;
+    for (int p = threadIdx.x; p < hw; p += 256) {
+        const h16x4 eu = *reinterpret_cast<const h16x4*>(pu + (size_t)p * ld_eps);
+        const h16x4 ec = *reinterpret_cast<const h16x4*>(pc + (size_t)p * ld_eps);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { const float u = (float)eu[c], cv = (float)ec[c]; sc += cv; sg += u + g * (cv - u); }
+    }
+    block_sum2(sc, sg, red);
+    const float n = 4.f * (float)hw;
+    const float mc = sc / n, mg = sg / n;
+    float qc = 0.f, qg = 0.f;
+    for (int p = threadIdx.x; p < hw; p += 256) {
+        const h16x4 eu = *reinterpret_cast<const h16x4*>(pu + (size_t)p * ld_eps);
+        const h16x4 ec = *reinterpret_cast<const h16x4*>(pc + (size_t)p * ld_eps);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float u = (float)eu[c], cv = (float)ec[c];
+            const float dc = cv - mc, dg = (u + g * (cv - u)) - mg;
+            qc += dc * dc; qg += dg * dg;
+        }
+    }
+    block_sum2(qc, qg, red);
+    if (threadIdx.x == 0) {
+        const float std_c = sqrtf(qc / (n - 1.f)), std_g = sqrtf(qg / (n - 1.f));
+        factor[b] = phi * (std_c / std_g) + (1.f - phi);        // no epsilon: a zero std_g gives what the formula gives
     }
 }
 
@@ -411,6 +473,13 @@ int ladi_launch_timestep_embedding(const float* t, int count, int dim, float* ou
 int ladi_launch_sched_step(const StepArgs& a, hipStream_t st) {
     const int total = a.B * a.hw;
     hipLaunchKernelGGL(sched_step_kernel, dim3((total + 255) / 256), dim3(256), 0, st, a);
+    return ok();
+}
+
+int ladi_launch_cfg_stats(const h16* eps, int ld_eps, int B, int hw, const float* guidance_tab, const int* step_idx, float guidance,
+                          float phi, float* factor, hipStream_t st) {
+    if (B <= 0 || hw <= 0 || ld_eps < 4 || (ld_eps & 3) || ((uintptr_t)eps & 7) || (guidance_tab && !step_idx)) return -1;
+    hipLaunchKernelGGL(cfg_stats_kernel, dim3(B), dim3(256), 0, st, eps, ld_eps, B, hw, guidance_tab, step_idx, guidance, phi, factor);
     return ok();
 }
 

@@ -156,8 +156,20 @@ struct StepArgs {
     // per-evaluation noise (Euler-ancestral, DDIM with eta > 0): fp32 NCHW [evals][B][4][hw], indexed by the device step counter; read only where the
     // table's c_n != 0 (null = none)
     const float* step_noise;
+    // per-evaluation guidance (all null = the scalar path above, bit for bit).  guidance_tab: device fp32 [evals], indexed by the device step
+    // counter, replaces `guidance`; with cfg set, an entry <= 1 makes that evaluation cond-only: e is the conditional row [B, 2B) alone, the
+    // uncond row of eps is not read (both halves of unet_in are still refreshed).  factor: device fp32 [B] of ladi_launch_cfg_stats for this
+    // evaluation, multiplied into the guided e of a CFG evaluation before anything uses it (cond-only evaluations ignore it)
+    const float* guidance_tab;
+    const float* factor;
 };
 int ladi_launch_sched_step(const StepArgs& a, hipStream_t st);
+// guidance rescale statistics of one evaluation: eps as in StepArgs with cfg = 1 (rows [0,B) uncond, [B,2B) cond, row stride ld_eps halves, a
+// multiple of 4; lanes 4.. are never read), g = guidance_tab[*step_idx] (both device) or, with a null table, `guidance`.  Writes
+// factor[b] = phi * std(cond_b) / std(u_b + g (c_b - u_b)) + (1 - phi), unbiased stds over the 4 * hw elements of sample b, fp32, no epsilon.
+// Fixed-order reduction (one workgroup per sample): bit-reproducible across launches and graph replays
+int ladi_launch_cfg_stats(const h16* eps, int ld_eps, int B, int hw, const float* guidance_tab, const int* step_idx, float guidance,
+                          float phi, float* factor, hipStream_t st);
 
 // static part of the 31-channel UNet input: mask, masked-image latents, pose, cloth; uncond half zero pose/cloth
 int ladi_launch_assemble_static(h16* unet_in, int ld_in, int B, int hw, int cfg, const float* latents, const h16* mask_lat,

@@ -252,7 +252,11 @@ struct UNetLanes {
     // x [n,h,w,64] -> eps [n,h,w,ld] (both caller-owned, contiguous in n).  dry: planning pass (records arena / statistics peaks, no
     // launches); concurrent = false runs the lanes one after the other on main_st (first evaluation: per-shape tile measurement wants
     // a quiet chip)
-    void forward(UNet& u, hipStream_t main_st, bool dry, bool concurrent, const Act& x, const Act& eps, const float* temb, const int* tidx);
+    // sub-group form (cond-only evaluations of a CFG-shaped run): x / eps hold x.n < n samples that start at index sample0 of the context
+    // batch, and run on sub_lanes(x.n) of the configured lanes, in their arenas (planned by a dry pass of this form too)
+    void forward(UNet& u, hipStream_t main_st, bool dry, bool concurrent, const Act& x, const Act& eps, const float* temb, const int* tidx,
+                 int sample0 = 0);
+    int sub_lanes(int n_sub) const { int g = G; while (g > 1 && (n_sub % g)) --g; return g; }   // the default rule: lowered until it divides
     void commit_plan();                     // after the dry pass: (re)allocate what grew; not capturable
     unsigned long long key() const;         // part of the hipGraph key: lane count and every address a captured lane may touch
     ~UNetLanes();
@@ -458,6 +462,14 @@ struct TryOn {
     const float* step_noise_src = nullptr; int step_noise_steps = 0;
     float* step_noise_buf = nullptr; size_t step_noise_cap = 0;
     float eta = 0.f;   // DDIM's eta (ladi_tryon_set_eta), sticky; other kinds refuse a non-zero one
+    // per-evaluation guidance (ladi_tryon_set_guidance_schedule, sticky; empty = in.guidance for every evaluation) and guidance rescale phi
+    // (ladi_tryon_set_guidance_rescale).  A run is CFG-shaped (2B rows, both contexts) if any scale is > 1; inside such a run an evaluation
+    // whose scale is <= 1 runs the UNet over the conditional samples [B, 2B) only.  With a schedule or phi > 0 the scales come from the
+    // device table d_gtab, so the two captured graphs (full evaluation: gexec; cond-only evaluation: gexec_cond) serve every value
+    std::vector<float> g_sched; float phi = 0.f;
+    float* d_gtab = nullptr; int gtab_cap = 0; float* d_factor = nullptr; int factor_cap = 0;
+    hipGraph_t graph_cond = nullptr; hipGraphExec_t gexec_cond = nullptr;
+    int last_cond_only = 0;   // evaluations of the last run that ran cond-only (ladi_tryon_cond_only_evals)
     // step callback (ladi_tryon_set_step_callback): after evaluation i with i % cb_every == 0 the latents go to the caller's fp32 NCHW
     // cb_latents, cb_fn(cb_user, i) runs on the host, and cb_latents comes back (edits included); fn == null = off
     int (*cb_fn)(void*, int) = nullptr; void* cb_user = nullptr; int cb_every = 1; float* cb_latents = nullptr;

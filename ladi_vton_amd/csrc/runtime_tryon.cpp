@@ -12,6 +12,8 @@ namespace ladi {
 TryOn::~TryOn() {
     if (gexec) (void)hipGraphExecDestroy(gexec);
     if (graph) (void)hipGraphDestroy(graph);
+    if (gexec_cond) (void)hipGraphExecDestroy(gexec_cond);
+    if (graph_cond) (void)hipGraphDestroy(graph_cond);
     if (stats) (void)hipFree(stats);
     if (step_noise_buf) (void)hipFree(step_noise_buf);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
@@ -59,7 +61,13 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
     const int B = in.batch, H = in.height, W = in.width;
     if (H % 8 || W % 8) { set_error("height and width must be divisible by 8"); return -2; }
     const int h = H / 8, w = W / 8, hw = h * w;
-    const int cfgf = in.guidance > 1.0f ? 1 : 0;
+    // per-evaluation guidance: the run is CFG-shaped if ANY evaluation's scale is > 1; a set schedule replaces in.guidance
+    const bool has_sched = !g_sched.empty();
+    bool any_cfg = in.guidance > 1.0f;
+    if (has_sched) { any_cfg = false; for (float g : g_sched) any_cfg = any_cfg || g > 1.0f; }
+    const int cfgf = any_cfg ? 1 : 0;
+    // guided: the scales come from a device table (a schedule, or the scalar repeated for the rescale statistics); else today's scalar path
+    const bool guided = cfgf && (has_sched || phi > 0.f);
     const int n = cfgf ? 2 * B : B;
     const bool has_cloth = in.warped_cloth != nullptr;
     const int pose_ch = in.pose_channels;
@@ -74,12 +82,27 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
     std::vector<double> timesteps; std::vector<StepTable> table; SchedInfo sinfo;
     build_step_table(in.scheduler, in.steps, ac.data(), in.cloth_zero_from, timesteps, table, &sinfo, eta);
     const int evals = (int)timesteps.size();
+    if (has_sched && (int)g_sched.size() != evals) {
+        set_error("tryon: the guidance schedule has " + std::to_string(g_sched.size()) + " entries, this run has " + std::to_string(evals) +
+                  " evaluations (PNDM: steps + 1)");
+        return -9;
+    }
+    // scale of evaluation i, and whether it runs cond-only (scale <= 1: no unconditional half, as do_classifier_free_guidance of a whole run)
+    std::vector<float> gtab(evals, in.guidance);
+    if (has_sched) gtab = g_sched;
+    auto cond_only = [&](int i) { return guided && !(gtab[i] > 1.0f); };
+    bool any_cond_only = false;
+    for (int i = 0; i < evals; ++i) any_cond_only = any_cond_only || cond_only(i);
+    const bool use_factor = guided && phi > 0.f;
     const bool cloth_zero_from_start = has_cloth && in.cloth_zero_from <= 0;
     last_evals = evals;
+    last_cond_only = 0;      // counted below, where an evaluation over B samples is actually launched
 
     if (!d_step) d_step = reinterpret_cast<int*>(pool.alloc(256));
     if (!sk_cnt) { sk_cnt = reinterpret_cast<int*>(pool.alloc(1024 * sizeof(int))); HIP_OK(hipMemset(sk_cnt, 0, 1024 * sizeof(int))); }
     if (evals > table_cap) { d_table = reinterpret_cast<StepTable*>(pool.alloc((size_t)evals * sizeof(StepTable))); table_cap = evals; }
+    if (guided && evals > gtab_cap) { d_gtab = reinterpret_cast<float*>(pool.alloc((size_t)evals * sizeof(float))); gtab_cap = evals; }
+    if (use_factor && B > factor_cap) { d_factor = reinterpret_cast<float*>(pool.alloc((size_t)B * sizeof(float))); factor_cap = B; }
     if (!ev[0]) for (auto& e : ev) HIP_OK(hipEventCreate(&e));
     // a table with a stochastic term (Euler-ancestral, DDIM with eta > 0): the caller's per-step noise is copied into a runtime-owned buffer
     // (below, on the run's stream) so that the pointer the captured graph holds stays valid after the caller frees theirs
@@ -116,6 +139,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                     if (pr[i] && !(i > 0 && pr[i] == pr[0]) && !(i > 1 && pr[i] == pr[1])) pr[i]->reset(st);
                 HIP_OK(hipMemcpyAsync(d_table, table.data(), (size_t)evals * sizeof(StepTable), hipMemcpyHostToDevice, st));
                 HIP_OK(hipMemsetAsync(d_step, 0, 2 * sizeof(int), st));    // evaluation index + the step kernel's arrival ticket
+                if (guided) HIP_OK(hipMemcpyAsync(d_gtab, gtab.data(), (size_t)evals * sizeof(float), hipMemcpyHostToDevice, st));
                 if (use_step_noise) HIP_OK(hipMemcpyAsync(step_noise_buf, step_noise_src, step_noise_bytes, hipMemcpyDeviceToDevice, st));
                 std::vector<float> tsf(timesteps.begin(), timesteps.end());
                 if (unet->compute_temb(tsf.data(), evals, st)) { rc = -5; break; }
@@ -201,15 +225,28 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
             sa.table = d_table; sa.step_idx = d_step; sa.unet_in = unet_in.p; sa.ld_in = 64; sa.cloth_ch0 = 9 + pose_ch;
             sa.trace_eps = trace_eps; sa.trace_lat = trace_lat; sa.trace_cap = trace_cap;
             sa.step_noise = use_step_noise ? step_noise_buf : nullptr;
+            sa.guidance_tab = guided ? d_gtab : nullptr;
+            sa.factor = use_factor ? d_factor : nullptr;
             // the UNet forward runs as lanes.G independent sample groups on as many streams (runtime.h UNetLanes); the lanes own their
             // arenas, the shared noise prediction lives in this one
             const int eps_ld = (unet->cfg.out_channels + 3) / 4 * 4;
             Act eps = c.new_act(n, h, w, unet->cfg.out_channels, eps_ld);
             const size_t mk_loop = arena.mark();
-            auto one_step = [&](bool concurrent) {
+            // cond: a cond-only evaluation of a guided run -- the UNet runs over the conditional samples [B, 2B) (their rows of unet_in and
+            // eps, their part of the K/V cache) and the step kernel, told by the table, reads only those rows of eps
+            auto one_step = [&](bool concurrent, bool cond = false) {
                 arena.release(mk_loop);
-                lanes.forward(*unet, st, c.dry(), concurrent, unet_in, eps, unet->temb_table, d_step);
-                if (!c.dry()) { sa.eps = eps.p; sa.ld_eps = eps.ld; c.check(ladi_launch_sched_step(sa, st), "sched_step"); }
+                if (cond) {
+                    Act xs = unet_in, es = eps;
+                    xs.n = B; xs.p = unet_in.p + (size_t)B * hw * unet_in.ld;
+                    es.n = B; es.p = eps.p + (size_t)B * hw * eps.ld;
+                    lanes.forward(*unet, st, c.dry(), concurrent, xs, es, unet->temb_table, d_step, B);
+                } else lanes.forward(*unet, st, c.dry(), concurrent, unet_in, eps, unet->temb_table, d_step);
+                if (c.dry()) return;
+                sa.eps = eps.p; sa.ld_eps = eps.ld;
+                if (use_factor && !cond)
+                    c.check(ladi_launch_cfg_stats(eps.p, eps.ld, B, hw, d_gtab, d_step, 0.f, phi, d_factor, st), "cfg_stats");
+                c.check(ladi_launch_sched_step(sa, st), "sched_step");
             };
             // step callback after evaluation i (between launches, never inside a capture): latents out to the caller's NCHW buffer, the host
             // call, the buffer back into the loop and the next UNet input.  Work the callback queued on the caller's stream comes first.
@@ -226,15 +263,26 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 HIP_OK(hipStreamWaitEvent(st, ev_in, 0));
                 c.check(ladi_launch_latents_import(cb_latents, B, hw, latents, unet_in.p, 64, cfgf, table[i].in_scale_next, st), "callback import");
             };
-            if (c.dry()) one_step(false);
-            else if (!in.use_graph || evals < 3) { for (int i = 0; i < evals && !cb_rc; ++i) { one_step(i > 0); callback_point(i); } }
-            else {
-                one_step(false);  // eager first evaluation, lanes one after the other (one-time function attribute setup, per-shape tile measurement)
+            // the first evaluation of either form runs its lanes one after the other (one-time function attribute setup, per-shape tile measurement)
+            bool seen[2] = {false, false};
+            // an evaluation whose forward ran over B samples (launched eagerly or by replaying the cond-only graph; every one of a run without CFG)
+            auto ran = [&](bool co) { if (co || !cfgf) ++last_cond_only; };
+            if (c.dry()) { one_step(false); if (any_cond_only) one_step(false, true); }
+            else if (!in.use_graph || evals < 3) {
+                for (int i = 0; i < evals && !cb_rc; ++i) {
+                    const bool co = cond_only(i);
+                    one_step(i > 0 && seen[co], co); seen[co] = true; ran(co);
+                    callback_point(i);
+                }
+            } else {
+                one_step(false, cond_only(0));  // eager first evaluation
+                seen[cond_only(0)] = true; ran(cond_only(0));
                 callback_point(0);
                 unsigned long long key = 0x1234;
                 key = mix(key, (unsigned long long)(uintptr_t)arena.base); key = mix(key, (unsigned long long)B * 1000003ULL + H * 4099ULL + W);
                 key = mix(key, (unsigned long long)cfgf); key = mix(key, (unsigned long long)L);
-                unsigned gb; std::memcpy(&gb, &in.guidance, 4); key = mix(key, gb);
+                unsigned gb = 0; if (!guided) std::memcpy(&gb, &in.guidance, 4);     // with a table the scalar is ignored: not part of the key
+                key = mix(key, gb);
                 key = mix(key, (unsigned long long)(uintptr_t)unet->temb_table); key = mix(key, (unsigned long long)(uintptr_t)unet->mid_xf.kv_cache);
                 key = mix(key, (unsigned long long)(uintptr_t)d_table); key = mix(key, (unsigned long long)(uintptr_t)stats);
                 key = mix(key, (unsigned long long)pose_ch * 7 + has_cloth);
@@ -245,16 +293,39 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 // a graph captured without the probe launches is never replayed with it, nor one that holds another probe's slots: the id is
                 // unique per Probe (0 = none), and within one Probe a name keeps its slot
                 key = mix(key, unet->probe ? unet->probe->id : 0ULL);
-                if (!cb_rc && (!gexec || key != graph_key)) {
+                // both graphs (full and cond-only evaluation) live under one key, with the guidance table, the factor buffer and phi
+                unsigned pb; std::memcpy(&pb, &phi, 4);
+                key = mix(key, (unsigned long long)(uintptr_t)sa.guidance_tab); key = mix(key, (unsigned long long)(uintptr_t)sa.factor);
+                key = mix(key, guided ? 0x100000000ULL | pb : 0ULL);
+                if (key != graph_key) {
                     if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
                     if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
-                    HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-                    try { one_step(true); } catch (...) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(st, &g); if (g) (void)hipGraphDestroy(g); throw; }
-                    HIP_OK(hipStreamEndCapture(st, &graph));
-                    HIP_OK(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
+                    if (gexec_cond) { (void)hipGraphExecDestroy(gexec_cond); gexec_cond = nullptr; }
+                    if (graph_cond) { (void)hipGraphDestroy(graph_cond); graph_cond = nullptr; }
                     graph_key = key;
                 }
-                for (int i = 1; i < evals && !cb_rc; ++i) { HIP_OK(hipGraphLaunch(gexec, st)); callback_point(i); }
+                auto capture = [&](bool co) {
+                    hipGraph_t& gr = co ? graph_cond : graph;
+                    hipGraphExec_t& ge = co ? gexec_cond : gexec;
+                    if (gr) { (void)hipGraphDestroy(gr); gr = nullptr; }     // left by a capture whose instantiation failed
+                    HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+                    try { one_step(true, co); } catch (...) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(st, &g); if (g) (void)hipGraphDestroy(g); throw; }
+                    HIP_OK(hipStreamEndCapture(st, &gr));
+                    HIP_OK(hipGraphInstantiate(&ge, gr, nullptr, nullptr, 0));
+                };
+                // the host knows the schedule and picks the graph; the values come from the device table.  A form that this run has not yet
+                // run eagerly and that has no graph runs eagerly once (see above), its next evaluation captures
+                for (int i = 1; i < evals && !cb_rc; ++i) {
+                    const bool co = cond_only(i);
+                    hipGraphExec_t& ge = co ? gexec_cond : gexec;
+                    if (!ge && !seen[co]) { one_step(false, co); seen[co] = true; }
+                    else {
+                        if (!ge) capture(co);
+                        HIP_OK(hipGraphLaunch(ge, st));
+                    }
+                    ran(co);
+                    callback_point(i);
+                }
             }
             arena.release(mk_loop);
             if (cb_rc) {

@@ -355,7 +355,7 @@ void UNetLanes::reset() {
     for (int i = 0; i < MAXG; ++i) {
         if (st[i]) (void)hipStreamSynchronize(st[i]);
         arena[i].~Arena(); new (&arena[i]) Arena();
-        peak[i] = 0;
+        peak[i] = 0; stats_peak[i] = 0;
     }
 }
 
@@ -371,11 +371,13 @@ void UNetLanes::configure(int n, int g) {
     }
 }
 
-void UNetLanes::forward(UNet& u, hipStream_t main_st, bool dry, bool concurrent, const Act& x, const Act& eps, const float* temb, const int* tidx) {
-    const int ng = x.n / G;
-    const bool par = concurrent && !dry && G > 1;
+void UNetLanes::forward(UNet& u, hipStream_t main_st, bool dry, bool concurrent, const Act& x, const Act& eps, const float* temb, const int* tidx,
+                        int sample0) {
+    const int Gu = sub_lanes(x.n);          // the configured count when it divides x.n (always, for the whole batch)
+    const int ng = x.n / Gu;
+    const bool par = concurrent && !dry && Gu > 1;
     if (par) HIP_OK_L(hipEventRecord(fork, main_st));
-    for (int g = 0; g < G; ++g) {
+    for (int g = 0; g < Gu; ++g) {
         hipStream_t sg = (par && g > 0) ? st[g] : main_st;
         if (par && g > 0) HIP_OK_L(hipStreamWaitEvent(sg, fork, 0));
         arena[g].dry = dry; arena[g].off = 0;
@@ -383,8 +385,8 @@ void UNetLanes::forward(UNet& u, hipStream_t main_st, bool dry, bool concurrent,
         if (!dry && stats_cap[g]) HIP_OK_L(hipMemsetAsync(stats[g], 0, stats_cap[g] * sizeof(float), sg));
         Act xg = x; xg.n = ng; xg.p = x.p + (size_t)g * ng * x.h * x.w * x.ld;
         Act eg = eps; eg.n = ng; eg.p = eps.p + (size_t)g * ng * eps.h * eps.w * eps.ld; eg.st_part = nullptr; eg.st_px = 0;
-        (void)u.forward(c, xg, temb, tidx, &eg, g * ng);
-        if (dry) { peak[g] = arena[g].peak; stats_peak[g] = c.stats_peak; }
+        (void)u.forward(c, xg, temb, tidx, &eg, sample0 + g * ng);
+        if (dry) { peak[g] = arena[g].peak; if (c.stats_peak > stats_peak[g]) stats_peak[g] = c.stats_peak; }
         if (par && g > 0) { HIP_OK_L(hipEventRecord(join[g], sg)); HIP_OK_L(hipStreamWaitEvent(main_st, join[g], 0)); }
     }
 }

@@ -8,6 +8,7 @@ Two execution modes with identical semantics:
 import ctypes
 import inspect
 import math
+import numbers
 from types import SimpleNamespace
 
 import numpy as np
@@ -22,6 +23,45 @@ from .schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncest
 # the schedulers the fused native loop runs (ladi_tryon_run): the native step table of each is the mirror's arithmetic
 FUSED_SCHEDULERS = (DDIMScheduler, PNDMScheduler, LMSDiscreteScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler,
                     EulerAncestralDiscreteScheduler)
+
+
+def guidance_interval(n_evals, scale, start=0.0, stop=1.0):
+    """a guidance schedule for `guidance_scale=`: `scale` on the evaluations ceil(start * n_evals) <= i < ceil(stop * n_evals), 1.0 (cond-only:
+    no unconditional forward) elsewhere"""
+    n = int(n_evals)
+    if n < 0 or not (0.0 <= start <= 1.0) or not (0.0 <= stop <= 1.0):
+        raise ValueError("guidance_interval: n_evals >= 0 and start, stop in [0, 1]")
+    lo, hi = math.ceil(start * n), math.ceil(stop * n)
+    return [float(scale) if lo <= i < hi else 1.0 for i in range(n)]
+
+
+def guidance_plan(guidance_scale, n_evals, guidance_rescale=0.0):
+    """-> (table, scalar, do_cfg).  guidance_scale: a float (table is None: one scale for the run), a sequence of n_evals scales, or a
+    callable f(i, n_evals); n_evals: len(scheduler.timesteps) or a callable returning it (only asked for a schedule).  do_cfg: any scale > 1.
+    An evaluation whose scale is <= 1 runs cond-only.  Raises ValueError for a wrong length, a negative or non-finite entry, or a
+    guidance_rescale outside [0, 1]."""
+    phi = float(guidance_rescale)
+    if not (0.0 <= phi <= 1.0):
+        raise ValueError("`guidance_rescale` has to be in [0, 1] but is %r." % (guidance_rescale,))
+    if isinstance(guidance_scale, numbers.Real) or (not callable(guidance_scale) and getattr(guidance_scale, "ndim", 1) == 0):
+        return None, float(guidance_scale), float(guidance_scale) > 1.0
+    n = int(n_evals() if callable(n_evals) else n_evals)
+    if callable(guidance_scale):
+        table = [float(guidance_scale(i, n)) for i in range(n)]
+    else:
+        table = [float(g) for g in guidance_scale]
+        if len(table) != n:
+            raise ValueError("`guidance_scale` has %d entries but the scheduler runs %d evaluations (len(scheduler.timesteps))." % (len(table), n))
+    for i, g in enumerate(table):
+        if not math.isfinite(g) or g < 0.0:
+            raise ValueError("`guidance_scale[%d]` = %r: every scale has to be finite and >= 0." % (i, g))
+    return table, (table[0] if table else 1.0), any(g > 1.0 for g in table)
+
+
+def rescale_noise_cfg(eps, eps_cond, phi):
+    """guidance rescale: eps * (phi * std(eps_cond) / std(eps) + 1 - phi), per-sample unbiased stds, no epsilon"""
+    dims = list(range(1, eps.ndim))
+    return eps * (phi * (eps_cond.std(dim=dims, keepdim=True) / eps.std(dim=dims, keepdim=True)) + (1.0 - phi))
 
 
 def numpy_to_pil(images):
@@ -167,8 +207,11 @@ class StableDiffusionTryOnePipeline:
                  guidance_scale=7.5, negative_prompt=None, num_images_per_prompt=1, eta=0.0, prompt_embeds=None,
                  negative_prompt_embeds=None, generator=None, latents=None, output_type="pil", return_dict=True, callback=None,
                  callback_steps=1, cloth_cond_rate=1.0, no_pose=False, cloth_input_type="warped", fused=True, noise=None,
-                 use_graph=True):
-        """tryon_pipe.py's __call__.  `height` / `width`: any multiple of 8, as the reference's check_inputs.  Latent sides that are not
+                 use_graph=True, guidance_rescale=0.0):
+        """tryon_pipe.py's __call__.  `guidance_scale`: a float, a sequence with one scale per evaluation (len(scheduler.timesteps); PNDM: steps
+        + 1) or a callable f(i, n_evals) -- see guidance_interval.  Classifier-free guidance is on if any scale is > 1; an evaluation whose scale
+        is <= 1 then runs the UNet over the conditional samples only.  `guidance_rescale` (rescale_noise_cfg's phi, [0, 1]) acts on the CFG
+        evaluations.  `height` / `width`: any multiple of 8, as the reference's check_inputs.  Latent sides that are not
         multiples of 8 (e.g. 640x480 -> 80x60) run diffusers' `forward_upsample_size` arithmetic on both the fused and the modular path."""
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
@@ -184,8 +227,11 @@ class StableDiffusionTryOnePipeline:
         # can run are image batches that already hold B * k samples -- the same rule applies here (shape checks below)
         if not isinstance(num_images_per_prompt, int) or num_images_per_prompt < 1:
             raise ValueError("num_images_per_prompt must be a positive integer")
+        def n_evals():
+            self.scheduler.set_timesteps(num_inference_steps)
+            return len(self.scheduler.timesteps)
+        g_table, guidance_scale, do_cfg = guidance_plan(guidance_scale, n_evals, guidance_rescale)
         device = self._execution_device
-        do_cfg = guidance_scale > 1.0
         pe, neg = self._encode_prompt(prompt, device, num_images_per_prompt, do_cfg, negative_prompt, prompt_embeds, negative_prompt_embeds)
         B = pe.shape[0]
         self._validate_images(image, mask_image)
@@ -218,14 +264,15 @@ class StableDiffusionTryOnePipeline:
             images = self._run_fused(image, mask_image, pose_map, warped_cloth if cloth_input_type == "warped" else None, pe, neg,
                                      n_cloth, n_lat, n_mask, height, width, num_inference_steps, guidance_scale, cloth_cond_rate,
                                      no_pose, use_graph, step_noise=step_noise, eta=ddim_eta, callback=callback,
-                                     callback_steps=callback_steps)
+                                     callback_steps=callback_steps, guidance_table=g_table, guidance_rescale=guidance_rescale)
             # prepare_mask_and_masked_image binarises the caller's mask in place; keep that side effect
             mask_image[mask_image < 0.5] = 0
             mask_image[mask_image >= 0.5] = 1
         else:
             images = self._run_modular(image, mask_image, pose_map, warped_cloth if cloth_input_type == "warped" else None, pe, neg,
                                        n_cloth, n_lat, n_mask, height, width, num_inference_steps, guidance_scale, cloth_cond_rate,
-                                       no_pose, eta, generator, callback, callback_steps)
+                                       no_pose, eta, generator, callback, callback_steps, guidance_table=g_table,
+                                       guidance_rescale=guidance_rescale)
         if output_type == "pil":
             images = numpy_to_pil(images)
         if not return_dict:
@@ -234,11 +281,13 @@ class StableDiffusionTryOnePipeline:
 
     # -------------------------------------------------------------------------------------------------------
     def _run_fused(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose,
-                   use_graph, return_device=False, out_uint8=False, lanes=None, step_noise=None, eta=0.0, callback=None, callback_steps=1):
+                   use_graph, return_device=False, out_uint8=False, lanes=None, step_noise=None, eta=0.0, callback=None, callback_steps=1,
+                   guidance_table=None, guidance_rescale=0.0):
         """return_device: hand back the device tensor (no host copy); out_uint8: the batch as uint8 [B,H,W,3] = numpy_to_pil's
         (images * 255).round() computed by the decode epilogue (ladi_tryon_run_u8); lanes: sample-group lanes of the UNet forward;
         step_noise: fp32 [steps, B, 4, h, w], the per-step noise of EulerAncestralDiscreteScheduler and of DDIM with eta > 0
-        (ladi_tryon_set_step_noise); eta: DDIM's eta (ladi_tryon_set_eta, DDIM only);
+        (ladi_tryon_set_step_noise); eta: DDIM's eta (ladi_tryon_set_eta, DDIM only); guidance_table: one scale per evaluation, replaces
+        `guidance` (ladi_tryon_set_guidance_schedule; None = off); guidance_rescale: phi of ladi_tryon_set_guidance_rescale;
         callback / callback_steps: called as callback(i, self.scheduler.timesteps[i], latents) after every evaluation i with
         i % callback_steps == 0, latents an fp32 [B, 4, h, w] device tensor whose in-place edits the loop takes over
         (ladi_tryon_set_step_callback).  An exception in the callback aborts the run and is re-raised here.  When the decode's fp16-range
@@ -301,6 +350,12 @@ class StableDiffusionTryOnePipeline:
         else:
             check(lib.ladi_tryon_set_step_noise(self._tryon, None, 0), "ladi_tryon_set_step_noise")
         check(lib.ladi_tryon_set_eta(self._tryon, float(eta)), "ladi_tryon_set_eta")
+        if guidance_table is not None:
+            gt = (ctypes.c_float * len(guidance_table))(*guidance_table)
+            check(lib.ladi_tryon_set_guidance_schedule(self._tryon, gt, len(guidance_table)), "ladi_tryon_set_guidance_schedule")
+        else:
+            check(lib.ladi_tryon_set_guidance_schedule(self._tryon, None, 0), "ladi_tryon_set_guidance_schedule")
+        check(lib.ladi_tryon_set_guidance_rescale(self._tryon, float(guidance_rescale)), "ladi_tryon_set_guidance_rescale")
         cb_error = []
         cb_latents = trampoline = None
         if callback is not None:
@@ -375,6 +430,10 @@ class StableDiffusionTryOnePipeline:
             raise _lib.NativeError("ladi_tryon_poll_overflow: " + _lib.last_error())
         return po == 1
 
+    def cond_only_evals(self):
+        """how many evaluations of the last fused run ran cond-only (ladi_tryon_cond_only_evals)"""
+        return _lib.load().ladi_tryon_cond_only_evals(self._tryon) if self._tryon else None
+
     def lib_lanes(self):
         """sample-group lanes the last fused run used"""
         return _lib.load().ladi_tryon_lanes(self._tryon) if self._tryon else None
@@ -386,7 +445,7 @@ class StableDiffusionTryOnePipeline:
 
     # -------------------------------------------------------------------------------------------------------
     def _run_modular(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose, eta,
-                     generator, callback, callback_steps):
+                     generator, callback, callback_steps, guidance_table=None, guidance_rescale=0.0):
         F = torch.nn.functional
         dev = self._execution_device
         do_cfg = neg is not None
@@ -426,17 +485,25 @@ class StableDiffusionTryOnePipeline:
             extra["eta"] = eta
         if "generator" in params:
             extra["generator"] = generator
+        B = latents.shape[0]
         for i, t in enumerate(timesteps):
-            x = torch.cat([latents] * 2) if do_cfg else latents
+            g_i = guidance_table[i] if guidance_table is not None else guidance
+            # a cond-only evaluation of a CFG run (scale <= 1): the B conditional samples and the conditional context alone
+            cfg_i = do_cfg and (guidance_table is None or g_i > 1.0)
+            x = torch.cat([latents] * 2) if cfg_i else latents
             if cloth_lat is not None and i >= (steps - ccs):
                 cloth_lat = torch.zeros_like(cloth_lat)
             x = self.scheduler.scale_model_input(x, t)
             parts = [x, mask_lat, masked_lat, pose] + ([cloth_lat] if cloth_lat is not None else [])
+            if do_cfg and not cfg_i:
+                parts = [x] + [p[B:] for p in parts[1:]]
             x = torch.cat([p.float() for p in parts], dim=1)
-            eps = self.unet(x, t, encoder_hidden_states=ehs).sample.float()
-            if do_cfg:
+            eps = self.unet(x, t, encoder_hidden_states=ehs if cfg_i or not do_cfg else pe).sample.float()
+            if cfg_i:
                 eu, et = eps.chunk(2)
-                eps = eu + guidance * (et - eu)
+                eps = eu + g_i * (et - eu)
+                if guidance_rescale > 0.0:
+                    eps = rescale_noise_cfg(eps, et, guidance_rescale)
             latents = self.scheduler.step(eps, t, latents, **extra).prev_sample
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, latents)
