@@ -38,10 +38,10 @@
 
 int ladi_igemm_num_cfgs();
 #include "igemm_tiles.h"
-// one launcher per ring-kernel tile shape, defined in igemm_inst_*.hip (igemm_kernel.h)
-#define X(base, WQ, WP, TQ, TP, BK, NST, OCC, ILV) int ladi_igemm_launch_base_##base(IGemmArgs a, int batch, hipStream_t st);
-LADI_IGEMM_TILES_ALL(X)
-#undef X
+// one launcher per kernel form (row of igemm_tiles.h), defined in the unit that instantiates the form
+#define LADI_PER_BASE(base) int ladi_igemm_launch_base_##base(IGemmArgs a, int batch, hipStream_t st);
+LADI_IGEMM_LAUNCHER_BASES
+#undef LADI_PER_BASE
 
 namespace {
 
@@ -109,157 +109,197 @@ bool ensure_ws(size_t bytes, hipStream_t st) {
     return true;
 }
 
-struct CfgInfo { int bq, bp, blocks_per_cu; bool geglu_ok; float eff; int tp; int base; int split; int bk; bool tune; };
-// tile configurations (0 = choose: measured per shape when autotuning is on, else the cost model below).
-// {bq, bp, workgroups per CU (cost model), GEGLU-capable, cost-model efficiency (0 = measured selection only), tp, base kernel, split-K,
-//  K step, offered to the tuner}
+// What a kernel form is, derived from its row of igemm_tiles.h and indexed by base id: the family (the code its launcher passes to
+// ladi_igemm_note_launch), the workgroup tile bq x bp, tp = 32-pixel blocks per wave (the statistics row height), the K step, and for the
+// halo forms the widest image row, the 2-D blocked / folded-upsample kind and th = image rows per 2-D block.  The X-stationary kernel has
+// no tile of its own (see CfgInfo): its row gives the family and the weight-ring depth only.
+enum { FAM_RING = 1, FAM_IGEMM8 = 2, FAM_LC = 3, FAM_HALO = 4, FAM_XS = 5 };
+struct BaseTrait { int family, bq, bp, tp, bk, wmax, g2d, ups, th, xs_nst; };
+constexpr int NBASE = 107;
+struct BaseTable { BaseTrait t[NBASE]; };
+constexpr BaseTable make_base_table() {
+    BaseTable b{};
+#define X(base, WQ, WP, TQ, TP, BK, NST, OCC, ILV) b.t[base] = {FAM_RING, 32 * WQ * TQ, 32 * WP * TP, TP, BK, 0, 0, 0, 0, 0};
+    LADI_IGEMM_TILES_ALL(X)
+#undef X
+#define X(base, TQ, TP) b.t[base] = {FAM_IGEMM8, 64 * TQ, 128 * TP, TP, 64, 0, 0, 0, 0, 0};
+    LADI_IGEMM8_TILES(X)
+#undef X
+#define X(base, WQ, WP, TQ, TP, NL, NST) b.t[base] = {FAM_LC, 32 * WQ * TQ, 32 * WP * TP, TP, 64, 0, 0, 0, 0, 0};
+    LADI_IGEMM_LC_TILES(X)
+#undef X
+#define X(base, TQ, TP, NXB, NSTW, WPN, WMAX, ONE, G2D, UPS) b.t[base] = {FAM_HALO, 64 * TQ, 32 * WPN * TP, TP, 64, WMAX, G2D, UPS, WPN * TP, 0};
+    LADI_HALO_TILES_ALL(X)
+#undef X
+#define X(base, NST) b.t[base] = {FAM_XS, 0, 0, 0, 0, 0, 0, 0, 0, NST};
+    LADI_LINEAR_XS_FORMS(X)
+#undef X
+    return b;
+}
+constexpr BaseTable kBase = make_base_table();
+
+// What is genuinely per configuration: {base kernel form, split-K, workgroups per CU (cost model), GEGLU-capable, cost-model efficiency (0 =
+// measured selection only), offered to the tuner}, and for the X-stationary kernel, whose configurations share one form, {32-pixel blocks per
+// wave, channel slices over gridDim.y}.  Configuration 0 = choose: measured per shape when autotuning is on, else the cost model below.
+struct CfgInfo { int base, split, blocks_per_cu; bool geglu_ok; float eff; bool tune; int xs_pb = 0, xs_qs = 0; };
 constexpr int NCFG = 109;
-const CfgInfo kCfg[NCFG + 1] = {
-    {0, 0, 0, false, 0.f, 0, 0, 1, 0, false},
-    {128, 256, 2, true, 0.80f, 4, 1, 1, 32, true},   // 1: <2,2,2,4> BK32 NST3
-    {320, 128, 2, false, 1.00f, 2, 2, 1, 32, true},  // 2: <2,2,5,2> BK32 NST2 (Cout = 320 layers, no padding waste)
-    {128, 128, 3, true, 1.00f, 2, 3, 1, 32, true},   // 3: <2,2,2,2> BK32 NST3
-    {128, 64, 4, true, 0.80f, 1, 4, 1, 32, true},    // 4: <2,2,2,1> BK32 NST3
-    {64, 64, 6, false, 0.60f, 1, 5, 1, 32, true},    // 5: <2,2,1,1> BK32 NST3
-    {256, 128, 2, true, 0.85f, 2, 6, 1, 32, true},   // 6: <2,2,4,2> BK32 NST3
-    {128, 128, 2, true, 0.00f, 2, 7, 1, 64, true},   // 7: <2,2,2,2> BK64 NST2   (eff 0: picked by measurement only, not by the fallback cost model)
-    {128, 256, 1, true, 0.00f, 4, 8, 1, 64, false},  // 8: <2,2,2,4> BK64 NST2   (never won a shape: not offered to the tuner)
-    {128, 64, 2, true, 0.00f, 1, 9, 1, 64, true},    // 9: <2,2,2,1> BK64 NST3
-    {320, 128, 1, false, 0.00f, 2, 10, 1, 64, false},  // 10: <2,2,5,2> BK64 NST2
-    {128, 64, 2, false, 0.00f, 1, 9, 2, 64, true},    // 11: cfg 9 + split-K 2
-    {128, 64, 2, false, 0.00f, 1, 9, 4, 64, true},    // 12: cfg 9 + split-K 4
-    {128, 64, 2, false, 0.00f, 1, 9, 8, 64, true},    // 13: cfg 9 + split-K 8
-    {128, 128, 2, false, 0.00f, 2, 7, 2, 64, true},   // 14: cfg 7 + split-K 2
-    {128, 128, 2, false, 0.00f, 2, 7, 4, 64, true},   // 15: cfg 7 + split-K 4
-    {64, 64, 5, false, 0.00f, 1, 16, 1, 32, true},    // 16: <2,2,1,1> BK32 NST4 (deeper prefetch for shallow-K, latency-bound GEMMs)
-    {128, 64, 3, true, 0.00f, 1, 17, 1, 32, true},    // 17: <2,2,2,1> BK32 NST4
-    {128, 128, 2, true, 0.00f, 2, 18, 1, 32, true},   // 18: <2,2,2,2> BK32 NST4
-    {128, 256, 2, true, 0.00f, 2, 19, 1, 32, true},   // 19: <2,4,2,2> BK32 NST3   8 waves (512 threads)
-    {256, 128, 2, true, 0.00f, 2, 20, 1, 32, true},   // 20: <4,2,2,2> BK32 NST3   8 waves
-    {256, 256, 1, true, 0.00f, 2, 21, 1, 32, true},   // 21: <2,4,4,2> BK32 NST3   8 waves, 96 KB LDS
-    {320, 256, 1, false, 0.00f, 2, 22, 1, 64, true},  // 22: <2,4,5,2> BK64 NST2   8 waves, 144 KB LDS
-    // 23..27: X-stationary linear kernel (linear_xs.hip; K = 320 / 640 token-wise projections).  bq field = channel slices
-    // over gridDim.y, tp field = 32-pixel blocks per wave
-    {1, 256, 2, false, 0.00f, 2, 23, 1, 0, true},    // 23: 64 pixels / wave, 1 channel slice
-    {2, 256, 2, false, 0.00f, 2, 23, 1, 0, true},    // 24: 64 pixels / wave, 2 channel slices
-    {1, 128, 2, true, 0.00f, 1, 23, 1, 0, true},     // 25: 32 pixels / wave, 1 channel slice   (25..27 also: residual, GEGLU)
-    {2, 128, 2, true, 0.00f, 1, 23, 1, 0, true},     // 26: 32 pixels / wave, 2 channel slices
-    {5, 128, 2, true, 0.00f, 1, 23, 1, 0, true},     // 27: 32 pixels / wave, 5 channel slices
+constexpr CfgInfo kCfg[NCFG + 1] = {
+    {0, 1, 0, false, 0.f, false},
+    {1, 1, 2, true, 0.80f, true},         // 1: <2,2,2,4> BK32 NST3
+    {2, 1, 2, false, 1.00f, true},        // 2: <2,2,5,2> BK32 NST2 (Cout = 320 layers, no padding waste)
+    {3, 1, 3, true, 1.00f, true},         // 3: <2,2,2,2> BK32 NST3
+    {4, 1, 4, true, 0.80f, true},         // 4: <2,2,2,1> BK32 NST3
+    {5, 1, 6, false, 0.60f, true},        // 5: <2,2,1,1> BK32 NST3
+    {6, 1, 2, true, 0.85f, true},         // 6: <2,2,4,2> BK32 NST3
+    {7, 1, 2, true, 0.00f, true},         // 7: <2,2,2,2> BK64 NST2   (eff 0: picked by measurement only, not by the fallback cost model)
+    {8, 1, 1, true, 0.00f, false},        // 8: <2,2,2,4> BK64 NST2   (never won a shape: not offered to the tuner)
+    {9, 1, 2, true, 0.00f, true},         // 9: <2,2,2,1> BK64 NST3
+    {10, 1, 1, false, 0.00f, false},      // 10: <2,2,5,2> BK64 NST2
+    {9, 2, 2, false, 0.00f, true},        // 11: cfg 9 + split-K 2
+    {9, 4, 2, false, 0.00f, true},        // 12: cfg 9 + split-K 4
+    {9, 8, 2, false, 0.00f, true},        // 13: cfg 9 + split-K 8
+    {7, 2, 2, false, 0.00f, true},        // 14: cfg 7 + split-K 2
+    {7, 4, 2, false, 0.00f, true},        // 15: cfg 7 + split-K 4
+    {16, 1, 5, false, 0.00f, true},       // 16: <2,2,1,1> BK32 NST4 (deeper prefetch for shallow-K, latency-bound GEMMs)
+    {17, 1, 3, true, 0.00f, true},        // 17: <2,2,2,1> BK32 NST4
+    {18, 1, 2, true, 0.00f, true},        // 18: <2,2,2,2> BK32 NST4
+    {19, 1, 2, true, 0.00f, true},        // 19: <2,4,2,2> BK32 NST3   8 waves (512 threads)
+    {20, 1, 2, true, 0.00f, true},        // 20: <4,2,2,2> BK32 NST3   8 waves
+    {21, 1, 1, true, 0.00f, true},        // 21: <2,4,4,2> BK32 NST3   8 waves, 96 KB LDS
+    {22, 1, 1, false, 0.00f, true},       // 22: <2,4,5,2> BK64 NST2   8 waves, 144 KB LDS
+    // 23..27: X-stationary linear kernel (linear_xs.hip; K = 320 / 640 token-wise projections), with its two own fields: 32-pixel blocks per
+    // wave, channel slices over gridDim.y
+    {23, 1, 2, false, 0.00f, true, 2, 1}, // 23: 64 pixels / wave, 1 channel slice
+    {23, 1, 2, false, 0.00f, true, 2, 2}, // 24: 64 pixels / wave, 2 channel slices
+    {23, 1, 2, true, 0.00f, true, 1, 1},  // 25: 32 pixels / wave, 1 channel slice   (25..27 also: residual, GEGLU)
+    {23, 1, 2, true, 0.00f, true, 1, 2},  // 26: 32 pixels / wave, 2 channel slices
+    {23, 1, 2, true, 0.00f, true, 1, 5},  // 27: 32 pixels / wave, 5 channel slices
     // 28..31: 8-wave tiles + split-K for the deep-K, few-pixel levels (half the staging bytes per MAC of the 128x64 tile)
-    {256, 128, 2, false, 0.00f, 2, 20, 4, 32, true},  // 28: cfg 20 + split-K 4
-    {256, 128, 2, false, 0.00f, 2, 20, 8, 32, true},  // 29: cfg 20 + split-K 8
-    {128, 256, 2, false, 0.00f, 2, 19, 4, 32, true},  // 30: cfg 19 + split-K 4
-    {128, 256, 2, false, 0.00f, 2, 19, 8, 32, true},  // 31: cfg 19 + split-K 8
+    {20, 4, 2, false, 0.00f, true},       // 28: cfg 20 + split-K 4
+    {20, 8, 2, false, 0.00f, true},       // 29: cfg 20 + split-K 8
+    {19, 4, 2, false, 0.00f, true},       // 30: cfg 19 + split-K 4
+    {19, 8, 2, false, 0.00f, true},       // 31: cfg 19 + split-K 8
     // 32..38: igemm8_kernel, the phase-staggered 8-wave large-tile pipeline (BK = 64, one workgroup per CU, 2 K-tile buffers)
-    {320, 256, 1, false, 0.00f, 2, 32, 1, 64, true},  // 32: igemm8<5,2>  (Cout = 320 / 640 / 960 / 1280 layers without padding waste)
-    {256, 256, 1, true, 0.00f, 2, 33, 1, 64, true},   // 33: igemm8<4,2>
-    {320, 256, 1, false, 0.00f, 2, 32, 2, 64, true},  // 34: cfg 32 + split-K 2
-    {320, 256, 1, false, 0.00f, 2, 32, 4, 64, true},  // 35: cfg 32 + split-K 4
-    {256, 256, 1, false, 0.00f, 2, 33, 2, 64, true},  // 36: cfg 33 + split-K 2
-    {256, 256, 1, false, 0.00f, 2, 33, 4, 64, true},  // 37: cfg 33 + split-K 4
-    {256, 256, 1, false, 0.00f, 2, 33, 8, 64, true},  // 38: cfg 33 + split-K 8
+    {32, 1, 1, false, 0.00f, true},       // 32: igemm8<5,2>  (Cout = 320 / 640 / 960 / 1280 layers without padding waste)
+    {33, 1, 1, true, 0.00f, true},        // 33: igemm8<4,2>
+    {32, 2, 1, false, 0.00f, true},       // 34: cfg 32 + split-K 2
+    {32, 4, 1, false, 0.00f, true},       // 35: cfg 32 + split-K 4
+    {33, 2, 1, false, 0.00f, true},       // 36: cfg 33 + split-K 2
+    {33, 4, 1, false, 0.00f, true},       // 37: cfg 33 + split-K 4
+    {33, 8, 1, false, 0.00f, true},       // 38: cfg 33 + split-K 8
     // 39..53 (round 3): 4-wave tiles with ONE workgroup per CU (one wave per SIMD, up to 240 accumulator registers): grids that fill the
     // 256 CUs at batch 8 and rings that keep 64-128 KB in flight per CU; DMA issue interleaved with the MFMA groups
-    {320, 192, 1, false, 0.00f, 3, 39, 1, 64, true},  // 39: <2,2,5,3> BK64 NST2 interleaved: 256 tiles on the 49 152-pixel level
-    {320, 192, 1, false, 0.00f, 3, 40, 1, 32, true},  // 40: <2,2,5,3> BK32 NST4 interleaved (every stage issued 3 K steps ahead)
-    {256, 256, 1, true, 0.00f, 4, 41, 1, 64, true},   // 41: <2,2,4,4> BK64 NST2
-    {128, 128, 1, true, 0.00f, 2, 42, 1, 64, true},   // 42: <2,2,2,2> BK64 NST4 (128 KB ring)
-    {128, 256, 1, true, 0.00f, 4, 43, 1, 64, true},   // 43: <2,2,2,4> BK64 NST3 (144 KB ring)
-    {128, 64, 1, true, 0.00f, 1, 44, 1, 64, true},    // 44: <2,2,2,1> BK64 NST5 (120 KB ring)
-    {256, 192, 1, true, 0.00f, 3, 45, 1, 64, true},   // 45: <2,2,4,3> BK64 NST2
-    {320, 192, 1, false, 0.00f, 3, 39, 2, 64, true},  // 46: cfg 39 + split-K 2
-    {128, 128, 2, true, 0.00f, 2, 47, 1, 64, true},   // 47: cfg 7 with interleaved DMA issue
-    {128, 64, 2, true, 0.00f, 1, 48, 1, 64, true},    // 48: cfg 9 with interleaved DMA issue
-    {256, 256, 1, false, 0.00f, 4, 41, 4, 64, true},  // 49: cfg 41 + split-K 4
-    {256, 256, 1, false, 0.00f, 4, 41, 2, 64, true},  // 50: cfg 41 + split-K 2
-    {256, 192, 1, false, 0.00f, 3, 45, 3, 64, true},  // 51: cfg 45 + split-K 3
-    {128, 128, 2, false, 0.00f, 2, 47, 2, 64, true},  // 52: cfg 47 + split-K 2
-    {128, 64, 2, false, 0.00f, 1, 48, 4, 64, true},   // 53: cfg 48 + split-K 4
+    {39, 1, 1, false, 0.00f, true},       // 39: <2,2,5,3> BK64 NST2 interleaved: 256 tiles on the 49 152-pixel level
+    {40, 1, 1, false, 0.00f, true},       // 40: <2,2,5,3> BK32 NST4 interleaved (every stage issued 3 K steps ahead)
+    {41, 1, 1, true, 0.00f, true},        // 41: <2,2,4,4> BK64 NST2
+    {42, 1, 1, true, 0.00f, true},        // 42: <2,2,2,2> BK64 NST4 (128 KB ring)
+    {43, 1, 1, true, 0.00f, true},        // 43: <2,2,2,4> BK64 NST3 (144 KB ring)
+    {44, 1, 1, true, 0.00f, true},        // 44: <2,2,2,1> BK64 NST5 (120 KB ring)
+    {45, 1, 1, true, 0.00f, true},        // 45: <2,2,4,3> BK64 NST2
+    {39, 2, 1, false, 0.00f, true},       // 46: cfg 39 + split-K 2
+    {47, 1, 2, true, 0.00f, true},        // 47: cfg 7 with interleaved DMA issue
+    {48, 1, 2, true, 0.00f, true},        // 48: cfg 9 with interleaved DMA issue
+    {41, 4, 1, false, 0.00f, true},       // 49: cfg 41 + split-K 4
+    {41, 2, 1, false, 0.00f, true},       // 50: cfg 41 + split-K 2
+    {45, 3, 1, false, 0.00f, true},       // 51: cfg 45 + split-K 3
+    {47, 2, 2, false, 0.00f, true},       // 52: cfg 47 + split-K 2
+    {48, 4, 2, false, 0.00f, true},       // 53: cfg 48 + split-K 4
     // 54..61 (round 3): more shapes of the phase-staggered 8-wave pipeline, igemm8<TQ,TP> = (64 TQ) x (128 TP)
-    {128, 256, 1, true, 0.00f, 2, 54, 1, 64, true},   // 54: igemm8<2,2>
-    {256, 128, 1, true, 0.00f, 1, 55, 1, 64, true},   // 55: igemm8<4,1>
-    {128, 128, 2, true, 0.00f, 1, 56, 1, 64, true},   // 56: igemm8<2,1> (64 KB of LDS: two workgroups = 16 waves per CU)
-    {320, 128, 1, false, 0.00f, 1, 57, 1, 64, true},  // 57: igemm8<5,1>
-    {192, 256, 1, false, 0.00f, 2, 58, 1, 64, true},  // 58: igemm8<3,2>
-    {128, 256, 1, false, 0.00f, 2, 54, 2, 64, true},  // 59: cfg 54 + split-K 2
-    {256, 128, 1, false, 0.00f, 1, 55, 2, 64, true},  // 60: cfg 55 + split-K 2
-    {320, 128, 1, false, 0.00f, 1, 57, 2, 64, true},  // 61: cfg 57 + split-K 2
+    {54, 1, 1, true, 0.00f, true},        // 54: igemm8<2,2>
+    {55, 1, 1, true, 0.00f, true},        // 55: igemm8<4,1>
+    {56, 1, 2, true, 0.00f, true},        // 56: igemm8<2,1> (64 KB of LDS: two workgroups = 16 waves per CU)
+    {57, 1, 1, false, 0.00f, true},       // 57: igemm8<5,1>
+    {58, 1, 1, false, 0.00f, true},       // 58: igemm8<3,2>
+    {54, 2, 1, false, 0.00f, true},       // 59: cfg 54 + split-K 2
+    {55, 2, 1, false, 0.00f, true},       // 60: cfg 55 + split-K 2
+    {57, 2, 1, false, 0.00f, true},       // 61: cfg 57 + split-K 2
     // 62..73 (round 3): loader / consumer kernel (igemm_lc.hip): 2 x 2 consumer waves that only read LDS and issue MFMAs + 2 loader waves
     // that keep NST-1 whole K tiles of LDS-DMA in flight; one workgroup (6 waves) per CU
-    {128, 128, 1, true, 0.00f, 2, 62, 1, 64, true},   // 62: 128x128, 4-deep ring (128 KB)
-    {128, 128, 1, true, 0.00f, 2, 63, 1, 64, true},   // 63: 128x128, 5-deep ring (160 KB)
-    {256, 128, 1, true, 0.00f, 2, 64, 1, 64, true},   // 64: 256x128, 3-deep ring (144 KB)
-    {128, 256, 1, true, 0.00f, 4, 65, 1, 64, true},   // 65: 128x256, 3-deep ring (144 KB)
-    {128, 64, 1, true, 0.00f, 1, 66, 1, 64, true},    // 66: 128x64, 6-deep ring (144 KB)
-    {320, 128, 1, false, 0.00f, 2, 67, 1, 64, true},  // 67: 320x128, 2-deep ring (112 KB)
-    {192, 192, 1, false, 0.00f, 3, 68, 1, 64, true},  // 68: 192x192, 3-deep ring (144 KB)
-    {128, 128, 1, false, 0.00f, 2, 62, 2, 64, true},  // 69: cfg 62 + split-K 2
-    {256, 128, 1, false, 0.00f, 2, 64, 2, 64, true},  // 70: cfg 64 + split-K 2
-    {256, 128, 1, false, 0.00f, 2, 64, 4, 64, true},  // 71: cfg 64 + split-K 4
-    {128, 64, 1, false, 0.00f, 1, 66, 4, 64, true},   // 72: cfg 66 + split-K 4
-    {128, 128, 1, false, 0.00f, 2, 62, 4, 64, true},  // 73: cfg 62 + split-K 4
+    {62, 1, 1, true, 0.00f, true},        // 62: 128x128, 4-deep ring (128 KB)
+    {63, 1, 1, true, 0.00f, true},        // 63: 128x128, 5-deep ring (160 KB)
+    {64, 1, 1, true, 0.00f, true},        // 64: 256x128, 3-deep ring (144 KB)
+    {65, 1, 1, true, 0.00f, true},        // 65: 128x256, 3-deep ring (144 KB)
+    {66, 1, 1, true, 0.00f, true},        // 66: 128x64, 6-deep ring (144 KB)
+    {67, 1, 1, false, 0.00f, true},       // 67: 320x128, 2-deep ring (112 KB)
+    {68, 1, 1, false, 0.00f, true},       // 68: 192x192, 3-deep ring (144 KB)
+    {62, 2, 1, false, 0.00f, true},       // 69: cfg 62 + split-K 2
+    {64, 2, 1, false, 0.00f, true},       // 70: cfg 64 + split-K 2
+    {64, 4, 1, false, 0.00f, true},       // 71: cfg 64 + split-K 4
+    {66, 4, 1, false, 0.00f, true},       // 72: cfg 66 + split-K 4
+    {62, 4, 1, false, 0.00f, true},       // 73: cfg 62 + split-K 4
     // 74..83 (round 3): halo-resident 3x3 convolution (igemm_halo.hip): the pixel range of all nine taps staged ONCE per channel chunk,
     // only the weight tile streamed per tap; 8 waves, one workgroup per CU
-    {128, 256, 1, false, 0.00f, 2, 74, 1, 64, true},  // 74: 128x256, double halo buffer
-    {256, 256, 1, false, 0.00f, 2, 75, 1, 64, true},  // 75: 256x256, single halo buffer
-    {320, 256, 1, false, 0.00f, 2, 76, 1, 64, true},  // 76: 320x256, single halo buffer
-    {128, 128, 1, false, 0.00f, 1, 77, 1, 64, true},  // 77: 128x128
-    {256, 128, 1, false, 0.00f, 1, 78, 1, 64, true},  // 78: 256x128
-    {128, 256, 1, false, 0.00f, 2, 74, 2, 64, true},  // 79: cfg 74 + split-K 2
-    {128, 128, 1, false, 0.00f, 1, 77, 2, 64, true},  // 80: cfg 77 + split-K 2
-    {256, 128, 1, false, 0.00f, 1, 78, 2, 64, true},  // 81: cfg 78 + split-K 2
-    {256, 256, 1, false, 0.00f, 2, 75, 2, 64, true},  // 82: cfg 75 + split-K 2
-    {128, 128, 1, false, 0.00f, 1, 77, 4, 64, true},  // 83: cfg 77 + split-K 4
-    {128, 128, 2, false, 0.00f, 2, 84, 1, 64, true},  // 84: halo 128x128, 4 waves, two workgroups per CU
-    {128, 192, 2, false, 0.00f, 3, 85, 1, 64, true},  // 85: halo 128x192, 4 waves, two workgroups per CU
-    {128, 128, 2, false, 0.00f, 2, 84, 2, 64, true},  // 86: cfg 84 + split-K 2
-    {128, 128, 2, false, 0.00f, 2, 84, 4, 64, true},  // 87: cfg 84 + split-K 4
+    {74, 1, 1, false, 0.00f, true},       // 74: 128x256, double halo buffer
+    {75, 1, 1, false, 0.00f, true},       // 75: 256x256, single halo buffer
+    {76, 1, 1, false, 0.00f, true},       // 76: 320x256, single halo buffer
+    {77, 1, 1, false, 0.00f, true},       // 77: 128x128
+    {78, 1, 1, false, 0.00f, true},       // 78: 256x128
+    {74, 2, 1, false, 0.00f, true},       // 79: cfg 74 + split-K 2
+    {77, 2, 1, false, 0.00f, true},       // 80: cfg 77 + split-K 2
+    {78, 2, 1, false, 0.00f, true},       // 81: cfg 78 + split-K 2
+    {75, 2, 1, false, 0.00f, true},       // 82: cfg 75 + split-K 2
+    {77, 4, 1, false, 0.00f, true},       // 83: cfg 77 + split-K 4
+    {84, 1, 2, false, 0.00f, true},       // 84: halo 128x128, 4 waves, two workgroups per CU
+    {85, 1, 2, false, 0.00f, true},       // 85: halo 128x192, 4 waves, two workgroups per CU
+    {84, 2, 2, false, 0.00f, true},       // 86: cfg 84 + split-K 2
+    {84, 4, 2, false, 0.00f, true},       // 87: cfg 84 + split-K 4
     // 88..92 (round 4): halo kernel with the buffer sized for rows <= 24 pixels (a third weight slot at two workgroups per CU), and the
     // 12-wave 320x192 form: 256 workgroups on the 64x48 level at batch 8 (the 320x256 tiles leave a quarter of the chip idle there)
-    {128, 128, 2, false, 0.00f, 2, 88, 1, 64, true},  // 88: halo 128x128, 4 waves, W <= 24, 3 weight slots
-    {128, 192, 2, false, 0.00f, 3, 89, 1, 64, true},  // 89: halo 128x192, 4 waves, W <= 24, 3 weight slots
-    {128, 128, 2, false, 0.00f, 2, 88, 2, 64, true},  // 90: cfg 88 + split-K 2
-    {128, 128, 2, false, 0.00f, 2, 88, 4, 64, true},  // 91: cfg 88 + split-K 4
-    {320, 192, 1, false, 0.00f, 1, 92, 1, 64, true},  // 92: halo 320x192, 12 waves
+    {88, 1, 2, false, 0.00f, true},       // 88: halo 128x128, 4 waves, W <= 24, 3 weight slots
+    {89, 1, 2, false, 0.00f, true},       // 89: halo 128x192, 4 waves, W <= 24, 3 weight slots
+    {88, 2, 2, false, 0.00f, true},       // 90: cfg 88 + split-K 2
+    {88, 4, 2, false, 0.00f, true},       // 91: cfg 88 + split-K 4
+    {92, 1, 1, false, 0.00f, true},       // 92: halo 320x192, 12 waves
     // 93..95 (round 4): X-stationary kernel with a two-slot weight ring = THREE workgroups per CU (K = 320: the 64x48 level)
-    {1, 128, 3, true, 0.00f, 1, 93, 1, 0, true},     // 93: 32 pixels / wave, 1 channel slice
-    {2, 128, 3, true, 0.00f, 1, 93, 1, 0, true},     // 94: 32 pixels / wave, 2 channel slices
-    {5, 128, 3, true, 0.00f, 1, 93, 1, 0, true},     // 95: 32 pixels / wave, 5 channel slices
+    {93, 1, 3, true, 0.00f, true, 1, 1},  // 93: 32 pixels / wave, 1 channel slice
+    {93, 1, 3, true, 0.00f, true, 1, 2},  // 94: 32 pixels / wave, 2 channel slices
+    {93, 1, 3, true, 0.00f, true, 1, 5},  // 95: 32 pixels / wave, 5 channel slices
     // 96 (round 5): halo 320x192 on FOUR waves, one per SIMD (160 x 96 per wave): the twelve-wave tile's fill of the 64x48 level with the
     // LDS reads per MFMA of the one-wave-per-SIMD ring tiles
     // measured (profiles/r05_halo_one_wave.txt): 107 us on the 320 -> 320 convolution where the twelve-wave form takes 92 -- at one wave per SIMD
     // nothing covers the exposed halo-tile load of each channel chunk and the wave's own ds_read latency; kept selectable, not offered to the tuner
-    {320, 192, 1, false, 0.00f, 3, 96, 1, 64, false},  // 96: halo 320x192, 4 waves, one per SIMD
+    {96, 1, 1, false, 0.00f, false},      // 96: halo 320x192, 4 waves, one per SIMD
     // 97..99 (round 5): halo 128x256 on four waves of 64 x 128, two workgroups per CU, rows <= 24 pixels -- what the ablation of cfg 88 asks for
     // (profiles/r05_halo_ablate.txt: its fragment reads cost twice what its DMA costs): 0.75 KB of LDS reads per MFMA instead of 1, half the
     // weight DMA per MFMA; split-K keeps two workgroups per CU on the 32x24 / 16x12 levels
-    {128, 256, 2, false, 0.00f, 4, 97, 1, 64, true},  // 97: halo 128x256, 4 waves, W <= 24
-    {128, 256, 2, false, 0.00f, 4, 97, 2, 64, true},  // 98: cfg 97 + split-K 2
-    {128, 256, 2, false, 0.00f, 4, 97, 4, 64, true},  // 99: cfg 97 + split-K 4
+    {97, 1, 2, false, 0.00f, true},       // 97: halo 128x256, 4 waves, W <= 24
+    {97, 2, 2, false, 0.00f, true},       // 98: cfg 97 + split-K 2
+    {97, 4, 2, false, 0.00f, true},       // 99: cfg 97 + split-K 4
     // 100..103 (round 5): 2-D BLOCKED halo tiles (igemm_halo.hip G2D): stride-1 3x3 convolutions on images wider than 48 pixels -- the VAE /
     // EMASC levels above 64x48 and the 128x96 latent grid of 1024x768 -- stage (TH + 2) x 34 pixels per TH x 32 block instead of nine shifted copies
-    {128, 256, 1, false, 0.00f, 2, 100, 1, 64, true},  // 100: halo2d 128x256 (8 rows x 32), 8 waves
-    {256, 256, 1, false, 0.00f, 2, 101, 1, 64, true},  // 101: halo2d 256x256, 8 waves
-    {320, 256, 1, false, 0.00f, 2, 102, 1, 64, true},  // 102: halo2d 320x256, 8 waves
-    {128, 128, 2, false, 0.00f, 2, 103, 1, 64, true},  // 103: halo2d 128x128 (4 rows x 32), 4 waves, two workgroups per CU
+    {100, 1, 1, false, 0.00f, true},      // 100: halo2d 128x256 (8 rows x 32), 8 waves
+    {101, 1, 1, false, 0.00f, true},      // 101: halo2d 256x256, 8 waves
+    {102, 1, 1, false, 0.00f, true},      // 102: halo2d 320x256, 8 waves
+    {103, 1, 2, false, 0.00f, true},      // 103: halo2d 128x128 (4 rows x 32), 4 waves, two workgroups per CU
     // 104..108 (round 6): halo forms of the FOLDED-UPSAMPLE convolution (igemm_halo_kernel.h UPS: nearest 2x + 3x3 of Upsample2D): the low-resolution
     // rows a tile touches staged once per channel chunk, taps applied at read time -- the ring kernels gather every tap with per-lane addressing
     // (64x48 640 -> 640: 382 us, 32x24 1280 -> 1280: 379 us in round 5; here 307 / 304 us, profiles/r06_halo_ups.txt)
-    {128, 192, 2, false, 0.00f, 3, 104, 1, 64, true},  // 104: halo-ups 128x192, 4 waves, two workgroups per CU
-    {320, 192, 1, false, 0.00f, 1, 105, 1, 64, true},  // 105: halo-ups 320x192, 12 waves
-    {128, 128, 2, false, 0.00f, 2, 106, 1, 64, true},  // 106: halo-ups 128x128, 4 waves, two workgroups per CU
-    {128, 192, 2, false, 0.00f, 3, 104, 2, 64, true},  // 107: cfg 104 + split-K 2
-    {128, 128, 2, false, 0.00f, 2, 106, 2, 64, true},  // 108: cfg 106 + split-K 2
+    {104, 1, 2, false, 0.00f, true},      // 104: halo-ups 128x192, 4 waves, two workgroups per CU
+    {105, 1, 1, false, 0.00f, true},      // 105: halo-ups 320x192, 12 waves
+    {106, 1, 2, false, 0.00f, true},      // 106: halo-ups 128x128, 4 waves, two workgroups per CU
+    {104, 2, 2, false, 0.00f, true},      // 107: cfg 104 + split-K 2
+    {106, 2, 2, false, 0.00f, true},      // 108: cfg 106 + split-K 2
     // 109 (round 6): the 8x6 level's convolutions are chains of 45 dependent K steps per slice at split 4 (latency, not bandwidth: profiles/r06_halo_map3.txt);
     // split 8 on the two-workgroups-per-CU form halves the chain (480 workgroups = one round) at the price of twice the slab traffic -- offered, the tuner decides
-    {128, 128, 2, false, 0.00f, 2, 88, 8, 64, true},   // 109: cfg 88 + split-K 8
+    {88, 8, 2, false, 0.00f, true},       // 109: cfg 88 + split-K 8
 };
-inline bool is_xs(int base) { return base == 23 || base == 93; }
-inline int xs_nst(int base) { return base == 93 ? 2 : 3; }
-inline bool is_lc(int base) { return base >= 62 && base <= 68; }
+constexpr bool every_cfg_has_a_form() {
+    for (int c = 1; c <= NCFG; ++c)
+        if (kCfg[c].base < 0 || kCfg[c].base >= NBASE || !kBase.t[kCfg[c].base].family) return false;
+    return true;
+}
+static_assert(every_cfg_has_a_form(), "a kCfg row names a base id that has no row in igemm_tiles.h");
+// geometry of configuration c: its form's trait record, with the X-stationary kernel's fields filled in from the configuration (bq = channel
+// slices over gridDim.y, tp = 32-pixel blocks per wave, a workgroup of four waves covers 128 tp pixels)
+inline BaseTrait cfg_trait(int c) {
+    BaseTrait t = kBase.t[kCfg[c].base];
+    if (t.family == FAM_XS) { t.bq = kCfg[c].xs_qs; t.tp = kCfg[c].xs_pb; t.bp = 128 * t.tp; }
+    return t;
+}
+inline bool is_xs(int c) { return kBase.t[kCfg[c].base].family == FAM_XS; }
 // kernels whose every wave reaches the shared epilogue can combine their K slices in the launch (igemm_common.h igemm_splitk_combine); the
 // loader / consumer kernel (its loader waves hold no accumulators) and the X-stationary kernel keep the two-pass form
-inline bool sk_inline_ok(int base) { return base != 23 && base != 93 && !is_lc(base); }
+inline bool sk_inline_ok(int c) { const int f = kBase.t[kCfg[c].base].family; return f != FAM_XS && f != FAM_LC; }
 // arrival counters for launches that bring none (op-level entry points and the module handles that set no Ctx::sk_cnt): one buffer per
 // (device, stream), zeroed once, every launch leaves it zeroed -- two handles working on different streams or devices at the same time
 // never share a tile's ticket.  Never freed (a captured graph may hold the pointer).
@@ -285,97 +325,37 @@ bool sk_two_pass_forced() {
     if (g_sk_two_pass < 0) g_sk_two_pass = getenv("LADI_SPLITK_TWO_PASS") != nullptr ? 1 : 0;
     return g_sk_two_pass == 1;
 }
-inline bool is_halo(int base) { return (base >= 74 && base <= 78) || base == 84 || base == 85 || base == 88 || base == 89 || base == 92 || base == 96 || base == 97; }
-inline bool is_halo2d(int base) { return base >= 100 && base <= 103; }
-inline int halo2d_th(int base) { return base == 103 ? 4 : 8; }
-inline bool is_halo_ups(int base) { return base >= 104 && base <= 106; }
-
 // rocprofv3's name of the kernel a configuration launches (bench.py groups its per-launch timings by symbol)
 std::string cfg_symbol(int c) {
-    const int b = kCfg[c].base;
-    if (b == 23 || b == 93) return "linear_xs_kernel";
-    switch (b) {
-        case 32: return "igemm8_kernel<5, 2, 0>";
-        case 33: return "igemm8_kernel<4, 2, 0>";
-        case 54: return "igemm8_kernel<2, 2, 0>";
-        case 55: return "igemm8_kernel<4, 1, 0>";
-        case 56: return "igemm8_kernel<2, 1, 0>";
-        case 57: return "igemm8_kernel<5, 1, 0>";
-        case 58: return "igemm8_kernel<3, 2, 0>";
-        case 74: return "igemm_halo_kernel<2, 2, 2, 3, 4, 48, 0, 0, 0>";
-        case 75: return "igemm_halo_kernel<4, 2, 1, 3, 4, 48, 0, 0, 0>";
-        case 76: return "igemm_halo_kernel<5, 2, 1, 2, 4, 48, 0, 0, 0>";
-        case 77: return "igemm_halo_kernel<2, 1, 2, 4, 4, 48, 0, 0, 0>";
-        case 78: return "igemm_halo_kernel<4, 1, 1, 3, 4, 48, 0, 0, 0>";
-        case 84: return "igemm_halo_kernel<2, 2, 1, 2, 2, 48, 0, 0, 0>";
-        case 85: return "igemm_halo_kernel<2, 3, 1, 2, 2, 48, 0, 0, 0>";
-        case 88: return "igemm_halo_kernel<2, 2, 1, 3, 2, 24, 0, 0, 0>";
-        case 104: return "igemm_halo_kernel<2, 3, 1, 2, 2, 48, 0, 0, 1>";
-        case 105: return "igemm_halo_kernel<5, 1, 1, 2, 6, 48, 0, 0, 1>";
-        case 106: return "igemm_halo_kernel<2, 2, 1, 2, 2, 48, 0, 0, 1>";
-        case 89: return "igemm_halo_kernel<2, 3, 1, 3, 2, 24, 0, 0, 0>";
-        case 92: return "igemm_halo_kernel<5, 1, 1, 2, 6, 48, 0, 0, 0>";
-        case 96: return "igemm_halo_kernel<5, 3, 1, 2, 2, 48, 1, 0, 0>";
-        case 97: return "igemm_halo_kernel<2, 4, 1, 2, 2, 24, 0, 0, 0>";
-        case 100: return "igemm_halo_kernel<2, 2, 1, 3, 4, 48, 0, 1, 0>";
-        case 101: return "igemm_halo_kernel<4, 2, 1, 3, 4, 48, 0, 1, 0>";
-        case 102: return "igemm_halo_kernel<5, 2, 1, 2, 4, 48, 0, 1, 0>";
-        case 103: return "igemm_halo_kernel<2, 2, 1, 2, 2, 48, 0, 1, 0>";
-        case 62: return "igemm_lc_kernel<2, 2, 2, 2, 2, 4>";
-        case 63: return "igemm_lc_kernel<2, 2, 2, 2, 2, 5>";
-        case 64: return "igemm_lc_kernel<2, 2, 4, 2, 2, 3>";
-        case 65: return "igemm_lc_kernel<2, 2, 2, 4, 2, 3>";
-        case 66: return "igemm_lc_kernel<2, 2, 2, 1, 2, 6>";
-        case 67: return "igemm_lc_kernel<2, 2, 5, 2, 2, 2>";
-        case 68: return "igemm_lc_kernel<2, 2, 3, 3, 2, 3>";
+    switch (kCfg[c].base) {
 #define X(base, WQ, WP, TQ, TP, BK, NST, OCC, ILV) \
         case base: return "igemm_kernel<" #WQ ", " #WP ", " #TQ ", " #TP ", " #BK ", " #NST ", " #OCC ", " #ILV ">";
         LADI_IGEMM_TILES_ALL(X)
+#undef X
+#define X(base, TQ, TP) case base: return "igemm8_kernel<" #TQ ", " #TP ", 0>";
+        LADI_IGEMM8_TILES(X)
+#undef X
+#define X(base, WQ, WP, TQ, TP, NL, NST) case base: return "igemm_lc_kernel<" #WQ ", " #WP ", " #TQ ", " #TP ", " #NL ", " #NST ">";
+        LADI_IGEMM_LC_TILES(X)
+#undef X
+#define X(base, TQ, TP, NXB, NSTW, WPN, WMAX, ONE, G2D, UPS) \
+        case base: return "igemm_halo_kernel<" #TQ ", " #TP ", " #NXB ", " #NSTW ", " #WPN ", " #WMAX ", " #ONE ", " #G2D ", " #UPS ">";
+        LADI_HALO_TILES_ALL(X)
+#undef X
+#define X(base, NST) case base: return "linear_xs_kernel";   // the template arguments depend on the launch (ladi_linear_xs_symbol)
+        LADI_LINEAR_XS_FORMS(X)
 #undef X
         default: return "?";
     }
 }
 
 int launch_base(int cfg, const IGemmArgs& a, int batch, hipStream_t st) {
+    const BaseTrait t = cfg_trait(cfg);
+    if (t.family == FAM_XS) return ladi_launch_linear_xs(a, t.tp, t.bq, st, t.xs_nst);
     switch (kCfg[cfg].base) {
-#define X(base, WQ, WP, TQ, TP, BK, NST, OCC, ILV) case base: return ladi_igemm_launch_base_##base(a, batch, st);
-        LADI_IGEMM_TILES_ALL(X)
-#undef X
-        case 23: return ladi_launch_linear_xs(a, kCfg[cfg].tp, kCfg[cfg].bq, st, 3);
-        case 93: return ladi_launch_linear_xs(a, kCfg[cfg].tp, kCfg[cfg].bq, st, 2);
-        case 32: return ladi_launch_igemm8(a, 5, 2, batch, st);
-        case 33: return ladi_launch_igemm8(a, 4, 2, batch, st);
-        case 54: return ladi_launch_igemm8(a, 2, 2, batch, st);
-        case 55: return ladi_launch_igemm8(a, 4, 1, batch, st);
-        case 56: return ladi_launch_igemm8(a, 2, 1, batch, st);
-        case 57: return ladi_launch_igemm8(a, 5, 1, batch, st);
-        case 58: return ladi_launch_igemm8(a, 3, 2, batch, st);
-        case 74: return ladi_launch_igemm_halo(a, 2, 2, 2, batch, st);
-        case 75: return ladi_launch_igemm_halo(a, 4, 2, 1, batch, st);
-        case 76: return ladi_launch_igemm_halo(a, 5, 2, 1, batch, st);
-        case 77: return ladi_launch_igemm_halo(a, 2, 1, 2, batch, st);
-        case 78: return ladi_launch_igemm_halo(a, 4, 1, 1, batch, st);
-        case 84: return ladi_launch_igemm_halo(a, 2, 2, 10, batch, st);
-        case 85: return ladi_launch_igemm_halo(a, 2, 3, 10, batch, st);
-        case 88: return ladi_launch_igemm_halo(a, 2, 2, 11, batch, st);
-        case 89: return ladi_launch_igemm_halo(a, 2, 3, 11, batch, st);
-        case 92: return ladi_launch_igemm_halo(a, 5, 1, 12, batch, st);
-        case 96: return ladi_launch_igemm_halo(a, 5, 3, 13, batch, st);
-        case 97: return ladi_launch_igemm_halo(a, 2, 4, 11, batch, st);
-        case 100: return ladi_launch_igemm_halo(a, 2, 2, 20, batch, st);
-        case 101: return ladi_launch_igemm_halo(a, 4, 2, 20, batch, st);
-        case 102: return ladi_launch_igemm_halo(a, 5, 2, 20, batch, st);
-        case 103: return ladi_launch_igemm_halo(a, 2, 2, 21, batch, st);
-        case 104: return ladi_launch_igemm_halo(a, 2, 3, 30, batch, st);
-        case 105: return ladi_launch_igemm_halo(a, 5, 1, 31, batch, st);
-        case 106: return ladi_launch_igemm_halo(a, 2, 2, 30, batch, st);
-        case 62: return ladi_launch_igemm_lc(a, 2, 2, 4, batch, st);
-        case 63: return ladi_launch_igemm_lc(a, 2, 2, 5, batch, st);
-        case 64: return ladi_launch_igemm_lc(a, 4, 2, 3, batch, st);
-        case 65: return ladi_launch_igemm_lc(a, 2, 4, 3, batch, st);
-        case 66: return ladi_launch_igemm_lc(a, 2, 1, 6, batch, st);
-        case 67: return ladi_launch_igemm_lc(a, 5, 2, 2, batch, st);
-        case 68: return ladi_launch_igemm_lc(a, 3, 3, 3, batch, st);
+#define LADI_PER_BASE(base) case base: return ladi_igemm_launch_base_##base(a, batch, st);
+        LADI_IGEMM_LAUNCHER_BASES
+#undef LADI_PER_BASE
         default: return -7;
     }
 }
@@ -458,7 +438,8 @@ const char* ladi_igemm_cfg_symbol(int cfg) {
 
 // the split-K admission rule (shared by the tuner and the workspace planner): few output tiles, deep K
 static bool splitk_admissible(const IGemmArgs& a, int c) {
-    const long long tiles = (long long)((a.Q + kCfg[c].bq - 1) / kCfg[c].bq) * ((a.P + kCfg[c].bp - 1) / kCfg[c].bp);
+    const BaseTrait t = cfg_trait(c);
+    const long long tiles = (long long)((a.Q + t.bq - 1) / t.bq) * ((a.P + t.bp - 1) / t.bp);
     return !(tiles * kCfg[c].split > 1024 || tiles > 256 || (a.K / 64) / kCfg[c].split < 8);
 }
 
@@ -468,22 +449,26 @@ static bool splitk_admissible(const IGemmArgs& a, int c) {
 // per-pixel bias or an fp32 output, nor one whose planned slab was sized without it).
 static bool cfg_admissible(const IGemmArgs& a, int batch, int c, bool strict) {
     const CfgInfo& ci = kCfg[c];
+    const BaseTrait t = cfg_trait(c);
     const bool geglu = a.act == LADI_ACT_GEGLU;
-    if (is_xs(ci.base)) {
-        IGemmArgs t = a; t.stats = nullptr;
-        return ladi_linear_xs_eligible(t, batch, ci.tp, ci.bq, xs_nst(ci.base));
+    if (t.family == FAM_XS) {
+        IGemmArgs x = a; x.stats = nullptr;
+        return ladi_linear_xs_eligible(x, batch, t.tp, t.bq, t.xs_nst);
     }
     if (a.gn_ss) return false;                                        // GroupNorm affine of the operand: X-stationary kernel only
     if (a.ln_gamma && !a.ln_scratch) return false;                    // no scratch: only the fused (X-stationary) form
-    if (is_lc(ci.base) && (a.ups || batch != 1)) return false;        // loader / consumer kernel: no folded upsample, no batched launches
-    if (is_halo_ups(ci.base) && !ladi_igemm_halo_ups_eligible(a, batch, ci.bp)) return false;   // folded-upsample halo: single source, whole tiles inside a sample
-    if (is_halo2d(ci.base) && !ladi_igemm_halo2d_eligible(a, batch, halo2d_th(ci.base))) return false;   // 2-D blocked halo: W % 32 == 0, whole blocks
-    if (is_halo(ci.base) && (!ladi_igemm_halo_eligible(a, batch) || ((ci.base == 88 || ci.base == 89 || ci.base == 97) && a.Ws > 24))) return false;   // halo-resident kernel: 3x3 stride-1 convolutions on narrow images
+    if (t.family == FAM_LC && (a.ups || batch != 1)) return false;    // loader / consumer kernel: no folded upsample, no batched launches
+    if (t.family == FAM_HALO) {
+        // folded-upsample form: single source, whole tiles inside a sample; 2-D blocked form: W % 32 == 0, whole blocks; else the ring-halo form:
+        // 3x3 stride-1 convolutions on images no wider than the form's halo buffer was sized for
+        if (t.ups ? !ladi_igemm_halo_ups_eligible(a, batch, t.bp)
+                  : t.g2d ? !ladi_igemm_halo2d_eligible(a, batch, t.th) : (!ladi_igemm_halo_eligible(a, batch) || a.Ws > t.wmax)) return false;
+    }
     if (geglu && !ci.geglu_ok) return false;
-    if (ci.bk == 64 && ((a.C0 % 64) || (a.C1 % 64))) return false;
+    if (t.bk == 64 && ((a.C0 % 64) || (a.C1 % 64))) return false;
     if (ci.split > 1 && (batch != 1 || geglu || a.out_f32 || a.bias_per_pixel)) return false;
     if (strict) {
-        if (ci.bq > 2 * a.Q && ci.bq > 64) return false;              // grossly oversized in Q
+        if (t.bq > 2 * a.Q && t.bq > 64) return false;                // grossly oversized in Q
         if (ci.split > 1 && !splitk_admissible(a, c)) return false;   // split-K: few tiles, deep K only
     }
     return true;
@@ -491,15 +476,15 @@ static bool cfg_admissible(const IGemmArgs& a, int batch, int c, bool strict) {
 
 // slab bytes configuration c needs: the two-pass form writes [split][P][Q] floats, the in-launch form whole (padded) tile images
 static size_t splitk_cfg_bytes(const IGemmArgs& a, int c) {
-    const CfgInfo& ci = kCfg[c];
-    const size_t tiles = (size_t)((a.Q + ci.bq - 1) / ci.bq) * (size_t)((a.P + ci.bp - 1) / ci.bp);
-    return (size_t)ci.split * std::max((size_t)a.P * (size_t)a.Q, tiles * (size_t)ci.bq * (size_t)ci.bp) * sizeof(float);
+    const BaseTrait t = cfg_trait(c);
+    const size_t tiles = (size_t)((a.Q + t.bq - 1) / t.bq) * (size_t)((a.P + t.bp - 1) / t.bp);
+    return (size_t)kCfg[c].split * std::max((size_t)a.P * (size_t)a.Q, tiles * (size_t)t.bq * (size_t)t.bp) * sizeof(float);
 }
 size_t ladi_igemm_splitk_ws_bytes(const IGemmArgs& a, int batch) {
     if (batch != 1 || a.act == LADI_ACT_GEGLU || a.out_f32 || a.bias_per_pixel || a.P <= 0 || a.Q <= 0) return 0;
     size_t need = 0;
     for (int c = 1; c <= NCFG; ++c)
-        if (kCfg[c].split > 1 && !is_xs(kCfg[c].base) && splitk_admissible(a, c)) need = std::max(need, splitk_cfg_bytes(a, c));
+        if (kCfg[c].split > 1 && !is_xs(c) && splitk_admissible(a, c)) need = std::max(need, splitk_cfg_bytes(a, c));
     return need;
 }
 
@@ -542,10 +527,10 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
                 if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
                     float best_ms = 1e30f; int best_cfg = 0;
                     std::vector<std::pair<float, int>> cand;     // (ms per launch incl. penalty, cfg)
-                                        for (int c = 1; c <= NCFG; ++c) {
+                    for (int c = 1; c <= NCFG; ++c) {
                         if (!kCfg[c].tune || !cfg_admissible(a, batch, c, true)) continue;
                         // X-stationary kernel: no fused statistics there, charge the separate statistics pass the consumer then needs (~3 TB/s read)
-                        const float penalty_ms = (is_xs(kCfg[c].base) && a.stats) ? 3.f * (float)((double)a.P * a.Q * 2.0 / 3.0e9) : 0.f;
+                        const float penalty_ms = (is_xs(c) && a.stats) ? 3.f * (float)((double)a.P * a.Q * 2.0 / 3.0e9) : 0.f;
                         if (ladi_launch_igemm(a, batch, c, st, nullptr, ws, ws_bytes, sk_cnt) != 0) continue;   // warm-up (also sets function attributes)
                         (void)hipEventRecord(e0, st);
                         for (int r = 0; r < 3; ++r) (void)ladi_launch_igemm(a, batch, c, st, nullptr, ws, ws_bytes, sk_cnt);
@@ -566,7 +551,7 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
                         for (size_t i = 0; i < cand.size() && i < 3 && cand[i].first <= lim; ++i) {
                             const int c = cand[i].second;
                             float pen = 0.f;
-                            if (is_xs(kCfg[c].base) && a.stats) pen = (float)((double)a.P * a.Q * 2.0 / 3.0e9);
+                            if (is_xs(c) && a.stats) pen = (float)((double)a.P * a.Q * 2.0 / 3.0e9);
                             (void)hipEventRecord(e0, st);
                             for (int r = 0; r < 10; ++r) (void)ladi_launch_igemm(a, batch, c, st, nullptr, ws, ws_bytes, sk_cnt);
                             (void)hipEventRecord(e1, st);
@@ -589,14 +574,15 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
         double best = 1e300;
         for (int c = 1; c <= NCFG; ++c) {
             const CfgInfo& ci = kCfg[c];
-            if (is_xs(ci.base) || ci.split > 1 || !(ci.eff > 0.f) || !cfg_admissible(a, batch, c, false)) continue;
-            const long long tiles = (long long)((a.Q + ci.bq - 1) / ci.bq) * ((a.P + ci.bp - 1) / ci.bp) * batch;
+            const BaseTrait t = cfg_trait(c);
+            if (is_xs(c) || ci.split > 1 || !(ci.eff > 0.f) || !cfg_admissible(a, batch, c, false)) continue;
+            const long long tiles = (long long)((a.Q + t.bq - 1) / t.bq) * ((a.P + t.bp - 1) / t.bp) * batch;
             const long long slots = 256LL * ci.blocks_per_cu;
             const double waves = (double)((tiles + slots - 1) / slots);
             // partial last wave: count it in proportion but never below 35% (a lone straggler still takes a full tile time)
             const double frac = (double)(tiles % slots) / (double)slots;
             const double eff_waves = (tiles % slots) ? (waves - 1.0) + (frac < 0.35 ? 0.35 : frac) : waves;
-            const double cost = eff_waves * (double)ci.bq * ci.bp * ci.blocks_per_cu / ci.eff;
+            const double cost = eff_waves * (double)t.bq * t.bp * ci.blocks_per_cu / ci.eff;
             if (cost < best) { best = cost; cfg = c; }
         }
     }
@@ -604,19 +590,20 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
         for (int c : {25, 26, 27, 23, 24, 93, 94, 95}) if (cfg_admissible(a, batch, c, true)) { cfg = c; break; }
     }
     if (cfg < 1 || cfg > NCFG) return -7;
-    if (a.gn_ss && !is_xs(kCfg[cfg].base)) return -17;
-    if (a.ln_gamma && !is_xs(kCfg[cfg].base)) {   // LayerNorm as its own kernel into the caller's scratch (timed by the tuner as part of cfg)
+    const BaseTrait t = cfg_trait(cfg);
+    if (a.gn_ss && t.family != FAM_XS) return -17;
+    if (a.ln_gamma && t.family != FAM_XS) {   // LayerNorm as its own kernel into the caller's scratch (timed by the tuner as part of cfg)
         if (!a.ln_scratch || a.C1 || a.src1 || a.ksize != 1 || batch != 1) return -15;
         const int lrc = ladi_launch_layernorm(a.src0, a.ld0, a.ln_gamma, a.ln_beta, a.ln_eps, a.P, a.C0, a.ln_scratch, a.C0, st);
         if (lrc != 0) return -15;
         a.src0 = a.ln_scratch; a.ld0 = a.C0; a.ln_gamma = nullptr; a.ln_beta = nullptr;
     }
-    if (is_xs(kCfg[cfg].base)) {   // X-stationary linear kernel: no fused statistics (the consumer falls back to ladi_launch_gn_partial)
+    if (t.family == FAM_XS) {   // X-stationary linear kernel: no fused statistics (the consumer falls back to ladi_launch_gn_partial)
         a.stats = nullptr;
-        if (!ladi_linear_xs_eligible(a, batch, kCfg[cfg].tp, kCfg[cfg].bq, xs_nst(kCfg[cfg].base))) return -14;
+        if (!ladi_linear_xs_eligible(a, batch, t.tp, t.bq, t.xs_nst)) return -14;
     }
     if (geglu && !kCfg[cfg].geglu_ok) return -8;
-    if (kCfg[cfg].bk == 64 && ((a.C0 % 64) || (a.C1 % 64))) return -2;  // BK = 64 variants
+    if (t.bk == 64 && ((a.C0 % 64) || (a.C1 % 64))) return -2;  // BK = 64 variants
     const int split = kCfg[cfg].split;
     bool sk_inline = false;
     if (split > 1) {
@@ -626,15 +613,15 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
             if (!ensure_ws(need, st)) return -13;
             ws = g_ws;
         }
-        const long long tiles = (long long)((a.Q + kCfg[cfg].bq - 1) / kCfg[cfg].bq) * ((a.P + kCfg[cfg].bp - 1) / kCfg[cfg].bp);
-        sk_inline = sk_inline_ok(kCfg[cfg].base) && !sk_two_pass_forced() && tiles <= SK_MAX_TILES;
+        const long long tiles = (long long)((a.Q + t.bq - 1) / t.bq) * ((a.P + t.bp - 1) / t.bp);
+        sk_inline = sk_inline_ok(cfg) && !sk_two_pass_forced() && tiles <= SK_MAX_TILES;
         if (sk_inline && !sk_cnt) {
             sk_cnt = ensure_sk_cnt(st);
             if (!sk_cnt) sk_inline = false;     // first use inside a capture without caller counters: two-pass form
         }
     }
     if (a.stats) {  // fused output statistics need whole 32*TP-pixel row blocks inside one sample
-        const int px = ((split > 1 && !sk_inline) ? 1 : kCfg[cfg].tp) * 32;
+        const int px = ((split > 1 && !sk_inline) ? 1 : t.tp) * 32;
         if (geglu || batch != 1 || a.out_f32 || ((a.Ho * a.Wo) % px)) a.stats = nullptr;
         else if (stats_row_px) *stats_row_px = px;
     }
@@ -643,7 +630,7 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
     if (prof) {
         if (hipEventCreate(&rec.e0) != hipSuccess || hipEventCreate(&rec.e1) != hipSuccess) return -12;
         rec.cfg = cfg; rec.P = a.P; rec.Q = a.Q; rec.K = a.K; rec.ks = a.ksize;
-        if (is_xs(kCfg[cfg].base)) ladi_linear_xs_symbol(a, kCfg[cfg].tp, xs_nst(kCfg[cfg].base), rec.sym, (int)sizeof(rec.sym));
+        if (t.family == FAM_XS) ladi_linear_xs_symbol(a, t.tp, t.xs_nst, rec.sym, (int)sizeof(rec.sym));
         else snprintf(rec.sym, sizeof(rec.sym), "%s", cfg_symbol(cfg).c_str());
         rec.flops = 2.0 * (double)a.P * (double)a.Q * (double)a.K * (double)batch;
         (void)hipEventRecord(rec.e0, st);
@@ -660,7 +647,7 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
     } else a.splitk = 1;
     const int batch_l = lbatch;
     int rc;
-    ladi_igemm_note_launch(is_xs(kCfg[cfg].base) ? 5 : 0, 0, 1, 0);   // the tiled launchers overwrite it where they compute their grid
+    ladi_igemm_note_launch(t.family == FAM_XS ? FAM_XS : 0, 0, 1, 0);   // the tiled launchers overwrite it where they compute their grid
     rc = launch_base(cfg, a, batch_l, st);
     if (rc == 0 && split > 1 && !sk_inline) {
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((full.P + 31) / 32), (unsigned)((full.Q + 63) / 64)), dim3(256), 0, st, ws, split, full);

@@ -2,6 +2,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "igemm_common.h"
+#include "igemm_tiles.h"
 #include <cstdlib>
 
 namespace {
@@ -285,12 +286,12 @@ int launch_cfg8(IGemmArgs a, int batch, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? 0 : -11;
 }
 
-}  // namespace
-
-int ladi_launch_igemm8(const IGemmArgs& a, int tq, int tp, int batch, hipStream_t st) {
-#ifdef LADI_ABLATION      // timing-only instantiations (WRONG results): compiled into tools/ builds only, never into the shipped library
-    static const int abl = getenv("LADI_IGEMM8_ABL") ? atoi(getenv("LADI_IGEMM8_ABL")) : 0;
-    if (abl && tq == 5 && tp == 2) {
+// -DLADI_ABLATION: timing-only instantiations of igemm8<5, 2> (WRONG results), compiled into tools/ builds only, never into the shipped library
+template <int TQ, int TP>
+int launch_igemm8(const IGemmArgs& a, int batch, hipStream_t st) {
+#ifdef LADI_ABLATION
+    if constexpr (TQ == 5 && TP == 2) {
+        static const int abl = getenv("LADI_IGEMM8_ABL") ? atoi(getenv("LADI_IGEMM8_ABL")) : 0;
         switch (abl) {
             case 1: return launch_cfg8<5, 2, 1>(a, batch, st);       // no LDS-DMA in the loop
             case 4: return launch_cfg8<5, 2, 4>(a, batch, st);       // no MFMA
@@ -300,12 +301,12 @@ int ladi_launch_igemm8(const IGemmArgs& a, int tq, int tp, int batch, hipStream_
         }
     }
 #endif
-    if (tq == 5 && tp == 2) return launch_cfg8<5, 2>(a, batch, st);
-    if (tq == 4 && tp == 2) return launch_cfg8<4, 2>(a, batch, st);
-    if (tq == 2 && tp == 2) return launch_cfg8<2, 2>(a, batch, st);
-    if (tq == 4 && tp == 1) return launch_cfg8<4, 1>(a, batch, st);
-    if (tq == 2 && tp == 1) return launch_cfg8<2, 1>(a, batch, st);
-    if (tq == 5 && tp == 1) return launch_cfg8<5, 1>(a, batch, st);
-    if (tq == 3 && tp == 2) return launch_cfg8<3, 2>(a, batch, st);
-    return -7;
+    return launch_cfg8<TQ, TP>(a, batch, st);
 }
+
+}  // namespace
+
+// one launcher per row of igemm_tiles.h: the external entry point igemm.hip dispatches to
+#define X(base, TQ, TP) int ladi_igemm_launch_base_##base(IGemmArgs a, int batch, hipStream_t st) { return launch_igemm8<TQ, TP>(a, batch, st); }
+LADI_IGEMM8_TILES(X)
+#undef X

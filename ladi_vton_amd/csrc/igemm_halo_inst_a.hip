@@ -1,4 +1,4 @@
-// Instantiation unit of the halo-resident 3x3 convolution kernel (igemm_halo_kernel.h): two of its sixteen forms.
+// Instantiation unit of the halo-resident 3x3 convolution kernel (igemm_halo_kernel.h): form group A of igemm_tiles.h.
 #include "igemm_halo_kernel.h"
-LADI_HALO_INSTANTIATE(f128x256_d, 2, 2, 2, 3, 4)
-LADI_HALO_INSTANTIATE(f256x128, 4, 1, 1, 3, 4)
+#include "igemm_tiles.h"
+LADI_HALO_TILES_A(LADI_HALO_INSTANTIATE)

@@ -1,4 +1,4 @@
-// Instantiation unit of the halo-resident 3x3 convolution kernel (igemm_halo_kernel.h): two of its sixteen forms.
+// Instantiation unit of the halo-resident 3x3 convolution kernel (igemm_halo_kernel.h): form group B of igemm_tiles.h.
 #include "igemm_halo_kernel.h"
-LADI_HALO_INSTANTIATE(f256x256, 4, 2, 1, 3, 4)
-LADI_HALO_INSTANTIATE(f128x128_w2, 2, 2, 1, 2, 2)
+#include "igemm_tiles.h"
+LADI_HALO_TILES_B(LADI_HALO_INSTANTIATE)

@@ -1,4 +1,4 @@
-// Instantiation unit of the halo-resident 3x3 convolution kernel (igemm_halo_kernel.h): two of its sixteen forms.
+// Instantiation unit of the halo-resident 3x3 convolution kernel (igemm_halo_kernel.h): form group D of igemm_tiles.h.
 #include "igemm_halo_kernel.h"
-LADI_HALO_INSTANTIATE(f128x128_d, 2, 1, 2, 4, 4)
-LADI_HALO_INSTANTIATE(f128x192_w2, 2, 3, 1, 2, 2)
+#include "igemm_tiles.h"
+LADI_HALO_TILES_D(LADI_HALO_INSTANTIATE)

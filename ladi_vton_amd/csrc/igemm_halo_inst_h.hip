@@ -1,4 +1,4 @@
-// Instantiation unit of the halo-resident 3x3 convolution kernel (igemm_halo_kernel.h): two of its sixteen forms.
+// Instantiation unit of the halo-resident 3x3 convolution kernel (igemm_halo_kernel.h): form group H of igemm_tiles.h.
 #include "igemm_halo_kernel.h"
-LADI_HALO_INSTANTIATE(g256x256, 4, 2, 1, 3, 4, 48, 0, 1)
-LADI_HALO_INSTANTIATE(g320x256, 5, 2, 1, 2, 4, 48, 0, 1)
+#include "igemm_tiles.h"
+LADI_HALO_TILES_H(LADI_HALO_INSTANTIATE)

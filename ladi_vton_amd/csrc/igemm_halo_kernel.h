@@ -1,5 +1,5 @@
 // Halo-resident 3x3 convolution (round 3), reached through ladi_launch_igemm (cfg 74..): kernel template and launcher template.  Included by the
-// instantiation units igemm_halo_inst_*.hip (two forms each, so the build parallelises: one form takes ~30 s of hipcc) and by the harnesses under tools/.
+// instantiation units igemm_halo_inst_*.hip (at most two forms of igemm_tiles.h each, so the build parallelises: one form takes ~30 s of hipcc) and by the harnesses under tools/.
 //
 // Why.  What bounds every implicit-GEMM tile below 256x256 on this chip is the global -> LDS staging rate (25-32 B/clk/CU in these
 // kernels; tools/dma_conv_pattern.hip), and the ring kernels stage the PIXEL operand once per filter tap: nine
@@ -422,6 +422,6 @@ int launch_halo(IGemmArgs a, int batch, hipStream_t st) {
 
 }  // namespace
 
-// one line per form in an instantiation unit: the external entry point igemm_halo.hip dispatches to
-#define LADI_HALO_INSTANTIATE(NAME, ...) \
-    int ladi_halo_launch_##NAME(IGemmArgs a, int batch, hipStream_t st) { return launch_halo<__VA_ARGS__>(a, batch, st); }
+// one row of igemm_tiles.h per form in an instantiation unit: the external entry point igemm.hip dispatches to
+#define LADI_HALO_INSTANTIATE(BASE, ...) \
+    int ladi_igemm_launch_base_##BASE(IGemmArgs a, int batch, hipStream_t st) { return launch_halo<__VA_ARGS__>(a, batch, st); }

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "igemm_common.h"
+#include "igemm_tiles.h"
 
 namespace {
 
@@ -211,14 +212,8 @@ int launch_lc(IGemmArgs a, int batch, hipStream_t st) {
 
 }  // namespace
 
-// (tq, tp) = consumer wave tile in 32-blocks on a 2 x 2 consumer grid; nst = ring depth
-int ladi_launch_igemm_lc(const IGemmArgs& a, int tq, int tp, int nst, int batch, hipStream_t st) {
-    if (tq == 2 && tp == 2 && nst == 4) return launch_lc<2, 2, 2, 2, 2, 4>(a, batch, st);   // 128x128, 128 KB ring
-    if (tq == 2 && tp == 2 && nst == 5) return launch_lc<2, 2, 2, 2, 2, 5>(a, batch, st);   // 128x128, 160 KB ring
-    if (tq == 4 && tp == 2 && nst == 3) return launch_lc<2, 2, 4, 2, 2, 3>(a, batch, st);   // 256x128, 144 KB ring
-    if (tq == 2 && tp == 4 && nst == 3) return launch_lc<2, 2, 2, 4, 2, 3>(a, batch, st);   // 128x256, 144 KB ring
-    if (tq == 2 && tp == 1 && nst == 6) return launch_lc<2, 2, 2, 1, 2, 6>(a, batch, st);   // 128x64, 144 KB ring
-    if (tq == 5 && tp == 2 && nst == 2) return launch_lc<2, 2, 5, 2, 2, 2>(a, batch, st);   // 320x128, 112 KB ring
-    if (tq == 3 && tp == 3 && nst == 3) return launch_lc<2, 2, 3, 3, 2, 3>(a, batch, st);   // 192x192, 144 KB ring
-    return -7;
-}
+// one launcher per row of igemm_tiles.h: the external entry point igemm.hip dispatches to
+#define X(base, WQ, WP, TQ, TP, NL, NST) \
+    int ladi_igemm_launch_base_##base(IGemmArgs a, int batch, hipStream_t st) { return launch_lc<WQ, WP, TQ, TP, NL, NST>(a, batch, st); }
+LADI_IGEMM_LC_TILES(X)
+#undef X

@@ -17,18 +17,14 @@ int ladi_launch_igemm(const IGemmArgs& a, int batch, int cfg, hipStream_t st, in
 // the problem shape only, so a planning pass and the real pass allocate identically
 size_t ladi_igemm_splitk_ws_bytes(const IGemmArgs& a, int batch);
 
-// ---- igemm8.hip: phase-staggered 8-wave large-tile kernel, wave tile (tq*32 channels) x (tp*32 pixels); a.splitk / a.tile_map as set by
-// ladi_launch_igemm, which is the only caller
-int ladi_launch_igemm8(const IGemmArgs& a, int tq, int tp, int batch, hipStream_t st);
+// ---- igemm8.hip (phase-staggered 8-wave large-tile kernel), igemm_lc.hip (loader / consumer kernel), igemm_halo_inst_*.hip (halo-resident 3x3
+// convolution) and igemm_inst_*.hip (ring kernel) define one launcher ladi_igemm_launch_base_<id>(IGemmArgs, int batch, hipStream_t) per row of
+// igemm_tiles.h; igemm.hip, the only caller, declares them from the same rows and sets a.splitk / a.tile_map
 
-// ---- igemm_lc.hip: loader / consumer kernel, consumer wave tile (tq*32 channels) x (tp*32 pixels) on a 2 x 2 consumer grid, nst-deep ring
-int ladi_launch_igemm_lc(const IGemmArgs& a, int tq, int tp, int nst, int batch, hipStream_t st);
-
-// ---- igemm_halo.hip: halo-resident 3x3 convolution, workgroup tile (64 tq) x (128 tp), nxb halo buffers
-bool ladi_igemm_halo_eligible(const IGemmArgs& a, int batch);
-bool ladi_igemm_halo2d_eligible(const IGemmArgs& a, int batch, int th);
-bool ladi_igemm_halo_ups_eligible(const IGemmArgs& a, int batch, int bp);   // folded nearest-2x upsample + 3x3 (round 6)   // 2-D blocked form (nxb 20 / 21): W % 32 == 0, H % th == 0
-int ladi_launch_igemm_halo(const IGemmArgs& a, int tq, int tp, int nxb, int batch, hipStream_t st);
+// ---- igemm_halo.hip: what the halo-resident 3x3 convolution forms accept
+bool ladi_igemm_halo_eligible(const IGemmArgs& a, int batch);              // ring-halo forms: rows of at most 48 pixels
+bool ladi_igemm_halo2d_eligible(const IGemmArgs& a, int batch, int th);    // 2-D blocked forms: W % 32 == 0, H % th == 0
+bool ladi_igemm_halo_ups_eligible(const IGemmArgs& a, int batch, int bp);  // folded nearest-2x upsample + 3x3 (round 6): whole bp-pixel tiles inside a sample
 
 // ---- linear_xs.hip: X-stationary kernel for 1x1 layers with K = 320 / 640 (reached through ladi_launch_igemm cfg 23..27)
 // nst: weight-ring depth (3: two workgroups per CU; 2: three workgroups per CU, K = 320 plain / GEGLU projections only)

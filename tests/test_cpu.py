@@ -298,6 +298,10 @@ def test_igemm_tile_table_names_every_configuration(lib):
     # leading arguments (cfg 75 / 101) can never be taken for each other when bench.py looks a symbol up in a committed trace
     assert names[75 - 1] == "igemm_halo_kernel<4, 2, 1, 3, 4, 48, 0, 0, 0>" and names[101 - 1] == "igemm_halo_kernel<4, 2, 1, 3, 4, 48, 0, 1, 0>"
     assert names[105 - 1] == "igemm_halo_kernel<5, 1, 1, 2, 6, 48, 0, 0, 1>"      # round 6: the folded-upsample forms (UPS = 1)
+    # every name, byte for byte: bench.py looks these strings up in committed traces, and tune tables store the ids they belong to
+    with open(os.path.join(ROOT, "tests", "golden", "igemm_cfg_symbols.txt")) as fh:
+        golden = fh.read().split("\n")[:-1]
+    assert names == golden, [(c + 1, a, b) for c, (a, b) in enumerate(zip(names, golden)) if a != b]
     assert not lib.ladi_igemm_cfg_symbol_name(0) and not lib.ladi_igemm_cfg_symbol_name(n + 1)   # out of range: empty, not a crash
 
 

@@ -121,8 +121,8 @@ class ConvProblem:
         out[:, :, p0:p0 + ci - c0] = wp[:, :, c0:]
         return out.reshape(co, -1).contiguous().to(U.dev())
 
-    def launch(self, lib, cfg, out_ld=None):
-        """one ladi_op_igemm launch into a fresh guarded output; returns (output, what the launcher reports about the launch)"""
+    def try_launch(self, lib, cfg, out_ld=None):
+        """one ladi_op_igemm launch into a fresh guarded output; returns (return code, output)"""
         ldo = out_ld or self.cout + 8
         out = U.guarded_out(self.P, self.cout, ld=ldo, pre_rows=4, post_rows=4)
         d = _lib.IGemmDesc()
@@ -141,20 +141,30 @@ class ConvProblem:
             d.mask = self.M.ptr
         d.out, d.ldo = out.ptr, ldo
         rc = lib.ladi_op_igemm(ctypes.byref(d), 1, cfg, stream_ptr())
-        assert rc == 0, "cfg %d refused the launch: rc = %d (%s)" % (cfg, rc, _lib.last_error())
         torch.cuda.synchronize()
+        return rc, out
+
+    def launch(self, lib, cfg, out_ld=None):
+        """a launch that must be accepted; returns (output, what the launcher reports about the launch)"""
+        rc, out = self.try_launch(lib, cfg, out_ld)
+        assert rc == 0, "cfg %d refused the launch: rc = %d (%s)" % (cfg, rc, _lib.last_error())
         return out, _last_launch(lib)
 
-    def judge(self, lib, test, cfg, out_ld=None, repeats=1, case=None):
-        """launch, per-element check, untouched surroundings of the output AND of every input, bit-equal repeats; returns the launch info"""
-        out, info = self.launch(lib, cfg, out_ld)
+    def check(self, lib, cfg, out, what):
+        """per-element check of one launch's output, untouched surroundings of the output AND of every input; returns the worst err / limit"""
         bq, bp = _cfg_tile(lib, cfg)
-        what = "%s cfg %d %s" % (test, cfg, info)
         ratio = U.check_elem(out.cpu().float(), self.ref, self.bound, what, U.pixel_locator(self.N, self.Ho, self.Wo, self.cout, bq, bp))
         U.assert_untouched(out, what + " output")
         for name, g in (("x", self.X0), ("x2", self.X1), ("res", self.R), ("mask", self.M)):
             if g is not None:
                 U.assert_untouched(g, what + " input " + name)
+        return ratio
+
+    def judge(self, lib, test, cfg, out_ld=None, repeats=1, case=None):
+        """launch, per-element check, untouched surroundings of the output AND of every input, bit-equal repeats; returns the launch info"""
+        out, info = self.launch(lib, cfg, out_ld)
+        what = "%s cfg %d %s" % (test, cfg, info)
+        ratio = self.check(lib, cfg, out, what)
         first = out.cpu()
         for i in range(repeats):
             again, info2 = self.launch(lib, cfg, out_ld)
@@ -246,6 +256,42 @@ def test_conv3x3_halo_upsample(lib, cfg, N, cin, cout, hw, split):
     pb = _problem_kw((N, cin, 0, cout, hw[0], hw[1]), _kw(ups=1, seed=110, wscale=0.05 if cin < 1000 else None))
     info = pb.judge(lib, "conv3x3_halo_upsample", cfg, repeats=2)
     assert info["family"] == "halo" and info["split"] == split, info
+
+
+SYMBOL_FAMILY = {"igemm_kernel": "ring", "igemm8_kernel": "igemm8", "igemm_lc_kernel": "igemm_lc", "igemm_halo_kernel": "halo", "linear_xs_kernel": "linear_xs"}
+# the smallest problems at which every kind of form can still go wrong, (ConvProblem arguments, keywords), all with one sample:
+EVERY_CFG_PROBLEMS = [
+    ((1, 64, 0, 128, 16, 24), _kw(seed=180)),                               # 3x3 on rows of 24 pixels: ring, igemm8, lc, ring-halo and its W <= 24 forms, every split-K row
+    ((1, 64, 0, 128, 8, 32), _kw(seed=181)),                                # 3x3 at 8 x 32: the 2-D blocked halo forms (W % 32 == 0, H % 8 == 0)
+    ((1, 64, 0, 128, 8, 12), _kw(ups=1, seed=182, wscale=0.05)),            # folded upsample 8 x 12 -> 16 x 24: 384 pixels = whole 128- and 192-pixel tiles
+    ((1, 320, 0, 320, 16, 16), _kw(res=False, ksize=1, pad=0, seed=183)),   # 1x1, K = 320, P = 256 (one 64-pixels-per-wave panel), Q / 32 = 10 (1, 2 and 5 slices)
+    ((1, 640, 0, 320, 8, 16), _kw(res=False, ksize=1, pad=0, seed=184)),    # 1x1, K = 640, P = 128 (one 32-pixels-per-wave panel)
+]
+
+
+def test_every_configuration_launches_the_kernel_it_names(lib):
+    """the dispatch generated from csrc/igemm_tiles.h, end to end: EVERY tile configuration 1..ladi_igemm_cfg_count() is launched explicitly on each
+    of the problems above that it accepts, judged element by element against the float64 reference there (a form launched with another form's
+    grid, split-K slab or template arguments fails the bound or the poison checks), and the family its launcher reports must be the family of
+    the symbol the library names for it.  No configuration may be refused by all problems."""
+    n = lib.ladi_igemm_cfg_count()
+    problems = [_problem_kw(args, kw) for args, kw in EVERY_CFG_PROBLEMS]
+    uncovered, worst = [], 0.0
+    for cfg in range(1, n + 1):
+        family = SYMBOL_FAMILY[lib.ladi_igemm_cfg_symbol_name(cfg).decode().split("<")[0]]
+        accepted = 0
+        for i, pb in enumerate(problems):
+            rc, out = pb.try_launch(lib, cfg)
+            if rc != 0:
+                continue
+            accepted += 1
+            info = _last_launch(lib)
+            assert info["family"] == family, (cfg, i, info, family)
+            worst = max(worst, pb.check(lib, cfg, out, "every_configuration cfg %d problem %d %s" % (cfg, i, info)))
+        if not accepted:
+            uncovered.append(cfg)
+    assert not uncovered, "configurations no problem of this test reaches: %s" % uncovered
+    _record("every_configuration", "worst", worst)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- linear_xs
