@@ -477,6 +477,57 @@ int ladi_op_posterior_sample(const void* moments_dev, int ldm, const float* nois
  * CFG batch order [uncond(B); cond(B)] with zero pose / cloth in the uncond half; unet_in NHWC fp16 [(cfg ? 2B : B), hw, ld] */
 int ladi_op_assemble_input(void* unet_in_dev, int ld, int B, int hw, int cfg, const float* latents_dev, const void* mask_lat_dev,
                            const float* masked_lat_dev, const void* pose_dev, int pose_channels, const float* cloth_lat_dev, void* stream);
+/* ---- helper kernels on their own (tests/test_gpu_helpers.py): one entry point per launcher, device pointers, the launcher's return code.
+ * Row strides are in elements; columns [C, ld) of a strided row are neither read nor written unless a line below says they are zeroed.
+ * One query per (sample, head) -- the inversion adapter's pooling attention: q [n][ldq], k / v rows [n][Nk][ld] with sample strides sk / sv,
+ * head h at column h * d of every row, any d <= 128 (d > 128: -1), out [n][ldo] */
+int ladi_op_attention_single_query(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int n, int heads,
+                                   int d, int Nk, long long sk, long long sv, float scale, void* stream);
+/* fp32 path of the warping module (TPS network and refinement UNet called with fp32 tensors): NHWC fp32 activations, fp32 weights
+ * [Q][ksize * ksize * (C0 + C1)] tap-major / channel-minor (row stride ldw, 0 = K), out = act(conv + bias) (act: 0 none, 1 SiLU, 4 ReLU, 5 tanh).
+ * batch > 1 runs `batch` problems bs_src0 / bs_w / bs_out elements apart (the correlation: the weight operand is a feature map).
+ * Refused without a launch: -1 ksize outside 1..4, C0 / C1 not multiples of 8, ld0 / ld1 not multiples of 4, P or Q <= 0; -3 K != ksize^2 (C0 + C1)
+ * or ldw not a multiple of 4; -4 src0 / src1 / W / out not 16-byte aligned; -5 ld0 < C0 or ld1 < C1; -6 batch > 1 with a second source (it has
+ * no batch stride); -7 batch > 1 with bs_src0 or bs_w, or -- when ldo % 4 == 0, the vector store -- bs_out, not a multiple of 4 */
+typedef struct {
+    const float* src0; const float* src1; int C0, C1, ld0, ld1, Hs, Ws, Ho, Wo, P, ksize, stride, pad;
+    const float* W; int Q, K, ldw; long long bs_src0, bs_w, bs_out; const float* bias; int act; float* out; int ldo;
+} ladi_conv_f32_desc;
+int ladi_op_conv_f32(const ladi_conv_f32_desc* d, int batch, void* stream);
+/* NCHW (dtype 0 fp32 / 1 fp16) <-> NHWC fp32 [n][H W][ld]; to NHWC zeroes channels [C, ld) */
+int ladi_op_nchw_to_nhwc_f32(const void* src, int dtype, int n, int C, int H, int W, float* dst, int ld, void* stream);
+int ladi_op_nhwc_to_nchw_f32(const float* src, int ld, int n, int C, int H, int W, void* dst, int dtype, void* stream);
+/* x = x * scale[c] + shift[c] in place; x /= sqrt(sum_c x^2 + 1e-6) in place; dst[i][:] = src[rows[i]][:] (dense rows of H floats) */
+int ladi_op_channel_affine_f32(float* x, int ld, long long n_pix, int C, const float* scale, const float* shift, void* stream);
+int ladi_op_l2norm_rows_f32(float* x, int ld, int rows, int C, void* stream);
+int ladi_op_gather_rows_f32(const float* src, const int* rows, int n, int H, float* dst, void* stream);
+int ladi_op_maxpool2_f32(const float* src, int lds, int n, int H, int W, int C, float* dst, int ldd, void* stream);
+int ladi_op_upsample2x_bilinear_f32(const float* src, int lds, int n, int H, int W, int C, float* dst, int ldd, void* stream);
+/* out[m][n] = act(sum_k x[m][k] W[n][k] + b[n]), everything fp32, W dense [N][K] */
+int ladi_op_linear_f32(const float* x, int ldx, const float* W, const float* b, int M, int N, int K, int act, float* out, int ldo, void* stream);
+/* the fp16 forms of the TPS network (C, ldx, ldy multiples of 8; channel_affine may run in place) */
+int ladi_op_channel_affine(const void* x, int ldx, long long n_pix, int C, const float* scale, const float* shift, void* y, int ldy, void* stream);
+int ladi_op_l2norm_rows(const void* x, int ldx, int rows, int C, void* y, int ldy, void* stream);
+int ladi_op_gather_rows(const void* src, const int* rows, int n, int H, void* dst, void* stream);
+/* TPSGridGen: coor [B][N][2], inv [(N + 3)^2], ctrl [N][2] (fp32) -> grid fp32 [B][H][W][2]; 1 <= N <= 32 and H, W >= 2, else -1 */
+int ladi_op_tps_grid(const float* coor, const float* inv, const float* ctrl, int N, int B, int H, int W, float* grid, void* stream);
+/* CLIP text front end on device ids [B][T]: first[b] = position of the first `vstar` id (-1: none, or use_words == 0), eot[b] = b T + argmax
+ * (first maximum); out [B][T][H] = (token | spliced pseudo-word) + position embedding, ids clamped to [0, vocab), wemb [B][nv][H] or NULL */
+int ladi_op_text_meta(const int* ids, int B, int T, int vstar, int use_words, int* first, int* eot, void* stream);
+int ladi_op_text_embed(const int* ids, const int* first, int nv, const void* tok, const void* pos, const void* wemb, int B, int T, int H,
+                       int vocab, void* out, void* stream);
+/* ViT patch rows: px [B][3][S][S] (dtype) -> out fp16 [B][1 + (S / ps)^2][KP], row 0 and columns >= 3 ps^2 zero */
+int ladi_op_patchify(const void* px, int dtype, int B, int S, int ps, int KP, void* out, void* stream);
+/* glue of the denoising loop and the decoder */
+int ladi_op_timestep_embedding(const float* t, int count, int dim, float* out, void* stream);     /* [cos | sin], fp32 [count][dim] */
+int ladi_op_image_post(const void* src, int ld, int n_pix, void* dst, int dst_u8, void* stream);  /* clamp(x / 2 + 0.5, 0, 1): fp32 or round(255 v) u8, [n_pix][3] */
+int ladi_op_post_quant(const float* lat, const float* pq, float inv_sf, int n, void* dst, int ld, void* stream);   /* pq [16 w | 4 b] or NULL; channels [4, ld) zero */
+int ladi_op_lat_nchw_to_pix(const float* src, int B, int hw, float scale, float* dst, void* stream);
+int ladi_op_lat_pix_to_nchw(const float* src, int B, int hw, float* dst, void* stream);
+/* src fp32 NCHW [B][4][hw] -> latents [B][hw][4] and channels 0-3 of unet_in rows ([B], with cfg [2B]; ld_in >= 4, a multiple of 4) = fp16(x in_scale) */
+int ladi_op_latents_import(const float* src, int B, int hw, float* latents, void* unet_in, int ld_in, int cfg, float in_scale, void* stream);
+int ladi_op_scale_h16(const void* src, int lds, void* dst, int ldd, long long n_pix, int C, float s, void* stream);
+int ladi_op_fill_f32(float* p, long long n, float v, void* stream);
 
 /* ---- fp16 range probe (opt-in; with no probe attached nothing changes: same launches, same captured graph, same bits) ----
  * A probe records, for every named activation of the modules it is attached to, the largest finite |x| and the number of inf / NaN

@@ -81,6 +81,14 @@ class IGemmDesc(Structure):
                 ("sk_ws", c_void_p), ("sk_cnt", c_void_p), ("gn_ss", c_void_p), ("gn_hw", c_int)]
 
 
+class ConvF32Desc(Structure):
+    _fields_ = [("src0", c_void_p), ("src1", c_void_p), ("C0", c_int), ("C1", c_int), ("ld0", c_int), ("ld1", c_int),
+                ("Hs", c_int), ("Ws", c_int), ("Ho", c_int), ("Wo", c_int), ("P", c_int), ("ksize", c_int), ("stride", c_int), ("pad", c_int),
+                ("W", c_void_p), ("Q", c_int), ("K", c_int), ("ldw", c_int),
+                ("bs_src0", c_longlong), ("bs_w", c_longlong), ("bs_out", c_longlong),
+                ("bias", c_void_p), ("act", c_int), ("out", c_void_p), ("ldo", c_int)]
+
+
 # every symbol include/ladi_native.h declares: name -> (restype, argtypes)
 _P = c_void_p
 # ladi_step_callback: int (*)(void* user, int eval_index)
@@ -200,6 +208,32 @@ SIGNATURES = {
     "ladi_op_pose_down8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "ladi_op_posterior_sample": (c_int, [_P, c_int, _P, c_int, c_int, c_float, _P, _P]),
     "ladi_op_assemble_input": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P]),
+    "ladi_op_attention_single_query": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong,
+                                               c_float, _P]),
+    "ladi_op_conv_f32": (c_int, [POINTER(ConvF32Desc), c_int, _P]),
+    "ladi_op_nchw_to_nhwc_f32": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    "ladi_op_nhwc_to_nchw_f32": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    "ladi_op_channel_affine_f32": (c_int, [_P, c_int, c_longlong, c_int, _P, _P, _P]),
+    "ladi_op_l2norm_rows_f32": (c_int, [_P, c_int, c_int, c_int, _P]),
+    "ladi_op_gather_rows_f32": (c_int, [_P, _P, c_int, c_int, _P, _P]),
+    "ladi_op_maxpool2_f32": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    "ladi_op_upsample2x_bilinear_f32": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    "ladi_op_linear_f32": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    "ladi_op_channel_affine": (c_int, [_P, c_int, c_longlong, c_int, _P, _P, _P, c_int, _P]),
+    "ladi_op_l2norm_rows": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P]),
+    "ladi_op_gather_rows": (c_int, [_P, _P, c_int, c_int, _P, _P]),
+    "ladi_op_tps_grid": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    "ladi_op_text_meta": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "ladi_op_text_embed": (c_int, [_P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    "ladi_op_patchify": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "ladi_op_timestep_embedding": (c_int, [_P, c_int, c_int, _P, _P]),
+    "ladi_op_image_post": (c_int, [_P, c_int, c_int, _P, c_int, _P]),
+    "ladi_op_post_quant": (c_int, [_P, _P, c_float, c_int, _P, c_int, _P]),
+    "ladi_op_lat_nchw_to_pix": (c_int, [_P, c_int, c_int, c_float, _P, _P]),
+    "ladi_op_lat_pix_to_nchw": (c_int, [_P, c_int, c_int, _P, _P]),
+    "ladi_op_latents_import": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_float, _P]),
+    "ladi_op_scale_h16": (c_int, [_P, c_int, _P, c_int, c_longlong, c_int, c_float, _P]),
+    "ladi_op_fill_f32": (c_int, [_P, c_longlong, c_float, _P]),
 }
 
 _lib = None

@@ -35,6 +35,7 @@ static void set_module_probe(Probe*& slot, ladi_probe* p) {
 static_assert(TRYON_CALLBACK_ABORT == LADI_TRYON_CALLBACK_ABORTED, "callback abort code");
 
 static_assert(sizeof(ladi_igemm_desc) == sizeof(IGemmArgs), "public igemm descriptor must mirror IGemmArgs");
+static_assert(sizeof(ladi_conv_f32_desc) == sizeof(ConvF32Args), "public fp32 convolution descriptor must mirror ConvF32Args");
 
 static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
@@ -884,6 +885,82 @@ int ladi_op_assemble_input(void* unet_in, int ld, int B, int hw, int cfg, const 
     return ladi_launch_assemble_static((h16*)unet_in, ld, B, hw, cfg, latents, (const h16*)mask_lat, masked_lat, (const h16*)pose, pose_ch,
                                        cloth_lat, cloth_lat ? 1 : 0, 1.0f, S(stream));
 }
+// helper kernels on their own (tests/test_gpu_helpers.py): cast, launch, return the launcher's code
+int ladi_op_attention_single_query(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int n, int heads,
+                                   int d, int Nk, long long sk, long long sv, float scale, void* stream) {
+    return ladi_launch_attn_single_query((const h16*)q, ldq, (const h16*)k, ldk, (const h16*)v, ldv, (h16*)o, ldo, n, heads, d, Nk, sk, sv, scale,
+                                         S(stream));
+}
+int ladi_op_conv_f32(const ladi_conv_f32_desc* d, int batch, void* stream) {
+    if (!d) return -1;
+    ConvF32Args a;
+    std::memcpy(&a, d, sizeof(a));
+    return ladi_launch_conv_f32(a, batch, S(stream));
+}
+int ladi_op_nchw_to_nhwc_f32(const void* src, int dtype, int n, int C, int H, int W, float* dst, int ld, void* stream) {
+    return ladi_launch_nchw_to_nhwc_f32(src, dtype == LADI_F32, n, C, H, W, dst, ld, S(stream));
+}
+int ladi_op_nhwc_to_nchw_f32(const float* src, int ld, int n, int C, int H, int W, void* dst, int dtype, void* stream) {
+    return ladi_launch_nhwc_to_nchw_f32(src, ld, n, C, H, W, dst, dtype == LADI_F32, S(stream));
+}
+int ladi_op_channel_affine_f32(float* x, int ld, long long n_pix, int C, const float* scale, const float* shift, void* stream) {
+    return ladi_launch_channel_affine_f32(x, ld, (size_t)n_pix, C, scale, shift, S(stream));
+}
+int ladi_op_l2norm_rows_f32(float* x, int ld, int rows, int C, void* stream) { return ladi_launch_l2norm_rows_f32(x, ld, rows, C, S(stream)); }
+int ladi_op_gather_rows_f32(const float* src, const int* rows, int n, int H, float* dst, void* stream) {
+    return ladi_launch_gather_rows_f32(src, rows, n, H, dst, S(stream));
+}
+int ladi_op_maxpool2_f32(const float* src, int lds, int n, int H, int W, int C, float* dst, int ldd, void* stream) {
+    return ladi_launch_maxpool2_f32(src, lds, n, H, W, C, dst, ldd, S(stream));
+}
+int ladi_op_upsample2x_bilinear_f32(const float* src, int lds, int n, int H, int W, int C, float* dst, int ldd, void* stream) {
+    return ladi_launch_upsample2x_bilinear_ac_f32(src, lds, n, H, W, C, dst, ldd, S(stream));
+}
+int ladi_op_linear_f32(const float* x, int ldx, const float* W, const float* b, int M, int N, int K, int act, float* out, int ldo, void* stream) {
+    return ladi_launch_linear_f32(x, ldx, W, b, M, N, K, act, out, ldo, S(stream));
+}
+int ladi_op_channel_affine(const void* x, int ldx, long long n_pix, int C, const float* scale, const float* shift, void* y, int ldy, void* stream) {
+    return ladi_launch_channel_affine((const h16*)x, ldx, (size_t)n_pix, C, scale, shift, (h16*)y, ldy, S(stream));
+}
+int ladi_op_l2norm_rows(const void* x, int ldx, int rows, int C, void* y, int ldy, void* stream) {
+    return ladi_launch_l2norm_rows((const h16*)x, ldx, rows, C, (h16*)y, ldy, S(stream));
+}
+int ladi_op_gather_rows(const void* src, const int* rows, int n, int H, void* dst, void* stream) {
+    return ladi_launch_gather_rows((const h16*)src, rows, n, H, (h16*)dst, S(stream));
+}
+int ladi_op_tps_grid(const float* coor, const float* inv, const float* ctrl, int N, int B, int H, int W, float* grid, void* stream) {
+    return ladi_launch_tps_grid(coor, inv, ctrl, N, B, H, W, grid, S(stream));
+}
+int ladi_op_text_meta(const int* ids, int B, int T, int vstar, int use_words, int* first, int* eot, void* stream) {
+    return ladi_launch_text_meta(ids, B, T, vstar, use_words, first, eot, S(stream));
+}
+int ladi_op_text_embed(const int* ids, const int* first, int nv, const void* tok, const void* pos, const void* wemb, int B, int T, int H,
+                       int vocab, void* out, void* stream) {
+    return ladi_launch_text_embed(ids, first, nv, (const h16*)tok, (const h16*)pos, (const h16*)wemb, B, T, H, vocab, (h16*)out, S(stream));
+}
+int ladi_op_patchify(const void* px, int dtype, int B, int S_, int ps, int KP, void* out, void* stream) {
+    return ladi_launch_patchify(px, dtype == LADI_F32, B, S_, ps, KP, (h16*)out, S(stream));
+}
+int ladi_op_timestep_embedding(const float* t, int count, int dim, float* out, void* stream) {
+    return ladi_launch_timestep_embedding(t, count, dim, out, S(stream));
+}
+int ladi_op_image_post(const void* src, int ld, int n_pix, void* dst, int dst_u8, void* stream) {
+    return ladi_launch_image_post((const h16*)src, ld, n_pix, dst, dst_u8, S(stream));
+}
+int ladi_op_post_quant(const float* lat, const float* pq, float inv_sf, int n, void* dst, int ld, void* stream) {
+    return ladi_launch_post_quant(lat, pq, inv_sf, n, (h16*)dst, ld, S(stream));
+}
+int ladi_op_lat_nchw_to_pix(const float* src, int B, int hw, float scale, float* dst, void* stream) {
+    return ladi_launch_lat_nchw_to_pix(src, B, hw, scale, dst, S(stream));
+}
+int ladi_op_lat_pix_to_nchw(const float* src, int B, int hw, float* dst, void* stream) { return ladi_launch_lat_pix_to_nchw(src, B, hw, dst, S(stream)); }
+int ladi_op_latents_import(const float* src, int B, int hw, float* latents, void* unet_in, int ld_in, int cfg, float in_scale, void* stream) {
+    return ladi_launch_latents_import(src, B, hw, latents, (h16*)unet_in, ld_in, cfg, in_scale, S(stream));
+}
+int ladi_op_scale_h16(const void* src, int lds, void* dst, int ldd, long long n_pix, int C, float s, void* stream) {
+    return ladi_launch_scale_h16((const h16*)src, lds, (h16*)dst, ldd, (size_t)n_pix, C, s, S(stream));
+}
+int ladi_op_fill_f32(float* p, long long n, float v, void* stream) { return ladi_launch_fill_f32(p, (size_t)n, v, S(stream)); }
 static int sched_run_any(const char* name, int kind, int steps, const float* ac_host, const void* eps_seq, int evals, int B, int hw, int cfg,
                          float guidance, float* latents, const float* step_noise, int noise_steps, float eta, void* stream) {
     return guarded(name, [&]() {

@@ -216,6 +216,10 @@ int ladi_launch_conv_f32(const ConvF32Args& a, int batch, hipStream_t st) {
     if (a.ksize < 1 || a.ksize > 4 || (a.C0 % 8) || (a.C1 % 8) || (a.ld0 % 4) || (a.C1 && (a.ld1 % 4)) || a.P <= 0 || a.Q <= 0) return -1;
     if (a.K != a.ksize * a.ksize * (a.C0 + a.C1) || ((a.ldw ? a.ldw : a.K) % 4)) return -3;
     if ((reinterpret_cast<uintptr_t>(a.src0) | reinterpret_cast<uintptr_t>(a.src1) | reinterpret_cast<uintptr_t>(a.W) | reinterpret_cast<uintptr_t>(a.out)) & 15) return -4;
+    if (a.ld0 < a.C0 || (a.C1 && a.ld1 < a.C1)) return -5;      // a row stride shorter than the row: the float4 loads would run into the next pixel
+    if (batch > 1 && a.C1) return -6;                           // src1 has no batch stride: every grid.z plane would read the first problem's second source
+    // the batch strides move the float4 loads of src0 / W -- and, on the vector path of the epilogue (ldo % 4 == 0), the float4 stores -- off 16 bytes
+    if (batch > 1 && (((a.bs_src0 | a.bs_w) & 3) || (!(a.ldo & 3) && (a.bs_out & 3)))) return -7;
     if (a.Q <= 64) {       // narrow outputs (the 3-channel OutConv, 64-channel first layers): all four waves along the pixels
         const int np = (a.P + 255) / 256;
         hipLaunchKernelGGL((conv_f32_kernel<1, 4>), dim3((unsigned)np, 1, (unsigned)batch), dim3(256), 0, st, a);

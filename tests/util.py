@@ -7,7 +7,7 @@ import torch
 from ladi_vton_amd import _lib
 from ladi_vton_amd._lib import IGemmDesc, ptr, stream_ptr
 
-ACT = dict(none=0, silu=1, gelu=2, geglu=3, relu=4)
+ACT = dict(none=0, silu=1, gelu=2, geglu=3, relu=4, tanh=5)
 
 
 def dev():
@@ -187,19 +187,21 @@ def _poison_word(dtype):
     return (torch.int16, POISON16) if dtype == torch.float16 else (torch.int32, POISON32)
 
 
-def guarded(t, ld=None, pre_rows=2, post_rows=2, device=None):
+def guarded(t, ld=None, pre_rows=2, post_rows=2, device=None, any_ld=False):
     """Place an fp16 / fp32 operand t ([rows, C], or NHWC [N, H, W, C] flattened to pixel rows; CPU or GPU) inside a larger device buffer of
     NaN: pre_rows rows of poison, then the rows of t at row stride ld (default C: dense), columns [C, ld) of every row poison, then post_rows
     rows of poison.  ld % 8 == 0 (ld % 4 == 0 is accepted for the two strides the ABI itself defines that way: out_ld = 4 of the UNet's output
     layer and the V^T rows of the wide attention) and pre_rows rounded up to the next count that puts the view on a 16-byte boundary of the
     torch allocator's 256-byte aligned block, as every launcher requires.
     What t itself holds is the caller's business: channel padding the contract defines as ZERO (nhwc16's padding to 64, packed-weight padding)
-    is part of t and stays zero.  device: default the GPU ("cpu" for the harness's own CPU test).  Returns a Guarded."""
+    is part of t and stays zero.  device: default the GPU ("cpu" for the harness's own CPU test).  any_ld: accept a stride that is no multiple
+    of 4 (the helper kernels that address element by element: an fp32 output of 3 channels at ld = 3, dense buffers of odd length).
+    Returns a Guarded."""
     assert t.dtype in (torch.float16, torch.float32)
     t2 = t.reshape(-1, t.shape[-1])
     rows, C = t2.shape
     ld = C if ld is None else ld
-    assert ld >= C and ld % 4 == 0, (C, ld)
+    assert ld >= C and (ld % 4 == 0 or any_ld), (C, ld)
     while (pre_rows * ld * t.element_size()) % 16:
         pre_rows += 1
     it, word = _poison_word(t.dtype)
@@ -257,9 +259,9 @@ def guarded_batch(ts, ld=None, gap_rows=3, pre_rows=2, post_rows=2, device=None)
     return g
 
 
-def guarded_out(rows, C, ld=None, pre_rows=2, post_rows=2, dtype=torch.float16, device=None):
+def guarded_out(rows, C, ld=None, pre_rows=2, post_rows=2, dtype=torch.float16, device=None, any_ld=False):
     """an OUTPUT placed like guarded(): the view itself starts as NaN too, so an element the kernel never wrote fails check_elem"""
-    return guarded(torch.full((rows, C), float("nan"), dtype=dtype), ld, pre_rows, post_rows, device)
+    return guarded(torch.full((rows, C), float("nan"), dtype=dtype), ld, pre_rows, post_rows, device, any_ld)
 
 
 def assert_untouched(g, what=""):
@@ -317,8 +319,9 @@ def check_elem(got, ref, bound, what, locate=None, out_f32=False):
     return float(ratio.max())
 
 
-# Lipschitz constants of the epilogue's activations (sup |f'|): SiLU 1.0999 at x = 2.3994, exact GELU 1.1290 at x = sqrt(2), ReLU / none 1
-ACT_LIP = dict(none=1.0, relu=1.0, silu=1.1, gelu=1.13)
+# Lipschitz constants of the epilogue's activations (sup |f'|): SiLU 1.0999 at x = 2.3994, exact GELU 1.1290 at x = sqrt(2), ReLU / none 1,
+# tanh 1 at x = 0
+ACT_LIP = dict(none=1.0, relu=1.0, silu=1.1, gelu=1.13, tanh=1.0)
 # fp32 evaluation of an activation with the hardware's fast exp / reciprocal (v_exp_f32 and v_rcp_f32 are specified to 1 ulp, the erf / tanh
 # polynomial a few more): 16 fp32 ulps of the result, a documented allowance, not a measurement
 ACT_EVAL = 16.0 * U32
@@ -336,7 +339,7 @@ def _act_eval_err(x, t, act):
 
 def _act64(x, act):
     import torch.nn.functional as F
-    return dict(none=lambda v: v, relu=F.relu, silu=F.silu, gelu=F.gelu)[act](x)
+    return dict(none=lambda v: v, relu=F.relu, silu=F.silu, gelu=F.gelu, tanh=torch.tanh)[act](x)
 
 
 def conv_ref_bound(x, w, bias=None, rowadd=None, act="none", res=None, mask=None, stride=1, padding=1, x_err=None,
@@ -539,6 +542,35 @@ def attention_ref_bound(q, k, v, scale, causal=False):
     vsum = va.sum(-2, keepdim=True) if not causal else torch.cumsum(va, -2)
     bound = (p * torch.expm1(D + Dbar)) @ va + (U16 + (2 * Nk + 8) * U32) * (p @ va) + 2.0 ** -24 * vsum
     return p @ v, bound
+
+
+def single_query_ref_bound(q, k, v, scale):
+    """float64 softmax(scale q k^T) v for ONE query per (sample, head) -- q [.., d], k, v [.., Nk, d] -- and the bound of the library's
+    single-query kernel (attention.hip attn_single_query_kernel): scores s_j = fl(sum_c q_c k_jc) scale in fp32 (products of two fp16 values
+    are exact, d terms, one product with the scale), w_j = exp(s_j - m) with m the maximum of the computed scores, numerator sum_j w_j v_j and
+    denominator sum_j w_j summed in fp32 over the Nk keys in order, o = numerator * (1 / denominator), one rounding to fp16 (check_elem's ulp16).
+      score:   |ds_j| <= (d + 1) u scale sum_c |q_c| |k_jc|; the argument of the exponential adds the rounding of s_j - m and of its product
+               with log2 e inside the fast exponential, each u |s_j - m| <= u (|s_j| + max |s|), a third one granted:
+                   D_j = (d + 1) u scale sum_c |q_c| |k_jc| + 3 u (|s_j| + max_i |s_i|)
+      exp:     evaluated to ACT_EVAL relative, so w~_j = w_j (1 + delta_j), |delta_j| <= eps_j = e^(D_j) (1 + ACT_EVAL) - 1.  Whatever m is, it
+               cancels in the quotient, and with p = softmax(s)
+                   o~ - o = sum_j p_j delta_j (v_j - o) / (1 + sum_j p_j delta_j),   |o~ - o| <= sum_j p_j eps_j |v_j - o| / (1 - sum_j p_j eps_j):
+               a key with a large score error but no weight, or a value equal to the output, does not loosen the bound
+      sums:    an Nk-term fp32 sum of rounded products for the numerator, an Nk-term sum for the denominator, the reciprocal and the final
+               product: (2 Nk + 6) u sum_j p_j |v_j|
+    Returns (ref, bound), float64 [.., d]."""
+    q, k, v = q.double(), k.double(), v.double()
+    d, Nk = q.shape[-1], k.shape[-2]
+    s = (k @ q.unsqueeze(-1)).squeeze(-1) * scale                     # [.., Nk]
+    sa = (k.abs() @ q.abs().unsqueeze(-1)).squeeze(-1) * abs(scale)
+    p = torch.softmax(s, -1)
+    D = (d + 1) * U32 * sa + 3 * U32 * (s.abs() + s.abs().amax(-1, keepdim=True))
+    eps = torch.exp(D) * (1.0 + ACT_EVAL) - 1.0
+    ref = (p.unsqueeze(-2) @ v).squeeze(-2)                           # [.., d]
+    pe = p * eps
+    num = (pe.unsqueeze(-2) @ (v - ref.unsqueeze(-2)).abs()).squeeze(-2)
+    bound = num / (1.0 - pe.sum(-1, keepdim=True)) + (2 * Nk + 6) * U32 * (p.unsqueeze(-2) @ v.abs()).squeeze(-2)
+    return ref, bound
 
 
 def softmax_rows_ref_bound(s, scale):
