@@ -385,6 +385,16 @@ typedef struct {
 int ladi_op_igemm(const ladi_igemm_desc* d, int batch, int tile_cfg, void* stream);
 int ladi_op_group_norm(const void* src0, int C0, const void* src1, int C1, int n, int HW, int groups, const void* gamma,
                        const void* beta, float eps, int silu, const void* add, void* out, float* stats_scratch, void* stream);
+/* ladi_op_igemm, and *stats_row_px = pixels per row of the partial statistics the launch wrote into d->stats: [n HW / px][Q][2] floats (sum, sum
+ * of squares of the values as stored), rows [s HW / px, (s + 1) HW / px) belonging to sample s; 0 = none were written and d->stats is untouched
+ * (no d->stats, the X-stationary kernel, HW % px != 0, GEGLU, batch > 1, fp32 output) */
+int ladi_op_igemm_stats(const ladi_igemm_desc* d, int batch, int tile_cfg, int* stats_row_px, void* stream);
+/* ladi_op_group_norm whose sources bring such rows: partK = source K's rows of pxK pixels each; pxK = 0: the source has none (its statistics
+ * are taken from the data).  Runs the dispatch every model runs for the same rows.  pxK > 0 with HW % pxK != 0 or a null partK is refused
+ * before anything is launched. */
+int ladi_op_group_norm_rows(const void* src0, int C0, const float* part0, int px0, const void* src1, int C1, const float* part1, int px1, int n,
+                            int HW, int groups, const void* gamma, const void* beta, float eps, int silu, const void* add, void* out,
+                            void* stream);
 int ladi_op_layer_norm(const void* x, const void* gamma, const void* beta, float eps, int rows, int C, void* out, void* stream);
 /* the same on strided rows: x [rows][ldx], out [rows][ldo] (ldx, ldo >= C, multiples of 8; columns [C, ld) are neither read nor written) */
 int ladi_op_layer_norm_ld(const void* x, int ldx, const void* gamma, const void* beta, float eps, int rows, int C, void* out, int ldo,

@@ -176,6 +176,8 @@ SIGNATURES = {
     "ladi_igemm_cfg_symbol_name": (ctypes.c_char_p, [c_int]),
     "ladi_op_igemm": (c_int, [POINTER(IGemmDesc), c_int, c_int, _P]),
     "ladi_op_group_norm": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, c_float, c_int, _P, _P, _P, _P]),
+    "ladi_op_igemm_stats": (c_int, [POINTER(IGemmDesc), c_int, c_int, POINTER(c_int), _P]),
+    "ladi_op_group_norm_rows": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, c_float, c_int, _P, _P, _P]),
     "ladi_op_layer_norm": (c_int, [_P, _P, _P, c_float, c_int, c_int, _P, _P]),
     "ladi_op_layer_norm_ld": (c_int, [_P, c_int, _P, _P, c_float, c_int, c_int, _P, c_int, _P]),
     "ladi_op_xattn_block": (c_int, [_P, _P, _P, c_float, _P, _P, c_int, _P, _P, c_int, c_int, _P, _P]),

@@ -747,6 +747,34 @@ int ladi_op_group_norm(const void* src0, int C0, const void* src1, int C1, int n
         return 0;
     });
 }
+// ladi_op_igemm that also reports the pixels per row of the statistics the launch wrote into d->stats (0: it wrote none)
+int ladi_op_igemm_stats(const ladi_igemm_desc* d, int batch, int tile_cfg, int* stats_row_px, void* stream) {
+    return guarded("ladi_op_igemm_stats", [&]() {
+        IGemmArgs a;
+        std::memcpy(&a, d, sizeof(a));
+        int rc = ladi_launch_igemm(a, batch, tile_cfg, S(stream), stats_row_px);
+        if (rc) set_error("igemm launch rc=" + std::to_string(rc));
+        return rc;
+    });
+}
+// ladi_op_group_norm on sources that bring their producers' partial rows (Act::st_part / st_px): the runtime's own dispatch over gn_norm,
+// gn_reduce + gn_norm and gn_finalize + gn_apply, on rows the caller placed
+int ladi_op_group_norm_rows(const void* src0, int C0, const float* part0, int px0, const void* src1, int C1, const float* part1, int px1, int n,
+                            int HW, int groups, const void* gamma, const void* beta, float eps, int silu, const void* add, void* out, void* stream) {
+    return guarded("ladi_op_group_norm_rows", [&]() {
+        hipStream_t st = S(stream);
+        if (n < 1 || HW < 1 || px0 < 0 || px1 < 0 || (px0 > 0 && (!part0 || HW % px0)) || (C1 && px1 > 0 && (!part1 || HW % px1)))
+            throw std::runtime_error("rows of px pixels need a buffer and HW % px == 0");
+        Act x = op_view(src0, n, HW, C0), x2 = op_view(src1, n, HW, C1);
+        const Act ad = op_view(add, n, HW, C0 + C1), o = op_view(out, n, HW, C0 + C1);
+        if (px0 > 0) { x.st_part = const_cast<float*>(part0); x.st_px = px0; }
+        if (C1 && px1 > 0) { x2.st_part = const_cast<float*>(part1); x2.st_px = px1; }
+        DNorm nm; nm.g = reinterpret_cast<h16*>(const_cast<void*>(gamma)); nm.b = reinterpret_cast<h16*>(const_cast<void*>(beta)); nm.c = C0 + C1;
+        std::lock_guard<std::mutex> lk(g_op_mu);
+        run_planned(op_arena(st), st, [&](Ctx& c) { (void)group_norm(c, nm, x, C1 ? &x2 : nullptr, groups, eps, silu, add ? &ad : nullptr, &o); });
+        return 0;
+    });
+}
 // fused transformer sub-blocks of the C = 320 level from plain operands: the packings the kernels read are built here, per call (op-level
 // entry points are for tests; the UNet packs once at load / per context)
 int ladi_op_xattn_block(const void* x, const void* ln_gamma, const void* ln_beta, float eps, const void* wq, const void* kv, int L, const void* wo,

@@ -656,6 +656,7 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
     // work-complete timing: a split-K launch is not done until its reduce pass has written the output, so the pass is charged to the
     // symbol of the kernel that needed it (rocprofv3 lists splitk_reduce_kernel separately; profiles/README.md shows how to add it back)
     if (prof) { (void)hipEventRecord(rec.e1, st); g_recs.push_back(rec); }
+    if (rc != 0 && stats_row_px) *stats_row_px = 0;   // the form's launcher refused: no rows were written, none are reported
     return rc;
 }
 

@@ -214,7 +214,8 @@ __device__ __forceinline__ void igemm_epilogue_generic(const IGemmArgs& a, f32x1
                 if (lane < LPR) { ssum[e] += s1; ssq[e] += s2; }
             }
         }
-        if (lane < LPR && co8 < Qout) {
+        // (a wave whose pixels all lie behind P -- the ragged last tile -- has no row: the buffer holds ceil(P / px) of them)
+        if (lane < LPR && co8 < Qout && p0 + wp * TP * pstr < a.P) {
             const size_t row = (size_t)pt * WP + wp;
             float* sp = a.stats + (row * Qout + co8) * 2;
 #pragma unroll
@@ -398,7 +399,8 @@ __device__ __forceinline__ void igemm_epilogue_fast(const IGemmArgs& a, f32x16 (
                 if (lane < LPR) { ssum[e] += s1; ssq[e] += s2; }
             }
         }
-        if (lane < LPR && co8 < Qout) {
+        // (a wave whose pixels all lie behind P -- the ragged last tile -- has no row: the buffer holds ceil(P / px) of them)
+        if (lane < LPR && co8 < Qout && p0 + wp * TP * pstr < a.P) {
             const size_t row = (size_t)pt * WP + wp;
             float* sp = a.stats + (row * Qout + co8) * 2;
 #pragma unroll

@@ -511,6 +511,34 @@ def group_norm_ref_bound(x, groups, gamma, beta, eps, silu=False, add=None):
     return y, e
 
 
+def stats_rows_ref_bound(stored, n, HW):
+    """float64 per-sample, per-channel statistics of a STORED fp16 output -- stored: float64 [n HW, Q] pixel rows holding fp16-representable
+    values -- and the bound of an fp32 accumulation of them in ANY order: what the partial rows an igemm epilogue writes for the consuming
+    GroupNorm must add up to.  The unit is the sample: rows [s rps, (s + 1) rps) of a producer's buffer belong to sample s, and that is all
+    the three readers (gn_norm, gn_reduce, gn_finalize: norm.hip) rely on, so a producer is judged on the float64 sum of its fp32 rows per
+    sample (an exact combine of fp32 partial sums is one more summation order, and the most favourable one).
+
+    Derivation (u = 2^-24).  Every term of the sum is an fp16 value, exact in fp32.  For ANY order of an fp32 sum of HW terms the running-
+    error bound is |fl(S) - S| <= gamma_(HW - 1) sum|v| (Higham, Accuracy and Stability, eq. 4.4), gamma_k = k u / (1 - k u): granted as
+        HW u sum|v|                                                               for the sum,
+    which exceeds gamma_(HW - 1) while HW u < 1 / HW, i.e. for every HW up to 4096 pixels per sample, far above the shapes of the suite (the
+    call asserts it).  The square of an fp16 value has at most 22 significant bits and an exponent of at least -48: exact in fp32 as well, so
+    the sum of squares is the same kind of sum.  Its terms are granted one rounding each all the same (an implementation is free to form
+    them with a rounded multiply-add), and one further unit covers the second-order terms of gamma_(HW + 1):
+        (HW + 2) u sum v^2                                                        for the sum of squares.
+    Statistics of the UNROUNDED fp32 value differ from those of the stored fp16 value by the HW final roundings, each up to 2^-11 |v| and of
+    either sign: about sqrt(HW / 3) 2^-11 rms(v) for the sum, against a bound of HW u sum|v| ~ 0.8 HW^2 u rms(v) -- a ratio of about
+    6000 / HW^1.5, i.e. 0.8 at the 384 pixels per sample of the suite and less above.  That is less than this bound resolves: rows taken
+    before the final rounding would pass or fail by the luck of the signs, and nothing is asserted about that difference.  What the bound
+    does resolve is a row credited to the wrong sample, a missing or doubled block of pixels, and statistics taken before the residual add or
+    the mask (tests/test_cpu_stats_ref.py plants each of them).
+    Returns (sum, sumsq, bound_sum, bound_sumsq), float64 [n, Q] each."""
+    v = stored.double().reshape(n, HW, -1)
+    assert HW <= 4096, "HW u sum|v| stands in for gamma_(HW - 1) sum|v| only while HW <= 4096"
+    assert bool(torch.isfinite(v).all()) and bool((v == v.half().double()).all()), "the stored output must hold finite fp16 values"
+    return v.sum(1), (v * v).sum(1), HW * U32 * v.abs().sum(1), (HW + 2) * U32 * (v * v).sum(1)
+
+
 def attention_ref_bound(q, k, v, scale, causal=False):
     """float64 softmax(scale q k^T) v for q [.., Nq, d], k, v [.., Nk, d] (leading dims = samples x heads) and the bound of the library's
     flash kernels (attention.hip), whose arithmetic is: q' = fp16(q scale log2 e) -- ONE rounding of the pre-scaled query, relative 2^-11
