@@ -356,6 +356,33 @@ int ladi_igemm_cfg_count(void);
  * the launch that produced the output (the last one).  Not thread-safe, like the handles. */
 int ladi_igemm_last_launch(int out[4]);
 const char* ladi_igemm_cfg_symbol_name(int cfg);
+/* Host-only introspection of the tile selection a launch with tile_cfg = 0 makes (ladi_igemm_desc is declared below).  None of these launches
+ * anything or dereferences an operand pointer; only null / non-null is looked at.
+ *   tune_key:       the key the launch would look up, key = {P, Q, K, C0, C1, Wo, flags, batch}; returns 0, or the launch's own argument refusal
+ *                   (-1 .. -6, -18, -19) and leaves key alone.  The launch computes its key with the same function.
+ *   tune_lookup:    the configuration the selection table holds for key (the shipped tune_gfx950.txt, LADI_TUNE_CACHE and this process's
+ *                   measurements, loaded exactly as a launch loads them), 0 = none
+ *   tune_put:       process-local: set the table's entry for key (cfg = 0 erases it); returns the previous value (0 = none), -1 for a bad cfg
+ *   cfg_admissible: 1 if the launcher's admission rule accepts configuration cfg for this launch (strict = 1: as the tuner and a table hit
+ *                   are judged; strict = 0: as the cost model's candidates are), else 0
+ *   last_selection: out = {configuration launched, source} of the last launch made from outside the library: source 0 = tile_cfg given,
+ *                   1 = table, 2 = measured by this launch, 3 = cost model (also after an inadmissible table hit), 4 = the fixed list of
+ *                   X-stationary forms a gn_ss launch falls back to.  The tuner's own timing launches do not overwrite it.
+ *   launch_log:     on = 1 clears the log and starts recording, on = 0 stops (the log stays readable).  While on, every launch made from
+ *                   outside the library (product call sites and ladi_op_igemm alike; not the tuner's timing launches) adds one text line per
+ *                   DISTINCT launch: "name=value" pairs for every integer field of the descriptor, the four batch strides, batch,
+ *                   ops = bit mask of the operands present (1 src1, 2 bias, 4 rowadd, 8 rowadd_idx, 16 res0, 32 res1, 64 mask, 128 stats,
+ *                   256 ln_gamma, 512 ln_scratch, 1024 gn_ss, 2048 bias_mul not in {0, 1}, 4096 out_scale != 1), key = the eight key integers,
+ *                   cfg, src (as last_selection), rc, last = the four ladi_igemm_last_launch values, px = stats_row_px, n = repeat count.
+ *                   No pointer and no value is recorded.  launch_log_read has the calling convention of ladi_profile_igemm_symbols.
+ *   A launch that is refused AFTER its configuration was chosen (rc -2, -7 .. -9, -12 .. -15, -17) counts: last_selection reports its choice,
+ *   the log holds its line with that rc, and ladi_igemm_last_launch reports family 0.  A launch refused for its arguments (the codes tune_key
+ *   returns) has no key and no selection: it is not logged and leaves last_selection alone. */
+int ladi_igemm_tune_lookup(const int key[8]);
+int ladi_igemm_tune_put(const int key[8], int cfg);
+int ladi_igemm_last_selection(int out[2]);
+void ladi_igemm_launch_log(int on);
+int ladi_igemm_launch_log_read(char* buf, int n);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Op-level entry points (kernel parity tests; NHWC fp16 device tensors)
@@ -383,6 +410,8 @@ typedef struct {
          rc -19: out_f32 with an activation, rowadd, res0, res1 or mask: the fp32 store is (acc + bias * bias_mul) * out_scale only. */
 } ladi_igemm_desc;
 int ladi_op_igemm(const ladi_igemm_desc* d, int batch, int tile_cfg, void* stream);
+int ladi_igemm_tune_key(const ladi_igemm_desc* d, int batch, int key[8]);
+int ladi_igemm_cfg_admissible(const ladi_igemm_desc* d, int batch, int cfg, int strict);
 int ladi_op_group_norm(const void* src0, int C0, const void* src1, int C1, int n, int HW, int groups, const void* gamma,
                        const void* beta, float eps, int silu, const void* add, void* out, float* stats_scratch, void* stream);
 /* ladi_op_igemm, and *stats_row_px = pixels per row of the partial statistics the launch wrote into d->stats: [n HW / px][Q][2] floats (sum, sum

@@ -174,6 +174,13 @@ SIGNATURES = {
     "ladi_igemm_cfg_count": (c_int, []),
     "ladi_igemm_last_launch": (c_int, [POINTER(c_int)]),
     "ladi_igemm_cfg_symbol_name": (ctypes.c_char_p, [c_int]),
+    "ladi_igemm_tune_key": (c_int, [POINTER(IGemmDesc), c_int, POINTER(c_int)]),
+    "ladi_igemm_tune_lookup": (c_int, [POINTER(c_int)]),
+    "ladi_igemm_tune_put": (c_int, [POINTER(c_int), c_int]),
+    "ladi_igemm_cfg_admissible": (c_int, [POINTER(IGemmDesc), c_int, c_int, c_int]),
+    "ladi_igemm_last_selection": (c_int, [POINTER(c_int)]),
+    "ladi_igemm_launch_log": (None, [c_int]),
+    "ladi_igemm_launch_log_read": (c_int, [ctypes.c_char_p, c_int]),
     "ladi_op_igemm": (c_int, [POINTER(IGemmDesc), c_int, c_int, _P]),
     "ladi_op_group_norm": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, c_float, c_int, _P, _P, _P, _P]),
     "ladi_op_igemm_stats": (c_int, [POINTER(IGemmDesc), c_int, c_int, POINTER(c_int), _P]),

@@ -723,6 +723,27 @@ int ladi_igemm_last_launch(int out[4]) {
     return 0;
 }
 const char* ladi_igemm_cfg_symbol_name(int cfg) { return ladi_igemm_cfg_symbol(cfg); }
+int ladi_igemm_tune_key(const ladi_igemm_desc* d, int batch, int key[8]) {
+    if (!d || !key) return -100;
+    IGemmArgs a;
+    std::memcpy(&a, d, sizeof(a));
+    return ladi_igemm_key_of(a, batch, key);
+}
+int ladi_igemm_tune_lookup(const int key[8]) { return key ? ladi_igemm_tuned_lookup(key) : 0; }
+int ladi_igemm_tune_put(const int key[8], int cfg) { return key ? ladi_igemm_tuned_put(key, cfg) : -1; }
+int ladi_igemm_cfg_admissible(const ladi_igemm_desc* d, int batch, int cfg, int strict) {
+    if (!d) return 0;
+    IGemmArgs a;
+    std::memcpy(&a, d, sizeof(a));
+    return ladi_igemm_admissible(a, batch, cfg, strict);
+}
+int ladi_igemm_last_selection(int out[2]) {
+    if (!out) return -1;
+    ladi_igemm_selection(out);
+    return 0;
+}
+void ladi_igemm_launch_log(int on) { ladi_igemm_log_enable(on); }
+int ladi_igemm_launch_log_read(char* buf, int n) { return ladi_igemm_log_read(buf, n); }
 
 // ------------------------------------------------------------------------------------------------ op level
 int ladi_op_igemm(const ladi_igemm_desc* d, int batch, int tile_cfg, void* stream) {

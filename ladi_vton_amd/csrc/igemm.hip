@@ -488,10 +488,9 @@ size_t ladi_igemm_splitk_ws_bytes(const IGemmArgs& a, int batch) {
     return need;
 }
 
-int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st, int* stats_row_px, float* ws, size_t ws_bytes, int* sk_cnt) {
-    IGemmArgs a = a_in;
-    const int cfg_in = cfg;
-    if (stats_row_px) *stats_row_px = 0;
+// The argument refusals every launch makes before anything else, and the tune key of the launch: ladi_launch_igemm and the introspection
+// entry point ladi_igemm_key_of share this one function, so a test that asks for a key sees the packing the launch uses.
+static int igemm_tune_key(const IGemmArgs& a, int batch, TuneKey* key) {
     if (a.ksize != 1 && a.ksize != 3 && a.ksize != 4) return -1;   // 4: the stride-2 convs of the TPS matching network
     if ((a.C0 % 32) || (a.C1 % 32)) return -2;
     if (a.K != a.ksize * a.ksize * (a.C0 + a.C1)) return -3;
@@ -505,24 +504,65 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
     // read element 0's), and the fp32 store (igemm_epilogue_generic) applies bias and out_scale only
     if (batch > 1 && (a.src1 || a.C1)) return -18;
     if (a.out_f32 && (a.act != LADI_ACT_NONE || a.rowadd || a.res0 || a.res1 || a.mask)) return -19;
-    // ---- measured tile-shape selection ("measure, don't guess"): the first time a problem shape is seen outside a stream
-    //      capture, every admissible configuration is timed with HIP events on the launch stream and the fastest is cached.
-    //      Re-running a launch is idempotent (outputs never alias inputs in this library).
     // flags also carry the epilogue features that decide which kernels are admissible (residuals, fused statistics, other)
     // (bits 12 / 13 sit ABOVE the ksize field at bits 8..10: at 256 / 512 they were absorbed by ksize = 1 / 3 and a fused-GroupNorm
     // projection shared its entry with the plain 1x1 of the same shape -- ADVICE r04)
     const int epi = ((a.bias_mul != 0.f && a.bias_mul != 1.f) ? (1 << 13) : 0) | (a.gn_ss ? (1 << 12) : 0) | (a.ln_gamma ? 128 : 0) | ((a.res0 || a.res1) ? 2 : 0) | (a.stats ? 8 : 0) |
                     ((a.rowadd || a.mask || a.bias_per_pixel || a.out_f32 || a.out_scale != 1.f || (a.act != LADI_ACT_NONE && !geglu)) ? 64 : 0);
-    TuneKey key{a.P, a.Q, a.K, a.C0, a.C1, a.Wo, (a.ksize << 8) | (a.stride << 4) | (a.ups << 2) | (geglu ? 1 : 0) | epi, batch};
+    *key = TuneKey{a.P, a.Q, a.K, a.C0, a.C1, a.Wo, (a.ksize << 8) | (a.stride << 4) | (a.ups << 2) | (geglu ? 1 : 0) | epi, batch};
+    return 0;
+}
+
+// ---- introspection of the selection path (host only; tests/tuned_cases.py): what the last TOP-LEVEL launch ran and why, and an optional
+//      text log of the distinct top-level launches.  The tuner's own timing launches (g_tuning > 0) touch neither.
+enum { SEL_EXPLICIT = 0, SEL_TABLE = 1, SEL_MEASURED = 2, SEL_COST_MODEL = 3, SEL_GN_LIST = 4 };
+static int g_tuning = 0;
+static int g_last_sel[2] = {0, 0};
+static bool g_log = false;
+static std::vector<std::string> g_log_lines;                 // distinct lines in order of first appearance
+static std::unordered_map<std::string, int> g_log_count;     // line -> index into g_log_lines / repeat count below
+static std::vector<int> g_log_reps;
+static void log_launch(const IGemmArgs& a, int batch, const TuneKey& k, int cfg, int src, int rc, int row_px) {
+    const int ops = (a.src1 ? 1 : 0) | (a.bias ? 2 : 0) | (a.rowadd ? 4 : 0) | (a.rowadd_idx ? 8 : 0) | (a.res0 ? 16 : 0) | (a.res1 ? 32 : 0) | (a.mask ? 64 : 0) |
+                    (a.stats ? 128 : 0) | (a.ln_gamma ? 256 : 0) | (a.ln_scratch ? 512 : 0) | (a.gn_ss ? 1024 : 0) |
+                    ((a.bias_mul != 0.f && a.bias_mul != 1.f) ? 2048 : 0) | (a.out_scale != 1.f ? 4096 : 0);
+    char line[768];
+    snprintf(line, sizeof(line),
+             "C0=%d C1=%d ld0=%d ld1=%d Hs=%d Ws=%d Ho=%d Wo=%d P=%d ksize=%d stride=%d pad=%d ups=%d Q=%d K=%d ldw=%d bias_per_pixel=%d rowadd_stride=%d act=%d "
+             "ldr0=%d ldr1=%d ldo=%d out_f32=%d stats_groups=%d gn_hw=%d bs_src0=%lld bs_w=%lld bs_out=%lld bs_res=%lld batch=%d ops=%d "
+             "key=%d,%d,%d,%d,%d,%d,%d,%d cfg=%d src=%d rc=%d last=%d,%d,%d,%d px=%d",
+             a.C0, a.C1, a.ld0, a.ld1, a.Hs, a.Ws, a.Ho, a.Wo, a.P, a.ksize, a.stride, a.pad, a.ups, a.Q, a.K, a.ldw, a.bias_per_pixel, a.rowadd_stride, a.act,
+             a.ldr0, a.ldr1, a.ldo, a.out_f32, a.stats_groups, a.gn_hw, a.bs_src0, a.bs_w, a.bs_out, a.bs_res, batch, ops,
+             k.P, k.Q, k.K, k.C0, k.C1, k.Wo, k.flags, k.batch, cfg, src, rc, g_last_launch[0], g_last_launch[1], g_last_launch[2], g_last_launch[3], row_px);
+    auto it = g_log_count.find(line);
+    if (it != g_log_count.end()) { ++g_log_reps[it->second]; return; }
+    g_log_count.emplace(line, (int)g_log_lines.size());
+    g_log_lines.emplace_back(line);
+    g_log_reps.push_back(1);
+}
+
+int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st, int* stats_row_px, float* ws, size_t ws_bytes, int* sk_cnt) {
+    IGemmArgs a = a_in;
+    const int cfg_in = cfg;
+    const bool top = g_tuning == 0;
+    int sel = cfg ? SEL_EXPLICIT : SEL_COST_MODEL, row_px = 0;
+    if (stats_row_px) *stats_row_px = 0;
+    TuneKey key;
+    if (const int krc = igemm_tune_key(a, batch, &key)) return krc;
+    const bool geglu = a.act == LADI_ACT_GEGLU;
+    // ---- measured tile-shape selection ("measure, don't guess"): the first time a problem shape is seen outside a stream
+    //      capture, every admissible configuration is timed with HIP events on the launch stream and the fastest is cached.
+    //      Re-running a launch is idempotent (outputs never alias inputs in this library).
     if (cfg == 0 && g_autotune) {
         tune_cache_load();
         auto it = g_tuned.find(key);
-        if (it != g_tuned.end()) cfg = it->second;
+        if (it != g_tuned.end()) { cfg = it->second; sel = SEL_TABLE; }
         else {
             hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
             if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone && !g_prof) {
                 const bool was = g_autotune;
                 g_autotune = false;
+                ++g_tuning;
                 hipEvent_t e0, e1;
                 if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
                     float best_ms = 1e30f; int best_cfg = 0;
@@ -562,13 +602,14 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
                         if (best2_cfg) best_cfg = best2_cfg;
                     }
                     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-                    if (best_cfg) { g_tuned[key] = best_cfg; cfg = best_cfg; tune_cache_append(key, best_cfg); }
+                    if (best_cfg) { g_tuned[key] = best_cfg; cfg = best_cfg; sel = SEL_MEASURED; tune_cache_append(key, best_cfg); }
                 }
+                --g_tuning;
                 g_autotune = was;
             }
         }
     }
-    if (cfg >= 1 && cfg <= NCFG && cfg_in == 0 && !cfg_admissible(a, batch, cfg, true)) cfg = 0;   // stale table entry / key collision: cost model
+    if (cfg >= 1 && cfg <= NCFG && cfg_in == 0 && !cfg_admissible(a, batch, cfg, true)) { cfg = 0; sel = SEL_COST_MODEL; }   // stale table entry / key collision: cost model
     if (cfg == 0) {
         // fallback cost model: (waves of workgroups over the chip) x (tile work) / (per-tile efficiency)
         double best = 1e300;
@@ -587,30 +628,40 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
         }
     }
     if (cfg == 0 && a.gn_ss) {      // no measured selection and the cost model does not rank the X-stationary kernel: first eligible form
-        for (int c : {25, 26, 27, 23, 24, 93, 94, 95}) if (cfg_admissible(a, batch, c, true)) { cfg = c; break; }
+        for (int c : {25, 26, 27, 23, 24, 93, 94, 95}) if (cfg_admissible(a, batch, c, true)) { cfg = c; sel = SEL_GN_LIST; break; }
     }
-    if (cfg < 1 || cfg > NCFG) return -7;
+    // a launch refused after the selection was made launched nothing: it is still the last top-level launch (selection, log line with its rc),
+    // and what it reports as "last launch" is the empty record, not the launch before it
+    auto refused = [&](int rc) {
+        if (top) {
+            g_last_sel[0] = (cfg >= 1 && cfg <= NCFG) ? cfg : 0; g_last_sel[1] = sel;
+            ladi_igemm_note_launch(0, 0, 1, 0);
+            if (g_log) log_launch(a_in, batch, key, g_last_sel[0], sel, rc, 0);
+        }
+        return rc;
+    };
+    if (cfg < 1 || cfg > NCFG) return refused(-7);
     const BaseTrait t = cfg_trait(cfg);
-    if (a.gn_ss && t.family != FAM_XS) return -17;
+    if (a.gn_ss && t.family != FAM_XS) return refused(-17);
     if (a.ln_gamma && t.family != FAM_XS) {   // LayerNorm as its own kernel into the caller's scratch (timed by the tuner as part of cfg)
-        if (!a.ln_scratch || a.C1 || a.src1 || a.ksize != 1 || batch != 1) return -15;
+        if (!a.ln_scratch || a.C1 || a.src1 || a.ksize != 1 || batch != 1) return refused(-15);
         const int lrc = ladi_launch_layernorm(a.src0, a.ld0, a.ln_gamma, a.ln_beta, a.ln_eps, a.P, a.C0, a.ln_scratch, a.C0, st);
-        if (lrc != 0) return -15;
+        if (lrc != 0) return refused(-15);
         a.src0 = a.ln_scratch; a.ld0 = a.C0; a.ln_gamma = nullptr; a.ln_beta = nullptr;
     }
     if (t.family == FAM_XS) {   // X-stationary linear kernel: no fused statistics (the consumer falls back to ladi_launch_gn_partial)
         a.stats = nullptr;
-        if (!ladi_linear_xs_eligible(a, batch, t.tp, t.bq, t.xs_nst)) return -14;
+        if (!ladi_linear_xs_eligible(a, batch, t.tp, t.bq, t.xs_nst)) return refused(-14);
     }
-    if (geglu && !kCfg[cfg].geglu_ok) return -8;
-    if (t.bk == 64 && ((a.C0 % 64) || (a.C1 % 64))) return -2;  // BK = 64 variants
+    if (geglu && !kCfg[cfg].geglu_ok) return refused(-8);
+    if (t.bk == 64 && ((a.C0 % 64) || (a.C1 % 64))) return refused(-2);  // BK = 64 variants
     const int split = kCfg[cfg].split;
     bool sk_inline = false;
     if (split > 1) {
-        if (batch != 1 || geglu || a.out_f32 || a.bias_per_pixel) return -9;
+        if (batch != 1 || geglu || a.out_f32 || a.bias_per_pixel) return refused(-9);
         const size_t need = splitk_cfg_bytes(a, cfg);
         if (!ws || ws_bytes < need) {           // no (or too small a) caller slab: process-wide grow-only fallback
-            if (!ensure_ws(need, st)) return -13;
+            if (!ensure_ws(need, st)) return refused(-13);
             ws = g_ws;
         }
         const long long tiles = (long long)((a.Q + t.bq - 1) / t.bq) * ((a.P + t.bp - 1) / t.bp);
@@ -623,12 +674,12 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
     if (a.stats) {  // fused output statistics need whole 32*TP-pixel row blocks inside one sample
         const int px = ((split > 1 && !sk_inline) ? 1 : t.tp) * 32;
         if (geglu || batch != 1 || a.out_f32 || ((a.Ho * a.Wo) % px)) a.stats = nullptr;
-        else if (stats_row_px) *stats_row_px = px;
+        else { row_px = px; if (stats_row_px) *stats_row_px = px; }
     }
     ProfRec rec;
     const bool prof = g_prof;
     if (prof) {
-        if (hipEventCreate(&rec.e0) != hipSuccess || hipEventCreate(&rec.e1) != hipSuccess) return -12;
+        if (hipEventCreate(&rec.e0) != hipSuccess || hipEventCreate(&rec.e1) != hipSuccess) return refused(-12);
         rec.cfg = cfg; rec.P = a.P; rec.Q = a.Q; rec.K = a.K; rec.ks = a.ksize;
         if (t.family == FAM_XS) ladi_linear_xs_symbol(a, t.tp, t.xs_nst, rec.sym, (int)sizeof(rec.sym));
         else snprintf(rec.sym, sizeof(rec.sym), "%s", cfg_symbol(cfg).c_str());
@@ -648,6 +699,7 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
     const int batch_l = lbatch;
     int rc;
     ladi_igemm_note_launch(t.family == FAM_XS ? FAM_XS : 0, 0, 1, 0);   // the tiled launchers overwrite it where they compute their grid
+    if (top) { g_last_sel[0] = cfg; g_last_sel[1] = sel; }
     rc = launch_base(cfg, a, batch_l, st);
     if (rc == 0 && split > 1 && !sk_inline) {
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((full.P + 31) / 32), (unsigned)((full.Q + 63) / 64)), dim3(256), 0, st, ws, split, full);
@@ -657,7 +709,47 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
     // symbol of the kernel that needed it (rocprofv3 lists splitk_reduce_kernel separately; profiles/README.md shows how to add it back)
     if (prof) { (void)hipEventRecord(rec.e1, st); g_recs.push_back(rec); }
     if (rc != 0 && stats_row_px) *stats_row_px = 0;   // the form's launcher refused: no rows were written, none are reported
+    if (g_log && top) log_launch(a_in, batch, key, cfg, sel, rc, rc == 0 ? row_px : 0);
     return rc;
+}
+
+// ---- host-only introspection (no launch): the key a launch would use, the table, the admission rule, the last selection, the launch log
+int ladi_igemm_key_of(const IGemmArgs& a, int batch, int key[8]) {
+    TuneKey k;
+    if (const int rc = igemm_tune_key(a, batch, &k)) return rc;
+    const int v[8] = {k.P, k.Q, k.K, k.C0, k.C1, k.Wo, k.flags, k.batch};
+    for (int i = 0; i < 8; ++i) key[i] = v[i];
+    return 0;
+}
+int ladi_igemm_tuned_lookup(const int key[8]) {
+    tune_cache_load();
+    auto it = g_tuned.find(TuneKey{key[0], key[1], key[2], key[3], key[4], key[5], key[6], key[7]});
+    return it == g_tuned.end() ? 0 : it->second;
+}
+int ladi_igemm_tuned_put(const int key[8], int cfg) {
+    if (cfg < 0 || cfg > NCFG) return -1;
+    tune_cache_load();
+    const TuneKey k{key[0], key[1], key[2], key[3], key[4], key[5], key[6], key[7]};
+    auto it = g_tuned.find(k);
+    const int prev = it == g_tuned.end() ? 0 : it->second;
+    if (cfg == 0) { if (it != g_tuned.end()) g_tuned.erase(it); }
+    else g_tuned[k] = cfg;
+    return prev;
+}
+int ladi_igemm_admissible(const IGemmArgs& a, int batch, int cfg, int strict) {
+    if (cfg < 1 || cfg > NCFG) return 0;
+    return cfg_admissible(a, batch, cfg, strict != 0) ? 1 : 0;
+}
+void ladi_igemm_selection(int out[2]) { out[0] = g_last_sel[0]; out[1] = g_last_sel[1]; }
+void ladi_igemm_log_enable(int on) {
+    g_log = on != 0;
+    if (g_log) { g_log_lines.clear(); g_log_count.clear(); g_log_reps.clear(); }   // switching on starts a new log; off keeps it readable
+}
+int ladi_igemm_log_read(char* buf, int n) {
+    std::string out;
+    for (size_t i = 0; i < g_log_lines.size(); ++i) out += g_log_lines[i] + " n=" + std::to_string(g_log_reps[i]) + "\n";
+    if (n > 0) { snprintf(buf, (size_t)n, "%s", out.c_str()); }
+    return (int)out.size();
 }
 
 // ---- optional per-launch timing (bench.py roofline leg): HIP events on the launch stream around every igemm launch

@@ -261,6 +261,17 @@ int ladi_igemm_num_cfgs();
 // {kernel family, tile_map, split factor, blocks} of the last implicit-GEMM launch (igemm_common.h ladi_igemm_note_launch)
 void ladi_igemm_last_launch_info(int out[4]);
 const char* ladi_igemm_cfg_symbol(int cfg);
+// host-only introspection of the tile selection path (igemm.hip; none launches anything): the tune key ladi_launch_igemm would use (or its
+// argument refusal code), the selection table (shipped rows + LADI_TUNE_CACHE + process-local puts; cfg 0 erases, returns the previous value),
+// cfg_admissible itself, {cfg, source} of the last top-level launch (0 explicit, 1 table, 2 measured now, 3 cost model, 4 gn_ss list), and the
+// text log of distinct top-level launches
+int ladi_igemm_key_of(const IGemmArgs& a, int batch, int key[8]);
+int ladi_igemm_tuned_lookup(const int key[8]);
+int ladi_igemm_tuned_put(const int key[8], int cfg);
+int ladi_igemm_admissible(const IGemmArgs& a, int batch, int cfg, int strict);
+void ladi_igemm_selection(int out[2]);
+void ladi_igemm_log_enable(int on);
+int ladi_igemm_log_read(char* buf, int n);
 int ladi_igemm_profile_collect(double* out, int n_out);
 // the same records grouped by kernel SYMBOL (exact rocprofv3 name): lines "symbol\tms\tflop\tlaunches\n" into buf (truncated at n); does
 // NOT clear the records (call before ladi_igemm_profile_collect)

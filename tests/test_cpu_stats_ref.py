@@ -40,10 +40,12 @@ def _values(kind):
         return p.stored, p.n, p.HW
     if kind == "positive":                       # all of one sign: nothing cancels, the running sum grows past every term's binade
         return (S.rand((2 * 3072, 16), 790).abs() + 0.25).half().double(), 2, 3072
-    return S.rand((2 * 4096, 8), 791, 30.0).double(), 2, 4096          # the largest HW the helper accepts, large values
+    if kind == "vae":                            # 6144 pixels per sample, all of one sign (a reduced VAE level of tests/test_gpu_tuned.py): above
+        return (S.rand((2 * 6144, 8), 792).abs() + 0.25).half().double(), 2, 6144      # 4096 the helper grants gamma_(HW - 1) itself
+    return S.rand((2 * 4096, 8), 791, 30.0).double(), 2, 4096          # the largest HW for which HW u stands in for gamma_(HW - 1), large values
 
 
-@pytest.mark.parametrize("kind", ["epilogue", "positive", "wide"])
+@pytest.mark.parametrize("kind", ["epilogue", "positive", "wide", "vae"])
 @pytest.mark.parametrize("order", sorted(ORDERS))
 def test_bound_holds_for_fp32_summation_orders(order, kind):
     stored, n, HW = _values(kind)
@@ -65,6 +67,26 @@ def test_bound_is_tight_enough_to_see_one_missing_pixel():
     px = int(p.stored[:p.HW].abs().sum(1).argmax())
     drop = p.stored[px] ** 2
     assert int((drop > bsq[0]).sum()) > p.Q // 2, int((drop > bsq[0]).sum())
+
+
+def test_judge_on_samples_above_4096_pixels():
+    """HW = 6144 in rows of 256 pixels (the gamma branch of stats_rows_ref_bound): faithful rows pass; a row credited to the other sample, a
+    block of pixels counted twice and one missing pixel fail"""
+    stored, n, HW = _values("vae")
+    px = 256
+    rows = S.block_rows(stored, n, HW, px)
+    cap = (n * HW + 31) // 32
+    assert S.judge_rows(S.rows_buffer(rows, 4, device="cpu", cap=cap), px, stored, n, HW, "faithful") < 1.0
+    rps = HW // px
+    swapped = rows.clone()
+    swapped[[rps - 1, rps]] = rows[[rps, rps - 1]]
+    doubled = rows.clone()
+    doubled[3] = rows[3] + S.block_rows(stored[3 * px:3 * px + 32], 1, 32, 32)[0]
+    missing = rows.clone()
+    missing[rps + 1] = S.block_rows(torch.cat([stored[(rps + 1) * px:(rps + 2) * px - 1], torch.zeros(1, stored.shape[1]).double()]), 1, px, px)[0]
+    for name, bad in (("row in the other sample", swapped), ("32 pixels twice", doubled), ("one pixel missing", missing)):
+        with pytest.raises(AssertionError):
+            S.judge_rows(S.rows_buffer(bad, 4, device="cpu", cap=cap), px, stored, n, HW, name)
 
 
 def test_judge_accepts_the_faithful_producer():
