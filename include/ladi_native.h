@@ -228,6 +228,17 @@ int ladi_sched_table(int kind, int num_inference_steps, const float* alphas_cump
  * non-zero eta with any kind but DDIM is an error (the other schedulers' step() takes no eta). */
 int ladi_sched_table_eta(int kind, int num_inference_steps, const float* alphas_cumprod_host, float eta, double* timesteps_out, float* rows_out,
                          int cap);
+/* the table of a run that starts at step first_step of the num_inference_steps-step schedule (strength; ladi_tryon_set_init): the evaluations of
+ * steps first_step .. with the timesteps and sigmas of those steps, indexed from 0, same row layout.  Multistep history starts empty at the new
+ * start: LMSDiscrete and DPMSolverMultistep warm up again (orders 1, 2, ..), lower_order_final acts where it does in the whole run.  PNDM
+ * restarts as a fresh PLMS run over the tail's step timesteps u0 > u1 > ..: evaluations [u0, u1, u1, u2, ..], one more than tail steps -- NOT
+ * diffusers' slice of the N + 1 list, which leaves the sample one step under-denoised; a PNDM tail needs 2 steps (first_step <= N - 2), the
+ * others 1 (first_step <= N - 1).  start_out (may be null) = {k_x, k_n, in_scale0}: the start latents are k_x * init + k_n * noise (DDIM / PNDM /
+ * DPMSolverMultistep: sqrt(a_t), sqrt(1 - a_t) at t = timesteps[first_step]; LMS / Euler / Euler-ancestral: 1, sigma[first_step]; computed in
+ * double), in_scale0 the scale_model_input of the first evaluation.  first_step = 0 gives ladi_sched_table_eta's rows and timesteps bit for bit
+ * and start_out = {0, init_noise_sigma, in_scale0}.  A first_step out of range is an error. */
+int ladi_sched_table_from(int kind, int num_inference_steps, const float* alphas_cumprod_host, float eta, int first_step, double* timesteps_out,
+                          float* rows_out, int cap, float* start_out);
 /* host helper, LMSDiscrete (order 4): timesteps_out[N] (fractional, float64 as diffusers holds them), sigmas_out[N + 1] (trailing 0;
  * init_noise_sigma = sigmas_out[0]), coeffs_out[N][4] = linear-multistep weights of evaluation i over its derivatives
  * [d_i, d_{i-1}, d_{i-2}, d_{i-3}] (zero beyond the order min(i + 1, 4)).  alphas_cumprod_host null = default.  Any output may be null. */
@@ -284,6 +295,18 @@ int ladi_tryon_set_trace(ladi_tryon* t, float* eps_trace_dev, float* latents_tra
  * so the captured graph never reads the caller's buffer (which, like the run's other inputs, must stay valid until the run's work on the stream
  * has started); such a run with no noise, or fewer steps than evaluations, fails.  Runs without a stochastic term ignore it.  NULL = off. */
 int ladi_tryon_set_step_noise(ladi_tryon* t, const float* noise_dev, int steps);
+/* start the following runs from given latents at step first_step of the schedule instead of from noise at step 0 (strength; sticky per handle):
+ * init_latents_dev fp32 [B][4][hs][ws] on the device, in the loop's latent space (x scaling_factor), e.g. the latents_dev of an earlier run.
+ * The run has the evaluations of ladi_sched_table_from(first_step), and everything indexed per evaluation refers to them: the guidance
+ * schedule's count, the step callback's index, the trace and the step-noise steps; in->cloth_zero_from_eval too.  Its start latents are
+ * k_x * resample(init) + k_n * noise_latents_dev (start_out of ladi_sched_table_from; init_noise_sigma is not applied), resampled to the run's
+ * [h][w] like F.interpolate(mode="bilinear", align_corners=False) when (hs, ws) != (h, w) and copied exactly otherwise.  noisy != 0: the init is
+ * taken as the loop's latents at timesteps[first_step] unchanged (k_x = 1, k_n = 0, the noise is not read) -- resuming from latents a step
+ * callback exported.  The init is read once per run, on the run's stream before the loop, never by the captured graph; it must stay valid like
+ * the run's other inputs.  NULL or first_step == 0 switches it off (the run is then the plain one, bit for bit).  A first_step out of range for
+ * the run's scheduler and step count, or a guidance schedule / step-noise count that does not match the tail, fails the run before anything is
+ * launched; hs or ws < 1 or first_step < 0 is refused here. */
+int ladi_tryon_set_init(ladi_tryon* t, const float* init_latents_dev, int hs, int ws, int first_step, int noisy);
 /* DDIMScheduler.step's eta for the following runs (sticky per handle, default 0): > 0 adds the stochastic term std * noise[i], which needs
  * ladi_tryon_set_step_noise.  Only DDIM reads it: a run of any other scheduler with a non-zero eta fails.  eta < 0 or non-finite: error. */
 int ladi_tryon_set_eta(ladi_tryon* t, float eta);
@@ -563,6 +586,10 @@ int ladi_op_image_post(const void* src, int ld, int n_pix, void* dst, int dst_u8
 int ladi_op_post_quant(const float* lat, const float* pq, float inv_sf, int n, void* dst, int ld, void* stream);   /* pq [16 w | 4 b] or NULL; channels [4, ld) zero */
 int ladi_op_lat_nchw_to_pix(const float* src, int B, int hw, float scale, float* dst, void* stream);
 int ladi_op_lat_pix_to_nchw(const float* src, int B, int hw, float* dst, void* stream);
+/* start latents (ladi_tryon_set_init): out fp32 [B][h*w][4] = k_x * resample(init fp32 [B][4][hs][ws]) + k_n * noise fp32 [B][4][h][w]; bilinear,
+ * source coordinate max((o + 0.5) * in / out - 0.5, 0), no antialias; equal sizes: k_x * init + k_n * noise without interpolation arithmetic.
+ * noise may be NULL when k_n == 0 (it is never read then).  A null init / out, a size < 1 or a null noise with k_n != 0 is an error. */
+int ladi_op_init_latents(const float* init, int hs, int ws, const float* noise, int B, int h, int w, float k_x, float k_n, float* out, void* stream);
 /* src fp32 NCHW [B][4][hw] -> latents [B][hw][4] and channels 0-3 of unet_in rows ([B], with cfg [2B]; ld_in >= 4, a multiple of 4) = fp16(x in_scale) */
 int ladi_op_latents_import(const float* src, int B, int hw, float* latents, void* unet_in, int ld_in, int cfg, float in_scale, void* stream);
 int ladi_op_scale_h16(const void* src, int lds, void* dst, int ldd, long long n_pix, int C, float s, void* stream);

@@ -137,6 +137,7 @@ SIGNATURES = {
     "ladi_sched_lms": (c_int, [c_int, _P, _P, _P, _P]),
     "ladi_sched_table": (c_int, [c_int, c_int, _P, _P, _P, c_int]),
     "ladi_sched_table_eta": (c_int, [c_int, c_int, _P, c_float, _P, _P, c_int]),
+    "ladi_sched_table_from": (c_int, [c_int, c_int, _P, c_float, c_int, _P, _P, c_int, POINTER(c_float)]),
     "ladi_sched_alphas_cumprod": (c_int, [POINTER(c_float)]),
     "ladi_tryon_create": (_P, [_P, _P, _P]),
     "ladi_tryon_destroy": (None, [_P]),
@@ -146,6 +147,7 @@ SIGNATURES = {
     "ladi_tryon_poll_overflow": (c_int, [_P]),
     "ladi_tryon_set_trace": (c_int, [_P, _P, _P, c_int]),
     "ladi_tryon_set_step_noise": (c_int, [_P, _P, c_int]),
+    "ladi_tryon_set_init": (c_int, [_P, _P, c_int, c_int, c_int, c_int]),
     "ladi_tryon_set_eta": (c_int, [_P, c_float]),
     "ladi_tryon_set_guidance_schedule": (c_int, [_P, POINTER(c_float), c_int]),
     "ladi_tryon_set_guidance_rescale": (c_int, [_P, c_float]),
@@ -240,6 +242,7 @@ SIGNATURES = {
     "ladi_op_post_quant": (c_int, [_P, _P, c_float, c_int, _P, c_int, _P]),
     "ladi_op_lat_nchw_to_pix": (c_int, [_P, c_int, c_int, c_float, _P, _P]),
     "ladi_op_lat_pix_to_nchw": (c_int, [_P, c_int, c_int, _P, _P]),
+    "ladi_op_init_latents": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_float, _P, _P]),
     "ladi_op_latents_import": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_float, _P]),
     "ladi_op_scale_h16": (c_int, [_P, c_int, _P, c_int, c_longlong, c_int, c_float, _P]),
     "ladi_op_fill_f32": (c_int, [_P, c_longlong, c_float, _P]),

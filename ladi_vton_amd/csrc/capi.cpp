@@ -533,13 +533,14 @@ int ladi_sched_lms(int steps, const float* ac_host, double* timesteps_out, float
     });
 }
 static int sched_table_any(const char* name, int code, int steps, const float* ac_host, double* timesteps_out, float* rows_out, int cap,
-                           float eta) {
+                           float eta, int first_step = 0, float* start_out = nullptr) {
     return guarded(name, [&]() {
         std::vector<float> ac;
         if (ac_host) ac.assign(ac_host, ac_host + 1000); else default_alphas_cumprod(ac);
-        std::vector<double> ts; std::vector<StepTable> tb;
-        build_step_table(code, steps, ac.data(), 1 << 30, ts, tb, nullptr, eta);
+        std::vector<double> ts; std::vector<StepTable> tb; SchedInfo info;
+        build_step_table(code, steps, ac.data(), 1 << 30, ts, tb, &info, eta, first_step);
         if ((int)tb.size() > cap) throw std::runtime_error("table buffer too small");
+        if (start_out) { start_out[0] = info.start_kx; start_out[1] = info.start_kn; start_out[2] = info.in_scale0; }
         for (size_t i = 0; i < tb.size(); ++i) {
             const StepTable& e = tb[i];
             const float row[10] = {e.c_x, e.c_e, e.w[0], e.w[1], e.w[2], e.w[3], e.p_x, e.p_e, e.c_n, e.in_scale_next};
@@ -554,6 +555,10 @@ int ladi_sched_table(int code, int steps, const float* ac_host, double* timestep
 }
 int ladi_sched_table_eta(int code, int steps, const float* ac_host, float eta, double* timesteps_out, float* rows_out, int cap) {
     return sched_table_any("ladi_sched_table_eta", code, steps, ac_host, timesteps_out, rows_out, cap, eta);
+}
+int ladi_sched_table_from(int code, int steps, const float* ac_host, float eta, int first_step, double* timesteps_out, float* rows_out, int cap,
+                          float* start_out) {
+    return sched_table_any("ladi_sched_table_from", code, steps, ac_host, timesteps_out, rows_out, cap, eta, first_step, start_out);
 }
 int ladi_sched_alphas_cumprod(float* out) {
     std::vector<float> ac; default_alphas_cumprod(ac);
@@ -610,6 +615,20 @@ int ladi_tryon_lanes(ladi_tryon* t) { return t ? t->t.lanes.G : -1; }
 int ladi_tryon_set_step_noise(ladi_tryon* t, const float* noise_dev, int steps) {
     if (!t || steps < 0) { set_error("ladi_tryon_set_step_noise: null handle or negative steps"); return -1; }
     t->t.step_noise_src = noise_dev; t->t.step_noise_steps = noise_dev ? steps : 0;
+    return 0;
+}
+int ladi_tryon_set_init(ladi_tryon* t, const float* init_latents_dev, int hs, int ws, int first_step, int noisy) {
+    if (!t) { set_error("ladi_tryon_set_init: null handle"); return -1; }
+    if (first_step < 0) { set_error("ladi_tryon_set_init: first_step " + std::to_string(first_step) + " is negative"); return -1; }
+    if (!init_latents_dev || first_step == 0) {
+        t->t.init_src = nullptr; t->t.init_hs = t->t.init_ws = t->t.init_first = t->t.init_noisy = 0;
+        return 0;
+    }
+    if (hs < 1 || ws < 1 || hs > 8192 || ws > 8192) {
+        set_error("ladi_tryon_set_init: init latents of size " + std::to_string(hs) + " x " + std::to_string(ws) + " (each side has to be in [1, 8192])");
+        return -1;
+    }
+    t->t.init_src = init_latents_dev; t->t.init_hs = hs; t->t.init_ws = ws; t->t.init_first = first_step; t->t.init_noisy = noisy ? 1 : 0;
     return 0;
 }
 int ladi_tryon_set_eta(ladi_tryon* t, float eta) {
@@ -1001,6 +1020,16 @@ int ladi_op_post_quant(const float* lat, const float* pq, float inv_sf, int n, v
 }
 int ladi_op_lat_nchw_to_pix(const float* src, int B, int hw, float scale, float* dst, void* stream) {
     return ladi_launch_lat_nchw_to_pix(src, B, hw, scale, dst, S(stream));
+}
+int ladi_op_init_latents(const float* init, int hs, int ws, const float* noise, int B, int h, int w, float k_x, float k_n, float* out, void* stream) {
+    return guarded("ladi_op_init_latents", [&]() {
+        if (!init || !out) throw std::runtime_error("null init or out");
+        if (hs < 1 || ws < 1 || B < 1 || h < 1 || w < 1) throw std::runtime_error("every size has to be >= 1");
+        if (!noise && k_n != 0.f) throw std::runtime_error("null noise with k_n != 0");
+        const int rc = ladi_launch_init_latents(init, hs, ws, noise, B, h, w, k_x, k_n, out, S(stream));
+        if (rc) throw std::runtime_error("launch refused (sizes too large) or failed");
+        return 0;
+    });
 }
 int ladi_op_lat_pix_to_nchw(const float* src, int B, int hw, float* dst, void* stream) { return ladi_launch_lat_pix_to_nchw(src, B, hw, dst, S(stream)); }
 int ladi_op_latents_import(const float* src, int B, int hw, float* latents, void* unet_in, int ld_in, int cfg, float in_scale, void* stream) {

@@ -416,6 +416,47 @@ __global__ void lat_pix_to_nchw_kernel(const float* __restrict__ src, int B, int
     for (int c = 0; c < 4; ++c) dst[((size_t)b * 4 + c) * hw + p] = src[(size_t)idx * 4 + c];
 }
 
+// start latents of a run that begins at an intermediate step (strength): dst [B][hw][4] = k_x * resample(init) + k_n * noise, init fp32 NCHW
+// [B][4][hs][ws], noise fp32 NCHW [B][4][h][w].  The resample is F.interpolate(mode="bilinear", align_corners=False) without antialias in
+// fp32: source coordinate max((o + 0.5) * in / out - 0.5, 0), the upper neighbour clamped to the last row / column.  Equal sizes read the
+// sample itself (no interpolation arithmetic); k_n == 0 never touches `noise` (it may be null).  One thread per output pixel, one float4 store.
+__global__ __launch_bounds__(256) void init_latents_kernel(const float* __restrict__ init, int hs, int ws, const float* __restrict__ noise,
+                                                           int B, int h, int w, float kx, float kn, float* __restrict__ dst) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int hw = h * w;
+    if (idx >= B * hw) return;
+    const int b = idx / hw, p = idx - b * hw;
+    float v[4];
+    if (hs == h && ws == w) {
+        const float* s = init + (size_t)b * 4 * hw + p;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] = s[(size_t)c * hw];
+    } else {
+        const int oy = p / w, ox = p - oy * w;
+        const float sy = fmaxf(((float)oy + 0.5f) * ((float)hs / (float)h) - 0.5f, 0.f);
+        const float sx = fmaxf(((float)ox + 0.5f) * ((float)ws / (float)w) - 0.5f, 0.f);
+        const int y0 = min((int)sy, hs - 1), x0 = min((int)sx, ws - 1);
+        const int y1 = min(y0 + 1, hs - 1), x1 = min(x0 + 1, ws - 1);
+        const float ly = sy - (float)y0, lx = sx - (float)x0;
+        const float hy = 1.f - ly, hx = 1.f - lx;
+        const size_t plane = (size_t)hs * ws;
+        const float* s = init + (size_t)b * 4 * plane;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float* q = s + (size_t)c * plane;
+            v[c] = hy * (hx * q[(size_t)y0 * ws + x0] + lx * q[(size_t)y0 * ws + x1]) +
+                   ly * (hx * q[(size_t)y1 * ws + x0] + lx * q[(size_t)y1 * ws + x1]);
+        }
+    }
+    float4 o = make_float4(kx * v[0], kx * v[1], kx * v[2], kx * v[3]);
+    if (kn != 0.f) {
+        const float* nz = noise + (size_t)b * 4 * hw + p;
+        o.x += kn * nz[0]; o.y += kn * nz[hw];
+        o.z += kn * nz[2 * (size_t)hw]; o.w += kn * nz[3 * (size_t)hw];
+    }
+    reinterpret_cast<float4*>(dst)[idx] = o;
+}
+
 // step-callback import: the (possibly edited) NCHW latents back into the loop, and the next evaluation's UNet input refreshed from them exactly
 // as sched_step_body refreshes it (same scale, same fp16 rounding, uncond and cond rows), so an untouched round trip changes no bit
 __global__ __launch_bounds__(256) void latents_import_kernel(const float* __restrict__ src, int B, int hw, float* __restrict__ latents,
@@ -785,6 +826,14 @@ int ladi_launch_lat_nchw_to_pix(const float* src, int B, int hw, float scale, fl
 }
 int ladi_launch_lat_pix_to_nchw(const float* src, int B, int hw, float* dst, hipStream_t st) {
     hipLaunchKernelGGL(lat_pix_to_nchw_kernel, dim3((B * hw + 255) / 256), dim3(256), 0, st, src, B, hw, dst);
+    return ok();
+}
+int ladi_launch_init_latents(const float* init, int hs, int ws, const float* noise, int B, int h, int w, float k_x, float k_n, float* dst,
+                             hipStream_t st) {
+    if (!init || !dst || hs < 1 || ws < 1 || B < 1 || h < 1 || w < 1) return -1;
+    if (!noise && k_n != 0.f) return -1;
+    if ((long long)B * h * w > (1LL << 29) || (long long)hs * ws > (1LL << 29)) return -1;      // int pixel indices
+    hipLaunchKernelGGL(init_latents_kernel, dim3((B * h * w + 255) / 256), dim3(256), 0, st, init, hs, ws, noise, B, h, w, k_x, k_n, dst);
     return ok();
 }
 int ladi_launch_latents_import(const float* src, int B, int hw, float* latents, h16* unet_in, int ld_in, int cfg, float in_scale, hipStream_t st) {

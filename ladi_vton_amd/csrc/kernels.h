@@ -219,6 +219,11 @@ int ladi_launch_gather_rows(const h16* src, const int* rows, int n, int H, h16* 
 int ladi_launch_post_quant(const float* lat, const float* pq, float inv_sf, int n, h16* dst, int ld, hipStream_t st);
 int ladi_launch_lat_nchw_to_pix(const float* src, int B, int hw, float scale, float* dst, hipStream_t st);
 int ladi_launch_lat_pix_to_nchw(const float* src, int B, int hw, float* dst, hipStream_t st);
+// start latents of a run that begins at an intermediate step: dst [B][h*w][4] = k_x * resample(init [B][4][hs][ws]) + k_n * noise [B][4][h][w]
+// (fp32; bilinear, align_corners = False, no antialias; equal sizes: the samples themselves).  noise may be null when k_n == 0.  Returns -1
+// for a null init / dst, a size < 1, or a null noise with k_n != 0
+int ladi_launch_init_latents(const float* init, int hs, int ws, const float* noise, int B, int h, int w, float k_x, float k_n, float* dst,
+                             hipStream_t st);
 // step-callback import: fp32 NCHW [B][4][hw] src -> the loop's latents [B][hw][4], and the latent channels 0-3 of the next UNet input
 // (rows [B] or, with cfg, [2B], ld_in halves per row) rewritten as fp16(x * in_scale) -- what sched_step_kernel wrote from the unedited x
 int ladi_launch_latents_import(const float* src, int B, int hw, float* latents, h16* unet_in, int ld_in, int cfg, float in_scale, hipStream_t st);

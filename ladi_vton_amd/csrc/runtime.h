@@ -462,6 +462,10 @@ struct TryOn {
     const float* step_noise_src = nullptr; int step_noise_steps = 0;
     float* step_noise_buf = nullptr; size_t step_noise_cap = 0;
     float eta = 0.f;   // DDIM's eta (ladi_tryon_set_eta), sticky; other kinds refuse a non-zero one
+    // start from given latents at step init_first of the schedule (ladi_tryon_set_init, sticky; null or init_first = 0: off): the caller's fp32
+    // NCHW [B][4][init_hs][init_ws], read once by init_latents_kernel on the run's stream before the loop (never inside the captured graph),
+    // which resamples it to the run's latent size and mixes it with noise_latents (init_noisy: taken as the loop's latents unchanged)
+    const float* init_src = nullptr; int init_hs = 0, init_ws = 0, init_first = 0, init_noisy = 0;
     // per-evaluation guidance (ladi_tryon_set_guidance_schedule, sticky; empty = in.guidance for every evaluation) and guidance rescale phi
     // (ladi_tryon_set_guidance_rescale).  A run is CFG-shaped (2B rows, both contexts) if any scale is > 1; inside such a run an evaluation
     // whose scale is <= 1 runs the UNet over the conditional samples [B, 2B) only.  With a schedule or phi > 0 the scales come from the
@@ -495,14 +499,23 @@ SchedCode decode_sched_code(int code);
 void default_alphas_cumprod(std::vector<float>& ac);
 struct SchedInfo {
     float init_noise_sigma = 1.f;    // prepare_latents: latents = noise * init_noise_sigma (tryon_pipe.py:424)
-    float in_scale0 = 1.f;           // scale_model_input of evaluation 0 (later evaluations: StepTable::in_scale_next)
-    std::vector<float> sigmas;       // LMS / Euler / Euler-ancestral: steps + 1 values (trailing 0)
-    std::vector<float> lms_coeffs;   // LMS only: [steps][4], c_ij over [d_i, d_{i-1}, d_{i-2}, d_{i-3}]
+    float in_scale0 = 1.f;           // scale_model_input of the run's first evaluation (later evaluations: StepTable::in_scale_next)
+    std::vector<float> sigmas;       // LMS / Euler / Euler-ancestral: steps + 1 values (trailing 0), the whole schedule whatever first_step
+    std::vector<float> lms_coeffs;   // LMS only: [steps][4], c_ij over [d_i, d_{i-1}, d_{i-2}, d_{i-3}] (rows before first_step stay 0)
+    // start latents of a run that begins at step first_step > 0: x = start_kx * init + start_kn * noise (double arithmetic, held in fp32).
+    // DDIM / PNDM / DPM-Solver++: sqrt(a_t), sqrt(1 - a_t) at t = timesteps[first_step]; LMS / Euler / Euler-ancestral: 1, sigma[first_step].
+    // first_step = 0: {0, init_noise_sigma}, i.e. today's latents = noise * init_noise_sigma
+    float start_kx = 0.f, start_kn = 1.f;
 };
 // cloth_zero_from: first evaluation index that must see zero cloth latents (tryon_pipe.py:718), computed by the caller in float64;
-// code: the scheduler code above; eta: DDIMScheduler.step's eta (DDIM only, >= 0; > 0 puts the stochastic term into c_n)
+// code: the scheduler code above; eta: DDIMScheduler.step's eta (DDIM only, >= 0; > 0 puts the stochastic term into c_n).
+// first_step > 0 builds the tail of the `steps`-step schedule (strength): the evaluations of steps first_step .. with their own timesteps and
+// sigmas, indexed from 0 (cloth_zero_from too).  Multistep history starts empty there: LMS and DPM-Solver++ warm up again (orders 1, 2, ..),
+// lower_order_final acts where it does in the whole run, and PNDM restarts as a fresh PLMS run over the tail's step timesteps u0 > u1 > ..
+// (evaluations [u0, u1, u1, u2, ..]: tail steps + 1; not diffusers' slice of the N + 1 list, which leaves the sample one step
+// under-denoised).  first_step <= steps - 1 (PNDM: steps - 2); first_step = 0 gives the whole run's tables bit for bit.
 void build_step_table(int code, int steps, const float* alphas_cumprod, int cloth_zero_from, std::vector<double>& timesteps,
-                      std::vector<StepTable>& table, SchedInfo* info = nullptr, double eta = 0.0);
+                      std::vector<StepTable>& table, SchedInfo* info = nullptr, double eta = 0.0, int first_step = 0);
 // true if the table has a stochastic term (some c_n != 0: Euler-ancestral, DDIM with eta > 0), i.e. a run of it needs step noise
 bool table_needs_step_noise(const std::vector<StepTable>& table);
 

@@ -513,11 +513,16 @@ static std::vector<int> dpm_timesteps(int steps) {
 }
 
 void build_step_table(int code, int steps, const float* ac, int cloth_zero_from, std::vector<double>& timesteps,
-                      std::vector<StepTable>& table, SchedInfo* info, double eta) {
+                      std::vector<StepTable>& table, SchedInfo* info, double eta, int first_step) {
     const int T = 1000;
     if (steps < 2 || steps > T) throw std::runtime_error("num_inference_steps out of range [2, 1000]");   // ts[steps - 2] below
     const SchedCode sc = decode_sched_code(code);
     const int kind = sc.kind;
+    // a tail needs one step, a PNDM tail two (its second evaluation averages with the first)
+    const int max_first = kind == SCHED_PNDM ? steps - 2 : steps - 1;
+    if (first_step < 0 || first_step > max_first)
+        throw std::runtime_error("first_step " + std::to_string(first_step) + " out of range [0, " + std::to_string(max_first) + "] for " +
+                                 std::to_string(steps) + " steps" + (kind == SCHED_PNDM ? " (a PNDM tail needs at least 2 steps)" : ""));
     if (!(eta >= 0.0) || !std::isfinite(eta)) throw std::runtime_error("eta must be finite and >= 0, got " + std::to_string(eta));
     // only DDIMScheduler.step takes eta; the other schedulers ignore it, and a table that silently did the same would diverge from the caller's intent
     if (eta != 0.0 && kind != SCHED_DDIM) throw std::runtime_error("eta > 0 is DDIM only (scheduler kind " + std::to_string(kind) + ")");
@@ -533,16 +538,18 @@ void build_step_table(int code, int steps, const float* ac, int cloth_zero_from,
         for (float s : sig) smax = std::max(smax, s);
         if (info) {
             info->init_noise_sigma = smax;
-            info->in_scale0 = (float)(1.0 / std::sqrt((double)sig[0] * (double)sig[0] + 1.0));
+            info->in_scale0 = (float)(1.0 / std::sqrt((double)sig[first_step] * (double)sig[first_step] + 1.0));
             info->sigmas = sig;
+            info->start_kx = first_step ? 1.f : 0.f;
+            info->start_kn = first_step ? sig[first_step] : smax;
         }
     }
     if (kind == SCHED_LMS) {
         // diffusers 0.14 LMSDiscreteScheduler.step (order 4, epsilon prediction): derivative d_i = (x - (x - sigma_i eps)) / sigma_i = eps
         std::vector<float> coeffs((size_t)steps * 4, 0.f);
-        for (int i = 0; i < steps; ++i) {
+        for (int i = first_step; i < steps; ++i) {
             StepTable e; std::memset(&e, 0, sizeof(e));
-            const int order = std::min(i + 1, 4);
+            const int order = std::min(i - first_step + 1, 4);      // the derivatives this run has seen
             double nodes[4];
             for (int k = 0; k < order; ++k) nodes[k] = (double)sig[i - k];
             for (int j = 0; j < order; ++j) {
@@ -560,7 +567,7 @@ void build_step_table(int code, int steps, const float* ac, int cloth_zero_from,
         // diffusers 0.14 EulerDiscreteScheduler.step (s_churn = 0): x + (sigma_{i+1} - sigma_i) * eps; EulerAncestralDiscreteScheduler.step:
         // x + (sigma_down - sigma_i) * eps + sigma_up * noise_i, sigma_up = sqrt(s_to^2 (s_from^2 - s_to^2) / s_from^2),
         // sigma_down = sqrt(s_to^2 - sigma_up^2)
-        for (int i = 0; i < steps; ++i) {
+        for (int i = first_step; i < steps; ++i) {
             StepTable e; std::memset(&e, 0, sizeof(e));
             const double s0 = sig[i], s1 = sig[i + 1];
             e.c_x = 1.f; e.w[0] = 1.f;
@@ -582,11 +589,11 @@ void build_step_table(int code, int steps, const float* ac, int cloth_zero_from,
         auto sigma = [&](int t) { return std::sqrt(1.0 - (double)ac[t]); };
         auto lambda = [&](int t) { return std::log(alpha(t)) - std::log(sigma(t)); };
         const bool lof = sc.lower_order_final && steps < 15;
-        for (int i = 0; i < steps; ++i) {
-            timesteps.push_back(ts[i]);
+        for (int t : ts) timesteps.push_back(t);
+        for (int i = first_step; i < steps; ++i) {
             const int s0 = ts[i], t = i == steps - 1 ? 0 : ts[i + 1];
-            // warm-up: first order at step 0, at most second at step 1; lower_order_final: first order last, at most second before it
-            int order = std::min(sc.order, i + 1);
+            // warm-up: first order at the run's first step, at most second at its second; lower_order_final: first order last, at most second before it
+            int order = std::min(sc.order, i - first_step + 1);
             if (lof && i == steps - 1) order = 1;
             if (lof && i == steps - 2) order = std::min(order, 2);
             const double a_t = alpha(t), h = lambda(t) - lambda(s0);
@@ -620,7 +627,7 @@ void build_step_table(int code, int steps, const float* ac, int cloth_zero_from,
         }
     } else if (kind == 0) {
         for (int i = steps - 1; i >= 0; --i) timesteps.push_back(i * ratio + 1);
-        for (int i = 0; i < steps; ++i) {
+        for (int i = first_step; i < steps; ++i) {
             const int t = (int)timesteps[i], tp = t - ratio;
             const double a_t = ac[t], a_p = tp >= 0 ? (double)ac[tp] : final_ac;
             StepTable e; std::memset(&e, 0, sizeof(e));
@@ -637,12 +644,14 @@ void build_step_table(int code, int steps, const float* ac, int cloth_zero_from,
             table.push_back(e);
         }
     } else {
+        // a tail is a fresh PLMS run over the lowest steps - first_step step timesteps (spacing `ratio` of the whole schedule)
+        const int n = steps - first_step;
         std::vector<int> ts;
-        for (int i = 0; i < steps; ++i) ts.push_back(i * ratio + 1);
+        for (int i = 0; i < n; ++i) ts.push_back(i * ratio + 1);
         // concat(_ts[:-1], _ts[-2:-1], _ts[-1:])[::-1]
         std::vector<int> seq(ts.begin(), ts.end() - 1);
-        seq.push_back(ts[steps - 2]);
-        seq.push_back(ts[steps - 1]);
+        seq.push_back(ts[n - 2]);
+        seq.push_back(ts[n - 1]);
         for (int i = (int)seq.size() - 1; i >= 0; --i) timesteps.push_back(seq[i]);
         int npush = 0;  // number of pushes so far
         for (int i = 0; i < (int)timesteps.size(); ++i) {
@@ -676,6 +685,11 @@ void build_step_table(int code, int steps, const float* ac, int cloth_zero_from,
         }
     }
     if (!sigma_kind) for (auto& e : table) e.in_scale_next = 1.f;
+    if (kind != SCHED_PNDM) timesteps.erase(timesteps.begin(), timesteps.begin() + first_step);     // (PNDM built the tail's own list)
+    if (info && !sigma_kind && first_step) {
+        const double a = ac[(int)timesteps[0]];
+        info->start_kx = (float)std::sqrt(a); info->start_kn = (float)std::sqrt(1.0 - a);
+    }
     // `if i >= num_inference_steps - cloth_conditioning_steps: cloth = 0` (tryon_pipe.py:718-719), evaluated at the
     // START of evaluation i -> mark entry i-1 so that the step kernel zeroes the cloth channels for evaluation i.
     for (int i = 1; i < (int)table.size(); ++i)

@@ -80,11 +80,14 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
     std::vector<float> ac;
     if (in.alphas_cumprod) ac.assign(in.alphas_cumprod, in.alphas_cumprod + 1000); else default_alphas_cumprod(ac);
     std::vector<double> timesteps; std::vector<StepTable> table; SchedInfo sinfo;
-    build_step_table(in.scheduler, in.steps, ac.data(), in.cloth_zero_from, timesteps, table, &sinfo, eta);
+    // a set init (ladi_tryon_set_init) starts the run at step first_step of the schedule: the tables below are the tail's, indexed from 0
+    const int first_step = (init_src && init_first > 0) ? init_first : 0;
+    build_step_table(in.scheduler, in.steps, ac.data(), in.cloth_zero_from, timesteps, table, &sinfo, eta, first_step);
     const int evals = (int)timesteps.size();
     if (has_sched && (int)g_sched.size() != evals) {
         set_error("tryon: the guidance schedule has " + std::to_string(g_sched.size()) + " entries, this run has " + std::to_string(evals) +
-                  " evaluations (PNDM: steps + 1)");
+                  " evaluations (PNDM: steps + 1" + (first_step ? "; the run starts at step " + std::to_string(first_step) + " of " +
+                  std::to_string(in.steps) : std::string()) + ")");
         return -9;
     }
     // scale of evaluation i, and whether it runs cond-only (scale <= 1: no unconditional half, as do_classifier_free_guidance of a whole run)
@@ -198,7 +201,11 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 arena.release(mk);
             }
             // ---------------- 6. initial latents (RNG draw #2) * init_noise_sigma (1 for DDIM / PNDM; tryon_pipe.py:424)
-            if (!c.dry()) c.check(ladi_launch_lat_nchw_to_pix(in.noise_latents, B, hw, sinfo.init_noise_sigma, latents, st), "latents");
+            // with an init (strength): k_x * resample(init) + k_n * noise, or the init itself (init_noisy); init_noise_sigma is not applied
+            if (!c.dry() && first_step)
+                c.check(ladi_launch_init_latents(init_src, init_hs, init_ws, init_noisy ? nullptr : in.noise_latents, B, h, w,
+                                                 init_noisy ? 1.f : sinfo.start_kx, init_noisy ? 0.f : sinfo.start_kn, latents, st), "init_latents");
+            else if (!c.dry()) c.check(ladi_launch_lat_nchw_to_pix(in.noise_latents, B, hw, sinfo.init_noise_sigma, latents, st), "latents");
             // ---------------- 7. masked-image latents (RNG draw #3) + EMASC skips
             {
                 Act feats[5];

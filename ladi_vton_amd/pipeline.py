@@ -58,6 +58,23 @@ def guidance_plan(guidance_scale, n_evals, guidance_rescale=0.0):
     return table, (table[0] if table else 1.0), any(g > 1.0 for g in table)
 
 
+def strength_first_step(strength, num_inference_steps):
+    """-> first_step: the step of the schedule a run with `strength` starts at.  diffusers' get_timesteps arithmetic in Python float64:
+    init_timestep = min(int(N * strength), N), first_step = N - init_timestep.  Raises ValueError for a strength outside [0, 1] or not finite,
+    or one that leaves no step to run (init_timestep < 1)."""
+    n = int(num_inference_steps)
+    try:
+        s = float(strength)
+    except (TypeError, ValueError):
+        raise ValueError("`strength` has to be a number in [0, 1] but is %r." % (strength,))
+    if not math.isfinite(s) or s < 0.0 or s > 1.0:
+        raise ValueError("`strength` has to be in [0, 1] but is %r." % (strength,))
+    init_timestep = min(int(n * s), n)
+    if init_timestep < 1:
+        raise ValueError("`strength` = %r leaves no step to run with num_inference_steps = %d (int(%d * strength) < 1)." % (strength, n, n))
+    return n - init_timestep
+
+
 def rescale_noise_cfg(eps, eps_cond, phi):
     """guidance rescale: eps * (phi * std(eps_cond) / std(eps) + 1 - phi), per-sample unbiased stds, no epsilon"""
     dims = list(range(1, eps.ndim))
@@ -207,12 +224,22 @@ class StableDiffusionTryOnePipeline:
                  guidance_scale=7.5, negative_prompt=None, num_images_per_prompt=1, eta=0.0, prompt_embeds=None,
                  negative_prompt_embeds=None, generator=None, latents=None, output_type="pil", return_dict=True, callback=None,
                  callback_steps=1, cloth_cond_rate=1.0, no_pose=False, cloth_input_type="warped", fused=True, noise=None,
-                 use_graph=True, guidance_rescale=0.0):
+                 use_graph=True, guidance_rescale=0.0, strength=1.0, init_image=None, init_latents=None, init_is_noisy=False):
         """tryon_pipe.py's __call__.  `guidance_scale`: a float, a sequence with one scale per evaluation (len(scheduler.timesteps); PNDM: steps
         + 1) or a callable f(i, n_evals) -- see guidance_interval.  Classifier-free guidance is on if any scale is > 1; an evaluation whose scale
         is <= 1 then runs the UNet over the conditional samples only.  `guidance_rescale` (rescale_noise_cfg's phi, [0, 1]) acts on the CFG
         evaluations.  `height` / `width`: any multiple of 8, as the reference's check_inputs.  Latent sides that are not
-        multiples of 8 (e.g. 640x480 -> 80x60) run diffusers' `forward_upsample_size` arithmetic on both the fused and the modular path."""
+        multiples of 8 (e.g. 640x480 -> 80x60) run diffusers' `forward_upsample_size` arithmetic on both the fused and the modular path.
+
+        `strength` < 1 starts the run at step first_step = N - min(int(N * strength), N) of the N-step schedule from an init instead of from
+        noise at step 0, and runs only the tail.  The init is `init_latents` (fp32 [B, 4, hs, ws] in the loop's latent space, e.g.
+        `pipe.last_latents` of an earlier run or what a step callback received) or `init_image` ([B, 3, Hi, Wi] in [-1, 1], sides multiples of
+        8: encoded with the pipeline's VAE, posterior mode * scaling_factor, no extra RNG draw); another size than the run's is resampled
+        bilinearly.  The start latents are k_x * init + k_n * noise with the scheduler's add_noise coefficients at timesteps[first_step] and the
+        noise of `latents=` / RNG draw #2; `init_is_noisy=True` takes the init as the loop's latents at that timestep unchanged (resume).
+        Everything indexed per evaluation (a guidance schedule, the callback's i, scheduler.timesteps, the cloth cut-off of `cloth_cond_rate`)
+        refers to the tail.  PNDM restarts as a fresh PLMS run over the tail (tail steps + 1 evaluations, at least 2 steps).  strength = 1.0
+        ignores a given init and is the plain run."""
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
@@ -227,9 +254,22 @@ class StableDiffusionTryOnePipeline:
         # can run are image batches that already hold B * k samples -- the same rule applies here (shape checks below)
         if not isinstance(num_images_per_prompt, int) or num_images_per_prompt < 1:
             raise ValueError("num_images_per_prompt must be a positive integer")
+        first_step = strength_first_step(strength, num_inference_steps)
+        if init_image is not None and init_latents is not None:
+            raise ValueError("Cannot forward both `init_image` and `init_latents`.")
+        if first_step > 0:
+            if init_image is None and init_latents is None:
+                raise ValueError("`strength` < 1 needs `init_image` or `init_latents` to start from.")
+            if not isinstance(self.scheduler, FUSED_SCHEDULERS):
+                raise ValueError("`strength` < 1 needs one of this package's schedulers (set_timesteps(..., first_step=)).")
+        # the scheduler's own keyword stays out of a plain run's call (first_step == 0: today's set_timesteps(n) / (n, device=))
+        ts_kw = {"first_step": first_step} if first_step > 0 else {}
+
         def n_evals():
-            self.scheduler.set_timesteps(num_inference_steps)
+            self.scheduler.set_timesteps(num_inference_steps, **ts_kw)
             return len(self.scheduler.timesteps)
+        if first_step > 0:
+            n_evals()      # a first_step the scheduler cannot start at (a PNDM tail of one step) fails here, before any work
         g_table, guidance_scale, do_cfg = guidance_plan(guidance_scale, n_evals, guidance_rescale)
         device = self._execution_device
         pe, neg = self._encode_prompt(prompt, device, num_images_per_prompt, do_cfg, negative_prompt, prompt_embeds, negative_prompt_embeds)
@@ -246,6 +286,7 @@ class StableDiffusionTryOnePipeline:
         if self._range_probe is not None:
             self._range_probe.attach_only(self.unet, self.vae, self.emasc)     # the modules of THIS call (one may have been replaced)
             self._range_probe.reset()
+        init = self._prepare_init(init_image, init_latents, B, device) if first_step > 0 else None
         native = isinstance(self.unet, NativeUNet) and isinstance(self.vae, NativeVAE) and (self.emasc is None or isinstance(self.emasc, NativeEMASC))
         # only DDIMScheduler.step takes eta (the modular path passes it to no other scheduler); a negative one stays on the modular path
         ddim_eta = float(eta) if isinstance(self.scheduler, DDIMScheduler) else 0.0
@@ -256,15 +297,16 @@ class StableDiffusionTryOnePipeline:
             # the fused path makes the same draws up front, in the same generator order (Euler's are unused, as in diffusers without churn)
             step_noise = None
             if isinstance(self.scheduler, (EulerDiscreteScheduler, EulerAncestralDiscreteScheduler)) or ddim_eta > 0.0:
-                draws = [self._draw((B, 4, h, w), generator, torch.float32, device) for _ in range(int(num_inference_steps))]
+                draws = [self._draw((B, 4, h, w), generator, torch.float32, device) for _ in range(int(num_inference_steps) - first_step)]
                 if not isinstance(self.scheduler, EulerDiscreteScheduler):
                     step_noise = torch.stack(draws).contiguous()
             if callback is not None:
-                self.scheduler.set_timesteps(num_inference_steps, device=device)    # the callback's t, as on the modular path
+                self.scheduler.set_timesteps(num_inference_steps, device=device, **ts_kw)    # the callback's t, as on the modular path
             images = self._run_fused(image, mask_image, pose_map, warped_cloth if cloth_input_type == "warped" else None, pe, neg,
                                      n_cloth, n_lat, n_mask, height, width, num_inference_steps, guidance_scale, cloth_cond_rate,
                                      no_pose, use_graph, step_noise=step_noise, eta=ddim_eta, callback=callback,
-                                     callback_steps=callback_steps, guidance_table=g_table, guidance_rescale=guidance_rescale)
+                                     callback_steps=callback_steps, guidance_table=g_table, guidance_rescale=guidance_rescale,
+                                     init_latents=init, first_step=first_step, init_is_noisy=init_is_noisy)
             # prepare_mask_and_masked_image binarises the caller's mask in place; keep that side effect
             mask_image[mask_image < 0.5] = 0
             mask_image[mask_image >= 0.5] = 1
@@ -272,17 +314,36 @@ class StableDiffusionTryOnePipeline:
             images = self._run_modular(image, mask_image, pose_map, warped_cloth if cloth_input_type == "warped" else None, pe, neg,
                                        n_cloth, n_lat, n_mask, height, width, num_inference_steps, guidance_scale, cloth_cond_rate,
                                        no_pose, eta, generator, callback, callback_steps, guidance_table=g_table,
-                                       guidance_rescale=guidance_rescale)
+                                       guidance_rescale=guidance_rescale, init_latents=init, first_step=first_step,
+                                       init_is_noisy=init_is_noisy)
         if output_type == "pil":
             images = numpy_to_pil(images)
         if not return_dict:
             return (images, None)
         return SimpleNamespace(images=images, nsfw_content_detected=None)
 
+    def _prepare_init(self, init_image, init_latents, B, device):
+        """-> the init of a strength < 1 run as fp32 [B, 4, hs, ws] latents on `device`.  init_image: the posterior MODE of the pipeline's own
+        vae.encode times scaling_factor (no RNG draw, so the pipeline's three draws keep their order; later diffusers releases sample it)"""
+        if init_latents is not None:
+            if not isinstance(init_latents, torch.Tensor) or init_latents.ndim != 4 or tuple(init_latents.shape[:2]) != (B, 4) \
+                    or min(init_latents.shape[2:]) < 1:
+                raise ValueError("`init_latents` has to be a [%d, 4, hs, ws] tensor but has shape %s."
+                                 % (B, tuple(getattr(init_latents, "shape", ()))))
+            return init_latents.to(device=device, dtype=torch.float32).contiguous()
+        if not isinstance(init_image, torch.Tensor) or init_image.ndim != 4 or tuple(init_image.shape[:2]) != (B, 3):
+            raise ValueError("`init_image` has to be a [%d, 3, Hi, Wi] tensor but has shape %s." % (B, tuple(getattr(init_image, "shape", ()))))
+        if init_image.shape[2] % 8 or init_image.shape[3] % 8 or min(init_image.shape[2:]) < 8:
+            raise ValueError("`init_image` sides have to be multiples of 8 but are %d and %d." % tuple(init_image.shape[2:]))
+        if init_image.min() < -1 or init_image.max() > 1:
+            raise ValueError("`init_image` should be in [-1, 1] range")
+        mode = self.vae.encode(init_image.to(device))[0].latent_dist.mode()
+        return (self.vae.config.scaling_factor * mode.float()).contiguous()
+
     # -------------------------------------------------------------------------------------------------------
     def _run_fused(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose,
                    use_graph, return_device=False, out_uint8=False, lanes=None, step_noise=None, eta=0.0, callback=None, callback_steps=1,
-                   guidance_table=None, guidance_rescale=0.0):
+                   guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0, init_is_noisy=False):
         """return_device: hand back the device tensor (no host copy); out_uint8: the batch as uint8 [B,H,W,3] = numpy_to_pil's
         (images * 255).round() computed by the decode epilogue (ladi_tryon_run_u8); lanes: sample-group lanes of the UNet forward;
         step_noise: fp32 [steps, B, 4, h, w], the per-step noise of EulerAncestralDiscreteScheduler and of DDIM with eta > 0
@@ -291,7 +352,10 @@ class StableDiffusionTryOnePipeline:
         callback / callback_steps: called as callback(i, self.scheduler.timesteps[i], latents) after every evaluation i with
         i % callback_steps == 0, latents an fp32 [B, 4, h, w] device tensor whose in-place edits the loop takes over
         (ladi_tryon_set_step_callback).  An exception in the callback aborts the run and is re-raised here.  When the decode's fp16-range
-        guard re-runs the batch (below), the whole loop runs again and the callback sees every step a second time."""
+        guard re-runs the batch (below), the whole loop runs again and the callback sees every step a second time.
+        init_latents / first_step / init_is_noisy (ladi_tryon_set_init): start at step first_step > 0 of the `steps`-step schedule from the fp32
+        [B, 4, hs, ws] init_latents (None or first_step = 0: off).  The run then has the tail's evaluations: step_noise, guidance_table, the
+        callback's i and the cloth cut-off of `ccr` all refer to them."""
         lib = _lib.load()
         if self._tryon is None:
             self._tryon = lib.ladi_tryon_create(self.unet.h, self.vae.h, self.emasc.h if self.emasc else None)
@@ -329,8 +393,12 @@ class StableDiffusionTryOnePipeline:
         inp.num_inference_steps, inp.guidance_scale = int(steps), float(guidance)
         inp.scheduler = self.scheduler.kind
         # tryon_pipe.py:654,718 in the reference's own float64 arithmetic: first evaluation index i with i >= steps - (1 - rate) * steps
-        ccs = (1 - ccr) * steps
-        inp.cloth_zero_from_eval = min(max(0, math.ceil(steps - ccs)), 1 << 30)
+        # (a run that starts at first_step: the tail's step count in the same formula, as the reference loop handed diffusers' truncated
+        # num_inference_steps would compute it)
+        first_step = int(first_step) if init_latents is not None else 0
+        tail = int(steps) - first_step
+        ccs = (1 - ccr) * tail
+        inp.cloth_zero_from_eval = min(max(0, math.ceil(tail - ccs)), 1 << 30)
         inp.no_pose, inp.use_graph = int(bool(no_pose)), int(bool(use_graph))
         ac = self.scheduler.alphas_cumprod.to("cpu", torch.float32).contiguous()
         inp.alphas_cumprod_host = ac.data_ptr()
@@ -343,13 +411,21 @@ class StableDiffusionTryOnePipeline:
         else:
             check(lib.ladi_tryon_set_trace(self._tryon, None, None, 0), "ladi_tryon_set_trace")
         if step_noise is not None:
-            if tuple(step_noise.shape[1:]) != (B, 4, h8, w8) or step_noise.shape[0] < int(steps):
-                raise ValueError("step noise has shape %s, expected (%d, %d, 4, %d, %d)" % (tuple(step_noise.shape), int(steps), B, h8, w8))
+            if tuple(step_noise.shape[1:]) != (B, 4, h8, w8) or step_noise.shape[0] < tail:
+                raise ValueError("step noise has shape %s, expected (%d, %d, 4, %d, %d)" % (tuple(step_noise.shape), tail, B, h8, w8))
             step_noise = step_noise.to(device=dev, dtype=torch.float32).contiguous()
             check(lib.ladi_tryon_set_step_noise(self._tryon, ptr(step_noise), step_noise.shape[0]), "ladi_tryon_set_step_noise")
         else:
             check(lib.ladi_tryon_set_step_noise(self._tryon, None, 0), "ladi_tryon_set_step_noise")
         check(lib.ladi_tryon_set_eta(self._tryon, float(eta)), "ladi_tryon_set_eta")
+        if first_step > 0:
+            if init_latents.ndim != 4 or tuple(init_latents.shape[:2]) != (B, 4):
+                raise ValueError("init latents have shape %s, expected (%d, 4, hs, ws)" % (tuple(init_latents.shape), B))
+            init_latents = init_latents.to(device=dev, dtype=torch.float32).contiguous()
+            check(lib.ladi_tryon_set_init(self._tryon, ptr(init_latents), init_latents.shape[2], init_latents.shape[3], first_step,
+                                          int(bool(init_is_noisy))), "ladi_tryon_set_init")
+        else:
+            check(lib.ladi_tryon_set_init(self._tryon, None, 0, 0, 0, 0), "ladi_tryon_set_init")
         if guidance_table is not None:
             gt = (ctypes.c_float * len(guidance_table))(*guidance_table)
             check(lib.ladi_tryon_set_guidance_schedule(self._tryon, gt, len(guidance_table)), "ladi_tryon_set_guidance_schedule")
@@ -445,7 +521,8 @@ class StableDiffusionTryOnePipeline:
 
     # -------------------------------------------------------------------------------------------------------
     def _run_modular(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose, eta,
-                     generator, callback, callback_steps, guidance_table=None, guidance_rescale=0.0):
+                     generator, callback, callback_steps, guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0,
+                     init_is_noisy=False):
         F = torch.nn.functional
         dev = self._execution_device
         do_cfg = neg is not None
@@ -461,10 +538,22 @@ class StableDiffusionTryOnePipeline:
         cloth_lat = None
         if cloth is not None:
             cloth_lat = sf * self.vae.encode(cloth.to(dev))[0].latent_dist.sample(noise=n_cloth).float()
-        self.scheduler.set_timesteps(steps, device=dev)
-        timesteps = self.scheduler.timesteps
+        first_step = int(first_step) if init_latents is not None else 0
+        if first_step > 0:
+            # strength: the tail of the schedule from k_x * resample(init) + k_n * noise (the scheduler's add_noise at the first timestep), or
+            # from the init itself (init_is_noisy); `steps` below is the tail's count, as diffusers hands the loop its truncated one
+            self.scheduler.set_timesteps(steps, device=dev, first_step=first_step)
+            timesteps = self.scheduler.timesteps
+            steps = int(steps) - first_step
+            x0 = init_latents.to(device=dev, dtype=torch.float32)
+            if tuple(x0.shape[2:]) != (H // 8, W // 8):
+                x0 = F.interpolate(x0, size=(H // 8, W // 8), mode="bilinear", align_corners=False)
+            latents = x0 if init_is_noisy else self.scheduler.add_noise(x0, n_lat.to(dev), timesteps[0])
+        else:
+            self.scheduler.set_timesteps(steps, device=dev)
+            timesteps = self.scheduler.timesteps
+            latents = n_lat * self.scheduler.init_noise_sigma
         ccs = (1 - ccr) * steps
-        latents = n_lat * self.scheduler.init_noise_sigma
         mask_lat = F.interpolate(mask.float(), size=(H // 8, W // 8))
         enc, feats = self.vae.encode(masked_image)
         masked_lat = sf * enc.latent_dist.sample(noise=n_mask).float()

@@ -55,6 +55,29 @@ class _SchedulerBase:
     def _a(self, t):
         return self.alphas_cumprod[t] if t >= 0 else self.final_alpha_cumprod
 
+    def _check_first_step(self, n, first_step, min_tail=1):
+        """strength: the run starts at step first_step of the n-step schedule; the tail keeps at least min_tail steps"""
+        first_step = int(first_step)
+        if first_step < 0 or first_step > int(n) - min_tail:
+            raise ValueError("first_step %d is out of range [0, %d] for %d steps%s"
+                             % (first_step, int(n) - min_tail, int(n), " (a PNDM tail needs at least 2 steps)" if min_tail == 2 else ""))
+        return first_step
+
+    def _native_table_from(self, n, first_step):
+        """-> (timesteps, rows [evals][10], (k_x, k_n, in_scale0)) of ladi_sched_table_from: the very numbers the fused loop uses for the tail"""
+        import ctypes
+        ts, rows, start = (ctypes.c_double * (n + 2))(), (ctypes.c_float * (10 * (n + 2)))(), (ctypes.c_float * 3)()
+        ac = self.alphas_cumprod.to("cpu", torch.float32).contiguous()
+        cnt = _lib.load().ladi_sched_table_from(self.kind, n, ctypes.c_void_p(ac.data_ptr()), 0.0, first_step, ts, rows, n + 2, start)
+        if cnt < 0:
+            raise _lib.NativeError("ladi_sched_table_from: " + _lib.last_error())
+        return list(ts[:cnt]), [list(rows[10 * i:10 * i + 10]) for i in range(cnt)], tuple(start)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """sqrt(a_t) x0 + sqrt(1 - a_t) noise at the integer timestep t (diffusers' add_noise; coefficients in float64)"""
+        a = float(self.alphas_cumprod[int(timesteps)].double())
+        return (a ** 0.5 * original_samples.double() + (1.0 - a) ** 0.5 * noise.double()).to(original_samples.dtype)
+
 
 def _step_noise(shape, dtype, generator, device):
     """diffusers 0.14 randn_tensor(shape, generator, device, dtype) as the schedulers' step() calls it: drawn on the generator's device;
@@ -71,10 +94,12 @@ def _step_noise(shape, dtype, generator, device):
 class DDIMScheduler(_SchedulerBase):
     kind = DDIM
 
-    def set_timesteps(self, num_inference_steps, device=None):
+    def set_timesteps(self, num_inference_steps, device=None, first_step=0):
+        """first_step > 0 (strength): the timesteps of steps first_step .. of the schedule"""
+        first_step = self._check_first_step(num_inference_steps, first_step)
         self.num_inference_steps = num_inference_steps
         self.ratio = 1000 // num_inference_steps
-        ts = self._native_timesteps(num_inference_steps)
+        ts = self._native_timesteps(num_inference_steps)[first_step:]
         self.timesteps = torch.tensor(ts, dtype=torch.int64, device=device)
 
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None, variance_noise=None, **kw):
@@ -100,10 +125,17 @@ class DDIMScheduler(_SchedulerBase):
 class PNDMScheduler(_SchedulerBase):
     kind = PNDM
 
-    def set_timesteps(self, num_inference_steps, device=None):
+    def set_timesteps(self, num_inference_steps, device=None, first_step=0):
+        """first_step > 0 (strength): a fresh PLMS run over the step timesteps u0 > u1 > .. of steps first_step .., evaluations
+        [u0, u1, u1, u2, ..] (tail steps + 1) -- not diffusers' slice of the N + 1 list, which leaves the sample one step under-denoised.
+        The tail needs at least 2 steps."""
+        first_step = self._check_first_step(num_inference_steps, first_step, min_tail=2 if first_step else 1)
         self.num_inference_steps = num_inference_steps
         self.ratio = 1000 // num_inference_steps
         ts = self._native_timesteps(num_inference_steps)
+        if first_step:
+            u = ([ts[0]] + ts[2:])[first_step:]          # the schedule's step timesteps, then the tail's
+            ts = [u[0], u[1], u[1]] + u[2:]
         self.timesteps = torch.tensor(ts, dtype=torch.int64, device=device)
         self.ets, self.counter, self.cur_sample = [], 0, None
 
@@ -170,10 +202,13 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         self.alpha_t, self.sigma_t = ac.sqrt(), (1 - ac).sqrt()
         self.lambda_t = self.alpha_t.log() - self.sigma_t.log()
 
-    def set_timesteps(self, num_inference_steps, device=None):
+    def set_timesteps(self, num_inference_steps, device=None, first_step=0):
+        """first_step > 0 (strength): steps first_step .. of the schedule; the solver warms up again there (no earlier data predictions) and
+        lower_order_final acts where it does in the whole run"""
         n = int(num_inference_steps)
+        first_step = self._check_first_step(n, first_step)
         self.num_inference_steps = n
-        self._ts = self._native_timesteps(n)
+        self._ts = self._native_timesteps(n)[first_step:]
         self.timesteps = torch.tensor(self._ts, dtype=torch.int64, device=device)
         self.model_outputs = [None] * self.config.solver_order
         self.lower_order_nums = 0
@@ -186,7 +221,7 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         ts, n, order = self._ts, len(self._ts), self.config.solver_order
         i = ts.index(t_s) if t_s in ts else n - 1
         prev_t = 0 if i == n - 1 else ts[i + 1]
-        lof = self.config.lower_order_final and n < 15
+        lof = self.config.lower_order_final and self.num_inference_steps < 15
         x, e = sample.float(), model_output.float()
         a_s, s_s, l_s = self._coef(t_s)
         m = (x - s_s * e) / a_s
@@ -227,9 +262,10 @@ class _SigmaScheduler(_SchedulerBase):
         self.sigmas = None
         self.init_noise_sigma = float(((1 - self.alphas_cumprod) / self.alphas_cumprod).sqrt().max())   # as diffusers before set_timesteps
 
-    def _set_sigma_tables(self, num_inference_steps, device):
+    def _set_sigma_tables(self, num_inference_steps, device, first_step=0):
         import ctypes
         n = int(num_inference_steps)
+        first_step = self._check_first_step(n, first_step)
         ts = (ctypes.c_double * n)()
         sg = (ctypes.c_float * (n + 1))()
         cf = (ctypes.c_float * (4 * n))()
@@ -237,11 +273,17 @@ class _SigmaScheduler(_SchedulerBase):
         if _lib.load().ladi_sched_lms(n, ctypes.c_void_p(ac.data_ptr()), ts, sg, cf) < 0:
             raise _lib.NativeError("ladi_sched_lms: " + _lib.last_error())
         self.num_inference_steps = n
-        self.timesteps = torch.tensor(list(ts), dtype=torch.float64, device=device)
-        self.sigmas = torch.tensor(list(sg), dtype=torch.float32)
-        self._ts = list(ts)
-        self.init_noise_sigma = float(self.sigmas.max())
+        # first_step > 0 (strength): the timesteps and sigmas of steps first_step ..; init_noise_sigma stays the whole schedule's
+        self.timesteps = torch.tensor(list(ts)[first_step:], dtype=torch.float64, device=device)
+        self.sigmas = torch.tensor(list(sg)[first_step:], dtype=torch.float32)
+        self._ts = list(ts)[first_step:]
+        self.init_noise_sigma = float(max(sg))
         return cf
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """x0 + sigma_t noise (diffusers' add_noise of the sigma schedulers)"""
+        sigma = float(self.sigmas[self._index(timesteps)])
+        return (original_samples.double() + sigma * noise.double()).to(original_samples.dtype)
 
     def _index(self, timestep):
         t = float(timestep)
@@ -258,8 +300,8 @@ class EulerDiscreteScheduler(_SigmaScheduler):
     Restated from memory, not pinned against diffusers."""
     kind = EULER
 
-    def set_timesteps(self, num_inference_steps, device=None):
-        self._set_sigma_tables(num_inference_steps, device)
+    def set_timesteps(self, num_inference_steps, device=None, first_step=0):
+        self._set_sigma_tables(num_inference_steps, device, first_step)
 
     def step(self, model_output, timestep, sample, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, generator=None,
              return_dict=True, **kw):
@@ -279,8 +321,8 @@ class EulerAncestralDiscreteScheduler(_SigmaScheduler):
     made up front in the same generator order (ladi_tryon_set_step_noise).  Restated from memory, not pinned against diffusers."""
     kind = EULER_ANCESTRAL
 
-    def set_timesteps(self, num_inference_steps, device=None):
-        self._set_sigma_tables(num_inference_steps, device)
+    def set_timesteps(self, num_inference_steps, device=None, first_step=0):
+        self._set_sigma_tables(num_inference_steps, device, first_step)
 
     def step(self, model_output, timestep, sample, generator=None, return_dict=True, **kw):
         i = self._index(timestep)
@@ -299,9 +341,13 @@ class LMSDiscreteScheduler(_SigmaScheduler):
     are the very numbers the fused device loop uses."""
     kind = LMS
 
-    def set_timesteps(self, num_inference_steps, device=None):
-        cf = self._set_sigma_tables(num_inference_steps, device)
-        self._coeffs = [list(cf[4 * i:4 * i + 4]) for i in range(self.num_inference_steps)]
+    def set_timesteps(self, num_inference_steps, device=None, first_step=0):
+        """first_step > 0 (strength): steps first_step .. with the multistep weights of a history that starts empty there (orders 1, 2, ..)"""
+        cf = self._set_sigma_tables(num_inference_steps, device, first_step)
+        if first_step:
+            self._coeffs = [row[2:6] for row in self._native_table_from(self.num_inference_steps, int(first_step))[1]]
+        else:
+            self._coeffs = [list(cf[4 * i:4 * i + 4]) for i in range(self.num_inference_steps)]
         self.derivatives = []
 
     def step(self, model_output, timestep, sample, order=4, **kw):
