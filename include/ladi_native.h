@@ -65,6 +65,25 @@ int ladi_unet_set_context(ladi_unet* u, const void* ehs_dev, int n, int L, void*
  * (`forward_upsample_size`, nearest as F.interpolate(size=...)); multiples of 8 double at every level, as before. */
 int ladi_unet_forward(ladi_unet* u, const void* sample_dev, int dtype, int n, int h, int w, float timestep, void* out_dev,
                       int out_dtype, void* stream);
+/* ladi_unet_forward with the deep-feature cache of the first (full-resolution) level (DeepCache; layer names are diffusers', L =
+ * layers_per_block).  The cached tensor is the hidden state that enters up_blocks.3.resnets.(L - branch), before the concatenation with its
+ * skip: the output of up_blocks.3.attentions.(L - branch - 1), or of up_blocks.2.upsamplers.0 for branch = L.  It is fp16 [n, h, w, C] with C =
+ * block_out_channels[0] (branch < L) or block_out_channels[1] (branch = L), owned by the handle, one row per sample of the context batch.
+ *   mode 0: ladi_unet_forward.
+ *   mode 1: the whole forward (same launches, same result), which also copies that tensor into the cache.
+ *   mode 2: the shallow forward from the cache: conv_in, layers 0 .. branch-1 of down_blocks.0 (resnet + attention), then up_blocks.3 layers
+ *           L-branch .. L, each with its usual skip, the first taking the cached tensor as its hidden state, conv_norm_out, conv_out; the time
+ *           embedding is that of `timestep`.  Nothing of the deeper levels or the mid block runs.
+ * branch: 0 .. L.  Mode 2 without a capture at the same (n, h, w, branch) since the last ladi_unet_set_context is an error with a message;
+ * nothing is launched.  A set_context, or a capture at another (h, w, branch), drops what the cache held. */
+int ladi_unet_forward_cached(ladi_unet* u, const void* sample_dev, int dtype, int n, int h, int w, float timestep, void* out_dev,
+                             int out_dtype, int mode, int branch, void* stream);
+/* Supported ABI, beyond the single-call form above (which is this entry with sample0 = 0 and n = the context's n): the same over n samples
+ * that start at index sample0 of the context batch (sample0 + n <= the context's n).  They use their own rows of the cross-attention K/V
+ * and of the feature cache, as a cond-only evaluation of the fused loop does (NativeUNet's `sample0=`; with mode 0 it is the plain forward
+ * over those rows).  Mode 2 needs every one of these rows captured (by whichever calls) at the same (h, w, branch). */
+int ladi_unet_forward_cached_rows(ladi_unet* u, const void* sample_dev, int dtype, int n, int h, int w, float timestep, void* out_dev,
+                                  int out_dtype, int mode, int branch, int sample0, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * VAE — replaces src/models/AutoencoderKL.py AutoencoderKL.encode (:145-157) / .decode (:174-188) with the EMASC
@@ -323,6 +342,18 @@ int ladi_tryon_set_guidance_schedule(ladi_tryon* t, const float* scales_host, in
 int ladi_tryon_set_guidance_rescale(ladi_tryon* t, float phi);
 /* how many evaluations of the last run ran cond-only, i.e. over B samples (all of them for a run without CFG) */
 int ladi_tryon_cond_only_evals(ladi_tryon* t);
+/* deep-feature cache (DeepCache, first level only) for the following runs (sticky per handle; copied): full_flags_host[i] != 0 runs
+ * evaluation i whole (and captures the tensor ladi_unet_forward_cached describes), 0 runs it shallow at `branch` from the last capture.
+ * NULL or count 0 switches it off; a plan without a 0 is the plain run bit for bit (capture stays off).  A run whose evaluation count is not
+ * `count` (PNDM: num_inference_steps + 1; a strength run: the tail's), or whose flag 0 is 0, fails with -10 before anything is launched;
+ * branch outside 0 .. 2 is refused here.  One promotion, decided on the host before the loop: in a CFG-shaped run a shallow evaluation over
+ * all 2B samples that follows a whole evaluation which ran cond-only (so only the conditional rows were refreshed) runs whole instead; a
+ * shallow cond-only evaluation is never promoted.  Nothing else is special: the cloth cut-off (cloth_zero_from_eval), a step callback's edit
+ * of the latents and PNDM's double evaluation reuse the cache as it is.  Everything indexed per evaluation keeps its meaning.  With use_graph
+ * the loop replays up to four graphs, {whole, shallow} x {2B samples, cond-only}.  Works with any lane count. */
+int ladi_tryon_set_feature_cache(ladi_tryon* t, const unsigned char* full_flags_host, int count, int branch);
+/* how many evaluations of the last run ran shallow, after promotion */
+int ladi_tryon_shallow_evals(ladi_tryon* t);
 /* step callback (diffusers' callback / callback_steps): after evaluation i with i % every == 0, on the run's stream, the loop's latents are
  * copied to latents_nchw_dev (caller-owned fp32 [B,4,h,w], what the modular path hands its callback), the stream is synchronised and
  * fn(user, i) runs on the calling thread.  Afterwards work queued on the run's `stream` argument is waited for, and latents_nchw_dev is copied
@@ -349,6 +380,10 @@ int ladi_tryon_lanes(ladi_tryon* t);
 /* run ONLY `iters` UNet forwards (n samples of h x w latents, context already set) bracketed by HIP events on `stream`
  * and return the average milliseconds per forward (synchronises). Used by bench.py for the roofline figure. */
 int ladi_unet_time_forward(ladi_unet* u, int n, int h, int w, int iters, float* avg_ms, void* stream);
+/* Supported ABI (what tools/bench_feature_cache.py times the shallow forward with): the same measurement of a forward in feature-cache
+ * mode `mode` (ladi_unet_forward_cached: 1 whole + capture, 2 shallow at `branch`; 0 is ladi_unet_time_forward) against a scratch cache of
+ * zeros: the launch sequence and shapes are those of the real thing */
+int ladi_unet_time_forward_cached(ladi_unet* u, int n, int h, int w, int iters, int mode, int branch, float* avg_ms, void* stream);
 /* the same measurement of the forward as the denoising loop runs it: `lanes` independent sample groups on as many HIP streams (0 =
  * the loop's own choice, LADI_UNET_LANES or 1; must divide n), replayed from one hipGraph with `lanes` parallel branches when
  * use_graph != 0.  Runs on an internal stream fenced against `stream`; synchronises. */

@@ -107,7 +107,10 @@ SIGNATURES = {
     "ladi_unet_destroy": (None, [_P]),
     "ladi_unet_set_context": (c_int, [_P, _P, c_int, c_int, _P]),
     "ladi_unet_forward": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, c_int, _P]),
+    "ladi_unet_forward_cached": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, c_int, c_int, c_int, _P]),
+    "ladi_unet_forward_cached_rows": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, c_int, c_int, c_int, c_int, _P]),
     "ladi_unet_time_forward": (c_int, [_P, c_int, c_int, c_int, c_int, POINTER(c_float), _P]),
+    "ladi_unet_time_forward_cached": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P]),
     "ladi_unet_time_forward_lanes": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P]),
     "ladi_vae_create": (_P, [POINTER(VAEConfig), _P]),
     "ladi_vae_destroy": (None, [_P]),
@@ -152,6 +155,8 @@ SIGNATURES = {
     "ladi_tryon_set_guidance_schedule": (c_int, [_P, POINTER(c_float), c_int]),
     "ladi_tryon_set_guidance_rescale": (c_int, [_P, c_float]),
     "ladi_tryon_cond_only_evals": (c_int, [_P]),
+    "ladi_tryon_set_feature_cache": (c_int, [_P, POINTER(ctypes.c_ubyte), c_int, c_int]),
+    "ladi_tryon_shallow_evals": (c_int, [_P]),
     "ladi_tryon_set_step_callback": (c_int, [_P, STEP_CALLBACK, _P, c_int, _P]),
     "ladi_tryon_set_lanes": (c_int, [_P, c_int]),
     "ladi_tryon_lanes": (c_int, [_P]),

@@ -137,10 +137,80 @@ int ladi_unet_forward(ladi_unet* u, const void* sample, int dtype, int n, int h,
     });
 }
 
-int ladi_unet_time_forward(ladi_unet* u, int n, int h, int w, int iters, float* avg_ms, void* stream) {
-    return guarded("ladi_unet_time_forward", [&]() {
+int ladi_unet_forward_cached_rows(ladi_unet* u, const void* sample, int dtype, int n, int h, int w, float timestep, void* out, int out_dtype,
+                                  int mode, int branch, int sample0, void* stream) {
+    return guarded("ladi_unet_forward_cached", [&]() {
+        if (!u) throw std::runtime_error("null handle");
         UNet& U = u->u;
         hipStream_t st = S(stream);
+        if (mode < 0 || mode > 2) throw std::runtime_error("mode " + std::to_string(mode) + " unknown: 0 plain, 1 whole + capture, 2 shallow");
+        if (mode && (branch < 0 || branch > U.cfg.layers_per_block))
+            throw std::runtime_error("branch " + std::to_string(branch) + " out of range [0, " + std::to_string(U.cfg.layers_per_block) + "]");
+        if (n < 1 || h < 1 || w < 1 || sample0 < 0 || sample0 + n > U.ctx_n)
+            throw std::runtime_error("samples [" + std::to_string(sample0) + ", " + std::to_string(sample0 + n) + ") are not inside the context batch of " +
+                                     std::to_string(U.ctx_n) + " (ladi_unet_set_context)");
+        // every check of the cache comes before the first launch
+        const bool same = U.fc_buf && U.fc_h == h && U.fc_w == w && U.fc_branch == branch;
+        if (mode == FeatCache::SHALLOW) {
+            bool ok = same && (int)U.fc_rows.size() >= sample0 + n;
+            for (int i = 0; ok && i < n; ++i) ok = U.fc_rows[sample0 + i] != 0;
+            if (!ok)
+                throw std::runtime_error("shallow forward without a feature cache captured for samples [" + std::to_string(sample0) + ", " +
+                                         std::to_string(sample0 + n) + ") at h = " + std::to_string(h) + ", w = " + std::to_string(w) + ", branch = " +
+                                         std::to_string(branch) + " since the last ladi_unet_set_context (run mode 1 first)");
+        }
+        if (mode == FeatCache::CAPTURE) {
+            const size_t need = (size_t)U.ctx_n * h * w * U.fc_channels(branch);
+            if (!same) U.fc_rows.assign((size_t)U.ctx_n, 0);          // another geometry: what the cache held is gone
+            if (need > U.fc_cap) {
+                std::fill(U.fc_rows.begin(), U.fc_rows.end(), 0);
+                if (U.fc_buf) HIP_OK(hipFree(U.fc_buf));
+                U.fc_buf = nullptr; U.fc_cap = 0;
+                HIP_OK(hipMalloc(reinterpret_cast<void**>(&U.fc_buf), need * sizeof(h16)));
+                U.fc_cap = need;
+            }
+            U.fc_h = h; U.fc_w = w; U.fc_branch = branch;
+        }
+        if (U.compute_temb(&timestep, 1, st)) return -1;
+        FeatCache fc; fc.mode = mode; fc.branch = branch; fc.buf = U.fc_buf;
+        const int eps_ld = (U.cfg.out_channels + 3) / 4 * 4;
+        run_planned(U.arena, st, [&](Ctx& c) {
+            Act x = c.new_act(n, h, w, 64);
+            Act eo = c.new_act(n, h, w, U.cfg.out_channels, eps_ld);
+            if (!c.dry()) c.check(ladi_launch_nchw_to_nhwc(sample, dtype == LADI_F32, n, U.cfg.in_channels, h, w, x.p, 64, st), "nchw_to_nhwc");
+            Act eps = U.forward(c, x, U.temb_table, nullptr, &eo, sample0, mode ? &fc : nullptr);
+            if (!c.dry()) c.check(ladi_launch_nhwc_to_nchw(eps.p, eps.ld, n, U.cfg.out_channels, h, w, out, out_dtype == LADI_F32, st), "nhwc_to_nchw");
+        }, &U.stats, &U.stats_cap);
+        if (mode == FeatCache::CAPTURE) for (int i = 0; i < n; ++i) U.fc_rows[sample0 + i] = 1;
+        return 0;
+    });
+}
+
+int ladi_unet_forward_cached(ladi_unet* u, const void* sample, int dtype, int n, int h, int w, float timestep, void* out, int out_dtype,
+                             int mode, int branch, void* stream) {
+    if (u && n != u->u.ctx_n) {
+        set_error("ladi_unet_forward_cached: n = " + std::to_string(n) + " is not the context batch of " + std::to_string(u->u.ctx_n) +
+                  " (ladi_unet_set_context); a cache captured at another n does not serve");
+        return -2;
+    }
+    return ladi_unet_forward_cached_rows(u, sample, dtype, n, h, w, timestep, out, out_dtype, mode, branch, 0, stream);
+}
+
+// mode / branch: time the shallow forward (2) or the capturing one (1) against a scratch cache that holds zeros; 0: the plain forward
+static int time_forward_any(const char* name, ladi_unet* u, int n, int h, int w, int iters, int mode, int branch, float* avg_ms, void* stream) {
+    return guarded(name, [&]() {
+        UNet& U = u->u;
+        hipStream_t st = S(stream);
+        if (mode < 0 || mode > 2 || (mode && (branch < 0 || branch > U.cfg.layers_per_block))) throw std::runtime_error("bad mode / branch");
+        FeatCache fcs; fcs.mode = mode; fcs.branch = branch;
+        struct Scratch { h16* p = nullptr; ~Scratch() { if (p) (void)hipFree(p); } } scratch;
+        if (mode) {
+            const size_t bytes = (size_t)n * h * w * U.fc_channels(branch) * sizeof(h16);
+            HIP_OK(hipMalloc(reinterpret_cast<void**>(&scratch.p), bytes));
+            HIP_OK(hipMemsetAsync(scratch.p, 0, bytes, st));
+            fcs.buf = scratch.p;
+        }
+        const FeatCache* fc = mode ? &fcs : nullptr;
         float t0 = 500.f;
         if (U.compute_temb(&t0, 1, st)) return -1;
         hipEvent_t e0, e1;
@@ -150,12 +220,12 @@ int ladi_unet_time_forward(ladi_unet* u, int n, int h, int w, int iters, float* 
             if (!c.dry()) HIP_OK(hipMemsetAsync(x.p, 0, x.pixels() * 64 * sizeof(h16), st));
             const size_t mk = c.ar->mark();
             // warm-up
-            c.stats_off = 0; (void)U.forward(c, x, U.temb_table, nullptr); c.ar->release(mk);
+            c.stats_off = 0; (void)U.forward(c, x, U.temb_table, nullptr, nullptr, 0, fc); c.ar->release(mk);
             if (!c.dry()) HIP_OK(hipEventRecord(e0, st));
             for (int i = 0; i < (c.dry() ? 1 : iters); ++i) {
                 c.stats_off = 0;
                 if (!c.dry() && c.stats_cap) HIP_OK(hipMemsetAsync(c.stats, 0, c.stats_cap * sizeof(float), st));
-                (void)U.forward(c, x, U.temb_table, nullptr);
+                (void)U.forward(c, x, U.temb_table, nullptr, nullptr, 0, fc);
                 c.ar->release(mk);
             }
             if (!c.dry()) HIP_OK(hipEventRecord(e1, st));
@@ -167,6 +237,12 @@ int ladi_unet_time_forward(ladi_unet* u, int n, int h, int w, int iters, float* 
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
         return 0;
     });
+}
+int ladi_unet_time_forward(ladi_unet* u, int n, int h, int w, int iters, float* avg_ms, void* stream) {
+    return time_forward_any("ladi_unet_time_forward", u, n, h, w, iters, 0, 0, avg_ms, stream);
+}
+int ladi_unet_time_forward_cached(ladi_unet* u, int n, int h, int w, int iters, int mode, int branch, float* avg_ms, void* stream) {
+    return time_forward_any("ladi_unet_time_forward_cached", u, n, h, w, iters, mode, branch, avg_ms, stream);
 }
 
 int ladi_unet_time_forward_lanes(ladi_unet* u, int n, int h, int w, int iters, int lanes, int use_graph, float* avg_ms, void* stream) {
@@ -652,6 +728,17 @@ int ladi_tryon_set_guidance_rescale(ladi_tryon* t, float phi) {
     return 0;
 }
 int ladi_tryon_cond_only_evals(ladi_tryon* t) { return t ? t->t.last_cond_only : -1; }
+int ladi_tryon_set_feature_cache(ladi_tryon* t, const unsigned char* full_flags_host, int count, int branch) {
+    if (!t || count < 0) { set_error("ladi_tryon_set_feature_cache: null handle or negative count"); return -1; }
+    if (!full_flags_host || count == 0) { t->t.fc_plan.clear(); t->t.fc_branch = 0; return 0; }
+    if (branch < 0 || branch > 2) { set_error("ladi_tryon_set_feature_cache: branch " + std::to_string(branch) + " out of range [0, 2]"); return -2; }
+    return guarded("ladi_tryon_set_feature_cache", [&]() {
+        t->t.fc_plan.assign(full_flags_host, full_flags_host + count);
+        t->t.fc_branch = branch;
+        return 0;
+    });
+}
+int ladi_tryon_shallow_evals(ladi_tryon* t) { return t ? t->t.last_shallow : -1; }
 int ladi_tryon_set_step_callback(ladi_tryon* t, ladi_step_callback fn, void* user, int every, float* latents_nchw_dev) {
     if (!t) { set_error("ladi_tryon_set_step_callback: null handle"); return -1; }
     if (fn && (every < 1 || !latents_nchw_dev)) { set_error("ladi_tryon_set_step_callback: every must be >= 1 and the latents buffer set"); return -1; }

@@ -201,6 +201,20 @@ struct UNetCfg {
     float eps = 1e-5f;
 };
 
+// Deep-feature cache of the 64x48 level (DeepCache, level 0 only).  A whole forward in mode CAPTURE copies the hidden state that enters
+// up_blocks.3.resnets.(L - branch) -- before the concatenation with its skip -- into `buf`; a forward in mode SHALLOW runs conv_in, layers
+// 0 .. branch-1 of down_blocks.0, then up_blocks.3 layers L-branch .. L from that tensor, conv_norm_out and conv_out, and nothing else.
+// That tensor has boc[0] channels for branch < L (an output of up_blocks.3) and boc[1] for branch = L (the output of up_blocks.2's
+// upsampler): UNet::fc_channels.
+// buf: caller-owned fp16 [samples of the context batch][h][w][fc_channels(branch)]; a forward reads / writes the rows of its own samples
+// (sample0, as the cross-attention K/V cache), so sub-batch forwards (cond-only evaluations, sample-group lanes) share one buffer.  The
+// cached half brings no statistics rows: the consuming GroupNorm recomputes them (gn_partial), as for any source without producer rows.
+struct FeatCache {
+    enum { NONE = 0, CAPTURE = 1, SHALLOW = 2 };
+    int mode = NONE, branch = 0;
+    h16* buf = nullptr;
+};
+
 struct UNet {
     UNetCfg cfg;
     DevPool pool;
@@ -226,7 +240,13 @@ struct UNet {
     int compute_temb(const float* timesteps_host, int count, hipStream_t st);  // fills temb_table rows [0,count)
     // x: [n,h,w,64] padded NHWC input; returns eps Act [n,h,w,4(ld 4)]
     // eps_out (optional): pre-allocated output view (rows of a shared buffer); sample0: index of x's first sample in the context batch
-    Act forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_idx, const Act* eps_out = nullptr, int sample0 = 0);
+    // fc (optional): deep-feature cache mode of this forward (FeatCache); null or mode NONE launches exactly the plain forward
+    Act forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_idx, const Act* eps_out = nullptr, int sample0 = 0,
+                const FeatCache* fc = nullptr);
+    int fc_channels(int branch) const { return cfg.boc[branch >= cfg.layers_per_block ? 1 : 0]; }   // channels of the cached tensor
+    // cache of the stand-alone entry ladi_unet_forward_cached: grow-only buffer over the context batch, the geometry it was captured at and
+    // which sample rows hold a capture made since the last set_context
+    h16* fc_buf = nullptr; size_t fc_cap = 0; int fc_h = 0, fc_w = 0, fc_branch = -1; std::vector<char> fc_rows;
     ~UNet();
 };
 
@@ -255,7 +275,7 @@ struct UNetLanes {
     // sub-group form (cond-only evaluations of a CFG-shaped run): x / eps hold x.n < n samples that start at index sample0 of the context
     // batch, and run on sub_lanes(x.n) of the configured lanes, in their arenas (planned by a dry pass of this form too)
     void forward(UNet& u, hipStream_t main_st, bool dry, bool concurrent, const Act& x, const Act& eps, const float* temb, const int* tidx,
-                 int sample0 = 0);
+                 int sample0 = 0, const FeatCache* fc = nullptr);
     int sub_lanes(int n_sub) const { int g = G; while (g > 1 && (n_sub % g)) --g; return g; }   // the default rule: lowered until it divides
     void commit_plan();                     // after the dry pass: (re)allocate what grew; not capturable
     unsigned long long key() const;         // part of the hipGraph key: lane count and every address a captured lane may touch
@@ -474,6 +494,14 @@ struct TryOn {
     float* d_gtab = nullptr; int gtab_cap = 0; float* d_factor = nullptr; int factor_cap = 0;
     hipGraph_t graph_cond = nullptr; hipGraphExec_t gexec_cond = nullptr;
     int last_cond_only = 0;   // evaluations of the last run that ran cond-only (ladi_tryon_cond_only_evals)
+    // deep-feature cache (ladi_tryon_set_feature_cache, sticky; empty plan = off): fc_plan holds one flag per evaluation, 1 = whole forward
+    // (which captures into fcache), 0 = shallow forward from fcache at fc_branch.  The loop then has up to four evaluation forms,
+    // {whole, shallow} x {2B samples, cond-only}: graph / gexec, graph_cond / gexec_cond and the two below, all under graph_key.  fcache is
+    // persistent (outside the per-evaluation arena region) and grow-only: fp16 [n][h][w][fc_channels]
+    std::vector<unsigned char> fc_plan; int fc_branch = 0;
+    h16* fcache = nullptr; size_t fcache_cap = 0;
+    hipGraph_t graph_sh[2] = {nullptr, nullptr}; hipGraphExec_t gexec_sh[2] = {nullptr, nullptr};   // shallow forms: [0] 2B samples, [1] cond-only
+    int last_shallow = 0;     // evaluations of the last run that ran shallow, after promotion (ladi_tryon_shallow_evals)
     // step callback (ladi_tryon_set_step_callback): after evaluation i with i % cb_every == 0 the latents go to the caller's fp32 NCHW
     // cb_latents, cb_fn(cb_user, i) runs on the host, and cb_latents comes back (edits included); fn == null = off
     int (*cb_fn)(void*, int) = nullptr; void* cb_user = nullptr; int cb_every = 1; float* cb_latents = nullptr;

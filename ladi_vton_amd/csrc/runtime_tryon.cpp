@@ -8,12 +8,17 @@
 namespace ladi {
 
 #define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw std::runtime_error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+// outside a try block of run(): report and return
+#define HIP_OK_RC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error(std::string("tryon: " #x ": ") + hipGetErrorString(e_)); return -100; } } while (0)
 
 TryOn::~TryOn() {
     if (gexec) (void)hipGraphExecDestroy(gexec);
     if (graph) (void)hipGraphDestroy(graph);
     if (gexec_cond) (void)hipGraphExecDestroy(gexec_cond);
     if (graph_cond) (void)hipGraphDestroy(graph_cond);
+    for (auto& g : gexec_sh) if (g) (void)hipGraphExecDestroy(g);
+    for (auto& g : graph_sh) if (g) (void)hipGraphDestroy(g);
+    if (fcache) (void)hipFree(fcache);
     if (stats) (void)hipFree(stats);
     if (step_noise_buf) (void)hipFree(step_noise_buf);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
@@ -96,6 +101,30 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
     auto cond_only = [&](int i) { return guided && !(gtab[i] > 1.0f); };
     bool any_cond_only = false;
     for (int i = 0; i < evals; ++i) any_cond_only = any_cond_only || cond_only(i);
+    // deep-feature cache plan (ladi_tryon_set_feature_cache): one flag per evaluation, 1 = whole forward.  A plan without a shallow evaluation
+    // is the plain run: capture stays off.  The one promotion, on the host: a shallow evaluation over all 2B samples needs a cache whose two
+    // halves were written by the same whole evaluation, so after a whole evaluation that ran cond-only (rows [B, 2B) only) it runs whole
+    if (!fc_plan.empty()) {
+        if ((int)fc_plan.size() != evals) {
+            set_error("tryon: the feature-cache plan has " + std::to_string(fc_plan.size()) + " entries, this run has " + std::to_string(evals) +
+                      " evaluations (PNDM: steps + 1" + (first_step ? "; the run starts at step " + std::to_string(first_step) + " of " +
+                      std::to_string(in.steps) : std::string()) + ")");
+            return -10;
+        }
+        if (!fc_plan[0]) { set_error("tryon: the feature-cache plan must start with a whole evaluation (flag 0 = 1)"); return -10; }
+    }
+    std::vector<unsigned char> whole(evals, 1);
+    bool fc_on = false;
+    if (!fc_plan.empty()) {
+        bool halves_differ = false;      // the most recent whole evaluation refreshed the conditional rows only
+        for (int i = 0; i < evals; ++i) {
+            whole[i] = fc_plan[i] ? 1 : 0;
+            if (!whole[i] && cfgf && !cond_only(i) && halves_differ) whole[i] = 1;
+            if (whole[i]) halves_differ = cfgf && cond_only(i);
+            fc_on = fc_on || !whole[i];
+        }
+    }
+    last_shallow = 0;
     const bool use_factor = guided && phi > 0.f;
     const bool cloth_zero_from_start = has_cloth && in.cloth_zero_from <= 0;
     last_evals = evals;
@@ -124,6 +153,16 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
             step_noise_buf = nullptr; step_noise_cap = 0;
             HIP_OK(hipMalloc(reinterpret_cast<void**>(&step_noise_buf), step_noise_bytes));
             step_noise_cap = step_noise_bytes;
+        }
+    }
+    // every argument check is behind us: only now grow the feature cache (a refused run leaves it, and the graphs that hold it, alone)
+    if (fc_on) {
+        const size_t need = (size_t)n * hw * unet->fc_channels(fc_branch);
+        if (need > fcache_cap) {
+            if (fcache) HIP_OK_RC(hipFree(fcache));
+            fcache = nullptr; fcache_cap = 0;
+            HIP_OK_RC(hipMalloc(reinterpret_cast<void**>(&fcache), need * sizeof(h16)));
+            fcache_cap = need;
         }
     }
 
@@ -241,14 +280,17 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
             const size_t mk_loop = arena.mark();
             // cond: a cond-only evaluation of a guided run -- the UNet runs over the conditional samples [B, 2B) (their rows of unet_in and
             // eps, their part of the K/V cache) and the step kernel, told by the table, reads only those rows of eps
-            auto one_step = [&](bool concurrent, bool cond = false) {
+            // sh: a shallow evaluation (feature cache); a whole evaluation of a cached run captures
+            auto one_step = [&](bool concurrent, bool cond = false, bool sh = false) {
                 arena.release(mk_loop);
+                FeatCache fcs; fcs.mode = sh ? FeatCache::SHALLOW : FeatCache::CAPTURE; fcs.branch = fc_branch; fcs.buf = fcache;
+                const FeatCache* fc = fc_on ? &fcs : nullptr;
                 if (cond) {
                     Act xs = unet_in, es = eps;
                     xs.n = B; xs.p = unet_in.p + (size_t)B * hw * unet_in.ld;
                     es.n = B; es.p = eps.p + (size_t)B * hw * eps.ld;
-                    lanes.forward(*unet, st, c.dry(), concurrent, xs, es, unet->temb_table, d_step, B);
-                } else lanes.forward(*unet, st, c.dry(), concurrent, unet_in, eps, unet->temb_table, d_step);
+                    lanes.forward(*unet, st, c.dry(), concurrent, xs, es, unet->temb_table, d_step, B, fc);
+                } else lanes.forward(*unet, st, c.dry(), concurrent, unet_in, eps, unet->temb_table, d_step, 0, fc);
                 if (c.dry()) return;
                 sa.eps = eps.p; sa.ld_eps = eps.ld;
                 if (use_factor && !cond)
@@ -270,20 +312,29 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 HIP_OK(hipStreamWaitEvent(st, ev_in, 0));
                 c.check(ladi_launch_latents_import(cb_latents, B, hw, latents, unet_in.p, 64, cfgf, table[i].in_scale_next, st), "callback import");
             };
-            // the first evaluation of either form runs its lanes one after the other (one-time function attribute setup, per-shape tile measurement)
-            bool seen[2] = {false, false};
+            // the forms of an evaluation: bit 0 cond-only, bit 1 shallow.  Which ones this run has, for the planning pass
+            auto form = [&](int i) { return (cond_only(i) ? 1 : 0) | (whole[i] ? 0 : 2); };
+            bool has_form[4] = {false, false, false, false};
+            for (int i = 0; i < evals; ++i) has_form[form(i)] = true;
+            // the first evaluation of any form runs its lanes one after the other (one-time function attribute setup, per-shape tile measurement)
+            bool seen[4] = {false, false, false, false};
             // an evaluation whose forward ran over B samples (launched eagerly or by replaying the cond-only graph; every one of a run without CFG)
-            auto ran = [&](bool co) { if (co || !cfgf) ++last_cond_only; };
-            if (c.dry()) { one_step(false); if (any_cond_only) one_step(false, true); }
+            auto ran = [&](int f) { if ((f & 1) || !cfgf) ++last_cond_only; if (f & 2) ++last_shallow; };
+            if (c.dry()) {
+                one_step(false);
+                if (any_cond_only) one_step(false, true);
+                if (has_form[2]) one_step(false, false, true);
+                if (has_form[3]) one_step(false, true, true);
+            }
             else if (!in.use_graph || evals < 3) {
                 for (int i = 0; i < evals && !cb_rc; ++i) {
-                    const bool co = cond_only(i);
-                    one_step(i > 0 && seen[co], co); seen[co] = true; ran(co);
+                    const int f = form(i);
+                    one_step(i > 0 && seen[f], f & 1, f & 2); seen[f] = true; ran(f);
                     callback_point(i);
                 }
             } else {
-                one_step(false, cond_only(0));  // eager first evaluation
-                seen[cond_only(0)] = true; ran(cond_only(0));
+                one_step(false, cond_only(0));  // eager first evaluation (always whole)
+                seen[form(0)] = true; ran(form(0));
                 callback_point(0);
                 unsigned long long key = 0x1234;
                 key = mix(key, (unsigned long long)(uintptr_t)arena.base); key = mix(key, (unsigned long long)B * 1000003ULL + H * 4099ULL + W);
@@ -304,33 +355,41 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 unsigned pb; std::memcpy(&pb, &phi, 4);
                 key = mix(key, (unsigned long long)(uintptr_t)sa.guidance_tab); key = mix(key, (unsigned long long)(uintptr_t)sa.factor);
                 key = mix(key, guided ? 0x100000000ULL | pb : 0ULL);
+                // ... and with the feature cache: its buffer, the branch and whether whole evaluations capture (a graph captured with
+                // capture on is never replayed for a plain run, nor the reverse)
+                key = mix(key, fc_on ? (unsigned long long)(uintptr_t)fcache : 0ULL);
+                key = mix(key, fc_on ? 0x200000000ULL | (unsigned long long)fc_branch : 0ULL);
                 if (key != graph_key) {
                     if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
                     if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
                     if (gexec_cond) { (void)hipGraphExecDestroy(gexec_cond); gexec_cond = nullptr; }
                     if (graph_cond) { (void)hipGraphDestroy(graph_cond); graph_cond = nullptr; }
+                    for (auto& g : gexec_sh) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+                    for (auto& g : graph_sh) if (g) { (void)hipGraphDestroy(g); g = nullptr; }
                     graph_key = key;
                 }
-                auto capture = [&](bool co) {
-                    hipGraph_t& gr = co ? graph_cond : graph;
-                    hipGraphExec_t& ge = co ? gexec_cond : gexec;
+                hipGraph_t* const grs[4] = {&graph, &graph_cond, &graph_sh[0], &graph_sh[1]};
+                hipGraphExec_t* const ges[4] = {&gexec, &gexec_cond, &gexec_sh[0], &gexec_sh[1]};
+                auto capture = [&](int f) {
+                    hipGraph_t& gr = *grs[f];
+                    hipGraphExec_t& ge = *ges[f];
                     if (gr) { (void)hipGraphDestroy(gr); gr = nullptr; }     // left by a capture whose instantiation failed
                     HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-                    try { one_step(true, co); } catch (...) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(st, &g); if (g) (void)hipGraphDestroy(g); throw; }
+                    try { one_step(true, f & 1, f & 2); } catch (...) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(st, &g); if (g) (void)hipGraphDestroy(g); throw; }
                     HIP_OK(hipStreamEndCapture(st, &gr));
                     HIP_OK(hipGraphInstantiate(&ge, gr, nullptr, nullptr, 0));
                 };
                 // the host knows the schedule and picks the graph; the values come from the device table.  A form that this run has not yet
                 // run eagerly and that has no graph runs eagerly once (see above), its next evaluation captures
                 for (int i = 1; i < evals && !cb_rc; ++i) {
-                    const bool co = cond_only(i);
-                    hipGraphExec_t& ge = co ? gexec_cond : gexec;
-                    if (!ge && !seen[co]) { one_step(false, co); seen[co] = true; }
+                    const int f = form(i);
+                    hipGraphExec_t& ge = *ges[f];
+                    if (!ge && !seen[f]) { one_step(false, f & 1, f & 2); seen[f] = true; }
                     else {
-                        if (!ge) capture(co);
+                        if (!ge) capture(f);
                         HIP_OK(hipGraphLaunch(ge, st));
                     }
-                    ran(co);
+                    ran(f);
                     callback_point(i);
                 }
             }

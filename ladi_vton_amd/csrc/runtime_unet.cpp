@@ -101,6 +101,7 @@ UNet::~UNet() {
     if (temb_table) (void)hipFree(temb_table);
     if (stats) (void)hipFree(stats);
     if (in_buf) (void)hipFree(in_buf);
+    if (fc_buf) (void)hipFree(fc_buf);
 }
 
 int UNet::set_context(const h16* ehs, int n, int L, hipStream_t st) {
@@ -122,6 +123,7 @@ int UNet::set_context(const h16* ehs, int n, int L, hipStream_t st) {
         ctx_cap_n = n * L; ctx_cap_samples = n;
     }
     ctx_n = n; ctx_L = L;
+    fc_rows.assign((size_t)n, 0);            // the stand-alone entry's deep-feature cache belongs to the context it was captured under
     for (auto* x : all) {
         IGemmArgs a; std::memset(&a, 0, sizeof(a));
         a.src0 = ehs; a.C0 = cfg.cross_dim; a.ld0 = cfg.cross_dim;
@@ -271,7 +273,20 @@ struct Fwd {
 
 }  // namespace
 
-Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_idx, const Act* eps_out, int sample0) {
+Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_idx, const Act* eps_out, int sample0, const FeatCache* fc) {
+    // deep-feature cache (runtime.h FeatCache): `shallow` skips every layer outside the 64x48 level's outermost `branch` layers; the layer
+    // sequence below stays the only one -- a skipped layer only advances the weight indices
+    const int L = cfg.layers_per_block;
+    const int fmode = fc ? fc->mode : FeatCache::NONE, fbranch = fc ? fc->branch : 0;
+    const bool shallow = fmode == FeatCache::SHALLOW;
+    if (fmode != FeatCache::NONE && (fbranch < 0 || fbranch > L || (!fc->buf && !c.dry())))
+        throw std::runtime_error("UNet::forward: feature cache needs a buffer and a branch in [0, layers_per_block]");
+    // the cached tensor: rows of this forward's samples, [n, h, w, fc_channels(branch)] dense, no producer statistics
+    auto cache_view = [&]() {
+        Act a; a.n = x.n; a.h = x.h; a.w = x.w; a.c = fc_channels(fbranch); a.ld = a.c;
+        a.p = fc->buf ? fc->buf + (size_t)sample0 * x.h * x.w * a.c : nullptr;
+        return a;
+    };
     if ((eps_out ? sample0 + x.n > ctx_n : ctx_n != x.n) && !c.dry()) throw std::runtime_error("UNet::forward: set_context batch mismatch");
     Fwd f{c, *this, temb_row, temb_idx, sample0};
     ProbeScope probe_scope(c, probe);
@@ -282,7 +297,6 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
         std::snprintf(name, sizeof(name), fmt, i, j);
         c.probe_point(name, a);
     };
-    const int L = cfg.layers_per_block;
     std::vector<Act> skips;
     ConvOpt o; o.stats = true;
     Act h = conv2d(c, conv_in, x, nullptr, o);
@@ -291,36 +305,54 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
     int ri = 0, xi = 0;
     for (int i = 0; i < 4; ++i) {
         for (int j = 0; j < L; ++j) {
+            if (shallow && (i > 0 || j >= fbranch)) { ++ri; if (i < 3) ++xi; continue; }
             h = f.res(down_res[ri++], h, nullptr);
             pp(h, "down_blocks.%d.resnets.%d", i, j);
             if (i < 3) { h = f.xf(down_xf[xi++], h); pp(h, "down_blocks.%d.attentions.%d", i, j); }
             skips.push_back(h);
         }
-        if (i < 3) {
+        if (i < 3 && !shallow) {
             ConvOpt od; od.stride = 2; od.pad = 1; od.stats = true;
             h = conv2d(c, down_samp[i], h, nullptr, od);
             pp(h, "down_blocks.%d.downsamplers.0", i);
             skips.push_back(h);
         }
     }
-    h = f.res(mid_res[0], h, nullptr);
-    pp(h, "mid_block.resnets.0");
-    h = f.xf(mid_xf, h);
-    pp(h, "mid_block.attentions.0");
-    h = f.res(mid_res[1], h, nullptr);
-    pp(h, "mid_block.resnets.1");
+    if (!shallow) {
+        h = f.res(mid_res[0], h, nullptr);
+        pp(h, "mid_block.resnets.0");
+        h = f.xf(mid_xf, h);
+        pp(h, "mid_block.attentions.0");
+        h = f.res(mid_res[1], h, nullptr);
+        pp(h, "mid_block.resnets.1");
+    }
     // diffusers' `forward_upsample_size`: when a latent side is not a multiple of 2^3 (three upsamplers), the down path rounded a level up
     // (ceil(H / 2)) and every upsampler stretches to the size of the skip it is concatenated with; else each one doubles
     const bool ups_to_skip = (x.h % 8) || (x.w % 8);
     ri = 0; xi = 0;
     for (int i = 0; i < 4; ++i) {
         for (int j = 0; j < L + 1; ++j) {
+            // the cache point: the hidden state that enters up_blocks.3.resnets.(L - branch), before the concatenation with its skip
+            const bool cache_pt = fmode != FeatCache::NONE && i == 3 && j == L - fbranch;
+            if (shallow && !cache_pt && (i < 3 || j < L - fbranch)) { ++ri; if (i > 0) ++xi; continue; }
+            if (cache_pt) {
+                Act cv = cache_view();
+                if (shallow) h = cv;
+                else {
+                    if (h.n != cv.n || h.h != cv.h || h.w != cv.w || h.c != cv.c || h.ld != h.c)
+                        throw std::runtime_error("UNet::forward: the tensor at the cache point does not have the cache's shape");
+                    if (!c.dry()) {
+                        hipError_t e = hipMemcpyAsync(cv.p, h.p, h.pixels() * (size_t)h.c * sizeof(h16), hipMemcpyDeviceToDevice, c.st);
+                        if (e != hipSuccess) throw std::runtime_error(std::string("UNet::forward: feature cache capture: ") + hipGetErrorString(e));
+                    }
+                }
+            }
             Act sk = skips.back(); skips.pop_back();
             h = f.res(up_res[ri++], h, &sk);
             pp(h, "up_blocks.%d.resnets.%d", i, j);
             if (i > 0) { h = f.xf(up_xf[xi++], h); pp(h, "up_blocks.%d.attentions.%d", i, j); }
         }
-        if (i < 3) {
+        if (i < 3 && !shallow) {
             ConvOpt ou; ou.ups = 1; ou.stats = true;
             if (ups_to_skip) { ou.ups_h = skips.back().h; ou.ups_w = skips.back().w; }
             h = conv2d(c, up_samp[i], h, nullptr, ou);
@@ -372,7 +404,7 @@ void UNetLanes::configure(int n, int g) {
 }
 
 void UNetLanes::forward(UNet& u, hipStream_t main_st, bool dry, bool concurrent, const Act& x, const Act& eps, const float* temb, const int* tidx,
-                        int sample0) {
+                        int sample0, const FeatCache* fc) {
     const int Gu = sub_lanes(x.n);          // the configured count when it divides x.n (always, for the whole batch)
     const int ng = x.n / Gu;
     const bool par = concurrent && !dry && Gu > 1;
@@ -385,7 +417,7 @@ void UNetLanes::forward(UNet& u, hipStream_t main_st, bool dry, bool concurrent,
         if (!dry && stats_cap[g]) HIP_OK_L(hipMemsetAsync(stats[g], 0, stats_cap[g] * sizeof(float), sg));
         Act xg = x; xg.n = ng; xg.p = x.p + (size_t)g * ng * x.h * x.w * x.ld;
         Act eg = eps; eg.n = ng; eg.p = eps.p + (size_t)g * ng * eps.h * eps.w * eps.ld; eg.st_part = nullptr; eg.st_px = 0;
-        (void)u.forward(c, xg, temb, tidx, &eg, sample0 + g * ng);
+        (void)u.forward(c, xg, temb, tidx, &eg, sample0 + g * ng, fc);
         if (dry) { peak[g] = arena[g].peak; if (c.stats_peak > stats_peak[g]) stats_peak[g] = c.stats_peak; }
         if (par && g > 0) { HIP_OK_L(hipEventRecord(join[g], sg)); HIP_OK_L(hipStreamWaitEvent(main_st, join[g], 0)); }
     }

@@ -142,15 +142,29 @@ class NativeUNet(_Base):
         self._ctx_key = key
         self._ctx_keepalive = (ehs, e)
 
-    def __call__(self, sample, timestep, encoder_hidden_states=None, **kw):
+    FEATURE_CACHE_MODES = {None: 0, "capture": 1, "reuse": 2}
+
+    def __call__(self, sample, timestep, encoder_hidden_states=None, feature_cache=None, cache_branch=0, sample0=0, **kw):
+        """feature_cache: None, "capture" (the whole forward, which also caches the deep features of the full-resolution level) or "reuse"
+        (the shallow forward from that cache: the outermost cache_branch + 1 layers only; ladi_unet_forward_cached).  sample0: the samples
+        are rows [sample0, sample0 + n) of the encoder_hidden_states batch (their own rows of the K/V and feature caches)."""
         if encoder_hidden_states is None:
             raise ValueError("encoder_hidden_states is required")
+        if feature_cache not in self.FEATURE_CACHE_MODES:
+            raise ValueError("feature_cache has to be None, 'capture' or 'reuse' but is %r" % (feature_cache,))
+        if isinstance(cache_branch, bool) or not isinstance(cache_branch, int) or not 0 <= cache_branch <= self.cfg["layers_per_block"]:
+            raise ValueError("cache_branch has to be in [0, %d] but is %r" % (self.cfg["layers_per_block"], cache_branch))
         self.set_context(encoder_hidden_states)
         x = sample.contiguous()
         n, C, h, w = x.shape
         if C != self.cfg["in_channels"]:
             raise ValueError("expected %d input channels, got %d" % (self.cfg["in_channels"], C))
         out = torch.empty((n, self.cfg["out_channels"], h, w), dtype=x.dtype, device=x.device)
+        if feature_cache is not None or sample0:
+            check(self.lib.ladi_unet_forward_cached_rows(self.h, ptr(x), dtype_code(x), n, h, w, float(timestep), ptr(out), dtype_code(out),
+                                                         self.FEATURE_CACHE_MODES[feature_cache], int(cache_branch), int(sample0), stream_ptr()),
+                  "ladi_unet_forward_cached")
+            return SimpleNamespace(sample=out)
         check(self.lib.ladi_unet_forward(self.h, ptr(x), dtype_code(x), n, h, w, float(timestep), ptr(out), dtype_code(out), stream_ptr()),
               "ladi_unet_forward")
         return SimpleNamespace(sample=out)
@@ -158,6 +172,13 @@ class NativeUNet(_Base):
     def time_forward(self, n, h, w, iters):
         ms = c_float(0)
         check(self.lib.ladi_unet_time_forward(self.h, n, h, w, iters, ctypes.byref(ms), stream_ptr()), "ladi_unet_time_forward")
+        return ms.value
+
+    def time_forward_cached(self, n, h, w, iters, feature_cache="reuse", cache_branch=0):
+        """average ms of one forward in a feature-cache mode ("capture" / "reuse"), measured like time_forward"""
+        ms = c_float(0)
+        check(self.lib.ladi_unet_time_forward_cached(self.h, n, h, w, iters, self.FEATURE_CACHE_MODES[feature_cache], int(cache_branch),
+                                                     ctypes.byref(ms), stream_ptr()), "ladi_unet_time_forward_cached")
         return ms.value
 
     def time_forward_lanes(self, n, h, w, iters, lanes=0, use_graph=True):

@@ -58,6 +58,62 @@ def guidance_plan(guidance_scale, n_evals, guidance_rescale=0.0):
     return table, (table[0] if table else 1.0), any(g > 1.0 for g in table)
 
 
+def feature_cache_plan(n_evals, interval, cond_only=None):
+    """-> one bool per evaluation, True = whole UNet forward (which refreshes the deep-feature cache), False = shallow forward from the cache,
+    after the loop's one promotion.  interval: an int N >= 1 (whole at i % N == 0) or a sequence of n_evals truthy / falsy entries; entry 0 is
+    always whole.  cond_only: None, or one truthy entry per evaluation that runs cond-only inside a CFG-shaped run (a guidance schedule's
+    scale <= 1).  Promotion: a shallow evaluation over all 2B samples needs both halves of the cache from the same whole evaluation, so when
+    the most recent whole evaluation ran cond-only it runs whole instead; a shallow cond-only evaluation is never promoted.  Raises ValueError
+    for an interval < 1 or of another type, or a sequence of the wrong length."""
+    n = int(n_evals)
+    if n < 0:
+        raise ValueError("feature_cache_plan: n_evals >= 0")
+    if isinstance(interval, bool) or (isinstance(interval, numbers.Real) and not isinstance(interval, numbers.Integral)):
+        raise ValueError("`feature_cache` interval has to be an integer >= 1 but is %r." % (interval,))
+    if isinstance(interval, numbers.Integral):
+        if interval < 1:
+            raise ValueError("`feature_cache` interval has to be an integer >= 1 but is %r." % (interval,))
+        flags = [i % int(interval) == 0 for i in range(n)]
+    else:
+        try:
+            flags = [bool(f) for f in interval]
+        except TypeError:
+            raise ValueError("`feature_cache` has to be an int, a dict or a sequence but is %r." % (interval,))
+        if len(flags) != n:
+            raise ValueError("`feature_cache` has %d entries but the scheduler runs %d evaluations (len(scheduler.timesteps))." % (len(flags), n))
+    if flags:
+        flags[0] = True
+    co = [False] * n if cond_only is None else [bool(c) for c in cond_only]
+    if len(co) != n:
+        raise ValueError("feature_cache_plan: cond_only has %d entries for %d evaluations" % (len(co), n))
+    halves_differ = False       # the most recent whole evaluation refreshed the conditional rows only
+    for i in range(n):
+        if not flags[i] and not co[i] and halves_differ:
+            flags[i] = True
+        if flags[i]:
+            halves_differ = co[i]
+    return flags
+
+
+def feature_cache_spec(feature_cache, n_evals):
+    """-> (flags or None, branch) of a `feature_cache=` argument: None (off), an int N >= 1, a dict {"interval": N or a sequence, "branch": k}
+    or a sequence of one truthy / falsy entry per evaluation.  flags is None when no evaluation would run shallow (N = 1, all true): that is
+    the plain run.  n_evals: the count or a callable returning it.  Raises ValueError for a bad interval, a branch outside 0..2, unknown dict
+    keys or a wrong sequence length."""
+    if feature_cache is None:
+        return None, 0
+    interval, branch = feature_cache, 0
+    if isinstance(feature_cache, dict):
+        extra = set(feature_cache) - {"interval", "branch"}
+        if extra or "interval" not in feature_cache:
+            raise ValueError("`feature_cache` dict takes the keys 'interval' and 'branch', got %r." % (sorted(feature_cache),))
+        interval, branch = feature_cache["interval"], feature_cache.get("branch", 0)
+    if isinstance(branch, bool) or not isinstance(branch, numbers.Integral) or not 0 <= branch <= 2:
+        raise ValueError("`feature_cache` branch has to be 0, 1 or 2 but is %r." % (branch,))
+    flags = feature_cache_plan(n_evals() if callable(n_evals) else n_evals, interval)
+    return (None if all(flags) else flags), int(branch)
+
+
 def strength_first_step(strength, num_inference_steps):
     """-> first_step: the step of the schedule a run with `strength` starts at.  diffusers' get_timesteps arithmetic in Python float64:
     init_timestep = min(int(N * strength), N), first_step = N - init_timestep.  Raises ValueError for a strength outside [0, 1] or not finite,
@@ -104,6 +160,14 @@ class StableDiffusionTryOnePipeline:
         self.trace_evals = 0          # > 0: the next fused runs record per-evaluation noise_pred / latents into self.last_trace
         self.lanes = None             # sample-group lanes of the fused loop's UNet forward (None: library default, LADI_UNET_LANES or 1)
         self._range_probe = None
+        self._shallow_evals = None    # modular runs count here; fused runs ask the library
+
+    @property
+    def shallow_evals(self):
+        """how many evaluations of the last run ran shallow (`feature_cache=`), after promotion (fused: ladi_tryon_shallow_evals)"""
+        if self._shallow_evals is not None:
+            return self._shallow_evals
+        return _lib.load().ladi_tryon_shallow_evals(self._tryon) if self._tryon else None
 
     @property
     def range_probe(self):
@@ -224,7 +288,8 @@ class StableDiffusionTryOnePipeline:
                  guidance_scale=7.5, negative_prompt=None, num_images_per_prompt=1, eta=0.0, prompt_embeds=None,
                  negative_prompt_embeds=None, generator=None, latents=None, output_type="pil", return_dict=True, callback=None,
                  callback_steps=1, cloth_cond_rate=1.0, no_pose=False, cloth_input_type="warped", fused=True, noise=None,
-                 use_graph=True, guidance_rescale=0.0, strength=1.0, init_image=None, init_latents=None, init_is_noisy=False):
+                 use_graph=True, guidance_rescale=0.0, strength=1.0, init_image=None, init_latents=None, init_is_noisy=False,
+                 feature_cache=None):
         """tryon_pipe.py's __call__.  `guidance_scale`: a float, a sequence with one scale per evaluation (len(scheduler.timesteps); PNDM: steps
         + 1) or a callable f(i, n_evals) -- see guidance_interval.  Classifier-free guidance is on if any scale is > 1; an evaluation whose scale
         is <= 1 then runs the UNet over the conditional samples only.  `guidance_rescale` (rescale_noise_cfg's phi, [0, 1]) acts on the CFG
@@ -239,7 +304,14 @@ class StableDiffusionTryOnePipeline:
         noise of `latents=` / RNG draw #2; `init_is_noisy=True` takes the init as the loop's latents at that timestep unchanged (resume).
         Everything indexed per evaluation (a guidance schedule, the callback's i, scheduler.timesteps, the cloth cut-off of `cloth_cond_rate`)
         refers to the tail.  PNDM restarts as a fresh PLMS run over the tail (tail steps + 1 evaluations, at least 2 steps).  strength = 1.0
-        ignores a given init and is the plain run."""
+        ignores a given init and is the plain run.
+
+        `feature_cache` (DeepCache on the full-resolution level; None = off): an int N (every N-th evaluation runs the whole UNet, the others
+        only its outermost layers on the deep features the last whole one cached), a dict {"interval": N, "branch": k} (k = 0, 1, 2: how many
+        layers of the first down block, and as many more of the last up block, a shallow evaluation runs; default 0) or a sequence of one
+        truthy (whole) / falsy (shallow) entry per evaluation.  Evaluation 0 is always whole; N = 1 or an all-true sequence is the plain run.
+        See feature_cache_plan for the one promotion rule; the cloth cut-off, a callback's edit of the latents and PNDM's double evaluation
+        reuse the cache as it is.  Needs the native UNet.  `pipe.shallow_evals` counts the shallow evaluations of the last run."""
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
@@ -271,6 +343,10 @@ class StableDiffusionTryOnePipeline:
         if first_step > 0:
             n_evals()      # a first_step the scheduler cannot start at (a PNDM tail of one step) fails here, before any work
         g_table, guidance_scale, do_cfg = guidance_plan(guidance_scale, n_evals, guidance_rescale)
+        fc_flags, fc_branch = feature_cache_spec(feature_cache, n_evals)
+        if feature_cache is not None and not isinstance(self.unet, NativeUNet):
+            raise ValueError("`feature_cache` needs the native UNet (NativeUNet), the pipeline holds %s." % type(self.unet).__name__)
+        self._shallow_evals = None
         device = self._execution_device
         pe, neg = self._encode_prompt(prompt, device, num_images_per_prompt, do_cfg, negative_prompt, prompt_embeds, negative_prompt_embeds)
         B = pe.shape[0]
@@ -306,7 +382,8 @@ class StableDiffusionTryOnePipeline:
                                      n_cloth, n_lat, n_mask, height, width, num_inference_steps, guidance_scale, cloth_cond_rate,
                                      no_pose, use_graph, step_noise=step_noise, eta=ddim_eta, callback=callback,
                                      callback_steps=callback_steps, guidance_table=g_table, guidance_rescale=guidance_rescale,
-                                     init_latents=init, first_step=first_step, init_is_noisy=init_is_noisy)
+                                     init_latents=init, first_step=first_step, init_is_noisy=init_is_noisy,
+                                     feature_cache=(fc_flags, fc_branch))
             # prepare_mask_and_masked_image binarises the caller's mask in place; keep that side effect
             mask_image[mask_image < 0.5] = 0
             mask_image[mask_image >= 0.5] = 1
@@ -315,7 +392,7 @@ class StableDiffusionTryOnePipeline:
                                        n_cloth, n_lat, n_mask, height, width, num_inference_steps, guidance_scale, cloth_cond_rate,
                                        no_pose, eta, generator, callback, callback_steps, guidance_table=g_table,
                                        guidance_rescale=guidance_rescale, init_latents=init, first_step=first_step,
-                                       init_is_noisy=init_is_noisy)
+                                       init_is_noisy=init_is_noisy, feature_cache=(fc_flags, fc_branch))
         if output_type == "pil":
             images = numpy_to_pil(images)
         if not return_dict:
@@ -343,7 +420,7 @@ class StableDiffusionTryOnePipeline:
     # -------------------------------------------------------------------------------------------------------
     def _run_fused(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose,
                    use_graph, return_device=False, out_uint8=False, lanes=None, step_noise=None, eta=0.0, callback=None, callback_steps=1,
-                   guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0, init_is_noisy=False):
+                   guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0, init_is_noisy=False, feature_cache=None):
         """return_device: hand back the device tensor (no host copy); out_uint8: the batch as uint8 [B,H,W,3] = numpy_to_pil's
         (images * 255).round() computed by the decode epilogue (ladi_tryon_run_u8); lanes: sample-group lanes of the UNet forward;
         step_noise: fp32 [steps, B, 4, h, w], the per-step noise of EulerAncestralDiscreteScheduler and of DDIM with eta > 0
@@ -355,7 +432,9 @@ class StableDiffusionTryOnePipeline:
         guard re-runs the batch (below), the whole loop runs again and the callback sees every step a second time.
         init_latents / first_step / init_is_noisy (ladi_tryon_set_init): start at step first_step > 0 of the `steps`-step schedule from the fp32
         [B, 4, hs, ws] init_latents (None or first_step = 0: off).  The run then has the tail's evaluations: step_noise, guidance_table, the
-        callback's i and the cloth cut-off of `ccr` all refer to them."""
+        callback's i and the cloth cut-off of `ccr` all refer to them.
+        feature_cache: (flags, branch) of feature_cache_spec, one flag per evaluation before promotion (ladi_tryon_set_feature_cache does the
+        promotion); None or flags None = off."""
         lib = _lib.load()
         if self._tryon is None:
             self._tryon = lib.ladi_tryon_create(self.unet.h, self.vae.h, self.emasc.h if self.emasc else None)
@@ -432,6 +511,13 @@ class StableDiffusionTryOnePipeline:
         else:
             check(lib.ladi_tryon_set_guidance_schedule(self._tryon, None, 0), "ladi_tryon_set_guidance_schedule")
         check(lib.ladi_tryon_set_guidance_rescale(self._tryon, float(guidance_rescale)), "ladi_tryon_set_guidance_rescale")
+        fc_flags, fc_branch = feature_cache if feature_cache is not None else (None, 0)
+        if fc_flags is not None:
+            ff = (ctypes.c_ubyte * len(fc_flags))(*[1 if f else 0 for f in fc_flags])
+            check(lib.ladi_tryon_set_feature_cache(self._tryon, ff, len(fc_flags), int(fc_branch)), "ladi_tryon_set_feature_cache")
+        else:
+            check(lib.ladi_tryon_set_feature_cache(self._tryon, None, 0, 0), "ladi_tryon_set_feature_cache")
+        self._shallow_evals = None
         cb_error = []
         cb_latents = trampoline = None
         if callback is not None:
@@ -522,7 +608,7 @@ class StableDiffusionTryOnePipeline:
     # -------------------------------------------------------------------------------------------------------
     def _run_modular(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose, eta,
                      generator, callback, callback_steps, guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0,
-                     init_is_noisy=False):
+                     init_is_noisy=False, feature_cache=None):
         F = torch.nn.functional
         dev = self._execution_device
         do_cfg = neg is not None
@@ -575,6 +661,15 @@ class StableDiffusionTryOnePipeline:
         if "generator" in params:
             extra["generator"] = generator
         B = latents.shape[0]
+        # feature cache: the plan after promotion; a cond-only evaluation of a CFG run then keeps the whole context and runs the conditional
+        # samples as rows [B, 2B) of it, so that it meets the rows of the cache the CFG evaluations wrote (as the fused loop does)
+        fc_flags, fc_branch = feature_cache if feature_cache is not None else (None, 0)
+        if fc_flags is not None:
+            co = [do_cfg and guidance_table is not None and not guidance_table[i] > 1.0 for i in range(len(timesteps))]
+            fc_flags = feature_cache_plan(len(timesteps), fc_flags, co)
+            self._shallow_evals = sum(1 for f in fc_flags if not f)
+        else:
+            self._shallow_evals = 0
         for i, t in enumerate(timesteps):
             g_i = guidance_table[i] if guidance_table is not None else guidance
             # a cond-only evaluation of a CFG run (scale <= 1): the B conditional samples and the conditional context alone
@@ -587,7 +682,11 @@ class StableDiffusionTryOnePipeline:
             if do_cfg and not cfg_i:
                 parts = [x] + [p[B:] for p in parts[1:]]
             x = torch.cat([p.float() for p in parts], dim=1)
-            eps = self.unet(x, t, encoder_hidden_states=ehs if cfg_i or not do_cfg else pe).sample.float()
+            if fc_flags is not None:
+                eps = self.unet(x, t, encoder_hidden_states=ehs, feature_cache="capture" if fc_flags[i] else "reuse", cache_branch=fc_branch,
+                                sample0=B if do_cfg and not cfg_i else 0).sample.float()
+            else:
+                eps = self.unet(x, t, encoder_hidden_states=ehs if cfg_i or not do_cfg else pe).sample.float()
             if cfg_i:
                 eu, et = eps.chunk(2)
                 eps = eu + g_i * (et - eu)
