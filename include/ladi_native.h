@@ -263,6 +263,10 @@ int ladi_sched_table_from(int kind, int num_inference_steps, const float* alphas
  * [d_i, d_{i-1}, d_{i-2}, d_{i-3}] (zero beyond the order min(i + 1, 4)).  alphas_cumprod_host null = default.  Any output may be null. */
 int ladi_sched_lms(int num_inference_steps, const float* alphas_cumprod_host, double* timesteps_out, float* sigmas_out, float* coeffs_out);
 /* host helper: default alphas_cumprod (scaled_linear 0.00085..0.012, 1000 steps), out[1000] */
+/* coefficients of the latent blend (ladi_tryon_set_preserve) of a run that starts at step first_step: out[i] = {k_x, k_n} of the scheduler's
+ * add_noise at timesteps[i + 1] (DDIM / PNDM / DPM-Solver++: sqrt(a), sqrt(1 - a); LMS / Euler / Euler-ancestral: 1, sigma[i + 1]), computed in
+ * double and held in fp32; the last row is {1, 0}.  One row per evaluation of ladi_sched_table_from; returns their count, < 0 when it exceeds cap */
+int ladi_sched_keep_coeffs(int kind, int num_inference_steps, const float* alphas_cumprod_host, int first_step, float* out, int cap);
 int ladi_sched_alphas_cumprod(float* out);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -354,6 +358,18 @@ int ladi_tryon_cond_only_evals(ladi_tryon* t);
 int ladi_tryon_set_feature_cache(ladi_tryon* t, const unsigned char* full_flags_host, int count, int branch);
 /* how many evaluations of the last run ran shallow, after promotion */
 int ladi_tryon_shallow_evals(ladi_tryon* t);
+/* keep the unmasked region for the following runs (sticky per handle; (0, 0) = off, the state of a new handle: nothing is launched for it and
+ * every result stays bit for bit).  mode_bits: bit 0 latents, bit 1 pixels.
+ * Latents: diffusers' 4-channel inpaint rule.  After the scheduler update of evaluation i every KEEP latent pixel is replaced by
+ * k_x[i] z0 + k_n[i] noise (ladi_sched_keep_coeffs: the scheduler's add_noise at timesteps[i + 1]), after the last evaluation by z0 itself.
+ * z0 = scaling_factor * mode(vae.encode(image_dev)) (one more encode per run, no RNG draw), noise = noise_latents_dev (also with an init),
+ * keep = 1 - maxpool8x8(binarised mask): the pixel's whole 8x8 footprint is unmasked.  A select on the mask: generated pixels keep their bits,
+ * keep pixels never see the UNet's values.  Scheduler state (PLMS cur_sample, the eps / data-prediction ring) is not blended -- what a loop
+ * gets that blends scheduler.step(...).prev_sample.  The latents trace, the step callback and the next UNet input see the blended latents.
+ * Pixels: the decode epilogue writes M g + (1 - M) p, g = clamp(decoded / 2 + 0.5, 0, 1), p = clamp(image / 2 + 0.5, 0, 1), M the binarised
+ * mask or, with feather_sigma > 0, its separable Gaussian blur (sigma in pixels, radius ceil(3 sigma), replicate border, fp32); M == 0 / 1
+ * select p / g bit for bit; fp32 and u8 output alike.  feather_sigma outside [0, 32], a feather without bit 1, or unknown bits: error. */
+int ladi_tryon_set_preserve(ladi_tryon* t, int mode_bits, float feather_sigma);
 /* step callback (diffusers' callback / callback_steps): after evaluation i with i % every == 0, on the run's stream, the loop's latents are
  * copied to latents_nchw_dev (caller-owned fp32 [B,4,h,w], what the modular path hands its callback), the stream is synchronised and
  * fn(user, i) runs on the calling thread.  Afterwards work queued on the run's `stream` argument is waited for, and latents_nchw_dev is copied
@@ -554,6 +570,11 @@ int ladi_op_sched_run_noise_eta(int kind, int steps, const float* alphas_cumprod
 int ladi_op_sched_run_guided(int kind, int steps, const float* alphas_cumprod_host, float eta, const void* eps_seq_dev, int ld_eps, int evals,
                              int B, int hw, const float* guidance_tab_host, float phi, float* latents_dev, const float* step_noise_dev,
                              int noise_steps, void* stream);
+/* ladi_op_sched_run_guided with the latent blend of ladi_tryon_set_preserve: keep_x0_dev / keep_noise_dev fp32 pixel-major [B][hw][4] (16-byte
+ * aligned), keep_mask_dev fp32 [B][hw] (non-zero = keep), the coefficients of ladi_sched_keep_coeffs(kind, steps, .., 0) */
+int ladi_op_sched_run_keep(int kind, int steps, const float* alphas_cumprod_host, float eta, const void* eps_seq_dev, int ld_eps, int evals, int B,
+                           int hw, const float* guidance_tab_host, float phi, float* latents_dev, const float* step_noise_dev, int noise_steps,
+                           const float* keep_x0_dev, const float* keep_noise_dev, const float* keep_mask_dev, void* stream);
 /* the guidance-rescale statistics kernel on its own: eps_dev [2B][hw] rows of 4 fp16 channels, ld_eps halves apart, uncond half first ->
  * factor_dev[b] = phi * std(cond_b) / std(u_b + guidance (c_b - u_b)) + (1 - phi), fp32 [B].  Bit-reproducible from call to call. */
 int ladi_op_cfg_stats(const void* eps_dev, int ld_eps, int B, int hw, float guidance, float phi, float* factor_dev, void* stream);
@@ -618,6 +639,15 @@ int ladi_op_patchify(const void* px, int dtype, int B, int S, int ps, int KP, vo
 /* glue of the denoising loop and the decoder */
 int ladi_op_timestep_embedding(const float* t, int count, int dim, float* out, void* stream);     /* [cos | sin], fp32 [count][dim] */
 int ladi_op_image_post(const void* src, int ld, int n_pix, void* dst, int dst_u8, void* stream);  /* clamp(x / 2 + 0.5, 0, 1): fp32 or round(255 v) u8, [n_pix][3] */
+/* preserve-unmasked kernels on their own.  mask_pool8: out fp32 [B][H/8][W/8] = F.max_pool2d(mask, 8) of the binarised fp16 mask [B][H][W]
+ * (16-byte aligned; H, W multiples of 8), with invert 1 - that (the keep mask).  mask_feather: out fp32 [B][H][W] = the separable Gaussian blur
+ * of the fp16 mask (sigma in (0, 32], radius ceil(3 sigma) = the return value, weights normalised in double, replicate border, rows into tmp
+ * fp32 [B][H][W] then columns).  image_composite: dst [B * HW][3] (fp32 or, dst_u8, round(255 v)) = M g + (1 - M) p from the decoded NHWC fp16
+ * tensor (row stride ld, a multiple of 4), the NCHW image (dtype) and the mask [B][HW] (fp16, or fp32 with mask_f32); HW a multiple of 4 */
+int ladi_op_mask_pool8(const void* mask_bin, int B, int H, int W, int invert, float* out, void* stream);
+int ladi_op_mask_feather(const void* mask_bin, int B, int H, int W, float sigma, float* tmp, float* out, void* stream);
+int ladi_op_image_composite(const void* decoded, int ld, const void* image, int dtype, const void* mask, int mask_f32, int B, int HW, void* dst,
+                            int dst_u8, void* stream);
 int ladi_op_post_quant(const float* lat, const float* pq, float inv_sf, int n, void* dst, int ld, void* stream);   /* pq [16 w | 4 b] or NULL; channels [4, ld) zero */
 int ladi_op_lat_nchw_to_pix(const float* src, int B, int hw, float scale, float* dst, void* stream);
 int ladi_op_lat_pix_to_nchw(const float* src, int B, int hw, float* dst, void* stream);

@@ -7,7 +7,7 @@ from . import configs  # noqa: F401
 from . import dataset  # noqa: F401  (host-side VITON-HD / DressCode readers)
 from ._lib import NativeError  # noqa: F401
 from .modules import (NativeEMASC, NativeInversionAdapter, NativeUNet, NativeVAE, mask_features)  # noqa: F401
-from .pipeline import StableDiffusionTryOnePipeline, feature_cache_plan, guidance_interval, strength_first_step  # noqa: F401
+from .pipeline import StableDiffusionTryOnePipeline, feature_cache_plan, guidance_interval, preserve_spec, strength_first_step  # noqa: F401
 from .probe import RangeProbe  # noqa: F401
 from .schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler,  # noqa: F401
                          LMSDiscreteScheduler, PNDMScheduler)

@@ -156,6 +156,8 @@ SIGNATURES = {
     "ladi_tryon_set_guidance_rescale": (c_int, [_P, c_float]),
     "ladi_tryon_cond_only_evals": (c_int, [_P]),
     "ladi_tryon_set_feature_cache": (c_int, [_P, POINTER(ctypes.c_ubyte), c_int, c_int]),
+    "ladi_tryon_set_preserve": (c_int, [_P, c_int, c_float]),
+    "ladi_sched_keep_coeffs": (c_int, [c_int, c_int, _P, c_int, POINTER(c_float), c_int]),
     "ladi_tryon_shallow_evals": (c_int, [_P]),
     "ladi_tryon_set_step_callback": (c_int, [_P, STEP_CALLBACK, _P, c_int, _P]),
     "ladi_tryon_set_lanes": (c_int, [_P, c_int]),
@@ -244,6 +246,10 @@ SIGNATURES = {
     "ladi_op_patchify": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "ladi_op_timestep_embedding": (c_int, [_P, c_int, c_int, _P, _P]),
     "ladi_op_image_post": (c_int, [_P, c_int, c_int, _P, c_int, _P]),
+    "ladi_op_mask_pool8": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "ladi_op_mask_feather": (c_int, [_P, c_int, c_int, c_int, c_float, _P, _P, _P]),
+    "ladi_op_image_composite": (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P]),
+    "ladi_op_sched_run_keep": (c_int, [c_int, c_int, _P, c_float, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_float, _P, _P, c_int, _P, _P, _P, _P]),
     "ladi_op_post_quant": (c_int, [_P, _P, c_float, c_int, _P, c_int, _P]),
     "ladi_op_lat_nchw_to_pix": (c_int, [_P, c_int, c_int, c_float, _P, _P]),
     "ladi_op_lat_pix_to_nchw": (c_int, [_P, c_int, c_int, _P, _P]),

@@ -636,6 +636,19 @@ int ladi_sched_table_from(int code, int steps, const float* ac_host, float eta, 
                           float* start_out) {
     return sched_table_any("ladi_sched_table_from", code, steps, ac_host, timesteps_out, rows_out, cap, eta, first_step, start_out);
 }
+int ladi_sched_keep_coeffs(int code, int steps, const float* ac_host, int first_step, float* out, int cap) {
+    return guarded("ladi_sched_keep_coeffs", [&]() {
+        if (!out) throw std::runtime_error("null out");
+        std::vector<float> ac;
+        if (ac_host) ac.assign(ac_host, ac_host + 1000); else default_alphas_cumprod(ac);
+        std::vector<float> kt;
+        build_keep_coeffs(code, steps, ac.data(), first_step, kt);
+        const int evals = (int)(kt.size() / 2);
+        if (evals > cap) throw std::runtime_error("coefficient buffer too small");
+        std::memcpy(out, kt.data(), kt.size() * sizeof(float));
+        return evals;
+    });
+}
 int ladi_sched_alphas_cumprod(float* out) {
     std::vector<float> ac; default_alphas_cumprod(ac);
     std::memcpy(out, ac.data(), 1000 * sizeof(float));
@@ -737,6 +750,17 @@ int ladi_tryon_set_feature_cache(ladi_tryon* t, const unsigned char* full_flags_
         t->t.fc_branch = branch;
         return 0;
     });
+}
+int ladi_tryon_set_preserve(ladi_tryon* t, int mode_bits, float feather_sigma) {
+    if (mode_bits < 0 || mode_bits > 3) { set_error("ladi_tryon_set_preserve: mode bits " + std::to_string(mode_bits) + " outside 0 .. 3 (bit 0 latents, bit 1 pixels)"); return -1; }
+    if (!(feather_sigma >= 0.f) || !(feather_sigma <= 32.f)) {
+        set_error("ladi_tryon_set_preserve: feather sigma " + std::to_string(feather_sigma) + " outside [0, 32]");
+        return -1;
+    }
+    if (feather_sigma > 0.f && !(mode_bits & 2)) { set_error("ladi_tryon_set_preserve: a feather needs the pixels mode (bit 1)"); return -1; }
+    if (!t) { set_error("ladi_tryon_set_preserve: null handle"); return -1; }
+    t->t.preserve_mode = mode_bits; t->t.preserve_sigma = feather_sigma;
+    return 0;
 }
 int ladi_tryon_shallow_evals(ladi_tryon* t) { return t ? t->t.last_shallow : -1; }
 int ladi_tryon_set_step_callback(ladi_tryon* t, ladi_step_callback fn, void* user, int every, float* latents_nchw_dev) {
@@ -1183,9 +1207,10 @@ int ladi_op_cfg_stats(const void* eps, int ld_eps, int B, int hw, float guidance
         return ladi_launch_cfg_stats(reinterpret_cast<const h16*>(eps), ld_eps, B, hw, nullptr, nullptr, guidance, phi, factor, S(stream));
     });
 }
-int ladi_op_sched_run_guided(int kind, int steps, const float* ac_host, float eta, const void* eps_seq, int ld_eps, int evals, int B, int hw,
-                             const float* guidance_tab_host, float phi, float* latents, const float* step_noise, int noise_steps, void* stream) {
-    return guarded("ladi_op_sched_run_guided", [&]() {
+static int sched_run_guided_any(const char* name, int kind, int steps, const float* ac_host, float eta, const void* eps_seq, int ld_eps, int evals,
+                                int B, int hw, const float* guidance_tab_host, float phi, float* latents, const float* step_noise, int noise_steps,
+                                const float* keep_x0, const float* keep_noise, const float* keep_mask, void* stream) {
+    return guarded(name, [&]() {
         hipStream_t st = S(stream);
         if (!eps_seq || !latents || !guidance_tab_host || evals <= 0 || B <= 0 || hw <= 0) throw std::runtime_error("null argument or empty shape");
         if (ld_eps < 4 || (ld_eps & 3) || ((uintptr_t)eps_seq & 7)) throw std::runtime_error("ld_eps must be a multiple of 4 (>= 4) and eps_seq 8-byte aligned");
@@ -1204,15 +1229,21 @@ int ladi_op_sched_run_guided(int kind, int steps, const float* ac_host, float et
         const size_t tb_bytes = (tb.size() * sizeof(StepTable) + 255) & ~(size_t)255;
         const size_t gt_bytes = ((size_t)evals * sizeof(float) + 255) & ~(size_t)255;
         const size_t fc_bytes = ((size_t)B * sizeof(float) + 255) & ~(size_t)255;
-        HIP_OK(hipMalloc(reinterpret_cast<void**>(&buf), tb_bytes + 256 + gt_bytes + fc_bytes + 5 * plane));
+        // the latent blend's coefficients, one row per evaluation of the whole run (evals may stop earlier)
+        std::vector<float> kt;
+        if (keep_mask) build_keep_coeffs(kind, steps, ac.data(), 0, kt);
+        const size_t kt_bytes = (kt.size() * sizeof(float) + 255) & ~(size_t)255;
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&buf), tb_bytes + 256 + gt_bytes + fc_bytes + kt_bytes + 5 * plane));
         StepTable* dt = reinterpret_cast<StepTable*>(buf);
         int* dstep = reinterpret_cast<int*>(buf + tb_bytes);
         float* dgt = reinterpret_cast<float*>(buf + tb_bytes + 256);
         float* dfc = reinterpret_cast<float*>(buf + tb_bytes + 256 + gt_bytes);
-        float* cur = reinterpret_cast<float*>(buf + tb_bytes + 256 + gt_bytes + fc_bytes);
+        float* dkt = reinterpret_cast<float*>(buf + tb_bytes + 256 + gt_bytes + fc_bytes);
+        float* cur = reinterpret_cast<float*>(buf + tb_bytes + 256 + gt_bytes + fc_bytes + kt_bytes);
         float* ets = cur + (size_t)B * hw * 4;
         int rc = 0;
         try {
+            if (keep_mask) HIP_OK(hipMemcpyAsync(dkt, kt.data(), kt.size() * sizeof(float), hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(dt, tb.data(), tb.size() * sizeof(StepTable), hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(dgt, guidance_tab_host, (size_t)evals * sizeof(float), hipMemcpyHostToDevice, st));
             HIP_OK(hipMemsetAsync(dstep, 0, 8, st));       // evaluation index + the step kernel's arrival ticket
@@ -1223,6 +1254,7 @@ int ladi_op_sched_run_guided(int kind, int steps, const float* ac_host, float et
                 sa.B = B; sa.hw = hw; sa.cfg = 1; sa.latents = latents; sa.cur_sample = cur; sa.ets = ets;
                 sa.table = dt; sa.step_idx = dstep; sa.unet_in = nullptr; sa.step_noise = step_noise;
                 sa.guidance_tab = dgt; sa.factor = phi > 0.f ? dfc : nullptr;
+                if (keep_mask) { sa.keep_x0 = keep_x0; sa.keep_noise = keep_noise; sa.keep_mask = keep_mask; sa.keep_tab = dkt; }
                 if (phi > 0.f && guidance_tab_host[i] > 1.0f) rc = ladi_launch_cfg_stats(sa.eps, ld_eps, B, hw, dgt, dstep, 0.f, phi, dfc, st);
                 if (!rc) rc = ladi_launch_sched_step(sa, st);
             }
@@ -1230,6 +1262,49 @@ int ladi_op_sched_run_guided(int kind, int steps, const float* ac_host, float et
         } catch (...) { (void)hipFree(buf); throw; }
         (void)hipFree(buf);
         return rc;
+    });
+}
+int ladi_op_sched_run_guided(int kind, int steps, const float* ac_host, float eta, const void* eps_seq, int ld_eps, int evals, int B, int hw,
+                             const float* guidance_tab_host, float phi, float* latents, const float* step_noise, int noise_steps, void* stream) {
+    return sched_run_guided_any("ladi_op_sched_run_guided", kind, steps, ac_host, eta, eps_seq, ld_eps, evals, B, hw, guidance_tab_host, phi, latents,
+                                step_noise, noise_steps, nullptr, nullptr, nullptr, stream);
+}
+int ladi_op_sched_run_keep(int kind, int steps, const float* ac_host, float eta, const void* eps_seq, int ld_eps, int evals, int B, int hw,
+                           const float* guidance_tab_host, float phi, float* latents, const float* step_noise, int noise_steps,
+                           const float* keep_x0, const float* keep_noise, const float* keep_mask, void* stream) {
+    if (!keep_x0 || !keep_noise || !keep_mask) { set_error("ladi_op_sched_run_keep: null keep_x0, keep_noise or keep_mask"); return -1; }
+    if (((uintptr_t)keep_x0 | (uintptr_t)keep_noise) & 15) { set_error("ladi_op_sched_run_keep: keep_x0 and keep_noise must be 16-byte aligned"); return -1; }
+    return sched_run_guided_any("ladi_op_sched_run_keep", kind, steps, ac_host, eta, eps_seq, ld_eps, evals, B, hw, guidance_tab_host, phi, latents,
+                                step_noise, noise_steps, keep_x0, keep_noise, keep_mask, stream);
+}
+int ladi_op_mask_pool8(const void* mask_bin, int B, int H, int W, int invert, float* out, void* stream) {
+    return guarded("ladi_op_mask_pool8", [&]() {
+        if (!mask_bin || !out) throw std::runtime_error("null mask or out");
+        if (B < 1 || H < 8 || W < 8 || (H & 7) || (W & 7)) throw std::runtime_error("B >= 1, H and W multiples of 8");
+        if ((uintptr_t)mask_bin & 15) throw std::runtime_error("the mask must be 16-byte aligned");
+        if (ladi_launch_mask_pool8(reinterpret_cast<const h16*>(mask_bin), B, H, W, invert ? 1 : 0, out, S(stream))) throw std::runtime_error("launch refused or failed");
+        return 0;
+    });
+}
+int ladi_op_mask_feather(const void* mask_bin, int B, int H, int W, float sigma, float* tmp, float* out, void* stream) {
+    return guarded("ladi_op_mask_feather", [&]() {
+        if (!mask_bin || !tmp || !out || tmp == out) throw std::runtime_error("null mask, tmp or out (tmp and out must differ)");
+        if (B < 1 || H < 1 || W < 1) throw std::runtime_error("every size has to be >= 1");
+        if (!(sigma > 0.f) || !(sigma <= 32.f)) throw std::runtime_error("sigma " + std::to_string(sigma) + " outside (0, 32]");
+        if (ladi_launch_mask_feather(reinterpret_cast<const h16*>(mask_bin), B, H, W, sigma, tmp, out, S(stream))) throw std::runtime_error("launch refused or failed");
+        return ladi_feather_radius(sigma);
+    });
+}
+int ladi_op_image_composite(const void* decoded, int ld, const void* image, int dtype, const void* mask, int mask_f32, int B, int HW, void* dst,
+                            int dst_u8, void* stream) {
+    return guarded("ladi_op_image_composite", [&]() {
+        if (!decoded || !image || !mask || !dst) throw std::runtime_error("null argument");
+        if (dtype != LADI_F32 && dtype != LADI_F16) throw std::runtime_error("image dtype must be fp32 or fp16");
+        if (B < 1 || HW < 4 || (HW & 3)) throw std::runtime_error("B >= 1 and H * W a multiple of 4");
+        if (ld < 4 || (ld & 3) || ((uintptr_t)decoded & 7)) throw std::runtime_error("ld must be a multiple of 4 (>= 4) and decoded 8-byte aligned");
+        if (ladi_launch_image_composite(reinterpret_cast<const h16*>(decoded), ld, image, dtype == LADI_F32, mask, mask_f32 ? 1 : 0, B, HW, dst, dst_u8 ? 1 : 0,
+                                        S(stream))) throw std::runtime_error("launch refused or failed");
+        return 0;
     });
 }
 

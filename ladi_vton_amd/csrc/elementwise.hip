@@ -3,6 +3,8 @@
 // step + next-UNet-input assembly, posterior sampling, mask / pose resizes.
 #include "common.h"
 #include "kernels.h"
+#include <algorithm>
+#include <cmath>
 
 namespace {
 
@@ -187,6 +189,18 @@ __device__ __forceinline__ void sched_step_body(const StepArgs& a, const int idx
         xn.x += T.c_n * nz[0]; xn.y += T.c_n * nz[a.hw];
         xn.z += T.c_n * nz[2 * (size_t)a.hw]; xn.w += T.c_n * nz[3 * (size_t)a.hw];
     }
+    if (a.keep_mask && a.keep_mask[idx] != 0.f) {
+        // preserve-unmasked: a keep pixel (its whole 8x8 footprint unmasked) leaves the update as the known image noised to the NEXT timestep,
+        // k_x z0 + k_n noise -- a select, so nothing the UNet produced reaches it; the row (1, 0) after the last evaluation is z0 itself
+        const float kx = a.keep_tab[2 * step], kn = a.keep_tab[2 * step + 1];
+        const float4 z = reinterpret_cast<const float4*>(a.keep_x0)[idx];
+        if (kx == 1.f && kn == 0.f) xn = z;
+        else {
+            const float4 nz = reinterpret_cast<const float4*>(a.keep_noise)[idx];
+            xn.x = kx * z.x + kn * nz.x; xn.y = kx * z.y + kn * nz.y;
+            xn.z = kx * z.z + kn * nz.z; xn.w = kx * z.w + kn * nz.w;
+        }
+    }
     reinterpret_cast<float4*>(a.latents)[idx] = xn;
     if (step < a.trace_cap) {
         if (a.trace_eps) reinterpret_cast<float4*>(a.trace_eps)[(size_t)step * total + idx] = make_float4(e[0], e[1], e[2], e[3]);
@@ -300,12 +314,17 @@ __global__ __launch_bounds__(256) void posterior_sample_kernel(const h16* __rest
     if (idx >= B * hw) return;
     const int b = idx / hw, p = idx - b * hw;
     const h16* m = moments + (size_t)idx * ldm;
+    if (!noise) {        // the posterior mode: the mean, no draw and no exp
+#pragma unroll
+        for (int c = 0; c < 4; ++c) lat[(size_t)idx * 4 + c] = (float)m[c] * scaling;
+        return;
+    }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const float mean = (float)m[c];
         float lv = fminf(fmaxf((float)m[4 + c], -30.f), 20.f);
         const float std = __expf(0.5f * lv);
-        const float nz = noise ? noise[((size_t)b * 4 + c) * hw + p] : 0.f;
+        const float nz = noise[((size_t)b * 4 + c) * hw + p];
         lat[(size_t)idx * 4 + c] = (mean + std * nz) * scaling;
     }
 }
@@ -981,4 +1000,175 @@ int ladi_launch_scale_h16(const h16* src, int lds_, h16* dst, int ldd, size_t n_
     const size_t total = n_pix * (C / 8);
     hipLaunchKernelGGL(scale_h16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, lds_, dst, ldd, n_pix, C / 8, s);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ------------------------------------------------------------------------------------------------
+// preserve-unmasked (ladi_tryon_set_preserve): the keep mask of the latent blend, the feathered mask and the composite decode epilogue
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// dst[b][y][x] = max over the 8x8 footprint of latent pixel (y, x) of the binarised mask src fp16 [B][H][W] (F.max_pool2d(mask, 8)), or with
+// `invert` 1 - that: the keep mask of the latent blend (1 = the whole footprint is unmasked).  One thread per latent pixel, eight 16-byte loads.
+__global__ __launch_bounds__(256) void mask_pool8_kernel(const h16* __restrict__ src, int B, int H, int W, int invert, float* __restrict__ dst) {
+    const int h = H / 8, w = W / 8;
+    const int total = B * h * w;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int b = idx / (h * w), r = idx - b * h * w, y = r / w, x = r - y * w;
+        const h16* p = src + ((size_t)b * H + (size_t)y * 8) * W + (size_t)x * 8;
+        float m = 0.f;
+#pragma unroll
+        for (int dy = 0; dy < 8; ++dy) {
+            const h16x8 v = *reinterpret_cast<const h16x8*>(p + (size_t)dy * W);     // W % 8 == 0 and a 16-byte aligned base: aligned
+#pragma unroll
+            for (int e = 0; e < 8; ++e) m = fmaxf(m, (float)v[e]);
+        }
+        dst[idx] = invert ? 1.f - m : m;
+    }
+}
+
+// one pass of the separable Gaussian: dst[b][y][x] = sum_{k = -r..r} w[|k|] src[b][..clamp(. + k)..] along x (DIR 0) or y (DIR 1), replicate
+// border, fp32 accumulation in the fixed order k = -r .. r; a window of equal values returns that value exactly.  The weights (normalised in float64 on the host, then fp32) travel as a kernel
+// argument: the index is wave-uniform, so they are scalar loads.
+constexpr int FEATHER_MAX_R = 96;      // ceil(3 * 32)
+struct FeatherW { int r; float w[FEATHER_MAX_R + 1]; };
+template <typename ST, int DIR>
+__global__ __launch_bounds__(256) void mask_feather_kernel(const ST* __restrict__ src, int B, int H, int W, const FeatherW fw,
+                                                           float* __restrict__ dst) {
+    const size_t total = (size_t)B * H * W;
+    const int r = fw.r;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const int x = (int)(idx % W);
+        const int y = (int)((idx / W) % H);
+        const ST* row = DIR == 0 ? src + (idx - x) : src + (idx - (size_t)y * W);     // the line this pass runs along, at position 0
+        const int n = DIR == 0 ? W : H, pos = DIR == 0 ? x : y;
+        const size_t stride = DIR == 0 ? 1 : (size_t)W;
+        float acc = 0.f, lo = 2.f, hi = -1.f;
+        for (int k = -r; k <= r; ++k) {
+            const int q = min(max(pos + k, 0), n - 1);
+            const float v = (float)row[(size_t)q * stride];
+            acc += fw.w[k < 0 ? -k : k] * v;
+            lo = fminf(lo, v); hi = fmaxf(hi, v);
+        }
+        // a window over which the input is constant returns that constant itself (the fp32 weights sum to 1 only within a few ulp): away
+        // from its edges the feathered mask is exactly 0 or 1, which is what the composite's select keys on
+        dst[idx] = lo == hi ? lo : acc;
+    }
+}
+
+// four consecutive elements: one 16-byte (fp32) / 8-byte (fp16) access when `vec` (the address is aligned to it), else element by element
+__device__ __forceinline__ void load4(const float* p, bool vec, float v[4]) {
+    if (vec) { const float4 t = *reinterpret_cast<const float4*>(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+    else { v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3]; }
+}
+__device__ __forceinline__ void load4(const h16* p, bool vec, float v[4]) {
+    if (vec) { const h16x4 t = *reinterpret_cast<const h16x4*>(p); v[0] = (float)t[0]; v[1] = (float)t[1]; v[2] = (float)t[2]; v[3] = (float)t[3]; }
+    else { v[0] = (float)p[0]; v[1] = (float)p[1]; v[2] = (float)p[2]; v[3] = (float)p[3]; }
+}
+
+// composite form of image_post_kernel: out = M g + (1 - M) p with g = clamp(decoded / 2 + 0.5, 0, 1) (src NHWC fp16, 3 valid channels) and
+// p = clamp(image / 2 + 0.5, 0, 1) (the caller's NCHW image), M the binarised (fp16) or feathered (fp32) mask [B][HW].  M == 0 selects p and
+// M == 1 selects g: those pixels are image_post_kernel's bits of the one source, and a NaN in the other cannot reach them.  Four pixels per
+// thread (HW % 4 == 0, so a group never straddles two samples): 16-byte plane / mask loads and 16-byte stores where the pointers allow.
+template <typename IT, typename MT, bool U8>
+__global__ __launch_bounds__(256) void image_composite_kernel(const h16* __restrict__ src, int ld, const IT* __restrict__ image,
+                                                              const MT* __restrict__ mask, int B, int HW, int vec_in, int vec_out,
+                                                              void* __restrict__ dst) {
+    const size_t groups = (size_t)B * HW / 4;
+    for (size_t gi = (size_t)blockIdx.x * 256 + threadIdx.x; gi < groups; gi += (size_t)gridDim.x * 256) {
+        const size_t pix = gi * 4;
+        const int b = (int)(pix / HW);
+        const size_t p0 = pix - (size_t)b * HW;
+        float m[4], iv[3][4], o[12];
+        load4(mask + pix, vec_in, m);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) load4(image + ((size_t)b * 3 + c) * HW + p0, vec_in, iv[c]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const h16x4 s = *reinterpret_cast<const h16x4*>(src + (pix + j) * ld);      // ld % 4 == 0 and an 8-byte aligned base
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float g = fminf(fmaxf((float)s[c] * 0.5f + 0.5f, 0.f), 1.f);
+                const float p = fminf(fmaxf(iv[c][j] * 0.5f + 0.5f, 0.f), 1.f);
+                o[j * 3 + c] = m[j] == 0.f ? p : (m[j] == 1.f ? g : m[j] * g + (1.f - m[j]) * p);
+            }
+        }
+        if constexpr (U8) {
+            unsigned w3[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                unsigned w = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) w |= (unsigned)(unsigned char)rintf(o[q * 4 + e] * 255.0f) << (8 * e);
+                w3[q] = w;
+            }
+            unsigned char* d = reinterpret_cast<unsigned char*>(dst) + pix * 3;
+            if (vec_out) { unsigned* dw = reinterpret_cast<unsigned*>(d); dw[0] = w3[0]; dw[1] = w3[1]; dw[2] = w3[2]; }
+            else {
+#pragma unroll
+                for (int e = 0; e < 12; ++e) d[e] = (unsigned char)(w3[e >> 2] >> (8 * (e & 3)));
+            }
+        } else {
+            float* d = reinterpret_cast<float*>(dst) + pix * 3;
+            if (vec_out) {
+                float4* dv = reinterpret_cast<float4*>(d);
+                dv[0] = make_float4(o[0], o[1], o[2], o[3]); dv[1] = make_float4(o[4], o[5], o[6], o[7]); dv[2] = make_float4(o[8], o[9], o[10], o[11]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 12; ++e) d[e] = o[e];
+            }
+        }
+    }
+}
+
+inline unsigned capped_grid(size_t items) { return (unsigned)std::min<size_t>((items + 255) / 256, 2048); }
+
+template <typename IT, typename MT>
+void launch_composite(const h16* src, int ld, const void* image, const void* mask, int B, int HW, int vec_in, int vec_out, void* dst, int dst_u8,
+                      hipStream_t st) {
+    const dim3 grid(capped_grid((size_t)B * HW / 4));
+    if (dst_u8) hipLaunchKernelGGL((image_composite_kernel<IT, MT, true>), grid, dim3(256), 0, st, src, ld, (const IT*)image, (const MT*)mask, B, HW, vec_in, vec_out, dst);
+    else hipLaunchKernelGGL((image_composite_kernel<IT, MT, false>), grid, dim3(256), 0, st, src, ld, (const IT*)image, (const MT*)mask, B, HW, vec_in, vec_out, dst);
+}
+
+}  // namespace
+
+int ladi_launch_mask_pool8(const h16* mask_bin, int B, int H, int W, int invert, float* dst, hipStream_t st) {
+    if (!mask_bin || !dst || B < 1 || H < 8 || W < 8 || (H & 7) || (W & 7) || ((uintptr_t)mask_bin & 15)) return -1;
+    if ((size_t)B * (H / 8) * (W / 8) > 0x7fffffffULL) return -1;
+    hipLaunchKernelGGL(mask_pool8_kernel, dim3(capped_grid((size_t)B * (H / 8) * (W / 8))), dim3(256), 0, st, mask_bin, B, H, W, invert, dst);
+    return hipGetLastError() == hipSuccess ? 0 : -11;
+}
+
+int ladi_feather_radius(float sigma) { return (int)std::ceil(3.0 * (double)sigma); }
+
+int ladi_launch_mask_feather(const h16* mask_bin, int B, int H, int W, float sigma, float* tmp, float* dst, hipStream_t st) {
+    if (!mask_bin || !tmp || !dst || tmp == dst || B < 1 || H < 1 || W < 1) return -1;
+    if (!(sigma > 0.f) || !(sigma <= 32.f)) return -2;
+    FeatherW fw;
+    fw.r = ladi_feather_radius(sigma);
+    if (fw.r < 1 || fw.r > FEATHER_MAX_R) return -2;
+    double wd[FEATHER_MAX_R + 1], sum = 0.0;
+    for (int k = 0; k <= fw.r; ++k) {
+        wd[k] = std::exp(-0.5 * (double)k * (double)k / ((double)sigma * (double)sigma));
+        sum += k ? 2.0 * wd[k] : wd[k];
+    }
+    for (int k = 0; k <= FEATHER_MAX_R; ++k) fw.w[k] = k <= fw.r ? (float)(wd[k] / sum) : 0.f;
+    const dim3 grid(capped_grid((size_t)B * H * W));
+    hipLaunchKernelGGL((mask_feather_kernel<h16, 0>), grid, dim3(256), 0, st, mask_bin, B, H, W, fw, tmp);
+    hipLaunchKernelGGL((mask_feather_kernel<float, 1>), grid, dim3(256), 0, st, (const float*)tmp, B, H, W, fw, dst);
+    return hipGetLastError() == hipSuccess ? 0 : -11;
+}
+
+int ladi_launch_image_composite(const h16* src, int ld, const void* image_nchw, int img_f32, const void* mask, int mask_f32, int B, int HW,
+                                void* dst, int dst_u8, hipStream_t st) {
+    if (!src || !image_nchw || !mask || !dst || B < 1 || HW < 4 || (HW & 3) || ld < 4 || (ld & 3) || ((uintptr_t)src & 7)) return -1;
+    const uintptr_t ia = (uintptr_t)image_nchw, ma = (uintptr_t)mask;
+    // one flag for the plane and mask loads: every 4-pixel group of both is aligned to its vector width (HW % 4 == 0 keeps the planes so)
+    const int vec_in = (ia % (img_f32 ? 16 : 8) == 0) && (ma % (mask_f32 ? 16 : 8) == 0);
+    const int vec_out = (uintptr_t)dst % (dst_u8 ? 4 : 16) == 0;
+    if (img_f32 && mask_f32) launch_composite<float, float>(src, ld, image_nchw, mask, B, HW, vec_in, vec_out, dst, dst_u8, st);
+    else if (img_f32) launch_composite<float, h16>(src, ld, image_nchw, mask, B, HW, vec_in, vec_out, dst, dst_u8, st);
+    else if (mask_f32) launch_composite<h16, float>(src, ld, image_nchw, mask, B, HW, vec_in, vec_out, dst, dst_u8, st);
+    else launch_composite<h16, h16>(src, ld, image_nchw, mask, B, HW, vec_in, vec_out, dst, dst_u8, st);
+    return hipGetLastError() == hipSuccess ? 0 : -11;
 }

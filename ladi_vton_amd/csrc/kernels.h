@@ -158,6 +158,11 @@ struct StepArgs {
     // evaluation, multiplied into the guided e of a CFG evaluation before anything uses it (cond-only evaluations ignore it)
     const float* guidance_tab;
     const float* factor;
+    // preserve-unmasked latent blend (all null = the code path above, bit for bit).  keep_mask fp32 [B][hw]: non-zero = a keep pixel; after the
+    // update of evaluation i its latents are replaced by keep_tab[i][0] * keep_x0 + keep_tab[i][1] * keep_noise (both fp32 [B][hw][4]; keep_tab
+    // device fp32 [evals][2], indexed by the device step counter; the row (1, 0) stores keep_x0 itself).  A select: the other pixels keep their
+    // bits, and a keep pixel never sees eps.  The ring, cur_sample and the eps trace are not blended; trace_lat and unet_in get the blended value
+    const float* keep_x0; const float* keep_noise; const float* keep_mask; const float* keep_tab;
 };
 int ladi_launch_sched_step(const StepArgs& a, hipStream_t st);
 // guidance rescale statistics of one evaluation: eps as in StepArgs with cfg = 1 (rows [0,B) uncond, [B,2B) cond, row stride ld_eps halves, a
@@ -172,7 +177,7 @@ int ladi_launch_assemble_static(h16* unet_in, int ld_in, int B, int hw, int cfg,
                                 const float* masked_lat, const h16* pose, int pose_ch, const float* cloth_lat, int has_cloth,
                                 float lat_scale, hipStream_t st);
 // posterior sample: lat[b][hw][4] = (mean + exp(0.5*clamp(logvar,-30,20)) * noise) * scaling ; moments NHWC [..][ldm] (8 ch),
-// noise fp32 NCHW [B][4][h][w]
+// noise fp32 NCHW [B][4][h][w]; a null noise is the mode form: lat = mean * scaling
 int ladi_launch_posterior_sample(const h16* moments, int ldm, const float* noise_nchw, int B, int hw, float scaling, float* lat,
                                  hipStream_t st);
 // mask binarise (>=0.5 -> 1) at full res + masked image: img NHWC (ld) *= (mask<0.5); also writes binarised mask fp16 [B][H*W]
@@ -227,6 +232,18 @@ int ladi_launch_init_latents(const float* init, int hs, int ws, const float* noi
 // step-callback import: fp32 NCHW [B][4][hw] src -> the loop's latents [B][hw][4], and the latent channels 0-3 of the next UNet input
 // (rows [B] or, with cfg, [2B], ld_in halves per row) rewritten as fp16(x * in_scale) -- what sched_step_kernel wrote from the unedited x
 int ladi_launch_latents_import(const float* src, int B, int hw, float* latents, h16* unet_in, int ld_in, int cfg, float in_scale, hipStream_t st);
+// preserve-unmasked.  mask_pool8: dst fp32 [B][H/8][W/8] = max over each 8x8 block of the binarised fp16 mask [B][H][W] (F.max_pool2d(mask, 8)),
+// with `invert` 1 - that (the keep mask of StepArgs); H, W multiples of 8, mask 16-byte aligned, else -1
+int ladi_launch_mask_pool8(const h16* mask_bin, int B, int H, int W, int invert, float* dst, hipStream_t st);
+// separable Gaussian blur of the binarised fp16 mask [B][H][W] -> dst fp32 [B][H][W]: radius ceil(3 sigma), weights normalised in float64 on the
+// host, replicate border, fp32 sums in the order k = -r .. r, two launches (rows into tmp fp32 [B][H][W], then columns).  -2: sigma outside (0, 32]
+int ladi_launch_mask_feather(const h16* mask_bin, int B, int H, int W, float sigma, float* tmp, float* dst, hipStream_t st);
+int ladi_feather_radius(float sigma);
+// composite decode epilogue: dst [B*HW][3] (fp32, or u8 = round(255 v) as image_post) = M g + (1 - M) p, g = clamp(src / 2 + 0.5, 0, 1) from the
+// decoded NHWC fp16 src (ld % 4 == 0), p the same of the NCHW image (fp32 / fp16), M fp16 or fp32 [B][HW]; M == 0 / 1 select p / g bit for bit.
+// HW % 4 == 0 (else -1); 16-byte accesses where the pointers are aligned to them, element accesses otherwise
+int ladi_launch_image_composite(const h16* src, int ld, const void* image_nchw, int img_f32, const void* mask, int mask_f32, int B, int HW,
+                                void* dst, int dst_u8, hipStream_t st);
 
 // ---- f32path.hip: fp32 kernels of the warping module (fp32 NHWC activations, fp32 weights, v_mfma_f32_32x32x2_f32)
 struct ConvF32Args {

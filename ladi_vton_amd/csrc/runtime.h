@@ -502,6 +502,13 @@ struct TryOn {
     h16* fcache = nullptr; size_t fcache_cap = 0;
     hipGraph_t graph_sh[2] = {nullptr, nullptr}; hipGraphExec_t gexec_sh[2] = {nullptr, nullptr};   // shallow forms: [0] 2B samples, [1] cond-only
     int last_shallow = 0;     // evaluations of the last run that ran shallow, after promotion (ladi_tryon_shallow_evals)
+    // preserve-unmasked (ladi_tryon_set_preserve, sticky; 0 = off: nothing below is allocated or launched).  Bit 0, latents: after every
+    // scheduler update the keep pixels (1 - maxpool8x8 of the binarised mask) become k_x z0 + k_n noise at the next timestep, z0 = scaling *
+    // mode(encode(image)); z0, the noise (a copy of noise_latents) and the keep mask live in the persistent part of the arena, the
+    // coefficients in d_keep_tab, so a captured graph holds no caller pointer.  Bit 1, pixels: the decode epilogue composites the decoded
+    // image over the input image with the binarised mask, blurred with a Gaussian of preserve_sigma pixels when that is > 0
+    int preserve_mode = 0; float preserve_sigma = 0.f;
+    float* d_keep_tab = nullptr; int keep_tab_cap = 0;
     // step callback (ladi_tryon_set_step_callback): after evaluation i with i % cb_every == 0 the latents go to the caller's fp32 NCHW
     // cb_latents, cb_fn(cb_user, i) runs on the host, and cb_latents comes back (edits included); fn == null = off
     int (*cb_fn)(void*, int) = nullptr; void* cb_user = nullptr; int cb_every = 1; float* cb_latents = nullptr;
@@ -544,6 +551,13 @@ struct SchedInfo {
 // under-denoised).  first_step <= steps - 1 (PNDM: steps - 2); first_step = 0 gives the whole run's tables bit for bit.
 void build_step_table(int code, int steps, const float* alphas_cumprod, int cloth_zero_from, std::vector<double>& timesteps,
                       std::vector<StepTable>& table, SchedInfo* info = nullptr, double eta = 0.0, int first_step = 0);
+// preserve-unmasked latent blend: out[i] = {k_x, k_n} of the scheduler's add_noise at timesteps[i + 1], the timestep the latents belong to
+// after the update of evaluation i (DDIM / PNDM / DPM-Solver++: sqrt(a), sqrt(1 - a); LMS / Euler / Euler-ancestral: 1, sigma[i + 1]), float64
+// arithmetic held in fp32; the last row is {1, 0}.  For a whole run or a tail (first_step), one row per evaluation of build_step_table
+void build_keep_coeffs(int code, int steps, const float* alphas_cumprod, int first_step, std::vector<float>& out);
+// the same from the timesteps and SchedInfo a build_step_table(code, .., first_step) call returned
+void keep_coeffs_of(int code, const std::vector<double>& timesteps, const SchedInfo& info, const float* alphas_cumprod, int first_step,
+                    std::vector<float>& out);
 // true if the table has a stochastic term (some c_n != 0: Euler-ancestral, DDIM with eta > 0), i.e. a run of it needs step noise
 bool table_needs_step_noise(const std::vector<StepTable>& table);
 

@@ -696,6 +696,28 @@ void build_step_table(int code, int steps, const float* ac, int cloth_zero_from,
         if (i >= cloth_zero_from) table[i - 1].zero_cloth_next = 1;
 }
 
+void build_keep_coeffs(int code, int steps, const float* ac, int first_step, std::vector<float>& out) {
+    std::vector<double> ts; std::vector<StepTable> tb; SchedInfo info;
+    build_step_table(code, steps, ac, 1 << 30, ts, tb, &info, 0.0, first_step);
+    keep_coeffs_of(code, ts, info, ac, first_step, out);
+}
+
+void keep_coeffs_of(int code, const std::vector<double>& timesteps, const SchedInfo& info, const float* ac, int first_step,
+                    std::vector<float>& out) {
+    const int kind = decode_sched_code(code).kind;
+    const bool sigma_kind = kind == SCHED_LMS || kind == SCHED_EULER || kind == SCHED_EULER_A;
+    const int evals = (int)timesteps.size();
+    out.assign((size_t)evals * 2, 0.f);
+    for (int i = 0; i < evals; ++i) {
+        double kx = 1.0, kn = 0.0;      // after the last evaluation: the clean latents
+        if (i + 1 < evals) {
+            if (sigma_kind) kn = (double)info.sigmas[(size_t)first_step + i + 1];
+            else { const double a = ac[(int)timesteps[i + 1]]; kx = std::sqrt(a); kn = std::sqrt(1.0 - a); }
+        }
+        out[2 * (size_t)i] = (float)kx; out[2 * (size_t)i + 1] = (float)kn;
+    }
+}
+
 bool table_needs_step_noise(const std::vector<StepTable>& table) {
     for (const StepTable& e : table)
         if (e.c_n != 0.f) return true;

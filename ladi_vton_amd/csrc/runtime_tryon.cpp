@@ -135,6 +135,13 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
     if (evals > table_cap) { d_table = reinterpret_cast<StepTable*>(pool.alloc((size_t)evals * sizeof(StepTable))); table_cap = evals; }
     if (guided && evals > gtab_cap) { d_gtab = reinterpret_cast<float*>(pool.alloc((size_t)evals * sizeof(float))); gtab_cap = evals; }
     if (use_factor && B > factor_cap) { d_factor = reinterpret_cast<float*>(pool.alloc((size_t)B * sizeof(float))); factor_cap = B; }
+    // preserve-unmasked: the blend's coefficients per evaluation, float64 on the host like the step table
+    const bool keep_lat = (preserve_mode & 1) != 0, keep_pix = (preserve_mode & 2) != 0;
+    std::vector<float> keep_tab;
+    if (keep_lat) {
+        keep_coeffs_of(in.scheduler, timesteps, sinfo, ac.data(), first_step, keep_tab);
+        if (evals > keep_tab_cap) { d_keep_tab = reinterpret_cast<float*>(pool.alloc((size_t)evals * 2 * sizeof(float))); keep_tab_cap = evals; }
+    }
     if (!ev[0]) for (auto& e : ev) HIP_OK(hipEventCreate(&e));
     // a table with a stochastic term (Euler-ancestral, DDIM with eta > 0): the caller's per-step noise is copied into a runtime-owned buffer
     // (below, on the run's stream) so that the pointer the captured graph holds stays valid after the caller frees theirs
@@ -182,6 +189,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 HIP_OK(hipMemcpyAsync(d_table, table.data(), (size_t)evals * sizeof(StepTable), hipMemcpyHostToDevice, st));
                 HIP_OK(hipMemsetAsync(d_step, 0, 2 * sizeof(int), st));    // evaluation index + the step kernel's arrival ticket
                 if (guided) HIP_OK(hipMemcpyAsync(d_gtab, gtab.data(), (size_t)evals * sizeof(float), hipMemcpyHostToDevice, st));
+                if (keep_lat) HIP_OK(hipMemcpyAsync(d_keep_tab, keep_tab.data(), (size_t)evals * 2 * sizeof(float), hipMemcpyHostToDevice, st));
                 if (use_step_noise) HIP_OK(hipMemcpyAsync(step_noise_buf, step_noise_src, step_noise_bytes, hipMemcpyDeviceToDevice, st));
                 std::vector<float> tsf(timesteps.begin(), timesteps.end());
                 if (unet->compute_temb(tsf.data(), evals, st)) { rc = -5; break; }
@@ -206,6 +214,10 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 const int sh[5] = {H, H, H / 2, H / 4, H / 8}, sw[5] = {W, W, W / 2, W / 4, W / 8};
                 for (int i = 0; i < 5; ++i) skips[i] = c.new_act(B, sh[i], sw[i], emasc->cfg.out_ch[i]);
             }
+            // preserve-unmasked latent blend: runtime-owned for the whole run (the captured graph holds these, never the caller's noise)
+            float* keep_x0 = keep_lat ? c.alloc_f32((size_t)B * hw * 4) : nullptr;
+            float* keep_noise = keep_lat ? c.alloc_f32((size_t)B * hw * 4) : nullptr;
+            float* keep_mask = keep_lat ? c.alloc_f32((size_t)B * hw) : nullptr;
             const size_t mk_persist = arena.mark();
 
             if (!c.dry()) {
@@ -237,6 +249,24 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 c.stats_off = 0;
                 Act mom = vae->encode(c, cloth, feats);
                 if (!c.dry()) c.check(ladi_launch_posterior_sample(mom.p, mom.ld, in.noise_cloth, B, hw, vae->cfg.scaling_factor, cloth_lat, st), "posterior");
+                arena.release(mk);
+            }
+            // ---------------- 4c. preserve-unmasked: z0 = scaling * mode(encode(image)) (no RNG draw), the noise, the keep mask
+            if (keep_lat) {
+                const size_t mk = arena.mark();
+                Act full = c.new_act(B, H, W, 64);
+                if (!c.dry()) {
+                    c.check(ladi_launch_nchw_to_nhwc(in.image, in.in_f32, B, 3, H, W, full.p, 64, st), "nchw_to_nhwc");
+                    if (stats_cap) HIP_OK(hipMemsetAsync(stats, 0, stats_cap * sizeof(float), st));
+                }
+                Act feats[5];
+                c.stats_off = 0;
+                Act mom = vae->encode(c, full, feats);
+                if (!c.dry()) {
+                    c.check(ladi_launch_posterior_sample(mom.p, mom.ld, nullptr, B, hw, vae->cfg.scaling_factor, keep_x0, st), "posterior mode");
+                    c.check(ladi_launch_lat_nchw_to_pix(in.noise_latents, B, hw, 1.f, keep_noise, st), "keep noise");
+                    c.check(ladi_launch_mask_pool8(mask_bin, B, H, W, 1, keep_mask, st), "mask_pool8");
+                }
                 arena.release(mk);
             }
             // ---------------- 6. initial latents (RNG draw #2) * init_noise_sigma (1 for DDIM / PNDM; tryon_pipe.py:424)
@@ -273,6 +303,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
             sa.step_noise = use_step_noise ? step_noise_buf : nullptr;
             sa.guidance_tab = guided ? d_gtab : nullptr;
             sa.factor = use_factor ? d_factor : nullptr;
+            if (keep_lat) { sa.keep_x0 = keep_x0; sa.keep_noise = keep_noise; sa.keep_mask = keep_mask; sa.keep_tab = d_keep_tab; }
             // the UNet forward runs as lanes.G independent sample groups on as many streams (runtime.h UNetLanes); the lanes own their
             // arenas, the shared noise prediction lives in this one
             const int eps_ld = (unet->cfg.out_channels + 3) / 4 * 4;
@@ -359,6 +390,10 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 // capture on is never replayed for a plain run, nor the reverse)
                 key = mix(key, fc_on ? (unsigned long long)(uintptr_t)fcache : 0ULL);
                 key = mix(key, fc_on ? 0x200000000ULL | (unsigned long long)fc_branch : 0ULL);
+                // ... and with the latent blend: its buffers, the coefficient table and the mode
+                key = mix(key, (unsigned long long)(uintptr_t)sa.keep_x0); key = mix(key, (unsigned long long)(uintptr_t)sa.keep_noise);
+                key = mix(key, (unsigned long long)(uintptr_t)sa.keep_mask); key = mix(key, (unsigned long long)(uintptr_t)sa.keep_tab);
+                key = mix(key, keep_lat ? 0x400000000ULL | (unsigned long long)preserve_mode : 0ULL);
                 if (key != graph_key) {
                     if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
                     if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
@@ -407,6 +442,10 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
             // ---------------- 11. decode (tryon_pipe.py:349-359)
             {
                 Act z = c.new_act(B, h, w, 64);
+                // pixel composite with a feathered mask: the blurred mask and the row pass's scratch
+                const bool feather = keep_pix && preserve_sigma > 0.f;
+                float* m_soft = feather ? c.alloc_f32((size_t)B * H * W) : nullptr;
+                float* m_tmp = feather ? c.alloc_f32((size_t)B * H * W) : nullptr;
                 if (!c.dry()) {
                     if (stats_cap) HIP_OK(hipMemsetAsync(stats, 0, stats_cap * sizeof(float), st));
                     c.check(ladi_launch_post_quant(latents, vae->d_pq, 1.0f / vae->cfg.scaling_factor, B * hw, z.p, 64, st), "post_quant");
@@ -426,7 +465,11 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                     c.stats_off = 0;
                     if (stats_cap) HIP_OK(hipMemsetAsync(stats, 0, stats_cap * sizeof(float), st));
                     Act img = vae->decode(c, z, use_emasc ? skips : nullptr, sh);
-                    c.check(ladi_launch_image_post(img.p, img.ld, B * H * W, images_out, images_u8, st), "image_post");
+                    if (keep_pix) {
+                        if (feather) c.check(ladi_launch_mask_feather(mask_bin, B, H, W, preserve_sigma, m_tmp, m_soft, st), "mask_feather");
+                        c.check(ladi_launch_image_composite(img.p, img.ld, in.image, in.in_f32, feather ? (const void*)m_soft : (const void*)mask_bin,
+                                                            feather ? 1 : 0, B, H * W, images_out, images_u8, st), "image_composite");
+                    } else c.check(ladi_launch_image_post(img.p, img.ld, B * H * W, images_out, images_u8, st), "image_post");
                     vae->last_shift = sh;
                     vae->post_overflow_check(st);
                     if (latents_out) c.check(ladi_launch_lat_pix_to_nchw(latents, B, hw, latents_out, st), "latents_out");

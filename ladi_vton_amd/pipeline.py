@@ -131,6 +131,45 @@ def strength_first_step(strength, num_inference_steps):
     return n - init_timestep
 
 
+PRESERVE_MODES = {None: 0, "latents": 1, "pixels": 2, "both": 3}
+MAX_FEATHER = 32.0
+
+
+def preserve_spec(preserve_unmasked, mask_feather=0.0):
+    """-> (mode_bits, sigma) of `preserve_unmasked=` / `mask_feather=`: bit 0 latents, bit 1 pixels (ladi_tryon_set_preserve).  Raises ValueError
+    for an unknown mode, a feather that is negative, not finite or above 32, or a feather without a pixels mode."""
+    if not (preserve_unmasked is None or isinstance(preserve_unmasked, str)) or preserve_unmasked not in PRESERVE_MODES:
+        raise ValueError("`preserve_unmasked` has to be None, 'latents', 'pixels' or 'both' but is %r." % (preserve_unmasked,))
+    bits = PRESERVE_MODES[preserve_unmasked]
+    try:
+        sigma = float(mask_feather)
+    except (TypeError, ValueError):
+        raise ValueError("`mask_feather` has to be a number in [0, %g] but is %r." % (MAX_FEATHER, mask_feather))
+    if not math.isfinite(sigma) or sigma < 0.0 or sigma > MAX_FEATHER:
+        raise ValueError("`mask_feather` has to be in [0, %g] but is %r." % (MAX_FEATHER, mask_feather))
+    if sigma > 0.0 and not bits & 2:
+        raise ValueError("`mask_feather` > 0 needs preserve_unmasked='pixels' or 'both' (it acts on the pixel composite only).")
+    return bits, sigma
+
+
+def feather_mask(mask, sigma):
+    """the separable Gaussian blur of the pixel composite in torch fp32: mask [B, 1, H, W], radius ceil(3 sigma), weights normalised in
+    float64, replicate border, rows then columns; a window of equal values returns that value exactly"""
+    r = int(math.ceil(3.0 * sigma))
+    k = torch.arange(-r, r + 1, dtype=torch.float64)
+    wgt = torch.exp(-0.5 * k * k / (sigma * sigma))
+    wgt = (wgt / wgt.sum()).to(device=mask.device, dtype=torch.float32)
+    F = torch.nn.functional
+
+    def one_pass(x, pad, shape):
+        # a window of equal values returns that value itself, as the device kernel does: away from its edges the mask stays exactly 0 or 1
+        xp = F.pad(x, pad, mode="replicate")
+        size = (1, 2 * r + 1) if shape[-1] == -1 else (2 * r + 1, 1)
+        hi, lo = F.max_pool2d(xp, size, stride=1), -F.max_pool2d(-xp, size, stride=1)
+        return torch.where(lo == hi, lo, F.conv2d(xp, wgt.view(shape)))
+    return one_pass(one_pass(mask.float(), (r, r, 0, 0), (1, 1, 1, -1)), (0, 0, r, r), (1, 1, -1, 1))
+
+
 def rescale_noise_cfg(eps, eps_cond, phi):
     """guidance rescale: eps * (phi * std(eps_cond) / std(eps) + 1 - phi), per-sample unbiased stds, no epsilon"""
     dims = list(range(1, eps.ndim))
@@ -289,7 +328,7 @@ class StableDiffusionTryOnePipeline:
                  negative_prompt_embeds=None, generator=None, latents=None, output_type="pil", return_dict=True, callback=None,
                  callback_steps=1, cloth_cond_rate=1.0, no_pose=False, cloth_input_type="warped", fused=True, noise=None,
                  use_graph=True, guidance_rescale=0.0, strength=1.0, init_image=None, init_latents=None, init_is_noisy=False,
-                 feature_cache=None):
+                 feature_cache=None, preserve_unmasked=None, mask_feather=0.0):
         """tryon_pipe.py's __call__.  `guidance_scale`: a float, a sequence with one scale per evaluation (len(scheduler.timesteps); PNDM: steps
         + 1) or a callable f(i, n_evals) -- see guidance_interval.  Classifier-free guidance is on if any scale is > 1; an evaluation whose scale
         is <= 1 then runs the UNet over the conditional samples only.  `guidance_rescale` (rescale_noise_cfg's phi, [0, 1]) acts on the CFG
@@ -311,7 +350,16 @@ class StableDiffusionTryOnePipeline:
         layers of the first down block, and as many more of the last up block, a shallow evaluation runs; default 0) or a sequence of one
         truthy (whole) / falsy (shallow) entry per evaluation.  Evaluation 0 is always whole; N = 1 or an all-true sequence is the plain run.
         See feature_cache_plan for the one promotion rule; the cloth cut-off, a callback's edit of the latents and PNDM's double evaluation
-        reuse the cache as it is.  Needs the native UNet.  `pipe.shallow_evals` counts the shallow evaluations of the last run."""
+        reuse the cache as it is.  Needs the native UNet.  `pipe.shallow_evals` counts the shallow evaluations of the last run.
+
+        `preserve_unmasked` (None = off) hands the region outside `mask_image` back unchanged.  "latents" is diffusers' 4-channel inpaint
+        rule: after every scheduler update the latent pixels whose whole 8x8 footprint is unmasked are replaced by the known image noised to
+        the next timestep, k_x z0 + k_n noise with the scheduler's add_noise coefficients at timesteps[i + 1], and by z0 after the last
+        evaluation; z0 is the posterior mode of vae.encode(image) times scaling_factor (one more encode, no extra RNG draw) and the noise is
+        that of `latents=` / RNG draw #2, also with `strength` < 1.  Scheduler state is not blended; a callback sees the blended latents.
+        "pixels" composites the decoded picture over the input image, M g + (1 - M) p with the binarised mask M, or its Gaussian blur of
+        `mask_feather` pixels sigma (0 .. 32); where M is 0 or 1 the pixel is p or g bit for bit, in the float and the uint8 output alike.
+        "both" does both.  `mask_feather` needs a pixels mode."""
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
@@ -327,6 +375,7 @@ class StableDiffusionTryOnePipeline:
         if not isinstance(num_images_per_prompt, int) or num_images_per_prompt < 1:
             raise ValueError("num_images_per_prompt must be a positive integer")
         first_step = strength_first_step(strength, num_inference_steps)
+        preserve = preserve_spec(preserve_unmasked, mask_feather)
         if init_image is not None and init_latents is not None:
             raise ValueError("Cannot forward both `init_image` and `init_latents`.")
         if first_step > 0:
@@ -383,7 +432,7 @@ class StableDiffusionTryOnePipeline:
                                      no_pose, use_graph, step_noise=step_noise, eta=ddim_eta, callback=callback,
                                      callback_steps=callback_steps, guidance_table=g_table, guidance_rescale=guidance_rescale,
                                      init_latents=init, first_step=first_step, init_is_noisy=init_is_noisy,
-                                     feature_cache=(fc_flags, fc_branch))
+                                     feature_cache=(fc_flags, fc_branch), preserve=preserve)
             # prepare_mask_and_masked_image binarises the caller's mask in place; keep that side effect
             mask_image[mask_image < 0.5] = 0
             mask_image[mask_image >= 0.5] = 1
@@ -392,7 +441,7 @@ class StableDiffusionTryOnePipeline:
                                        n_cloth, n_lat, n_mask, height, width, num_inference_steps, guidance_scale, cloth_cond_rate,
                                        no_pose, eta, generator, callback, callback_steps, guidance_table=g_table,
                                        guidance_rescale=guidance_rescale, init_latents=init, first_step=first_step,
-                                       init_is_noisy=init_is_noisy, feature_cache=(fc_flags, fc_branch))
+                                       init_is_noisy=init_is_noisy, feature_cache=(fc_flags, fc_branch), preserve=preserve)
         if output_type == "pil":
             images = numpy_to_pil(images)
         if not return_dict:
@@ -420,7 +469,8 @@ class StableDiffusionTryOnePipeline:
     # -------------------------------------------------------------------------------------------------------
     def _run_fused(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose,
                    use_graph, return_device=False, out_uint8=False, lanes=None, step_noise=None, eta=0.0, callback=None, callback_steps=1,
-                   guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0, init_is_noisy=False, feature_cache=None):
+                   guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0, init_is_noisy=False, feature_cache=None,
+                   preserve=None):
         """return_device: hand back the device tensor (no host copy); out_uint8: the batch as uint8 [B,H,W,3] = numpy_to_pil's
         (images * 255).round() computed by the decode epilogue (ladi_tryon_run_u8); lanes: sample-group lanes of the UNet forward;
         step_noise: fp32 [steps, B, 4, h, w], the per-step noise of EulerAncestralDiscreteScheduler and of DDIM with eta > 0
@@ -434,7 +484,8 @@ class StableDiffusionTryOnePipeline:
         [B, 4, hs, ws] init_latents (None or first_step = 0: off).  The run then has the tail's evaluations: step_noise, guidance_table, the
         callback's i and the cloth cut-off of `ccr` all refer to them.
         feature_cache: (flags, branch) of feature_cache_spec, one flag per evaluation before promotion (ladi_tryon_set_feature_cache does the
-        promotion); None or flags None = off."""
+        promotion); None or flags None = off.
+        preserve: (mode_bits, feather sigma) of preserve_spec (ladi_tryon_set_preserve); None = off."""
         lib = _lib.load()
         if self._tryon is None:
             self._tryon = lib.ladi_tryon_create(self.unet.h, self.vae.h, self.emasc.h if self.emasc else None)
@@ -517,6 +568,8 @@ class StableDiffusionTryOnePipeline:
             check(lib.ladi_tryon_set_feature_cache(self._tryon, ff, len(fc_flags), int(fc_branch)), "ladi_tryon_set_feature_cache")
         else:
             check(lib.ladi_tryon_set_feature_cache(self._tryon, None, 0, 0), "ladi_tryon_set_feature_cache")
+        p_bits, p_sigma = preserve if preserve is not None else (0, 0.0)
+        check(lib.ladi_tryon_set_preserve(self._tryon, int(p_bits), float(p_sigma)), "ladi_tryon_set_preserve")
         self._shallow_evals = None
         cb_error = []
         cb_latents = trampoline = None
@@ -608,7 +661,7 @@ class StableDiffusionTryOnePipeline:
     # -------------------------------------------------------------------------------------------------------
     def _run_modular(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose, eta,
                      generator, callback, callback_steps, guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0,
-                     init_is_noisy=False, feature_cache=None):
+                     init_is_noisy=False, feature_cache=None, preserve=None):
         F = torch.nn.functional
         dev = self._execution_device
         do_cfg = neg is not None
@@ -640,6 +693,12 @@ class StableDiffusionTryOnePipeline:
             timesteps = self.scheduler.timesteps
             latents = n_lat * self.scheduler.init_noise_sigma
         ccs = (1 - ccr) * steps
+        p_bits, p_sigma = preserve if preserve is not None else (0, 0.0)
+        if p_bits & 1:
+            # preserve-unmasked, latents: z0 (the posterior mode: no RNG draw) and the latent pixels whose whole 8x8 footprint is unmasked
+            z0 = (sf * self.vae.encode(image.to(dev))[0].latent_dist.mode().float()).contiguous()
+            keep = F.max_pool2d(mask.float(), 8) < 0.5
+            keep_noise = n_lat.to(dev)
         mask_lat = F.interpolate(mask.float(), size=(H // 8, W // 8))
         enc, feats = self.vae.encode(masked_image)
         masked_lat = sf * enc.latent_dist.sample(noise=n_mask).float()
@@ -693,10 +752,20 @@ class StableDiffusionTryOnePipeline:
                 if guidance_rescale > 0.0:
                     eps = rescale_noise_cfg(eps, et, guidance_rescale)
             latents = self.scheduler.step(eps, t, latents, **extra).prev_sample
+            if p_bits & 1:
+                known = self.scheduler.add_noise(z0, keep_noise, timesteps[i + 1]) if i + 1 < len(timesteps) else z0
+                latents = torch.where(keep, known.to(latents.dtype), latents)
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, latents)
         self.last_latents = latents
         images = self.decode_latents(latents, inter)
+        if p_bits & 2:
+            # preserve-unmasked, pixels: the decoded picture over the input image, a select where the (feathered) mask is 0 or 1
+            m = feather_mask(mask, p_sigma) if p_sigma > 0.0 else mask.float()
+            m = m.permute(0, 2, 3, 1).cpu()
+            g = torch.from_numpy(images)
+            p = (image.to(dev).float() / 2 + 0.5).clamp(0, 1).permute(0, 2, 3, 1).cpu()
+            images = torch.where(m == 0, p, torch.where(m == 1, g, m * g + (1 - m) * p)).numpy()
         bad = self._check_range_probe()
         if bad is not None:
             raise self._range_error(bad)
