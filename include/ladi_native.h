@@ -404,6 +404,13 @@ int ladi_unet_time_forward_cached(ladi_unet* u, int n, int h, int w, int iters, 
  * the loop's own choice, LADI_UNET_LANES or 1; must divide n), replayed from one hipGraph with `lanes` parallel branches when
  * use_graph != 0.  Runs on an internal stream fenced against `stream`; synchronises. */
 int ladi_unet_time_forward_lanes(ladi_unet* u, int n, int h, int w, int iters, int lanes, int use_graph, float* avg_ms, void* stream);
+/* FreeU (diffusers UNet2DConditionModel.enable_freeu, same argument order; sticky, off at creation).  on != 0: before every concatenation
+ * cat([hidden, skip]) of up_blocks.0 (s1, b1) and up_blocks.1 (s2, b2) the first half of the hidden state's channels is multiplied by b
+ * and the skip goes through diffusers' fourier_filter(threshold = 1, scale = s) -- one extra launch per site, 2 * (layers_per_block + 1)
+ * per whole forward; a shallow forward of the feature cache has no such site.  Every entry that runs this UNet honours it (forward,
+ * forward_cached, time_forward*, ladi_tryon_run, whose captured graphs are keyed on it).  on == 0 ignores the values and launches
+ * exactly the plain forward.  A null handle or a non-finite value returns -1 with a message. */
+int ladi_unet_set_freeu(ladi_unet* u, int on, float s1, float s2, float b1, float b2);
 
 /* per-launch HIP-event timing of the implicit-GEMM kernel family (the dominant kernel): enable, run any entry point,
  * then collect: out[cfg*3 + {0,1,2}] = {total ms, algorithmic FLOP = 2*P*Q*K, launches} for tile configuration cfg = 1..ladi_igemm_cfg_count()
@@ -659,6 +666,14 @@ int ladi_op_init_latents(const float* init, int hs, int ws, const float* noise, 
 int ladi_op_latents_import(const float* src, int B, int hw, float* latents, void* unet_in, int ld_in, int cfg, float in_scale, void* stream);
 int ladi_op_scale_h16(const void* src, int lds, void* dst, int ldd, long long n_pix, int C, float s, void* stream);
 int ladi_op_fill_f32(float* p, long long n, float v, void* stream);
+/* one FreeU site.  hidden NHWC fp16 [n][H][W] rows of ld_h halves: channels [0, C_h / 2) become fp16(float(x) * b) in place, every other
+ * half of a row keeps its bits.  skip NHWC fp16 (ld_s) -> skip_out NHWC fp16 (ld_d; skip_out == skip allowed): each (sample, channel) plane
+ * becomes x + (s - 1) lp, lp the part of x at the frequencies {0, -1 mod H} x {0, -1 mod W} (fourier_filter, threshold 1) -- fp32 sums in a
+ * fixed order (two launches are bit-equal), one rounding; halves outside [0, C_s) of a skip_out row are not written.  hidden == NULL or
+ * skip == NULL does only the other half.  Any H, W >= 1; C_h % 16 == 0, C_s % 8 == 0, every ld a multiple of 8 and >= C, 16-byte aligned
+ * pointers: anything else is refused with a message and nothing is launched. */
+int ladi_op_freeu(void* hidden, int ld_h, int C_h, float b, const void* skip, int ld_s, int C_s, float s, void* skip_out, int ld_d, int n, int H,
+                  int W, void* stream);
 
 /* ---- fp16 range probe (opt-in; with no probe attached nothing changes: same launches, same captured graph, same bits) ----
  * A probe records, for every named activation of the modules it is attached to, the largest finite |x| and the number of inf / NaN

@@ -112,6 +112,7 @@ SIGNATURES = {
     "ladi_unet_time_forward": (c_int, [_P, c_int, c_int, c_int, c_int, POINTER(c_float), _P]),
     "ladi_unet_time_forward_cached": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P]),
     "ladi_unet_time_forward_lanes": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P]),
+    "ladi_unet_set_freeu": (c_int, [_P, c_int, c_float, c_float, c_float, c_float]),
     "ladi_vae_create": (_P, [POINTER(VAEConfig), _P]),
     "ladi_vae_destroy": (None, [_P]),
     "ladi_vae_encode": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, POINTER(_P), _P]),
@@ -257,6 +258,7 @@ SIGNATURES = {
     "ladi_op_latents_import": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_float, _P]),
     "ladi_op_scale_h16": (c_int, [_P, c_int, _P, c_int, c_longlong, c_int, c_float, _P]),
     "ladi_op_fill_f32": (c_int, [_P, c_longlong, c_float, _P]),
+    "ladi_op_freeu": (c_int, [_P, c_int, c_int, c_float, _P, c_int, c_int, c_float, _P, c_int, c_int, c_int, c_int, _P]),
 }
 
 _lib = None

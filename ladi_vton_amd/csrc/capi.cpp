@@ -121,6 +121,20 @@ int ladi_unet_set_context(ladi_unet* u, const void* ehs, int n, int L, void* str
     return guarded("ladi_unet_set_context", [&]() { return u->u.set_context(reinterpret_cast<const h16*>(ehs), n, L, S(stream)); });
 }
 
+int ladi_unet_set_freeu(ladi_unet* u, int on, float s1, float s2, float b1, float b2) {
+    if (!u) { set_error("ladi_unet_set_freeu: null handle"); return -1; }
+    FreeU f;
+    if (on) {
+        if (!std::isfinite(s1) || !std::isfinite(s2) || !std::isfinite(b1) || !std::isfinite(b2)) {
+            set_error("ladi_unet_set_freeu: s1, s2, b1 and b2 have to be finite");
+            return -1;
+        }
+        f.on = true; f.s1 = s1; f.s2 = s2; f.b1 = b1; f.b2 = b2;
+    }
+    u->u.freeu = f;
+    return 0;
+}
+
 int ladi_unet_forward(ladi_unet* u, const void* sample, int dtype, int n, int h, int w, float timestep, void* out, int out_dtype,
                       void* stream) {
     return guarded("ladi_unet_forward", [&]() {
@@ -1150,6 +1164,23 @@ int ladi_op_scale_h16(const void* src, int lds, void* dst, int ldd, long long n_
     return ladi_launch_scale_h16((const h16*)src, lds, (h16*)dst, ldd, (size_t)n_pix, C, s, S(stream));
 }
 int ladi_op_fill_f32(float* p, long long n, float v, void* stream) { return ladi_launch_fill_f32(p, (size_t)n, v, S(stream)); }
+int ladi_op_freeu(void* hidden, int ld_h, int C_h, float b, const void* skip, int ld_s, int C_s, float s, void* skip_out, int ld_d, int n, int H,
+                  int W, void* stream) {
+    return guarded("ladi_op_freeu", [&]() {
+        if (!hidden && !skip) throw std::runtime_error("hidden and skip are both null");
+        if (n < 1 || H < 1 || W < 1) throw std::runtime_error("every size has to be >= 1");
+        if (hidden && (C_h < 16 || (C_h & 15))) throw std::runtime_error("C_h = " + std::to_string(C_h) + " is not a multiple of 16");
+        if (skip && (C_s < 8 || (C_s & 7))) throw std::runtime_error("C_s = " + std::to_string(C_s) + " is not a multiple of 8");
+        if (skip && !skip_out) throw std::runtime_error("skip without skip_out");
+        if ((hidden && (ld_h < C_h || (ld_h & 7) || ((uintptr_t)hidden & 15))) ||
+            (skip && (ld_s < C_s || ld_d < C_s || (ld_s & 7) || (ld_d & 7) || ((uintptr_t)skip & 15) || ((uintptr_t)skip_out & 15))))
+            throw std::runtime_error("every row stride has to be a multiple of 8 and >= its channel count, every pointer 16-byte aligned");
+        const int rc = ladi_launch_freeu(reinterpret_cast<h16*>(hidden), ld_h, C_h, b, reinterpret_cast<const h16*>(skip), ld_s, C_s, s,
+                                         reinterpret_cast<h16*>(skip_out), ld_d, n, H, W, S(stream));
+        if (rc) throw std::runtime_error("launch refused or failed (rc = " + std::to_string(rc) + ")");
+        return 0;
+    });
+}
 static int sched_run_any(const char* name, int kind, int steps, const float* ac_host, const void* eps_seq, int evals, int B, int hw, int cfg,
                          float guidance, float* latents, const float* step_noise, int noise_steps, float eta, void* stream) {
     return guarded(name, [&]() {

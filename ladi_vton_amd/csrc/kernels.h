@@ -245,6 +245,15 @@ int ladi_feather_radius(float sigma);
 int ladi_launch_image_composite(const h16* src, int ld, const void* image_nchw, int img_f32, const void* mask, int mask_f32, int B, int HW,
                                 void* dst, int dst_u8, hipStream_t st);
 
+// ---- freeu.hip: one FreeU site (diffusers apply_freeu) in one launch.  hidden NHWC (row stride ld_h): channels [0, C_h / 2) become
+// fp16(float(x) * b) in place, everything else of a row keeps its bits.  skip NHWC (ld_s) -> skip_out NHWC (ld_d, == skip allowed): per
+// (sample, channel) plane x + (s - 1) lp, lp the part of x at the frequencies {0, -1} x {0, -1} (fourier_filter with threshold 1), fp32 sums
+// in a fixed order, one rounding; bytes outside [0, C_s) of a row are not written.  Either half may be null (then only the other runs).
+// Any H, W >= 1.  -1: nothing to do / a size < 1; -2: C_h % 16 or C_s % 8; -3: a row stride below C, not a multiple of 8, or a pointer
+// that is not 16-byte aligned.  Nothing is launched on a refusal
+int ladi_launch_freeu(h16* hidden, int ld_h, int C_h, float b, const h16* skip, int ld_s, int C_s, float s, h16* skip_out, int ld_d, int n,
+                      int H, int W, hipStream_t st);
+
 // ---- f32path.hip: fp32 kernels of the warping module (fp32 NHWC activations, fp32 weights, v_mfma_f32_32x32x2_f32)
 struct ConvF32Args {
     const float* src0; const float* src1;   // up to two NHWC fp32 sources concatenated along channels

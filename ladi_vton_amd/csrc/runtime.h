@@ -215,8 +215,18 @@ struct FeatCache {
     h16* buf = nullptr;
 };
 
+// FreeU (diffusers enable_freeu; ladi_unet_set_freeu, sticky, off by default).  Before every concatenation cat([hidden, skip]) of
+// up_blocks.0 (b1, s1) and up_blocks.1 (b2, s2) -- 2 x (layers_per_block + 1) sites -- the first half of the hidden state's channels is
+// multiplied by b and the skip's lowest frequencies by s, one launch per site (freeu.hip), in place: both tensors have this resnet as
+// their only remaining reader.  Off launches exactly the plain forward.  A captured graph of the forward is keyed on all five fields
+struct FreeU {
+    bool on = false;
+    float s1 = 1.f, s2 = 1.f, b1 = 1.f, b2 = 1.f;
+};
+
 struct UNet {
     UNetCfg cfg;
+    FreeU freeu;
     DevPool pool;
     DConv conv_in, conv_out, time_l1, time_l2, temb_all;
     DNorm norm_out;

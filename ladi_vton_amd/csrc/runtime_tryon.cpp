@@ -394,6 +394,13 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 key = mix(key, (unsigned long long)(uintptr_t)sa.keep_x0); key = mix(key, (unsigned long long)(uintptr_t)sa.keep_noise);
                 key = mix(key, (unsigned long long)(uintptr_t)sa.keep_mask); key = mix(key, (unsigned long long)(uintptr_t)sa.keep_tab);
                 key = mix(key, keep_lat ? 0x400000000ULL | (unsigned long long)preserve_mode : 0ULL);
+                // ... and with FreeU: on / off and the bits of the four factors the captured launches carry as arguments
+                {
+                    const FreeU& fu = unet->freeu;
+                    const float fv[4] = {fu.s1, fu.s2, fu.b1, fu.b2};
+                    key = mix(key, fu.on ? 0x800000000ULL : 0ULL);
+                    for (int i = 0; i < 4; ++i) { unsigned fb = 0; if (fu.on) std::memcpy(&fb, &fv[i], 4); key = mix(key, fb); }
+                }
                 if (key != graph_key) {
                     if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
                     if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }

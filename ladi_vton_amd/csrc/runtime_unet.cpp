@@ -348,6 +348,15 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
                 }
             }
             Act sk = skips.back(); skips.pop_back();
+            if (freeu.on && i < 2) {
+                // FreeU site (runtime.h FreeU): in place, nothing is allocated.  The producers' statistics rows describe the unmodified
+                // tensors: the consuming GroupNorm computes them from the data, as it does for the cached tensor
+                if (!c.dry())
+                    c.check(ladi_launch_freeu(h.p, h.ld, h.c, i ? freeu.b2 : freeu.b1, sk.p, sk.ld, sk.c, i ? freeu.s2 : freeu.s1, sk.p, sk.ld,
+                                              h.n, h.h, h.w, c.st), "freeu");
+                h.st_part = nullptr; h.st_px = 0;
+                sk.st_part = nullptr; sk.st_px = 0;
+            }
             h = f.res(up_res[ri++], h, &sk);
             pp(h, "up_blocks.%d.resnets.%d", i, j);
             if (i > 0) { h = f.xf(up_xf[xi++], h); pp(h, "up_blocks.%d.attentions.%d", i, j); }

@@ -122,11 +122,24 @@ class NativeUNet(_Base):
                                       _diffusers_version="0.14.0")
         self._ctx_key = None
         self._ctx_keepalive = None
+        self.freeu = None             # (s1, s2, b1, b2) while FreeU is on
 
     def __del__(self):
         if getattr(self, "h", None):
             self.lib.ladi_unet_destroy(self.h)
             self.h = None
+
+    def enable_freeu(self, s1, s2, b1, b2):
+        """diffusers' UNet2DConditionModel.enable_freeu: in up_blocks.0 (s1, b1) and up_blocks.1 (s2, b2) the first half of the backbone
+        channels is scaled by b and the skip's lowest frequencies by s before each concatenation.  Holds for every later forward of this
+        UNet, stand-alone or inside the fused loop, until disable_freeu()."""
+        v = tuple(float(x) for x in (s1, s2, b1, b2))
+        check(self.lib.ladi_unet_set_freeu(self.h, 1, *v), "ladi_unet_set_freeu")
+        self.freeu = v
+
+    def disable_freeu(self):
+        check(self.lib.ladi_unet_set_freeu(self.h, 0, 1.0, 1.0, 1.0, 1.0), "ladi_unet_set_freeu")
+        self.freeu = None
 
     def enable_xformers_memory_efficient_attention(self, *a, **k):
         return None  # attention is always fused (flash-style) in the native kernels

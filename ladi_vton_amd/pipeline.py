@@ -201,6 +201,18 @@ class StableDiffusionTryOnePipeline:
         self._range_probe = None
         self._shallow_evals = None    # modular runs count here; fused runs ask the library
 
+    def enable_freeu(self, s1, s2, b1, b2):
+        """diffusers' pipe.enable_freeu(s1, s2, b1, b2): forwarded to the UNet (NativeUNet.enable_freeu), where the state lives; the fused
+        and the modular path both run it"""
+        if not hasattr(self.unet, "enable_freeu"):
+            raise ValueError("`enable_freeu` needs a UNet with enable_freeu (NativeUNet), the pipeline holds %s." % type(self.unet).__name__)
+        self.unet.enable_freeu(s1, s2, b1, b2)
+
+    def disable_freeu(self):
+        if not hasattr(self.unet, "disable_freeu"):
+            raise ValueError("`disable_freeu` needs a UNet with disable_freeu (NativeUNet), the pipeline holds %s." % type(self.unet).__name__)
+        self.unet.disable_freeu()
+
     @property
     def shallow_evals(self):
         """how many evaluations of the last run ran shallow (`feature_cache=`), after promotion (fused: ladi_tryon_shallow_evals)"""
