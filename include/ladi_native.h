@@ -411,6 +411,35 @@ int ladi_unet_time_forward_lanes(ladi_unet* u, int n, int h, int w, int iters, i
  * forward_cached, time_forward*, ladi_tryon_run, whose captured graphs are keyed on it).  on == 0 ignores the values and launches
  * exactly the plain forward.  A null handle or a non-finite value returns -1 with a message. */
 int ladi_unet_set_freeu(ladi_unet* u, int on, float s1, float s2, float b1, float b2);
+/* Perturbed-attention guidance (diffusers PAGMixin: pag_scale, pag_adaptive_scale, pag_applied_layers).  A PAG evaluation has one more
+ * sample group behind the conditional one, with the conditional group's inputs and context; in the SELECTED transformer blocks the
+ * self-attention (attn1) of those perturbed samples has the identity as its attention map, i.e. its output is to_out(to_v(norm1(x))):
+ * no attention is launched for them, one 16-byte copy kernel moves V into the attention output.  attn2, the feed-forward, every other block
+ * and every other sample are untouched.
+ * The transformer blocks are numbered in execution order: bits 0 .. 3L-1 down_blocks.{0,1,2}.attentions.{0..L-1}, bit 3L mid_block, bits
+ * 3L+1 .. 6L+3 up_blocks.{1,2,3}.attentions.{0..L} (L = layers_per_block; 16 blocks for L = 2, the mid block is bit 6).
+ * ladi_unet_pag_layer_count: the number of blocks.  ladi_unet_set_pag_layers: sticky; the state of a new handle is the mid block alone
+ * (diffusers' default); a mask of 0 or with bits beyond the count returns -1 with a message and changes nothing.  The mask has no effect on
+ * a forward without perturbed samples.  ladi_unet_pag_layers: the current mask (0 for a null handle).
+ * ladi_unet_forward_pag: ladi_unet_forward over the samples [sample0, sample0 + n) of the context batch (ladi_unet_set_context); samples
+ * whose index in that batch is >= pag_first are perturbed (pag_first >= sample0 + n: none, the plain forward bit for bit; <= sample0:
+ * all, and the selected blocks launch no self-attention).  The unperturbed samples' results do not depend on the others. */
+int ladi_unet_pag_layer_count(const ladi_unet* u);
+int ladi_unet_set_pag_layers(ladi_unet* u, unsigned layer_mask);
+unsigned ladi_unet_pag_layers(const ladi_unet* u);
+int ladi_unet_forward_pag(ladi_unet* u, const void* sample_dev, int dtype, int n, int h, int w, float timestep, void* out_dev, int out_dtype,
+                          int sample0, int pag_first, void* stream);
+/* PAG scales of the following runs (sticky per handle; copied): scales_host[i] = s_i of evaluation i.  NULL or count 0 switches it off; a
+ * table of zeros is the plain run bit for bit (nothing is allocated or launched for it).  With any s_i > 0 the run has the third sample group
+ * ([uncond ; cond ; perturbed], or [cond ; perturbed] without CFG; context [neg ; pe ; pe]) and the guided prediction of an evaluation with
+ * s_i > 0 is u + g_i (c - u) + s_i (c - p), or c + s_i (c - p) without CFG and in a cond-only evaluation; guidance rescale acts on the
+ * three-term sum of CFG evaluations.  An evaluation with s_i == 0 runs without the perturbed group.  The blocks are the UNet's
+ * (ladi_unet_set_pag_layers).  A run whose evaluation count is not `count` fails with -9 before anything is launched, like a guidance
+ * schedule of the wrong length; a negative or non-finite entry returns -1 here.  NOT supported together with the feature cache: a run with
+ * a positive entry and a feature-cache plan fails with LADI_TRYON_PAG_WITH_FEATURE_CACHE before anything is launched.  With use_graph the
+ * loop replays up to two more graphs (PAG evaluation over all groups, and over cond + perturbed); works with any lane count. */
+#define LADI_TRYON_PAG_WITH_FEATURE_CACHE (-12)
+int ladi_tryon_set_pag(ladi_tryon* t, const float* scales_host, int count);
 
 /* per-launch HIP-event timing of the implicit-GEMM kernel family (the dominant kernel): enable, run any entry point,
  * then collect: out[cfg*3 + {0,1,2}] = {total ms, algorithmic FLOP = 2*P*Q*K, launches} for tile configuration cfg = 1..ladi_igemm_cfg_count()
@@ -585,6 +614,22 @@ int ladi_op_sched_run_keep(int kind, int steps, const float* alphas_cumprod_host
 /* the guidance-rescale statistics kernel on its own: eps_dev [2B][hw] rows of 4 fp16 channels, ld_eps halves apart, uncond half first ->
  * factor_dev[b] = phi * std(cond_b) / std(u_b + guidance (c_b - u_b)) + (1 - phi), fp32 [B].  Bit-reproducible from call to call. */
 int ladi_op_cfg_stats(const void* eps_dev, int ld_eps, int B, int hw, float guidance, float phi, float* factor_dev, void* stream);
+/* ladi_op_sched_run_guided with perturbed-attention guidance (ladi_tryon_set_pag): pag_tab_host[i] = s_i >= 0 (required), cfg != 0 =
+ * CFG-shaped.  eps_seq_dev holds, per evaluation, 3B rows [uncond ; cond ; perturbed] with cfg, 2B rows [cond ; perturbed] without (then
+ * guidance_tab_host may be NULL and phi is ignored).  e = u + g (c - u) + s (c - p), or c + s (c - p) without cfg and in a cond-only
+ * evaluation, which reads c and p alone; an evaluation with s_i == 0 never reads its perturbed rows.  A table of zeros gives
+ * ladi_op_sched_run_guided's latents bit for bit. */
+int ladi_op_sched_run_pag(int kind, int steps, const float* alphas_cumprod_host, float eta, const void* eps_seq_dev, int ld_eps, int evals, int B,
+                          int hw, int cfg, const float* guidance_tab_host, const float* pag_tab_host, float phi, float* latents_dev,
+                          const float* step_noise_dev, int noise_steps, void* stream);
+/* ladi_op_cfg_stats with the perturbed rows: eps_dev [3B][hw], the guided prediction is u + guidance (c - u) + pag_scale (c - p).
+ * pag_scale == 0 reads the first 2B rows alone and is ladi_op_cfg_stats bit for bit; a negative or non-finite one is an error. */
+int ladi_op_cfg_stats_pag(const void* eps_dev, int ld_eps, int B, int hw, float guidance, float pag_scale, float phi, float* factor_dev,
+                          void* stream);
+/* the identity attention map of PAG on its own: o[row][0:C] = v[row][0:C] for `rows` rows, fp16, row strides ldv / ldo halves (v: the V
+ * third of a fused QKV buffer), 16-byte vectors.  C and both strides multiples of 8, strides >= C, both bases 16-byte aligned, else an
+ * error with a message and nothing is launched.  Columns [C, ld) are never touched. */
+int ladi_op_pag_identity(const void* v_dev, int ldv, void* o_dev, int ldo, long long rows, int C, void* stream);
 /* pipeline pre-processing kernels, one entry point per kernel so each can be checked on its own:
  * prepare_mask_and_masked_image (diffusers tensor branch; tryon_pipe.py:630): mask binarised at 0.5 -> mask_bin_dev fp16 [B,H,W];
  *   masked_image_dev NHWC fp16 [B,H,W,ld] (3 valid channels, the rest zero) = image * (mask < 0.5) */

@@ -113,6 +113,10 @@ SIGNATURES = {
     "ladi_unet_time_forward_cached": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P]),
     "ladi_unet_time_forward_lanes": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P]),
     "ladi_unet_set_freeu": (c_int, [_P, c_int, c_float, c_float, c_float, c_float]),
+    "ladi_unet_pag_layer_count": (c_int, [_P]),
+    "ladi_unet_set_pag_layers": (c_int, [_P, ctypes.c_uint]),
+    "ladi_unet_pag_layers": (ctypes.c_uint, [_P]),
+    "ladi_unet_forward_pag": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, c_int, c_int, c_int, _P]),
     "ladi_vae_create": (_P, [POINTER(VAEConfig), _P]),
     "ladi_vae_destroy": (None, [_P]),
     "ladi_vae_encode": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, POINTER(_P), _P]),
@@ -155,6 +159,7 @@ SIGNATURES = {
     "ladi_tryon_set_eta": (c_int, [_P, c_float]),
     "ladi_tryon_set_guidance_schedule": (c_int, [_P, POINTER(c_float), c_int]),
     "ladi_tryon_set_guidance_rescale": (c_int, [_P, c_float]),
+    "ladi_tryon_set_pag": (c_int, [_P, POINTER(c_float), c_int]),
     "ladi_tryon_cond_only_evals": (c_int, [_P]),
     "ladi_tryon_set_feature_cache": (c_int, [_P, POINTER(ctypes.c_ubyte), c_int, c_int]),
     "ladi_tryon_set_preserve": (c_int, [_P, c_int, c_float]),
@@ -222,6 +227,10 @@ SIGNATURES = {
     "ladi_op_sched_run_noise_eta": (c_int, [c_int, c_int, _P, c_float, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int, _P]),
     "ladi_op_sched_run_guided": (c_int, [c_int, c_int, _P, c_float, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_float, _P, _P, c_int, _P]),
     "ladi_op_cfg_stats": (c_int, [_P, c_int, c_int, c_int, c_float, c_float, _P, _P]),
+    "ladi_op_sched_run_pag": (c_int, [c_int, c_int, _P, c_float, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), c_float,
+                                      _P, _P, c_int, _P]),
+    "ladi_op_cfg_stats_pag": (c_int, [_P, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P]),
+    "ladi_op_pag_identity": (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_int, _P]),
     "ladi_op_prepare_mask": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
     "ladi_op_mask_down": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "ladi_op_pose_down8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),

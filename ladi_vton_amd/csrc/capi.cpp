@@ -135,6 +135,43 @@ int ladi_unet_set_freeu(ladi_unet* u, int on, float s1, float s2, float b1, floa
     return 0;
 }
 
+int ladi_unet_pag_layer_count(const ladi_unet* u) { return u ? u->u.pag_layer_count() : -1; }
+int ladi_unet_set_pag_layers(ladi_unet* u, unsigned layer_mask) {
+    if (!u) { set_error("ladi_unet_set_pag_layers: null handle"); return -1; }
+    const int cnt = u->u.pag_layer_count();
+    if (layer_mask == 0 || (cnt < 32 && (layer_mask >> cnt))) {
+        set_error("ladi_unet_set_pag_layers: the mask " + std::to_string(layer_mask) + " selects no transformer block or has bits beyond the " +
+                  std::to_string(cnt) + " blocks of this UNet");
+        return -1;
+    }
+    u->u.pag_mask = layer_mask;
+    return 0;
+}
+unsigned ladi_unet_pag_layers(const ladi_unet* u) { return u ? u->u.pag_mask : 0u; }
+
+int ladi_unet_forward_pag(ladi_unet* u, const void* sample, int dtype, int n, int h, int w, float timestep, void* out, int out_dtype,
+                          int sample0, int pag_first, void* stream) {
+    return guarded("ladi_unet_forward_pag", [&]() {
+        if (!u || !sample || !out) throw std::runtime_error("null argument");
+        UNet& U = u->u;
+        hipStream_t st = S(stream);
+        if (n < 1 || h < 1 || w < 1 || sample0 < 0 || sample0 + n > U.ctx_n)
+            throw std::runtime_error("samples [" + std::to_string(sample0) + ", " + std::to_string(sample0 + n) + ") are not inside the context batch of " +
+                                     std::to_string(U.ctx_n) + " (ladi_unet_set_context)");
+        if (pag_first < 0) throw std::runtime_error("pag_first " + std::to_string(pag_first) + " is negative");
+        if (U.compute_temb(&timestep, 1, st)) return -1;
+        const int eps_ld = (U.cfg.out_channels + 3) / 4 * 4;
+        run_planned(U.arena, st, [&](Ctx& c) {
+            Act x = c.new_act(n, h, w, 64);
+            Act eo = c.new_act(n, h, w, U.cfg.out_channels, eps_ld);
+            if (!c.dry()) c.check(ladi_launch_nchw_to_nhwc(sample, dtype == LADI_F32, n, U.cfg.in_channels, h, w, x.p, 64, st), "nchw_to_nhwc");
+            Act eps = U.forward(c, x, U.temb_table, nullptr, &eo, sample0, nullptr, pag_first);
+            if (!c.dry()) c.check(ladi_launch_nhwc_to_nchw(eps.p, eps.ld, n, U.cfg.out_channels, h, w, out, out_dtype == LADI_F32, st), "nhwc_to_nchw");
+        }, &U.stats, &U.stats_cap);
+        return 0;
+    });
+}
+
 int ladi_unet_forward(ladi_unet* u, const void* sample, int dtype, int n, int h, int w, float timestep, void* out, int out_dtype,
                       void* stream) {
     return guarded("ladi_unet_forward", [&]() {
@@ -749,6 +786,16 @@ int ladi_tryon_set_guidance_schedule(ladi_tryon* t, const float* scales_host, in
         }
     return guarded("ladi_tryon_set_guidance_schedule", [&]() { t->t.g_sched.assign(scales_host, scales_host + count); return 0; });
 }
+int ladi_tryon_set_pag(ladi_tryon* t, const float* scales_host, int count) {
+    if (!t || count < 0) { set_error("ladi_tryon_set_pag: null handle or negative count"); return -1; }
+    if (!scales_host || count == 0) { t->t.pag_sched.clear(); return 0; }
+    for (int i = 0; i < count; ++i)
+        if (!std::isfinite(scales_host[i]) || scales_host[i] < 0.f) {
+            set_error("ladi_tryon_set_pag: entry " + std::to_string(i) + " is negative or not finite");
+            return -1;
+        }
+    return guarded("ladi_tryon_set_pag", [&]() { t->t.pag_sched.assign(scales_host, scales_host + count); return 0; });
+}
 int ladi_tryon_set_guidance_rescale(ladi_tryon* t, float phi) {
     if (!t || !(phi >= 0.f && phi <= 1.f)) { set_error("ladi_tryon_set_guidance_rescale: null handle, or phi outside [0, 1]"); return -1; }
     t->t.phi = phi;
@@ -1181,6 +1228,18 @@ int ladi_op_freeu(void* hidden, int ld_h, int C_h, float b, const void* skip, in
         return 0;
     });
 }
+int ladi_op_pag_identity(const void* v, int ldv, void* o, int ldo, long long rows, int C, void* stream) {
+    return guarded("ladi_op_pag_identity", [&]() {
+        if (!v || !o) throw std::runtime_error("null v or o");
+        if (rows < 1) throw std::runtime_error("rows has to be >= 1");
+        if (C < 8 || (C & 7)) throw std::runtime_error("C = " + std::to_string(C) + " is not a multiple of 8");
+        if (ldv < C || ldo < C || (ldv & 7) || (ldo & 7) || ((uintptr_t)v & 15) || ((uintptr_t)o & 15))
+            throw std::runtime_error("every row stride has to be a multiple of 8 and >= C, every pointer 16-byte aligned");
+        const int rc = ladi_launch_pag_identity(reinterpret_cast<const h16*>(v), ldv, reinterpret_cast<h16*>(o), ldo, rows, C, S(stream));
+        if (rc) throw std::runtime_error("launch refused or failed (rc = " + std::to_string(rc) + ")");
+        return 0;
+    });
+}
 static int sched_run_any(const char* name, int kind, int steps, const float* ac_host, const void* eps_seq, int evals, int B, int hw, int cfg,
                          float guidance, float* latents, const float* step_noise, int noise_steps, float eta, void* stream) {
     return guarded(name, [&]() {
@@ -1238,12 +1297,18 @@ int ladi_op_cfg_stats(const void* eps, int ld_eps, int B, int hw, float guidance
         return ladi_launch_cfg_stats(reinterpret_cast<const h16*>(eps), ld_eps, B, hw, nullptr, nullptr, guidance, phi, factor, S(stream));
     });
 }
+// cfg / pag_tab_host: ladi_op_sched_run_pag's (the others: cfg = 1, no PAG table).  Without CFG the guidance table may be null
 static int sched_run_guided_any(const char* name, int kind, int steps, const float* ac_host, float eta, const void* eps_seq, int ld_eps, int evals,
                                 int B, int hw, const float* guidance_tab_host, float phi, float* latents, const float* step_noise, int noise_steps,
-                                const float* keep_x0, const float* keep_noise, const float* keep_mask, void* stream) {
+                                const float* keep_x0, const float* keep_noise, const float* keep_mask, void* stream, int cfg = 1,
+                                const float* pag_tab_host = nullptr) {
     return guarded(name, [&]() {
         hipStream_t st = S(stream);
+        std::vector<float> ones;
+        if (!cfg && !guidance_tab_host && evals > 0) { ones.assign((size_t)evals, 1.f); guidance_tab_host = ones.data(); }
         if (!eps_seq || !latents || !guidance_tab_host || evals <= 0 || B <= 0 || hw <= 0) throw std::runtime_error("null argument or empty shape");
+        for (int i = 0; pag_tab_host && i < evals; ++i)
+            if (!std::isfinite(pag_tab_host[i]) || pag_tab_host[i] < 0.f) throw std::runtime_error("PAG table entry negative or not finite");
         if (ld_eps < 4 || (ld_eps & 3) || ((uintptr_t)eps_seq & 7)) throw std::runtime_error("ld_eps must be a multiple of 4 (>= 4) and eps_seq 8-byte aligned");
         if (!(phi >= 0.f && phi <= 1.f)) throw std::runtime_error("phi outside [0, 1]");
         for (int i = 0; i < evals; ++i)
@@ -1264,7 +1329,8 @@ static int sched_run_guided_any(const char* name, int kind, int steps, const flo
         std::vector<float> kt;
         if (keep_mask) build_keep_coeffs(kind, steps, ac.data(), 0, kt);
         const size_t kt_bytes = (kt.size() * sizeof(float) + 255) & ~(size_t)255;
-        HIP_OK(hipMalloc(reinterpret_cast<void**>(&buf), tb_bytes + 256 + gt_bytes + fc_bytes + kt_bytes + 5 * plane));
+        const size_t pt_bytes = pag_tab_host ? gt_bytes : 0;
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&buf), tb_bytes + 256 + gt_bytes + fc_bytes + kt_bytes + 5 * plane + pt_bytes));
         StepTable* dt = reinterpret_cast<StepTable*>(buf);
         int* dstep = reinterpret_cast<int*>(buf + tb_bytes);
         float* dgt = reinterpret_cast<float*>(buf + tb_bytes + 256);
@@ -1272,21 +1338,25 @@ static int sched_run_guided_any(const char* name, int kind, int steps, const flo
         float* dkt = reinterpret_cast<float*>(buf + tb_bytes + 256 + gt_bytes + fc_bytes);
         float* cur = reinterpret_cast<float*>(buf + tb_bytes + 256 + gt_bytes + fc_bytes + kt_bytes);
         float* ets = cur + (size_t)B * hw * 4;
+        float* dpt = pag_tab_host ? ets + (size_t)4 * B * hw * 4 : nullptr;
         int rc = 0;
         try {
+            if (dpt) HIP_OK(hipMemcpyAsync(dpt, pag_tab_host, (size_t)evals * sizeof(float), hipMemcpyHostToDevice, st));
             if (keep_mask) HIP_OK(hipMemcpyAsync(dkt, kt.data(), kt.size() * sizeof(float), hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(dt, tb.data(), tb.size() * sizeof(StepTable), hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(dgt, guidance_tab_host, (size_t)evals * sizeof(float), hipMemcpyHostToDevice, st));
             HIP_OK(hipMemsetAsync(dstep, 0, 8, st));       // evaluation index + the step kernel's arrival ticket
-            const size_t per_eval = (size_t)2 * B * hw * ld_eps;
+            const size_t per_eval = (size_t)((cfg ? 2 : 1) + (dpt ? 1 : 0)) * B * hw * ld_eps;
             for (int i = 0; i < evals && !rc; ++i) {
                 StepArgs sa; std::memset(&sa, 0, sizeof(sa));
                 sa.eps = reinterpret_cast<const h16*>(eps_seq) + (size_t)i * per_eval; sa.ld_eps = ld_eps;
-                sa.B = B; sa.hw = hw; sa.cfg = 1; sa.latents = latents; sa.cur_sample = cur; sa.ets = ets;
+                sa.B = B; sa.hw = hw; sa.cfg = cfg ? 1 : 0; sa.latents = latents; sa.cur_sample = cur; sa.ets = ets;
                 sa.table = dt; sa.step_idx = dstep; sa.unet_in = nullptr; sa.step_noise = step_noise;
-                sa.guidance_tab = dgt; sa.factor = phi > 0.f ? dfc : nullptr;
+                sa.guidance_tab = dgt; sa.factor = (cfg && phi > 0.f) ? dfc : nullptr; sa.pag_tab = dpt;
                 if (keep_mask) { sa.keep_x0 = keep_x0; sa.keep_noise = keep_noise; sa.keep_mask = keep_mask; sa.keep_tab = dkt; }
-                if (phi > 0.f && guidance_tab_host[i] > 1.0f) rc = ladi_launch_cfg_stats(sa.eps, ld_eps, B, hw, dgt, dstep, 0.f, phi, dfc, st);
+                if (cfg && phi > 0.f && guidance_tab_host[i] > 1.0f)
+                    rc = dpt ? ladi_launch_cfg_stats_pag(sa.eps, ld_eps, B, hw, dgt, dstep, 0.f, dpt, 0.f, phi, dfc, st)
+                             : ladi_launch_cfg_stats(sa.eps, ld_eps, B, hw, dgt, dstep, 0.f, phi, dfc, st);
                 if (!rc) rc = ladi_launch_sched_step(sa, st);
             }
             HIP_OK(hipStreamSynchronize(st));
@@ -1299,6 +1369,23 @@ int ladi_op_sched_run_guided(int kind, int steps, const float* ac_host, float et
                              const float* guidance_tab_host, float phi, float* latents, const float* step_noise, int noise_steps, void* stream) {
     return sched_run_guided_any("ladi_op_sched_run_guided", kind, steps, ac_host, eta, eps_seq, ld_eps, evals, B, hw, guidance_tab_host, phi, latents,
                                 step_noise, noise_steps, nullptr, nullptr, nullptr, stream);
+}
+int ladi_op_sched_run_pag(int kind, int steps, const float* ac_host, float eta, const void* eps_seq, int ld_eps, int evals, int B, int hw, int cfg,
+                          const float* guidance_tab_host, const float* pag_tab_host, float phi, float* latents, const float* step_noise,
+                          int noise_steps, void* stream) {
+    if (!pag_tab_host) { set_error("ladi_op_sched_run_pag: null PAG table"); return -1; }
+    return sched_run_guided_any("ladi_op_sched_run_pag", kind, steps, ac_host, eta, eps_seq, ld_eps, evals, B, hw, guidance_tab_host, phi, latents,
+                                step_noise, noise_steps, nullptr, nullptr, nullptr, stream, cfg ? 1 : 0, pag_tab_host);
+}
+int ladi_op_cfg_stats_pag(const void* eps, int ld_eps, int B, int hw, float guidance, float pag_scale, float phi, float* factor, void* stream) {
+    return guarded("ladi_op_cfg_stats_pag", [&]() {
+        if (!eps || !factor || B <= 0 || hw <= 0) throw std::runtime_error("null argument or empty shape");
+        if (ld_eps < 4 || (ld_eps & 3) || ((uintptr_t)eps & 7)) throw std::runtime_error("ld_eps must be a multiple of 4 (>= 4) and eps 8-byte aligned");
+        if (!(phi >= 0.f && phi <= 1.f)) throw std::runtime_error("phi outside [0, 1]");
+        if (!std::isfinite(pag_scale) || pag_scale < 0.f) throw std::runtime_error("PAG scale negative or not finite");
+        return ladi_launch_cfg_stats_pag(reinterpret_cast<const h16*>(eps), ld_eps, B, hw, nullptr, nullptr, guidance, nullptr, pag_scale, phi, factor,
+                                         S(stream));
+    });
 }
 int ladi_op_sched_run_keep(int kind, int steps, const float* ac_host, float eta, const void* eps_seq, int ld_eps, int evals, int B, int hw,
                            const float* guidance_tab_host, float phi, float* latents, const float* step_noise, int noise_steps,

@@ -134,16 +134,29 @@ __device__ __forceinline__ void sched_step_body(const StepArgs& a, const int idx
     float e[4];
     // guidance table: this evaluation's scale; a scale <= 1 makes it a cond-only evaluation (e = the conditional row, the uncond row is not read)
     const float g = a.guidance_tab ? a.guidance_tab[step] : a.guidance;
+    // perturbed-attention guidance: this evaluation's scale (0 = none) and the perturbed group's row, behind the cond group's
+    const float ps = a.pag_tab ? a.pag_tab[step] : 0.f;
+    const size_t row_p = (size_t)idx + (size_t)(a.cfg ? 2 : 1) * (size_t)total;
     if (a.cfg && a.guidance_tab && !(g > 1.0f)) {
         const h16x4 ec = *reinterpret_cast<const h16x4*>(a.eps + row_c * a.ld_eps);
 #pragma unroll
         for (int c = 0; c < 4; ++c) e[c] = (float)ec[c];
+        if (ps > 0.f) {          // c + s (c - p): the uncond row stays unread
+            const h16x4 ep = *reinterpret_cast<const h16x4*>(a.eps + row_p * a.ld_eps);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) e[c] += ps * ((float)ec[c] - (float)ep[c]);
+        }
     } else {
         const h16x4 eu = *reinterpret_cast<const h16x4*>(a.eps + row_u * a.ld_eps);
         if (a.cfg) {
             const h16x4 ec = *reinterpret_cast<const h16x4*>(a.eps + row_c * a.ld_eps);
 #pragma unroll
             for (int c = 0; c < 4; ++c) { float u = (float)eu[c]; e[c] = u + g * ((float)ec[c] - u); }
+            if (ps > 0.f) {      // u + g (c - u) + s (c - p)
+                const h16x4 ep = *reinterpret_cast<const h16x4*>(a.eps + row_p * a.ld_eps);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) e[c] += ps * ((float)ec[c] - (float)ep[c]);
+            }
             if (a.factor) {      // guidance rescale: the per-sample factor cfg_stats_kernel wrote for this evaluation
                 const float f = a.factor[b];
 #pragma unroll
@@ -152,6 +165,11 @@ __device__ __forceinline__ void sched_step_body(const StepArgs& a, const int idx
         } else {
 #pragma unroll
             for (int c = 0; c < 4; ++c) e[c] = (float)eu[c];
+            if (ps > 0.f) {      // no CFG: the only row is the cond one, c + s (c - p)
+                const h16x4 ep = *reinterpret_cast<const h16x4*>(a.eps + row_p * a.ld_eps);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) e[c] += ps * ((float)eu[c] - (float)ep[c]);
+            }
         }
     }
     const size_t plane = (size_t)total * 4;
@@ -211,6 +229,10 @@ __device__ __forceinline__ void sched_step_body(const StepArgs& a, const int idx
         h16x4 o; o[0] = (h16)(xn.x * is); o[1] = (h16)(xn.y * is); o[2] = (h16)(xn.z * is); o[3] = (h16)(xn.w * is);
         *reinterpret_cast<h16x4*>(a.unet_in + row_u * a.ld_in) = o;
         if (a.cfg) *reinterpret_cast<h16x4*>(a.unet_in + row_c * a.ld_in) = o;
+        if (a.pag_tab) {         // the perturbed group sees the cond group's input
+            *reinterpret_cast<h16x4*>(a.unet_in + row_p * a.ld_in) = o;
+            if (T.zero_cloth_next) { h16* pp = a.unet_in + row_p * a.ld_in + a.cloth_ch0; pp[0] = (h16)0.f; pp[1] = (h16)0.f; pp[2] = (h16)0.f; pp[3] = (h16)0.f; }
+        }
         if (T.zero_cloth_next) {
             h16x4 zz = {0, 0, 0, 0};
             // cloth channels are not 8-byte aligned (27..30): scalar stores
@@ -249,20 +271,37 @@ __device__ __forceinline__ void block_sum2(float& x, float& y, float (*red)[4]) 
     x = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
     y = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
 }
+// PAG: the instantiation with the perturbed rows [2B, 3B) and a scale s (table entry or scalar); where s > 0 the guided prediction gains
+// s (c - p), where it is 0 those rows are not read.  The instantiation without is the kernel as it was
+template <bool PAG>
 __global__ __launch_bounds__(256) void cfg_stats_kernel(const h16* __restrict__ eps, int ld_eps, int B, int hw,
                                                         const float* __restrict__ guidance_tab, const int* __restrict__ step_idx,
-                                                        float guidance, float phi, float* __restrict__ factor) {
+                                                        float guidance, const float* __restrict__ pag_tab, float pag_scale, float phi,
+                                                        float* __restrict__ factor) {
     __shared__ float red[2][4];
     const int b = blockIdx.x;
     const float g = guidance_tab ? guidance_tab[*step_idx] : guidance;
     const h16* pu = eps + (size_t)b * hw * ld_eps;               // uncond rows of sample b
     const h16* pc = eps + ((size_t)B + b) * hw * ld_eps;         // cond rows
+    const h16* pp = eps + ((size_t)2 * B + b) * hw * ld_eps;     // perturbed rows (PAG)
+    const float s = PAG ? (pag_tab ? pag_tab[*step_idx] : pag_scale) : 0.f;
+    const bool has_p = PAG && s > 0.f;
     float sc = 0.f, sg = 0.f;
     for (int p = threadIdx.x; p < hw; p += 256) {
         const h16x4 eu = *reinterpret_cast<const h16x4*>(pu + (size_t)p * ld_eps);
         const h16x4 ec = *reinterpret_cast<const h16x4*>(pc + (size_t)p * ld_eps);
+        if (has_p) {
+            const h16x4 ep = *reinterpret_cast<const h16x4*>(pp + (size_t)p * ld_eps);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) { const float u = (float)eu[c], cv = (float)ec[c]; sc += cv; sg += u + g * (cv - u); }
+            for (int c = 0; c < 4; ++c) {
+                const float u = (float)eu[c], cv = (float)ec[c];
+                float gv = u + g * (cv - u); gv += s * (cv - (float)ep[c]);
+                sc += cv; sg += gv;
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) { const float u = (float)eu[c], cv = (float)ec[c]; sc += cv; sg += u + g * (cv - u); }
+        }
     }
     block_sum2(sc, sg, red);
     const float n = 4.f * (float)hw;
@@ -271,11 +310,22 @@ __global__ __launch_bounds__(256) void cfg_stats_kernel(const h16* __restrict__ 
     for (int p = threadIdx.x; p < hw; p += 256) {
         const h16x4 eu = *reinterpret_cast<const h16x4*>(pu + (size_t)p * ld_eps);
         const h16x4 ec = *reinterpret_cast<const h16x4*>(pc + (size_t)p * ld_eps);
+        if (has_p) {
+            const h16x4 ep = *reinterpret_cast<const h16x4*>(pp + (size_t)p * ld_eps);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float u = (float)eu[c], cv = (float)ec[c];
-            const float dc = cv - mc, dg = (u + g * (cv - u)) - mg;
-            qc += dc * dc; qg += dg * dg;
+            for (int c = 0; c < 4; ++c) {
+                const float u = (float)eu[c], cv = (float)ec[c];
+                float gv = u + g * (cv - u); gv += s * (cv - (float)ep[c]);
+                const float dc = cv - mc, dg = gv - mg;
+                qc += dc * dc; qg += dg * dg;
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float u = (float)eu[c], cv = (float)ec[c];
+                const float dc = cv - mc, dg = (u + g * (cv - u)) - mg;
+                qc += dc * dc; qg += dg * dg;
+            }
         }
     }
     block_sum2(qc, qg, red);
@@ -290,13 +340,14 @@ __global__ __launch_bounds__(256) void assemble_static_kernel(h16* __restrict__ 
                                                               const h16* __restrict__ mask_lat,
                                                               const float* __restrict__ masked_lat,
                                                               const h16* __restrict__ pose, int pose_ch,
-                                                              const float* __restrict__ cloth_lat, int has_cloth, float lat_scale) {
-    const int rows = (cfg ? 2 : 1) * B * hw;
+                                                              const float* __restrict__ cloth_lat, int has_cloth, float lat_scale, int pag) {
+    // pag: a third group of B samples behind the cond group, with the cond group's channels (perturbed-attention guidance)
+    const int rows = ((cfg ? 2 : 1) + (pag ? 1 : 0)) * B * hw;
     const int row = blockIdx.x * 256 + threadIdx.x;
     if (row >= rows) return;
     const int total = B * hw;
     const bool cond = cfg ? (row >= total) : true;
-    const int src = cfg ? (row % total) : row;
+    const int src = (cfg || pag) ? (row % total) : row;
     h16* o = unet_in + (size_t)row * ld_in;
     int c = 0;
     for (int i = 0; i < 4; ++i) o[c++] = (h16)(latents[(size_t)src * 4 + i] * lat_scale);   // scale_model_input of evaluation 0
@@ -479,7 +530,7 @@ __global__ __launch_bounds__(256) void init_latents_kernel(const float* __restri
 // step-callback import: the (possibly edited) NCHW latents back into the loop, and the next evaluation's UNet input refreshed from them exactly
 // as sched_step_body refreshes it (same scale, same fp16 rounding, uncond and cond rows), so an untouched round trip changes no bit
 __global__ __launch_bounds__(256) void latents_import_kernel(const float* __restrict__ src, int B, int hw, float* __restrict__ latents,
-                                                             h16* __restrict__ unet_in, int ld_in, int cfg, float is) {
+                                                             h16* __restrict__ unet_in, int ld_in, int cfg, float is, int pag) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     const int total = B * hw;
     if (idx >= total) return;
@@ -490,6 +541,7 @@ __global__ __launch_bounds__(256) void latents_import_kernel(const float* __rest
     h16x4 o; o[0] = (h16)(x.x * is); o[1] = (h16)(x.y * is); o[2] = (h16)(x.z * is); o[3] = (h16)(x.w * is);
     *reinterpret_cast<h16x4*>(unet_in + (size_t)idx * ld_in) = o;
     if (cfg) *reinterpret_cast<h16x4*>(unet_in + ((size_t)idx + total) * ld_in) = o;
+    if (pag) *reinterpret_cast<h16x4*>(unet_in + ((size_t)idx + (size_t)(cfg ? 2 : 1) * total) * ld_in) = o;     // the perturbed group
 }
 
 inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -11; }
@@ -539,17 +591,28 @@ int ladi_launch_sched_step(const StepArgs& a, hipStream_t st) {
 int ladi_launch_cfg_stats(const h16* eps, int ld_eps, int B, int hw, const float* guidance_tab, const int* step_idx, float guidance,
                           float phi, float* factor, hipStream_t st) {
     if (B <= 0 || hw <= 0 || ld_eps < 4 || (ld_eps & 3) || ((uintptr_t)eps & 7) || (guidance_tab && !step_idx)) return -1;
-    hipLaunchKernelGGL(cfg_stats_kernel, dim3(B), dim3(256), 0, st, eps, ld_eps, B, hw, guidance_tab, step_idx, guidance, phi, factor);
+    hipLaunchKernelGGL(cfg_stats_kernel<false>, dim3(B), dim3(256), 0, st, eps, ld_eps, B, hw, guidance_tab, step_idx, guidance, nullptr, 0.f, phi,
+                       factor);
+    return ok();
+}
+
+int ladi_launch_cfg_stats_pag(const h16* eps, int ld_eps, int B, int hw, const float* guidance_tab, const int* step_idx, float guidance,
+                              const float* pag_tab, float pag_scale, float phi, float* factor, hipStream_t st) {
+    if (!pag_tab && pag_scale == 0.f) return ladi_launch_cfg_stats(eps, ld_eps, B, hw, guidance_tab, step_idx, guidance, phi, factor, st);
+    if (B <= 0 || hw <= 0 || ld_eps < 4 || (ld_eps & 3) || ((uintptr_t)eps & 7) || ((guidance_tab || pag_tab) && !step_idx) ||
+        !(pag_scale >= 0.f)) return -1;
+    hipLaunchKernelGGL(cfg_stats_kernel<true>, dim3(B), dim3(256), 0, st, eps, ld_eps, B, hw, guidance_tab, step_idx, guidance, pag_tab,
+                       pag_scale, phi, factor);
     return ok();
 }
 
 int ladi_launch_assemble_static(h16* unet_in, int ld_in, int B, int hw, int cfg, const float* latents, const h16* mask_lat,
                                 const float* masked_lat, const h16* pose, int pose_ch, const float* cloth_lat, int has_cloth,
-                                float lat_scale, hipStream_t st) {
-    const int rows = (cfg ? 2 : 1) * B * hw;
+                                float lat_scale, hipStream_t st, int pag) {
+    const int rows = ((cfg ? 2 : 1) + (pag ? 1 : 0)) * B * hw;
     if (9 + pose_ch + (has_cloth ? 4 : 0) > ld_in) return -1;
     hipLaunchKernelGGL(assemble_static_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, unet_in, ld_in, B, hw, cfg, latents,
-                       mask_lat, masked_lat, pose, pose_ch, cloth_lat, has_cloth, lat_scale);
+                       mask_lat, masked_lat, pose, pose_ch, cloth_lat, has_cloth, lat_scale, pag);
     return ok();
 }
 
@@ -855,9 +918,10 @@ int ladi_launch_init_latents(const float* init, int hs, int ws, const float* noi
     hipLaunchKernelGGL(init_latents_kernel, dim3((B * h * w + 255) / 256), dim3(256), 0, st, init, hs, ws, noise, B, h, w, k_x, k_n, dst);
     return ok();
 }
-int ladi_launch_latents_import(const float* src, int B, int hw, float* latents, h16* unet_in, int ld_in, int cfg, float in_scale, hipStream_t st) {
+int ladi_launch_latents_import(const float* src, int B, int hw, float* latents, h16* unet_in, int ld_in, int cfg, float in_scale, hipStream_t st,
+                               int pag) {
     if (ld_in < 4 || ld_in % 4) return -1;      // 8-byte stores of channels 0-3 of every row
-    hipLaunchKernelGGL(latents_import_kernel, dim3((B * hw + 255) / 256), dim3(256), 0, st, src, B, hw, latents, unet_in, ld_in, cfg, in_scale);
+    hipLaunchKernelGGL(latents_import_kernel, dim3((B * hw + 255) / 256), dim3(256), 0, st, src, B, hw, latents, unet_in, ld_in, cfg, in_scale, pag);
     return ok();
 }
 

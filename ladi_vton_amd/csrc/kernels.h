@@ -163,6 +163,12 @@ struct StepArgs {
     // device fp32 [evals][2], indexed by the device step counter; the row (1, 0) stores keep_x0 itself).  A select: the other pixels keep their
     // bits, and a keep pixel never sees eps.  The ring, cur_sample and the eps trace are not blended; trace_lat and unet_in get the blended value
     const float* keep_x0; const float* keep_noise; const float* keep_mask; const float* keep_tab;
+    // perturbed-attention guidance (null = the code path above, bit for bit).  pag_tab: device fp32 [evals], indexed by the device step
+    // counter.  An evaluation with s = pag_tab[i] > 0 has a third sample group p behind the cond group, rows [(cfg ? 2 : 1) * B, ..+B) of eps,
+    // and its combine gains s (c - p): u + g (c - u) + s (c - p) with cfg, c + s (c - p) without or in a cond-only evaluation (which reads c
+    // and p only).  `factor` multiplies the three-term sum.  With a table, eps and unet_in have the third group's rows whatever s is: the
+    // refresh of unet_in (and the cloth zeroing) writes them too; an evaluation with s = 0 never reads the third group of eps
+    const float* pag_tab;
 };
 int ladi_launch_sched_step(const StepArgs& a, hipStream_t st);
 // guidance rescale statistics of one evaluation: eps as in StepArgs with cfg = 1 (rows [0,B) uncond, [B,2B) cond, row stride ld_eps halves, a
@@ -171,11 +177,16 @@ int ladi_launch_sched_step(const StepArgs& a, hipStream_t st);
 // Fixed-order reduction (one workgroup per sample): bit-reproducible across launches and graph replays
 int ladi_launch_cfg_stats(const h16* eps, int ld_eps, int B, int hw, const float* guidance_tab, const int* step_idx, float guidance,
                           float phi, float* factor, hipStream_t st);
+// the same with perturbed-attention guidance: s = pag_tab[*step_idx] (device) or, with a null table, pag_scale; with s > 0 the guided
+// prediction is u + g (c - u) + s (c - p), p the rows [2B, 3B) of eps; with s = 0 those rows are not read and the result is
+// ladi_launch_cfg_stats' bit for bit.  Same two passes, same fixed-order sums
+int ladi_launch_cfg_stats_pag(const h16* eps, int ld_eps, int B, int hw, const float* guidance_tab, const int* step_idx, float guidance,
+                              const float* pag_tab, float pag_scale, float phi, float* factor, hipStream_t st);
 
 // static part of the 31-channel UNet input: mask, masked-image latents, pose, cloth; uncond half zero pose/cloth
 int ladi_launch_assemble_static(h16* unet_in, int ld_in, int B, int hw, int cfg, const float* latents, const h16* mask_lat,
                                 const float* masked_lat, const h16* pose, int pose_ch, const float* cloth_lat, int has_cloth,
-                                float lat_scale, hipStream_t st);
+                                float lat_scale, hipStream_t st, int pag = 0);     // pag: a third group of B samples, a copy of the cond group
 // posterior sample: lat[b][hw][4] = (mean + exp(0.5*clamp(logvar,-30,20)) * noise) * scaling ; moments NHWC [..][ldm] (8 ch),
 // noise fp32 NCHW [B][4][h][w]; a null noise is the mode form: lat = mean * scaling
 int ladi_launch_posterior_sample(const h16* moments, int ldm, const float* noise_nchw, int B, int hw, float scaling, float* lat,
@@ -231,7 +242,9 @@ int ladi_launch_init_latents(const float* init, int hs, int ws, const float* noi
                              hipStream_t st);
 // step-callback import: fp32 NCHW [B][4][hw] src -> the loop's latents [B][hw][4], and the latent channels 0-3 of the next UNet input
 // (rows [B] or, with cfg, [2B], ld_in halves per row) rewritten as fp16(x * in_scale) -- what sched_step_kernel wrote from the unedited x
-int ladi_launch_latents_import(const float* src, int B, int hw, float* latents, h16* unet_in, int ld_in, int cfg, float in_scale, hipStream_t st);
+// pag: the perturbed group's rows (behind the cond group's) are rewritten too
+int ladi_launch_latents_import(const float* src, int B, int hw, float* latents, h16* unet_in, int ld_in, int cfg, float in_scale, hipStream_t st,
+                               int pag = 0);
 // preserve-unmasked.  mask_pool8: dst fp32 [B][H/8][W/8] = max over each 8x8 block of the binarised fp16 mask [B][H][W] (F.max_pool2d(mask, 8)),
 // with `invert` 1 - that (the keep mask of StepArgs); H, W multiples of 8, mask 16-byte aligned, else -1
 int ladi_launch_mask_pool8(const h16* mask_bin, int B, int H, int W, int invert, float* dst, hipStream_t st);
@@ -253,6 +266,12 @@ int ladi_launch_image_composite(const h16* src, int ld, const void* image_nchw, 
 // that is not 16-byte aligned.  Nothing is launched on a refusal
 int ladi_launch_freeu(h16* hidden, int ld_h, int C_h, float b, const h16* skip, int ld_s, int C_s, float s, h16* skip_out, int ld_d, int n,
                       int H, int W, hipStream_t st);
+
+// ---- pag.hip: the identity attention map of perturbed-attention guidance, O = V.  Copies rows x C halves from v (row stride ldv: the V third
+// of a fused QKV buffer) to o (row stride ldo) in 16-byte vectors; columns [C, ld) of either side are never touched.  -1: a null pointer or
+// rows < 1; -2: C < 8 or C % 8; -3: a row stride below C or not a multiple of 8, or a base that is not 16-byte aligned.  Nothing is launched
+// on a refusal
+int ladi_launch_pag_identity(const h16* v, int ldv, h16* o, int ldo, long long rows, int C, hipStream_t st);
 
 // ---- f32path.hip: fp32 kernels of the warping module (fp32 NHWC activations, fp32 weights, v_mfma_f32_32x32x2_f32)
 struct ConvF32Args {

@@ -224,9 +224,18 @@ struct FreeU {
     float s1 = 1.f, s2 = 1.f, b1 = 1.f, b2 = 1.f;
 };
 
+// Perturbed-attention guidance (diffusers PAGMixin): the context index from which a forward's samples are perturbed.  In the transformer
+// blocks selected by UNet::pag_mask a perturbed sample's self-attention map is the identity (pag.hip); everything else is untouched
+enum { PAG_NONE = 0x7fffffff };
+
 struct UNet {
     UNetCfg cfg;
     FreeU freeu;
+    // pag_applied_layers (ladi_unet_set_pag_layers, sticky): bit i = transformer block i in execution order -- down_blocks.{0,1,2}
+    // .attentions.{0..L-1}, mid_block, up_blocks.{1,2,3}.attentions.{0..L}; pag_layer_count() bits.  The default is the mid block, as in
+    // diffusers.  Without perturbed samples in a forward (pag_first = PAG_NONE) the mask has no effect
+    unsigned pag_mask = 0;
+    int pag_layer_count() const { return 6 * cfg.layers_per_block + 4; }
     DevPool pool;
     DConv conv_in, conv_out, time_l1, time_l2, temb_all;
     DNorm norm_out;
@@ -251,8 +260,10 @@ struct UNet {
     // x: [n,h,w,64] padded NHWC input; returns eps Act [n,h,w,4(ld 4)]
     // eps_out (optional): pre-allocated output view (rows of a shared buffer); sample0: index of x's first sample in the context batch
     // fc (optional): deep-feature cache mode of this forward (FeatCache); null or mode NONE launches exactly the plain forward
+    // pag_first: samples whose index in the context batch (the numbering of sample0) is >= pag_first are perturbed; this forward's own
+    // count of leading unperturbed samples is clamp(pag_first - sample0, 0, n).  Arena use does not depend on it
     Act forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_idx, const Act* eps_out = nullptr, int sample0 = 0,
-                const FeatCache* fc = nullptr);
+                const FeatCache* fc = nullptr, int pag_first = PAG_NONE);
     int fc_channels(int branch) const { return cfg.boc[branch >= cfg.layers_per_block ? 1 : 0]; }   // channels of the cached tensor
     // cache of the stand-alone entry ladi_unet_forward_cached: grow-only buffer over the context batch, the geometry it was captured at and
     // which sample rows hold a capture made since the last set_context
@@ -284,8 +295,9 @@ struct UNetLanes {
     // a quiet chip)
     // sub-group form (cond-only evaluations of a CFG-shaped run): x / eps hold x.n < n samples that start at index sample0 of the context
     // batch, and run on sub_lanes(x.n) of the configured lanes, in their arenas (planned by a dry pass of this form too)
+    // pag_first: as UNet::forward's, in the context batch's numbering; every lane clamps it to its own samples (a lane may hold both kinds)
     void forward(UNet& u, hipStream_t main_st, bool dry, bool concurrent, const Act& x, const Act& eps, const float* temb, const int* tidx,
-                 int sample0 = 0, const FeatCache* fc = nullptr);
+                 int sample0 = 0, const FeatCache* fc = nullptr, int pag_first = PAG_NONE);
     int sub_lanes(int n_sub) const { int g = G; while (g > 1 && (n_sub % g)) --g; return g; }   // the default rule: lowered until it divides
     void commit_plan();                     // after the dry pass: (re)allocate what grew; not capturable
     unsigned long long key() const;         // part of the hipGraph key: lane count and every address a captured lane may touch
@@ -475,6 +487,7 @@ struct TryOnInputs {
     int steps; float guidance; int scheduler; int cloth_zero_from; int no_pose; int use_graph;
     const float* alphas_cumprod;  // optional [1000] host
 };
+enum { TRYON_PAG_WITH_CACHE = -12 };  // TryOn::run: a PAG table with a positive entry together with a feature-cache plan (LADI_TRYON_PAG_WITH_FEATURE_CACHE)
 enum { TRYON_CALLBACK_ABORT = -8 };   // TryOn::run: the step callback returned non-zero (LADI_TRYON_CALLBACK_ABORTED, include/ladi_native.h)
 struct TryOn {
     UNet* unet = nullptr; VAE* vae = nullptr; EMASC* emasc = nullptr;
@@ -511,6 +524,14 @@ struct TryOn {
     std::vector<unsigned char> fc_plan; int fc_branch = 0;
     h16* fcache = nullptr; size_t fcache_cap = 0;
     hipGraph_t graph_sh[2] = {nullptr, nullptr}; hipGraphExec_t gexec_sh[2] = {nullptr, nullptr};   // shallow forms: [0] 2B samples, [1] cond-only
+    // perturbed-attention guidance (ladi_tryon_set_pag, sticky; empty = off: nothing below is allocated or launched): one scale per
+    // evaluation.  With any scale > 0 the run is PAG-shaped: unet_in, eps and the context grow by a third group of B samples behind the
+    // cond group ([uncond ; cond ; perturbed], or [cond ; perturbed] without CFG), the scales go to the device table d_pag, and an evaluation
+    // with a scale > 0 runs the forward over the perturbed group too (form bit 2; never together with the feature cache, which run() refuses):
+    // graph_pag [0] all groups, [1] cond + perturbed (a cond-only evaluation of a guided run), under graph_key like the others
+    std::vector<float> pag_sched;
+    float* d_pag = nullptr; int pag_cap = 0;
+    hipGraph_t graph_pag[2] = {nullptr, nullptr}; hipGraphExec_t gexec_pag[2] = {nullptr, nullptr};
     int last_shallow = 0;     // evaluations of the last run that ran shallow, after promotion (ladi_tryon_shallow_evals)
     // preserve-unmasked (ladi_tryon_set_preserve, sticky; 0 = off: nothing below is allocated or launched).  Bit 0, latents: after every
     // scheduler update the keep pixels (1 - maxpool8x8 of the binarised mask) become k_x z0 + k_n noise at the next timestep, z0 = scaling *

@@ -18,6 +18,8 @@ TryOn::~TryOn() {
     if (graph_cond) (void)hipGraphDestroy(graph_cond);
     for (auto& g : gexec_sh) if (g) (void)hipGraphExecDestroy(g);
     for (auto& g : graph_sh) if (g) (void)hipGraphDestroy(g);
+    for (auto& g : gexec_pag) if (g) (void)hipGraphExecDestroy(g);
+    for (auto& g : graph_pag) if (g) (void)hipGraphDestroy(g);
     if (fcache) (void)hipFree(fcache);
     if (stats) (void)hipFree(stats);
     if (step_noise_buf) (void)hipFree(step_noise_buf);
@@ -73,7 +75,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
     const int cfgf = any_cfg ? 1 : 0;
     // guided: the scales come from a device table (a schedule, or the scalar repeated for the rescale statistics); else today's scalar path
     const bool guided = cfgf && (has_sched || phi > 0.f);
-    const int n = cfgf ? 2 * B : B;
+    const int ng = cfgf ? 2 : 1;       // sample groups of a plain evaluation: [uncond ; cond] or [cond]
     const bool has_cloth = in.warped_cloth != nullptr;
     const int pose_ch = in.pose_channels;
     const int in_ch = 9 + pose_ch + (has_cloth ? 4 : 0);
@@ -95,6 +97,22 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                   std::to_string(in.steps) : std::string()) + ")");
         return -9;
     }
+    // perturbed-attention guidance: one scale per evaluation; the run is PAG-shaped (a third sample group) if ANY scale is > 0
+    if (!pag_sched.empty() && (int)pag_sched.size() != evals) {
+        set_error("tryon: the PAG table has " + std::to_string(pag_sched.size()) + " entries, this run has " + std::to_string(evals) +
+                  " evaluations (PNDM: steps + 1" + (first_step ? "; the run starts at step " + std::to_string(first_step) + " of " +
+                  std::to_string(in.steps) : std::string()) + ")");
+        return -9;
+    }
+    bool pag_on = false;
+    for (float s : pag_sched) pag_on = pag_on || s > 0.f;
+    if (pag_on && !fc_plan.empty()) {
+        set_error("tryon: perturbed-attention guidance together with a feature-cache plan is not supported (the cache's group promotion has "
+                  "no third group): clear one of ladi_tryon_set_pag / ladi_tryon_set_feature_cache");
+        return TRYON_PAG_WITH_CACHE;
+    }
+    auto pag_eval = [&](int i) { return pag_on && pag_sched[i] > 0.f; };
+    const int n = (ng + (pag_on ? 1 : 0)) * B;
     // scale of evaluation i, and whether it runs cond-only (scale <= 1: no unconditional half, as do_classifier_free_guidance of a whole run)
     std::vector<float> gtab(evals, in.guidance);
     if (has_sched) gtab = g_sched;
@@ -134,6 +152,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
     if (!sk_cnt) { sk_cnt = reinterpret_cast<int*>(pool.alloc(1024 * sizeof(int))); HIP_OK(hipMemset(sk_cnt, 0, 1024 * sizeof(int))); }
     if (evals > table_cap) { d_table = reinterpret_cast<StepTable*>(pool.alloc((size_t)evals * sizeof(StepTable))); table_cap = evals; }
     if (guided && evals > gtab_cap) { d_gtab = reinterpret_cast<float*>(pool.alloc((size_t)evals * sizeof(float))); gtab_cap = evals; }
+    if (pag_on && evals > pag_cap) { d_pag = reinterpret_cast<float*>(pool.alloc((size_t)evals * sizeof(float))); pag_cap = evals; }
     if (use_factor && B > factor_cap) { d_factor = reinterpret_cast<float*>(pool.alloc((size_t)B * sizeof(float))); factor_cap = B; }
     // preserve-unmasked: the blend's coefficients per evaluation, float64 on the host like the step table
     const bool keep_lat = (preserve_mode & 1) != 0, keep_pix = (preserve_mode & 2) != 0;
@@ -189,6 +208,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 HIP_OK(hipMemcpyAsync(d_table, table.data(), (size_t)evals * sizeof(StepTable), hipMemcpyHostToDevice, st));
                 HIP_OK(hipMemsetAsync(d_step, 0, 2 * sizeof(int), st));    // evaluation index + the step kernel's arrival ticket
                 if (guided) HIP_OK(hipMemcpyAsync(d_gtab, gtab.data(), (size_t)evals * sizeof(float), hipMemcpyHostToDevice, st));
+                if (pag_on) HIP_OK(hipMemcpyAsync(d_pag, pag_sched.data(), (size_t)evals * sizeof(float), hipMemcpyHostToDevice, st));
                 if (keep_lat) HIP_OK(hipMemcpyAsync(d_keep_tab, keep_tab.data(), (size_t)evals * 2 * sizeof(float), hipMemcpyHostToDevice, st));
                 if (use_step_noise) HIP_OK(hipMemcpyAsync(step_noise_buf, step_noise_src, step_noise_bytes, hipMemcpyDeviceToDevice, st));
                 std::vector<float> tsf(timesteps.begin(), timesteps.end());
@@ -228,6 +248,8 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                     HIP_OK(hipMemcpyAsync(ehs, in.negative_prompt_embeds, pe, hipMemcpyDeviceToDevice, st));
                     HIP_OK(hipMemcpyAsync(ehs + (size_t)B * L * D, in.prompt_embeds, pe, hipMemcpyDeviceToDevice, st));
                 } else HIP_OK(hipMemcpyAsync(ehs, in.prompt_embeds, pe, hipMemcpyDeviceToDevice, st));
+                // PAG: [neg ; pe ; pe] -- the perturbed group has the cond group's context
+                if (pag_on) HIP_OK(hipMemcpyAsync(ehs + (size_t)ng * B * L * D, in.prompt_embeds, pe, hipMemcpyDeviceToDevice, st));
                 if (unet->set_context(ehs, n, L, st)) { rc = -6; break; }
             }
             // ---------------- 4. mask / masked image / pose (tryon_pipe.py:630-636)
@@ -292,7 +314,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
             if (!c.dry()) {
                 c.check(ladi_launch_assemble_static(unet_in.p, 64, B, hw, cfgf, latents, mask8, masked_lat, pose_lat, pose_ch,
                                                     (has_cloth && !cloth_zero_from_start) ? cloth_lat : nullptr, has_cloth ? 1 : 0,
-                                                    sinfo.in_scale0, st), "assemble");
+                                                    sinfo.in_scale0, st, pag_on ? 1 : 0), "assemble");
                 HIP_OK(hipEventRecord(ev[1], st));
             }
             // ---------------- 9. denoising loop
@@ -303,6 +325,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
             sa.step_noise = use_step_noise ? step_noise_buf : nullptr;
             sa.guidance_tab = guided ? d_gtab : nullptr;
             sa.factor = use_factor ? d_factor : nullptr;
+            sa.pag_tab = pag_on ? d_pag : nullptr;
             if (keep_lat) { sa.keep_x0 = keep_x0; sa.keep_noise = keep_noise; sa.keep_mask = keep_mask; sa.keep_tab = d_keep_tab; }
             // the UNet forward runs as lanes.G independent sample groups on as many streams (runtime.h UNetLanes); the lanes own their
             // arenas, the shared noise prediction lives in this one
@@ -312,11 +335,19 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
             // cond: a cond-only evaluation of a guided run -- the UNet runs over the conditional samples [B, 2B) (their rows of unet_in and
             // eps, their part of the K/V cache) and the step kernel, told by the table, reads only those rows of eps
             // sh: a shallow evaluation (feature cache); a whole evaluation of a cached run captures
-            auto one_step = [&](bool concurrent, bool cond = false, bool sh = false) {
+            // pg: a PAG evaluation -- the forward also runs over the perturbed group, the rows behind the cond group's, perturbed from sample
+            // ng * B of the context batch.  In a PAG-shaped run an evaluation without PAG runs over the rows [0, ng * B) or [B, 2B): today's forms
+            auto one_step = [&](bool concurrent, bool cond = false, bool sh = false, bool pg = false) {
                 arena.release(mk_loop);
                 FeatCache fcs; fcs.mode = sh ? FeatCache::SHALLOW : FeatCache::CAPTURE; fcs.branch = fc_branch; fcs.buf = fcache;
                 const FeatCache* fc = fc_on ? &fcs : nullptr;
-                if (cond) {
+                if (pag_on) {
+                    const int s0 = cond ? B : 0, ns = ((cond ? 1 : ng) + (pg ? 1 : 0)) * B;
+                    Act xs = unet_in, es = eps;
+                    xs.n = ns; xs.p = unet_in.p + (size_t)s0 * hw * unet_in.ld;
+                    es.n = ns; es.p = eps.p + (size_t)s0 * hw * eps.ld;
+                    lanes.forward(*unet, st, c.dry(), concurrent, xs, es, unet->temb_table, d_step, s0, fc, pg ? ng * B : (int)PAG_NONE);
+                } else if (cond) {
                     Act xs = unet_in, es = eps;
                     xs.n = B; xs.p = unet_in.p + (size_t)B * hw * unet_in.ld;
                     es.n = B; es.p = eps.p + (size_t)B * hw * eps.ld;
@@ -325,7 +356,8 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 if (c.dry()) return;
                 sa.eps = eps.p; sa.ld_eps = eps.ld;
                 if (use_factor && !cond)
-                    c.check(ladi_launch_cfg_stats(eps.p, eps.ld, B, hw, d_gtab, d_step, 0.f, phi, d_factor, st), "cfg_stats");
+                    c.check(pag_on ? ladi_launch_cfg_stats_pag(eps.p, eps.ld, B, hw, d_gtab, d_step, 0.f, d_pag, 0.f, phi, d_factor, st)
+                                   : ladi_launch_cfg_stats(eps.p, eps.ld, B, hw, d_gtab, d_step, 0.f, phi, d_factor, st), "cfg_stats");
                 c.check(ladi_launch_sched_step(sa, st), "sched_step");
             };
             // step callback after evaluation i (between launches, never inside a capture): latents out to the caller's NCHW buffer, the host
@@ -341,14 +373,16 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 if ((cb_rc = cb_fn(cb_user, i)) != 0) return;
                 HIP_OK(hipEventRecord(ev_in, user_st));
                 HIP_OK(hipStreamWaitEvent(st, ev_in, 0));
-                c.check(ladi_launch_latents_import(cb_latents, B, hw, latents, unet_in.p, 64, cfgf, table[i].in_scale_next, st), "callback import");
+                c.check(ladi_launch_latents_import(cb_latents, B, hw, latents, unet_in.p, 64, cfgf, table[i].in_scale_next, st, pag_on ? 1 : 0),
+                        "callback import");
             };
-            // the forms of an evaluation: bit 0 cond-only, bit 1 shallow.  Which ones this run has, for the planning pass
-            auto form = [&](int i) { return (cond_only(i) ? 1 : 0) | (whole[i] ? 0 : 2); };
-            bool has_form[4] = {false, false, false, false};
+            // the forms of an evaluation: bit 0 cond-only, bit 1 shallow, bit 2 PAG (never with bit 1).  Which ones this run has, for the
+            // planning pass
+            auto form = [&](int i) { return (cond_only(i) ? 1 : 0) | (whole[i] ? 0 : 2) | (pag_eval(i) ? 4 : 0); };
+            bool has_form[8] = {false, false, false, false, false, false, false, false};
             for (int i = 0; i < evals; ++i) has_form[form(i)] = true;
             // the first evaluation of any form runs its lanes one after the other (one-time function attribute setup, per-shape tile measurement)
-            bool seen[4] = {false, false, false, false};
+            bool seen[8] = {false, false, false, false, false, false, false, false};
             // an evaluation whose forward ran over B samples (launched eagerly or by replaying the cond-only graph; every one of a run without CFG)
             auto ran = [&](int f) { if ((f & 1) || !cfgf) ++last_cond_only; if (f & 2) ++last_shallow; };
             if (c.dry()) {
@@ -356,15 +390,17 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 if (any_cond_only) one_step(false, true);
                 if (has_form[2]) one_step(false, false, true);
                 if (has_form[3]) one_step(false, true, true);
+                if (has_form[4]) one_step(false, false, false, true);
+                if (has_form[5]) one_step(false, true, false, true);
             }
             else if (!in.use_graph || evals < 3) {
                 for (int i = 0; i < evals && !cb_rc; ++i) {
                     const int f = form(i);
-                    one_step(i > 0 && seen[f], f & 1, f & 2); seen[f] = true; ran(f);
+                    one_step(i > 0 && seen[f], f & 1, f & 2, f & 4); seen[f] = true; ran(f);
                     callback_point(i);
                 }
             } else {
-                one_step(false, cond_only(0));  // eager first evaluation (always whole)
+                one_step(false, cond_only(0), false, pag_eval(0));  // eager first evaluation (always whole)
                 seen[form(0)] = true; ran(form(0));
                 callback_point(0);
                 unsigned long long key = 0x1234;
@@ -401,6 +437,10 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                     key = mix(key, fu.on ? 0x800000000ULL : 0ULL);
                     for (int i = 0; i < 4; ++i) { unsigned fb = 0; if (fu.on) std::memcpy(&fb, &fv[i], 4); key = mix(key, fb); }
                 }
+                // ... and with PAG: whether the run has the third group, the scale table and the selected blocks (a graph captured with PAG
+                // is never replayed without it, nor the reverse)
+                key = mix(key, pag_on ? 0x1000000000ULL | (unsigned long long)unet->pag_mask : 0ULL);
+                key = mix(key, (unsigned long long)(uintptr_t)sa.pag_tab);
                 if (key != graph_key) {
                     if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
                     if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
@@ -408,16 +448,18 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                     if (graph_cond) { (void)hipGraphDestroy(graph_cond); graph_cond = nullptr; }
                     for (auto& g : gexec_sh) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
                     for (auto& g : graph_sh) if (g) { (void)hipGraphDestroy(g); g = nullptr; }
+                    for (auto& g : gexec_pag) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+                    for (auto& g : graph_pag) if (g) { (void)hipGraphDestroy(g); g = nullptr; }
                     graph_key = key;
                 }
-                hipGraph_t* const grs[4] = {&graph, &graph_cond, &graph_sh[0], &graph_sh[1]};
-                hipGraphExec_t* const ges[4] = {&gexec, &gexec_cond, &gexec_sh[0], &gexec_sh[1]};
+                hipGraph_t* const grs[6] = {&graph, &graph_cond, &graph_sh[0], &graph_sh[1], &graph_pag[0], &graph_pag[1]};
+                hipGraphExec_t* const ges[6] = {&gexec, &gexec_cond, &gexec_sh[0], &gexec_sh[1], &gexec_pag[0], &gexec_pag[1]};
                 auto capture = [&](int f) {
                     hipGraph_t& gr = *grs[f];
                     hipGraphExec_t& ge = *ges[f];
                     if (gr) { (void)hipGraphDestroy(gr); gr = nullptr; }     // left by a capture whose instantiation failed
                     HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-                    try { one_step(true, f & 1, f & 2); } catch (...) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(st, &g); if (g) (void)hipGraphDestroy(g); throw; }
+                    try { one_step(true, f & 1, f & 2, f & 4); } catch (...) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(st, &g); if (g) (void)hipGraphDestroy(g); throw; }
                     HIP_OK(hipStreamEndCapture(st, &gr));
                     HIP_OK(hipGraphInstantiate(&ge, gr, nullptr, nullptr, 0));
                 };
@@ -426,7 +468,7 @@ int TryOn::run(const TryOnInputs& in, void* images_out, int images_u8, float* la
                 for (int i = 1; i < evals && !cb_rc; ++i) {
                     const int f = form(i);
                     hipGraphExec_t& ge = *ges[f];
-                    if (!ge && !seen[f]) { one_step(false, f & 1, f & 2); seen[f] = true; }
+                    if (!ge && !seen[f]) { one_step(false, f & 1, f & 2, f & 4); seen[f] = true; }
                     else {
                         if (!ge) capture(f);
                         HIP_OK(hipGraphLaunch(ge, st));

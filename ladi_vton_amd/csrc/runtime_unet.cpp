@@ -62,6 +62,7 @@ void UNet::load(const UNetCfg& c, const WeightStore& ws) {
     // see the same one (it used to be a getenv in every block of every pass)
     { const char* e = getenv("LADI_XF_FUSE"); xf_fuse = e ? atoi(e) : 0; }
     const int L = c.layers_per_block;
+    pag_mask = 1u << (3 * L);               // pag_applied_layers defaults to the mid block
     conv_in = load_conv(pool, ws, "conv_in", c.in_channels);
     time_l1 = load_conv(pool, ws, "time_embedding.linear_1");
     time_l2 = load_conv(pool, ws, "time_embedding.linear_2");
@@ -169,6 +170,7 @@ namespace {
 
 struct Fwd {
     Ctx& c; UNet& u; const float* temb; const int* tidx; int sample0;
+    int pag_first = PAG_NONE;   // context index of the first perturbed sample (PAG)
     Act res(const ResBlock& r, const Act& x, const Act* x2) {
         Act out;
         // block output is allocated first so temporaries can be released (stack discipline)
@@ -187,10 +189,18 @@ struct Fwd {
         c.ar->release(mk);
         return out;
     }
+    // np: the last np of the n samples are perturbed (PAG): the attention runs over the first n - np (one workgroup per (sample, head,
+    // query tile): the others' results do not depend on n), the perturbed rows of o are the rows of v themselves
     Act attn(const h16* q, int ldq, long long sq, const h16* k, const h16* v, int ldkv, long long skv, int n, int T, int Nk,
-             int heads) {
+             int heads, int np = 0) {
         Act o = c.new_act(n, T, 1, heads * 64);
         if (c.dry()) return o;
+        if (np > 0) {
+            const long long row0 = (long long)(n - np) * T;
+            c.check(ladi_launch_pag_identity(v + row0 * ldkv, ldkv, o.p + row0 * o.ld, o.ld, (long long)np * T, heads * 64, c.st), "pag_identity");
+            n -= np;
+            if (n == 0) return o;
+        }
         AttnArgs a;
         a.q = q; a.k = k; a.v = v; a.o = o.p;
         a.ldq = ldq; a.ldk = ldkv; a.ldv = ldkv; a.ldo = o.ld;
@@ -199,8 +209,14 @@ struct Fwd {
         c.check(ladi_launch_flash_attn64(a, c.st), "flash_attn64");
         return o;
     }
-    Act xf(const XfBlock& b, const Act& x) {
+    // bit: the block's index in execution order (UNet::pag_mask)
+    Act xf(const XfBlock& b, const Act& x, int bit) {
         const int n = x.n, T = x.h * x.w, C = b.C;
+        int np = 0;
+        if (pag_first != PAG_NONE && ((u.pag_mask >> bit) & 1u)) {
+            const int lead = pag_first - sample0;                       // leading unperturbed samples of this forward
+            np = n - (lead < 0 ? 0 : lead > n ? n : lead);
+        }
         Act out = new_act_with_stats(c, x.n, x.h, x.w, C);
         const size_t mk = c.ar->mark();
         // GroupNorm (no activation) -> proj_in: the normalisation's affine is applied to proj_in's register panel where the X-stationary
@@ -216,7 +232,7 @@ struct Fwd {
         Act t0 = conv2d(c, b.proj_in, tok, nullptr, op);
         ConvOpt oq; oq.ln = &b.ln1;                  // LayerNorm fused into the K = 320 / 640 projections (X-stationary kernel), else a launch
         Act qkv = conv2d(c, b.qkv, t0, nullptr, oq);
-        Act o1 = attn(qkv.p, 3 * C, (long long)T * 3 * C, qkv.p + C, qkv.p + 2 * C, 3 * C, (long long)T * 3 * C, n, T, T, b.heads);
+        Act o1 = attn(qkv.p, 3 * C, (long long)T * 3 * C, qkv.p + C, qkv.p + 2 * C, 3 * C, (long long)T * 3 * C, n, T, T, b.heads, np);
         ConvOpt or1; or1.res0 = &t0;
         Act t1 = conv2d(c, b.o1, o1, nullptr, or1);
         // attn2 and the feed-forward as ONE kernel each on the C = 320 level (xf_fused.hip; LADI_XF_FUSE=0 / =1 / =2: none / attn2 only / both,
@@ -273,7 +289,8 @@ struct Fwd {
 
 }  // namespace
 
-Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_idx, const Act* eps_out, int sample0, const FeatCache* fc) {
+Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_idx, const Act* eps_out, int sample0, const FeatCache* fc,
+                  int pag_first) {
     // deep-feature cache (runtime.h FeatCache): `shallow` skips every layer outside the 64x48 level's outermost `branch` layers; the layer
     // sequence below stays the only one -- a skipped layer only advances the weight indices
     const int L = cfg.layers_per_block;
@@ -288,7 +305,8 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
         return a;
     };
     if ((eps_out ? sample0 + x.n > ctx_n : ctx_n != x.n) && !c.dry()) throw std::runtime_error("UNet::forward: set_context batch mismatch");
-    Fwd f{c, *this, temb_row, temb_idx, sample0};
+    if (pag_first != PAG_NONE && fmode != FeatCache::NONE) throw std::runtime_error("UNet::forward: perturbed samples together with a feature cache");
+    Fwd f{c, *this, temb_row, temb_idx, sample0, pag_first};
     ProbeScope probe_scope(c, probe);
     // range probe points, named by the diffusers key prefix of the module that produced the tensor (off: one pointer test each)
     auto pp = [&](const Act& a, const char* fmt, int i = 0, int j = 0) {
@@ -308,7 +326,7 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
             if (shallow && (i > 0 || j >= fbranch)) { ++ri; if (i < 3) ++xi; continue; }
             h = f.res(down_res[ri++], h, nullptr);
             pp(h, "down_blocks.%d.resnets.%d", i, j);
-            if (i < 3) { h = f.xf(down_xf[xi++], h); pp(h, "down_blocks.%d.attentions.%d", i, j); }
+            if (i < 3) { h = f.xf(down_xf[xi], h, xi); ++xi; pp(h, "down_blocks.%d.attentions.%d", i, j); }
             skips.push_back(h);
         }
         if (i < 3 && !shallow) {
@@ -321,7 +339,7 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
     if (!shallow) {
         h = f.res(mid_res[0], h, nullptr);
         pp(h, "mid_block.resnets.0");
-        h = f.xf(mid_xf, h);
+        h = f.xf(mid_xf, h, 3 * L);
         pp(h, "mid_block.attentions.0");
         h = f.res(mid_res[1], h, nullptr);
         pp(h, "mid_block.resnets.1");
@@ -359,7 +377,7 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
             }
             h = f.res(up_res[ri++], h, &sk);
             pp(h, "up_blocks.%d.resnets.%d", i, j);
-            if (i > 0) { h = f.xf(up_xf[xi++], h); pp(h, "up_blocks.%d.attentions.%d", i, j); }
+            if (i > 0) { h = f.xf(up_xf[xi], h, 3 * L + 1 + xi); ++xi; pp(h, "up_blocks.%d.attentions.%d", i, j); }
         }
         if (i < 3 && !shallow) {
             ConvOpt ou; ou.ups = 1; ou.stats = true;
@@ -413,7 +431,7 @@ void UNetLanes::configure(int n, int g) {
 }
 
 void UNetLanes::forward(UNet& u, hipStream_t main_st, bool dry, bool concurrent, const Act& x, const Act& eps, const float* temb, const int* tidx,
-                        int sample0, const FeatCache* fc) {
+                        int sample0, const FeatCache* fc, int pag_first) {
     const int Gu = sub_lanes(x.n);          // the configured count when it divides x.n (always, for the whole batch)
     const int ng = x.n / Gu;
     const bool par = concurrent && !dry && Gu > 1;
@@ -426,7 +444,7 @@ void UNetLanes::forward(UNet& u, hipStream_t main_st, bool dry, bool concurrent,
         if (!dry && stats_cap[g]) HIP_OK_L(hipMemsetAsync(stats[g], 0, stats_cap[g] * sizeof(float), sg));
         Act xg = x; xg.n = ng; xg.p = x.p + (size_t)g * ng * x.h * x.w * x.ld;
         Act eg = eps; eg.n = ng; eg.p = eps.p + (size_t)g * ng * eps.h * eps.w * eps.ld; eg.st_part = nullptr; eg.st_px = 0;
-        (void)u.forward(c, xg, temb, tidx, &eg, sample0 + g * ng, fc);
+        (void)u.forward(c, xg, temb, tidx, &eg, sample0 + g * ng, fc, pag_first);
         if (dry) { peak[g] = arena[g].peak; if (c.stats_peak > stats_peak[g]) stats_peak[g] = c.stats_peak; }
         if (par && g > 0) { HIP_OK_L(hipEventRecord(join[g], sg)); HIP_OK_L(hipStreamWaitEvent(main_st, join[g], 0)); }
     }

@@ -141,6 +141,22 @@ class NativeUNet(_Base):
         check(self.lib.ladi_unet_set_freeu(self.h, 0, 1.0, 1.0, 1.0, 1.0), "ladi_unet_set_freeu")
         self.freeu = None
 
+    def set_pag_applied_layers(self, layers):
+        """diffusers' pag_applied_layers: the transformer blocks in which a perturbed sample's self-attention map is the identity
+        ("mid", "down", "up", "down.block_1", "up.block_2.attentions_0", .. as one string or a list; pipeline.pag_layer_mask), or the bit
+        mask itself.  Sticky; the default is "mid".  It has no effect on a forward without perturbed samples (pag_first)."""
+        if isinstance(layers, bool) or not isinstance(layers, int):
+            from .pipeline import pag_layer_mask
+            layers = pag_layer_mask(layers, self.cfg["layers_per_block"])
+        if layers < 0 or layers >> 32:
+            raise ValueError("the PAG layer mask has to fit 32 bits but is %r" % (layers,))
+        check(self.lib.ladi_unet_set_pag_layers(self.h, layers), "ladi_unet_set_pag_layers")
+
+    @property
+    def pag_applied_layers(self):
+        """the mask of selected transformer blocks, bit i = block i in execution order"""
+        return int(self.lib.ladi_unet_pag_layers(self.h))
+
     def enable_xformers_memory_efficient_attention(self, *a, **k):
         return None  # attention is always fused (flash-style) in the native kernels
 
@@ -157,8 +173,10 @@ class NativeUNet(_Base):
 
     FEATURE_CACHE_MODES = {None: 0, "capture": 1, "reuse": 2}
 
-    def __call__(self, sample, timestep, encoder_hidden_states=None, feature_cache=None, cache_branch=0, sample0=0, **kw):
-        """feature_cache: None, "capture" (the whole forward, which also caches the deep features of the full-resolution level) or "reuse"
+    def __call__(self, sample, timestep, encoder_hidden_states=None, feature_cache=None, cache_branch=0, sample0=0, pag_first=None, **kw):
+        """pag_first: None, or the index in the encoder_hidden_states batch from which the samples are perturbed (perturbed-attention
+        guidance: identity self-attention in the blocks of set_pag_applied_layers); not together with feature_cache.
+        feature_cache: None, "capture" (the whole forward, which also caches the deep features of the full-resolution level) or "reuse"
         (the shallow forward from that cache: the outermost cache_branch + 1 layers only; ladi_unet_forward_cached).  sample0: the samples
         are rows [sample0, sample0 + n) of the encoder_hidden_states batch (their own rows of the K/V and feature caches)."""
         if encoder_hidden_states is None:
@@ -173,6 +191,14 @@ class NativeUNet(_Base):
         if C != self.cfg["in_channels"]:
             raise ValueError("expected %d input channels, got %d" % (self.cfg["in_channels"], C))
         out = torch.empty((n, self.cfg["out_channels"], h, w), dtype=x.dtype, device=x.device)
+        if pag_first is not None:
+            if feature_cache is not None:
+                raise ValueError("`pag_first` and `feature_cache` cannot be combined.")
+            if isinstance(pag_first, bool) or not isinstance(pag_first, int) or pag_first < 0:
+                raise ValueError("pag_first has to be a non-negative int but is %r" % (pag_first,))
+            check(self.lib.ladi_unet_forward_pag(self.h, ptr(x), dtype_code(x), n, h, w, float(timestep), ptr(out), dtype_code(out), int(sample0),
+                                                 pag_first, stream_ptr()), "ladi_unet_forward_pag")
+            return SimpleNamespace(sample=out)
         if feature_cache is not None or sample0:
             check(self.lib.ladi_unet_forward_cached_rows(self.h, ptr(x), dtype_code(x), n, h, w, float(timestep), ptr(out), dtype_code(out),
                                                          self.FEATURE_CACHE_MODES[feature_cache], int(cache_branch), int(sample0), stream_ptr()),

@@ -114,6 +114,71 @@ def feature_cache_spec(feature_cache, n_evals):
     return (None if all(flags) else flags), int(branch)
 
 
+def pag_layer_mask(layers, layers_per_block=2):
+    """-> the bit mask of `pag_applied_layers`: bit i = transformer block i in execution order, i.e. bits 0 .. 3L-1
+    down_blocks.{0,1,2}.attentions.{0..L-1}, bit 3L the mid block, bits 3L+1 .. 6L+3 up_blocks.{1,2,3}.attentions.{0..L} (L =
+    layers_per_block).  layers: one name or a list of "mid", "down", "up", "down.block_i", "up.block_i", "down.block_i.attentions_j",
+    "up.block_i.attentions_j".  Raises ValueError for a name that selects no block (down.block_3 and up.block_0 have no attention), an
+    unknown name or an empty list."""
+    L = int(layers_per_block)
+    if isinstance(layers, str):
+        layers = [layers]
+    try:
+        names = list(layers)
+    except TypeError:
+        raise ValueError("`pag_applied_layers` has to be a name or a list of names but is %r." % (layers,))
+    if not names:
+        raise ValueError("`pag_applied_layers` selects no transformer block (empty list).")
+    mask = 0
+    for name in names:
+        bad = ValueError("`pag_applied_layers`: %r selects no transformer block (mid, down, up, down.block_{0,1,2}[.attentions_j], "
+                         "up.block_{1,2,3}[.attentions_j])." % (name,))
+        if not isinstance(name, str):
+            raise bad
+        parts = name.split(".")
+        if parts == ["mid"]:
+            mask |= 1 << (3 * L)
+            continue
+        if parts[0] not in ("down", "up") or len(parts) > 3:
+            raise bad
+        down = parts[0] == "down"
+        per = L if down else L + 1                    # attentions per block
+        blocks = (0, 1, 2) if down else (1, 2, 3)     # the blocks that have attention
+        base = (lambda i: i * L) if down else (lambda i: 3 * L + 1 + (i - 1) * (L + 1))
+        if len(parts) == 1:
+            sel = [(i, j) for i in blocks for j in range(per)]
+        else:
+            if not parts[1].startswith("block_") or not parts[1][6:].isdigit() or int(parts[1][6:]) not in blocks:
+                raise bad
+            i = int(parts[1][6:])
+            if len(parts) == 2:
+                sel = [(i, j) for j in range(per)]
+            else:
+                if not parts[2].startswith("attentions_") or not parts[2][11:].isdigit() or int(parts[2][11:]) >= per:
+                    raise bad
+                sel = [(i, int(parts[2][11:]))]
+        for i, j in sel:
+            mask |= 1 << (base(i) + j)
+    return mask
+
+
+def pag_plan(pag_scale, pag_adaptive_scale, timesteps):
+    """-> the PAG scale of every evaluation (diffusers PAGMixin._get_pag_scale): pag_scale when pag_adaptive_scale == 0, else
+    max(pag_scale - pag_adaptive_scale * (1000 - t_i), 0) with t_i the scheduler's timesteps.  Raises ValueError for a negative or non-finite
+    scale."""
+    try:
+        s, a = float(pag_scale), float(pag_adaptive_scale)
+    except (TypeError, ValueError):
+        raise ValueError("`pag_scale` and `pag_adaptive_scale` have to be numbers but are %r and %r." % (pag_scale, pag_adaptive_scale))
+    if not math.isfinite(s) or s < 0.0:
+        raise ValueError("`pag_scale` has to be finite and >= 0 but is %r." % (pag_scale,))
+    if not math.isfinite(a) or a < 0.0:
+        raise ValueError("`pag_adaptive_scale` has to be finite and >= 0 but is %r." % (pag_adaptive_scale,))
+    if a == 0.0:
+        return [s for _ in timesteps]
+    return [max(s - a * (1000.0 - float(t)), 0.0) for t in timesteps]
+
+
 def strength_first_step(strength, num_inference_steps):
     """-> first_step: the step of the schedule a run with `strength` starts at.  diffusers' get_timesteps arithmetic in Python float64:
     init_timestep = min(int(N * strength), N), first_step = N - init_timestep.  Raises ValueError for a strength outside [0, 1] or not finite,
@@ -207,6 +272,14 @@ class StableDiffusionTryOnePipeline:
         if not hasattr(self.unet, "enable_freeu"):
             raise ValueError("`enable_freeu` needs a UNet with enable_freeu (NativeUNet), the pipeline holds %s." % type(self.unet).__name__)
         self.unet.enable_freeu(s1, s2, b1, b2)
+
+    def set_pag_applied_layers(self, layers):
+        """diffusers' pag_applied_layers: the transformer blocks whose self-attention the perturbed samples of `pag_scale` > 0 run with the
+        identity map (pag_layer_mask's names; default "mid").  Forwarded to the UNet, where the state lives."""
+        if not hasattr(self.unet, "set_pag_applied_layers"):
+            raise ValueError("`set_pag_applied_layers` needs a UNet with set_pag_applied_layers (NativeUNet), the pipeline holds %s."
+                             % type(self.unet).__name__)
+        self.unet.set_pag_applied_layers(layers)
 
     def disable_freeu(self):
         if not hasattr(self.unet, "disable_freeu"):
@@ -340,7 +413,7 @@ class StableDiffusionTryOnePipeline:
                  negative_prompt_embeds=None, generator=None, latents=None, output_type="pil", return_dict=True, callback=None,
                  callback_steps=1, cloth_cond_rate=1.0, no_pose=False, cloth_input_type="warped", fused=True, noise=None,
                  use_graph=True, guidance_rescale=0.0, strength=1.0, init_image=None, init_latents=None, init_is_noisy=False,
-                 feature_cache=None, preserve_unmasked=None, mask_feather=0.0):
+                 feature_cache=None, preserve_unmasked=None, mask_feather=0.0, pag_scale=0.0, pag_adaptive_scale=0.0):
         """tryon_pipe.py's __call__.  `guidance_scale`: a float, a sequence with one scale per evaluation (len(scheduler.timesteps); PNDM: steps
         + 1) or a callable f(i, n_evals) -- see guidance_interval.  Classifier-free guidance is on if any scale is > 1; an evaluation whose scale
         is <= 1 then runs the UNet over the conditional samples only.  `guidance_rescale` (rescale_noise_cfg's phi, [0, 1]) acts on the CFG
@@ -371,7 +444,14 @@ class StableDiffusionTryOnePipeline:
         that of `latents=` / RNG draw #2, also with `strength` < 1.  Scheduler state is not blended; a callback sees the blended latents.
         "pixels" composites the decoded picture over the input image, M g + (1 - M) p with the binarised mask M, or its Gaussian blur of
         `mask_feather` pixels sigma (0 .. 32); where M is 0 or 1 the pixel is p or g bit for bit, in the float and the uint8 output alike.
-        "both" does both.  `mask_feather` needs a pixels mode."""
+        "both" does both.  `mask_feather` needs a pixels mode.
+
+        `pag_scale` > 0 is perturbed-attention guidance (diffusers PAGMixin): every evaluation also runs a perturbed copy of the conditional
+        samples, whose self-attention in the blocks of `set_pag_applied_layers` (default the mid block) is the identity map, and the
+        prediction becomes u + g (c - u) + s (c - p), or c + s (c - p) without classifier-free guidance; `guidance_rescale` acts on that
+        sum.  `pag_adaptive_scale` > 0 lowers the scale with the timestep, s_i = max(pag_scale - pag_adaptive_scale * (1000 - t_i), 0); an
+        evaluation with s_i = 0 runs without the perturbed samples.  Needs the native UNet; not together with `feature_cache`.  0 is the
+        plain run bit for bit."""
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
@@ -404,6 +484,17 @@ class StableDiffusionTryOnePipeline:
         if first_step > 0:
             n_evals()      # a first_step the scheduler cannot start at (a PNDM tail of one step) fails here, before any work
         g_table, guidance_scale, do_cfg = guidance_plan(guidance_scale, n_evals, guidance_rescale)
+        pag_plan(pag_scale, pag_adaptive_scale, ())          # negative / non-finite scales fail here, before any work
+        pag_table = None
+        if float(pag_scale) > 0.0:
+            if not hasattr(self.unet, "set_pag_applied_layers"):
+                raise ValueError("`pag_scale` needs the native UNet (NativeUNet), the pipeline holds %s." % type(self.unet).__name__)
+            if feature_cache is not None:
+                raise ValueError("`pag_scale` > 0 and `feature_cache` cannot be combined (the cache has no third sample group).")
+            n_evals()
+            pag_table = pag_plan(pag_scale, pag_adaptive_scale, self.scheduler.timesteps)
+            if not any(s > 0.0 for s in pag_table):
+                pag_table = None
         fc_flags, fc_branch = feature_cache_spec(feature_cache, n_evals)
         if feature_cache is not None and not isinstance(self.unet, NativeUNet):
             raise ValueError("`feature_cache` needs the native UNet (NativeUNet), the pipeline holds %s." % type(self.unet).__name__)
@@ -444,7 +535,7 @@ class StableDiffusionTryOnePipeline:
                                      no_pose, use_graph, step_noise=step_noise, eta=ddim_eta, callback=callback,
                                      callback_steps=callback_steps, guidance_table=g_table, guidance_rescale=guidance_rescale,
                                      init_latents=init, first_step=first_step, init_is_noisy=init_is_noisy,
-                                     feature_cache=(fc_flags, fc_branch), preserve=preserve)
+                                     feature_cache=(fc_flags, fc_branch), preserve=preserve, pag_table=pag_table)
             # prepare_mask_and_masked_image binarises the caller's mask in place; keep that side effect
             mask_image[mask_image < 0.5] = 0
             mask_image[mask_image >= 0.5] = 1
@@ -453,7 +544,8 @@ class StableDiffusionTryOnePipeline:
                                        n_cloth, n_lat, n_mask, height, width, num_inference_steps, guidance_scale, cloth_cond_rate,
                                        no_pose, eta, generator, callback, callback_steps, guidance_table=g_table,
                                        guidance_rescale=guidance_rescale, init_latents=init, first_step=first_step,
-                                       init_is_noisy=init_is_noisy, feature_cache=(fc_flags, fc_branch), preserve=preserve)
+                                       init_is_noisy=init_is_noisy, feature_cache=(fc_flags, fc_branch), preserve=preserve,
+                                       pag_table=pag_table)
         if output_type == "pil":
             images = numpy_to_pil(images)
         if not return_dict:
@@ -482,7 +574,7 @@ class StableDiffusionTryOnePipeline:
     def _run_fused(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose,
                    use_graph, return_device=False, out_uint8=False, lanes=None, step_noise=None, eta=0.0, callback=None, callback_steps=1,
                    guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0, init_is_noisy=False, feature_cache=None,
-                   preserve=None):
+                   preserve=None, pag_table=None):
         """return_device: hand back the device tensor (no host copy); out_uint8: the batch as uint8 [B,H,W,3] = numpy_to_pil's
         (images * 255).round() computed by the decode epilogue (ladi_tryon_run_u8); lanes: sample-group lanes of the UNet forward;
         step_noise: fp32 [steps, B, 4, h, w], the per-step noise of EulerAncestralDiscreteScheduler and of DDIM with eta > 0
@@ -497,7 +589,8 @@ class StableDiffusionTryOnePipeline:
         callback's i and the cloth cut-off of `ccr` all refer to them.
         feature_cache: (flags, branch) of feature_cache_spec, one flag per evaluation before promotion (ladi_tryon_set_feature_cache does the
         promotion); None or flags None = off.
-        preserve: (mode_bits, feather sigma) of preserve_spec (ladi_tryon_set_preserve); None = off."""
+        preserve: (mode_bits, feather sigma) of preserve_spec (ladi_tryon_set_preserve); None = off.
+        pag_table: one PAG scale per evaluation (pag_plan; ladi_tryon_set_pag); None = off."""
         lib = _lib.load()
         if self._tryon is None:
             self._tryon = lib.ladi_tryon_create(self.unet.h, self.vae.h, self.emasc.h if self.emasc else None)
@@ -580,6 +673,11 @@ class StableDiffusionTryOnePipeline:
             check(lib.ladi_tryon_set_feature_cache(self._tryon, ff, len(fc_flags), int(fc_branch)), "ladi_tryon_set_feature_cache")
         else:
             check(lib.ladi_tryon_set_feature_cache(self._tryon, None, 0, 0), "ladi_tryon_set_feature_cache")
+        if pag_table is not None:
+            pt = (ctypes.c_float * len(pag_table))(*pag_table)
+            check(lib.ladi_tryon_set_pag(self._tryon, pt, len(pag_table)), "ladi_tryon_set_pag")
+        else:
+            check(lib.ladi_tryon_set_pag(self._tryon, None, 0), "ladi_tryon_set_pag")
         p_bits, p_sigma = preserve if preserve is not None else (0, 0.0)
         check(lib.ladi_tryon_set_preserve(self._tryon, int(p_bits), float(p_sigma)), "ladi_tryon_set_preserve")
         self._shallow_evals = None
@@ -673,12 +771,14 @@ class StableDiffusionTryOnePipeline:
     # -------------------------------------------------------------------------------------------------------
     def _run_modular(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose, eta,
                      generator, callback, callback_steps, guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0,
-                     init_is_noisy=False, feature_cache=None, preserve=None):
+                     init_is_noisy=False, feature_cache=None, preserve=None, pag_table=None):
         F = torch.nn.functional
         dev = self._execution_device
         do_cfg = neg is not None
         sf = self.vae.config.scaling_factor
         ehs = torch.cat([neg, pe]) if do_cfg else pe
+        # PAG: the context of the whole run is [neg ; pe ; pe] (or [pe ; pe]); every evaluation runs its own rows of it
+        ehs_pag = torch.cat([ehs, pe]) if pag_table is not None else None
         mask_image[mask_image < 0.5] = 0
         mask_image[mask_image >= 0.5] = 1
         mask = mask_image.to(dev)
@@ -752,8 +852,16 @@ class StableDiffusionTryOnePipeline:
             parts = [x, mask_lat, masked_lat, pose] + ([cloth_lat] if cloth_lat is not None else [])
             if do_cfg and not cfg_i:
                 parts = [x] + [p[B:] for p in parts[1:]]
+            s_i = pag_table[i] if pag_table is not None else 0.0
+            if s_i > 0.0:      # the perturbed group: the conditional group's rows once more
+                parts = [torch.cat([p, p[-B:]]) for p in parts]
             x = torch.cat([p.float() for p in parts], dim=1)
-            if fc_flags is not None:
+            if pag_table is not None:
+                ng = 2 if do_cfg else 1
+                eps = self.unet(x, t, encoder_hidden_states=ehs_pag, sample0=B if do_cfg and not cfg_i else 0, pag_first=ng * B).sample.float()
+                if s_i > 0.0:
+                    eps, ep = eps[:-B], eps[-B:]
+            elif fc_flags is not None:
                 eps = self.unet(x, t, encoder_hidden_states=ehs, feature_cache="capture" if fc_flags[i] else "reuse", cache_branch=fc_branch,
                                 sample0=B if do_cfg and not cfg_i else 0).sample.float()
             else:
@@ -761,8 +869,12 @@ class StableDiffusionTryOnePipeline:
             if cfg_i:
                 eu, et = eps.chunk(2)
                 eps = eu + g_i * (et - eu)
+                if s_i > 0.0:
+                    eps = eps + s_i * (et - ep)
                 if guidance_rescale > 0.0:
                     eps = rescale_noise_cfg(eps, et, guidance_rescale)
+            elif s_i > 0.0:
+                eps = eps + s_i * (eps - ep)
             latents = self.scheduler.step(eps, t, latents, **extra).prev_sample
             if p_bits & 1:
                 known = self.scheduler.add_noise(z0, keep_noise, timesteps[i + 1]) if i + 1 < len(timesteps) else z0
