@@ -429,6 +429,36 @@ int ladi_unet_set_pag_layers(ladi_unet* u, unsigned layer_mask);
 unsigned ladi_unet_pag_layers(const ladi_unet* u);
 int ladi_unet_forward_pag(ladi_unet* u, const void* sample_dev, int dtype, int n, int h, int w, float timestep, void* out_dev, int out_dtype,
                           int sample0, int pag_first, void* stream);
+/* ---- LoRA adapters (DESIGN.md "LoRA").  The weights of a UNet stay where they are; an adapter is merged onto them on the device:
+ *   W = fp16(base + sum_a weight_a * alpha_a / rank_a * up_a down_a)    (fp32 arithmetic, one rounding, always from the pristine copy)
+ * so captured graphs, tile selections and arenas stay valid and the forward launches exactly what it launched before.
+ * Targets are the diffusers module names of every conv and linear of the UNet (conv_in, conv_out, time_embedding.linear_1 / 2, every
+ * resnet's conv1, conv2, conv_shortcut and time_emb_proj, the down- and upsampler convs, and per transformer proj_in, attn1.to_q / to_k /
+ * to_v / to_out.0, attn2.to_q / to_k / to_v / to_out.0, ff.net.0.proj, ff.net.2, proj_out); norms and biases are not targets.
+ *
+ * ladi_unet_lora_load: `ws` holds <module>.lora_down.weight ([r, in] or [r, in, k, k]), <module>.lora_up.weight ([out, r] or [out, r, 1, 1])
+ * and optionally <module>.alpha (one number; default r).  Everything is checked first -- unknown module, shapes against the target, r in
+ * [1, 256], a name already loaded, more than 8 loaded adapters, any other key -- and on an error nothing has changed.  The factors go to the
+ * device in fp32; the first time a packed weight is touched a pristine fp16 copy of it is kept (at most one extra copy of the touched
+ * weights, for the life of the UNet).  Loading does not activate.
+ * ladi_unet_set_adapters: the active set, in this order (count = 0: none, every weight is restored bit for bit).  The live weights are
+ * rewritten in place, so the call first waits for the whole device (work on any stream may be reading them).  Every block touched by
+ * the new or the previous set is merged again from its pristine copy on `stream`; the cross-attention K/V cache is dropped (a forward
+ * needs a new ladi_unet_set_context and says so), the stand-alone feature cache is dropped and the re-packed operands of the fused
+ * sub-blocks are packed again.  The call then reads a device counter of merged values outside the fp16 range (one synchronisation of
+ * `stream`): if there is one, the previous set is merged back and the error names the first such module.
+ * ladi_unet_lora_delete: refused while the adapter is active.  ladi_unet_lora_count / ladi_unet_lora_name: the loaded adapters, in load
+ * order (-1 / NULL for a null handle or a bad index).  ladi_unet_lora_active: the active set's size; the first min(size, cap) names
+ * (valid until the next change) and weights are written.
+ * ladi_unet_export_weight: the LIVE value of a diffusers .weight key of a target, in diffusers layout ([out][in][kh][kw], fp32 holding
+ * fp16 values), into host_out[cap]; returns the element count (host_out == NULL: the count alone), -1 on an error.  Synchronises. */
+int ladi_unet_lora_load(ladi_unet* u, const char* name, const ladi_weights* ws);
+int ladi_unet_set_adapters(ladi_unet* u, const char* const* names, const float* weights, int count, void* stream);
+int ladi_unet_lora_delete(ladi_unet* u, const char* name);
+int ladi_unet_lora_count(const ladi_unet* u);
+const char* ladi_unet_lora_name(const ladi_unet* u, int i);
+int ladi_unet_lora_active(const ladi_unet* u, const char** names_out, float* weights_out, int cap);
+long long ladi_unet_export_weight(ladi_unet* u, const char* key, float* host_out, long long cap);
 /* PAG scales of the following runs (sticky per handle; copied): scales_host[i] = s_i of evaluation i.  NULL or count 0 switches it off; a
  * table of zeros is the plain run bit for bit (nothing is allocated or launched for it).  With any s_i > 0 the run has the third sample group
  * ([uncond ; cond ; perturbed], or [cond ; perturbed] without CFG; context [neg ; pe ; pe]) and the guided prediction of an evaluation with
@@ -719,6 +749,18 @@ int ladi_op_fill_f32(float* p, long long n, float v, void* stream);
  * pointers: anything else is refused with a message and nothing is launched. */
 int ladi_op_freeu(void* hidden, int ld_h, int C_h, float b, const void* skip, int ld_s, int C_s, float s, void* skip_out, int ld_d, int n, int H,
                   int W, void* stream);
+/* one LoRA merge: rows [row0, row0 + rows) of the packed fp16 weight W (rows of `pitch` halves, each [taps][cin_pad]) become
+ *   fp16(float(base) + sum_a scale[a] * sum_r up[a][o][r] * down[a][r][t][i])      for the channels i < cin of every tap
+ * from the same rows of `base` (same layout, read only, not W itself).  up[a] fp32 [rows][rank[a]], down[a] fp32 [rank[a]][taps][cin].
+ * geglu_half = 0: source row o is row row0 + o; geglu_half = rows / 2: the GEGLU interleave (o < half -> row0 + 64 (o / 32) + o % 32, half + o
+ * -> the same + 32; half a multiple of 32, row0 of 64).  fp32 sums in a fixed order (ascending r, adapters in call order), one rounding: two
+ * launches are bit-equal; n_adapters = 0 or a delta of exactly zero copies the base's bits.  Channels [cin, cin_pad) and all other rows
+ * keep their bits.  nonfinite (device, may be NULL) += the number of results outside the fp16 range.  cin_pad a multiple of 64 and >= cin,
+ * pitch a multiple of 8 and >= taps * cin_pad, 16-byte aligned base / W, at most 8 adapters of rank 1 .. 256, finite scales: anything else is
+ * refused with a message and nothing is launched. */
+int ladi_op_lora_merge(const void* base, void* W, long long pitch, int cin, int cin_pad, int taps, int row0, int rows, int geglu_half,
+                       int n_adapters, const float* const* up, const float* const* down, const int* rank, const float* scale,
+                       unsigned* nonfinite, void* stream);
 
 /* ---- fp16 range probe (opt-in; with no probe attached nothing changes: same launches, same captured graph, same bits) ----
  * A probe records, for every named activation of the modules it is attached to, the largest finite |x| and the number of inf / NaN

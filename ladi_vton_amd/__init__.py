@@ -5,6 +5,7 @@ There is no CPU fallback: constructing any Native* module without a ROCm GPU rai
 """
 from . import configs  # noqa: F401
 from . import dataset  # noqa: F401  (host-side VITON-HD / DressCode readers)
+from . import lora  # noqa: F401  (LoRA key normalisation; the adapters live in NativeUNet)
 from ._lib import NativeError  # noqa: F401
 from .modules import (NativeEMASC, NativeInversionAdapter, NativeUNet, NativeVAE, mask_features)  # noqa: F401
 from .pipeline import StableDiffusionTryOnePipeline, feature_cache_plan, guidance_interval, preserve_spec, strength_first_step  # noqa: F401

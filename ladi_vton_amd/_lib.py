@@ -117,6 +117,13 @@ SIGNATURES = {
     "ladi_unet_set_pag_layers": (c_int, [_P, ctypes.c_uint]),
     "ladi_unet_pag_layers": (ctypes.c_uint, [_P]),
     "ladi_unet_forward_pag": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, c_int, c_int, c_int, _P]),
+    "ladi_unet_lora_load": (c_int, [_P, c_char_p, _P]),
+    "ladi_unet_set_adapters": (c_int, [_P, POINTER(c_char_p), POINTER(c_float), c_int, _P]),
+    "ladi_unet_lora_delete": (c_int, [_P, c_char_p]),
+    "ladi_unet_lora_count": (c_int, [_P]),
+    "ladi_unet_lora_name": (c_char_p, [_P, c_int]),
+    "ladi_unet_lora_active": (c_int, [_P, POINTER(c_char_p), POINTER(c_float), c_int]),
+    "ladi_unet_export_weight": (c_longlong, [_P, c_char_p, _P, c_longlong]),
     "ladi_vae_create": (_P, [POINTER(VAEConfig), _P]),
     "ladi_vae_destroy": (None, [_P]),
     "ladi_vae_encode": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, POINTER(_P), _P]),
@@ -267,6 +274,8 @@ SIGNATURES = {
     "ladi_op_latents_import": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_float, _P]),
     "ladi_op_scale_h16": (c_int, [_P, c_int, _P, c_int, c_longlong, c_int, c_float, _P]),
     "ladi_op_fill_f32": (c_int, [_P, c_longlong, c_float, _P]),
+    "ladi_op_lora_merge": (c_int, [_P, _P, c_longlong, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(_P), POINTER(_P), POINTER(c_int),
+                                   POINTER(c_float), _P, _P]),
     "ladi_op_freeu": (c_int, [_P, c_int, c_int, c_float, _P, c_int, c_int, c_float, _P, c_int, c_int, c_int, c_int, _P]),
 }
 

@@ -149,6 +149,84 @@ int ladi_unet_set_pag_layers(ladi_unet* u, unsigned layer_mask) {
 }
 unsigned ladi_unet_pag_layers(const ladi_unet* u) { return u ? u->u.pag_mask : 0u; }
 
+// ------------------------------------------------------------------------------------------------ LoRA (runtime_lora.cpp)
+int ladi_unet_lora_load(ladi_unet* u, const char* name, const ladi_weights* ws) {
+    return guarded("ladi_unet_lora_load", [&]() {
+        if (!u || !name || !ws) throw std::runtime_error("null handle, name or weights");
+        u->u.lora_load(name, ws->ws);
+        return 0;
+    });
+}
+int ladi_unet_set_adapters(ladi_unet* u, const char* const* names, const float* weights, int count, void* stream) {
+    return guarded("ladi_unet_set_adapters", [&]() {
+        if (!u) throw std::runtime_error("null handle");
+        if (count < 0 || (count > 0 && (!names || !weights))) throw std::runtime_error("count < 0, or null names / weights with count > 0");
+        std::vector<std::pair<std::string, float>> set;
+        for (int i = 0; i < count; ++i) {
+            if (!names[i]) throw std::runtime_error("null adapter name at index " + std::to_string(i));
+            set.emplace_back(names[i], weights[i]);
+        }
+        u->u.lora_set(set, S(stream));
+        return 0;
+    });
+}
+int ladi_unet_lora_delete(ladi_unet* u, const char* name) {
+    return guarded("ladi_unet_lora_delete", [&]() {
+        if (!u || !name) throw std::runtime_error("null handle or name");
+        u->u.lora_delete(name);
+        return 0;
+    });
+}
+int ladi_unet_lora_count(const ladi_unet* u) {
+    if (!u) { set_error("ladi_unet_lora_count: null handle"); return -1; }
+    return (int)u->u.lora_adapters.size();
+}
+const char* ladi_unet_lora_name(const ladi_unet* u, int i) {
+    if (!u || i < 0 || i >= (int)u->u.lora_adapters.size()) { set_error("ladi_unet_lora_name: null handle or index out of range"); return nullptr; }
+    return u->u.lora_adapters[i]->name.c_str();
+}
+int ladi_unet_lora_active(const ladi_unet* u, const char** names_out, float* weights_out, int cap) {
+    if (!u || cap < 0 || (cap > 0 && (!names_out || !weights_out))) { set_error("ladi_unet_lora_active: null handle, cap < 0 or null outputs"); return -1; }
+    const int n = (int)u->u.lora_active.size();
+    for (int i = 0; i < n && i < cap; ++i) { names_out[i] = u->u.lora_active[i].first.c_str(); weights_out[i] = u->u.lora_active[i].second; }
+    return n;
+}
+long long ladi_unet_export_weight(ladi_unet* u, const char* key, float* host_out, long long cap) {
+    long long n = -1;
+    const int rc = guarded("ladi_unet_export_weight", [&]() {
+        if (!u || !key) throw std::runtime_error("null handle or key");
+        if (host_out && cap < 0) throw std::runtime_error("cap < 0");
+        n = u->u.export_weight(key, host_out, cap);
+        return 0;
+    });
+    return rc ? -1 : n;
+}
+int ladi_op_lora_merge(const void* base, void* W, long long pitch, int cin, int cin_pad, int taps, int row0, int rows, int geglu_half,
+                       int n_adapters, const float* const* up, const float* const* down, const int* rank, const float* scale,
+                       unsigned* nonfinite, void* stream) {
+    return guarded("ladi_op_lora_merge", [&]() {
+        if (!base || !W || base == W) throw std::runtime_error("null base or W, or base == W");
+        if (n_adapters < 0 || n_adapters > LORA_MAX_ADAPTERS) throw std::runtime_error("n_adapters " + std::to_string(n_adapters) + " outside [0, 8]");
+        if (n_adapters > 0 && (!up || !down || !rank || !scale)) throw std::runtime_error("null up, down, rank or scale with n_adapters > 0");
+        if (((uintptr_t)nonfinite & 3)) throw std::runtime_error("the non-finite counter is not 4-byte aligned");
+        LoraMergeArgs a; std::memset(&a, 0, sizeof(a));
+        a.base = reinterpret_cast<const h16*>(base); a.W = reinterpret_cast<h16*>(W); a.pitch = pitch;
+        a.cin = cin; a.cin_pad = cin_pad; a.taps = taps; a.row0 = row0; a.rows = rows; a.geglu_half = geglu_half; a.n_adapters = n_adapters;
+        for (int i = 0; i < n_adapters; ++i) {
+            if (!std::isfinite(scale[i])) throw std::runtime_error("scale " + std::to_string(i) + " is not finite");
+            a.up[i] = up[i]; a.down[i] = down[i]; a.rank[i] = rank[i]; a.scale[i] = scale[i];
+        }
+        a.nonfinite = nonfinite;
+        const int rc = ladi_launch_lora_merge(a, S(stream));
+        static const char* const why[] = {"", "null or identical base / W", "a size < 1, cin_pad < cin or cin_pad not a multiple of 64",
+                                          "pitch below taps * cin_pad or not a multiple of 8, or base / W not 16-byte aligned",
+                                          "GEGLU map: half not a multiple of 32, rows != 2 half or row0 not a multiple of 64", "more than 8 adapters",
+                                          "a null or misaligned factor, or a rank outside [1, 256]", "grid too large"};
+        if (rc) throw std::runtime_error(std::string("launch refused or failed (rc = ") + std::to_string(rc) + (rc <= -1 && rc >= -7 ? std::string("): ") + why[-rc] : ")"));
+        return 0;
+    });
+}
+
 int ladi_unet_forward_pag(ladi_unet* u, const void* sample, int dtype, int n, int h, int w, float timestep, void* out, int out_dtype,
                           int sample0, int pag_first, void* stream) {
     return guarded("ladi_unet_forward_pag", [&]() {

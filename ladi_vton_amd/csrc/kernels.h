@@ -273,6 +273,28 @@ int ladi_launch_freeu(h16* hidden, int ld_h, int C_h, float b, const h16* skip, 
 // on a refusal
 int ladi_launch_pag_identity(const h16* v, int ldv, h16* o, int ldo, long long rows, int C, hipStream_t st);
 
+// ---- lora.hip: LoRA merge of one block of rows of one packed weight, from the pristine copy `base` into the live weight `W` (both fp16
+// [rows of the weight][taps][cin_pad], row pitch `pitch` halves):
+//   W[map(o)][t][i] = fp16(float(base[map(o)][t][i]) + sum_a scale[a] * sum_r up[a][o][r] * down[a][r][t][i]),  o < rows, i < cin
+// map(o) = row0 + o, or with geglu_half = rows / 2 the GEGLU interleave of load_geglu (row0 then a multiple of 64).  up[a] fp32 [rows][rank[a]],
+// down[a] fp32 [rank[a]][taps][cin].  fp32 throughout: the inner sum over ascending r, the adapters in call order, one add, one rounding; a
+// delta of exactly zero keeps the base's bits, so n_adapters = 0 copies the block.  Columns [cin, cin_pad) and every other row keep their
+// bits.  nonfinite (optional): += the number of results that are not finite after rounding.
+// -1: null or identical base / W; -2: a size < 1, cin_pad < cin or not a multiple of 64; -3: pitch below taps * cin_pad or not a multiple of
+// 8, or a base that is not 16-byte aligned; -4: a GEGLU map whose half is no multiple of 32, rows != 2 half or row0 % 64; -5: more than
+// LORA_MAX_ADAPTERS; -6: a null factor or a rank outside [1, LORA_MAX_RANK]; -7: grid too large.  Nothing is launched on a refusal
+enum { LORA_MAX_ADAPTERS = 8, LORA_MAX_RANK = 256 };
+struct LoraMergeArgs {
+    const h16* base; h16* W; long long pitch;
+    int cin, cin_pad, taps;
+    int row0, rows, geglu_half;
+    int n_adapters;
+    const float* up[LORA_MAX_ADAPTERS]; const float* down[LORA_MAX_ADAPTERS];
+    int rank[LORA_MAX_ADAPTERS]; float scale[LORA_MAX_ADAPTERS];
+    unsigned* nonfinite;
+};
+int ladi_launch_lora_merge(const LoraMergeArgs& a, hipStream_t st);
+
 // ---- f32path.hip: fp32 kernels of the warping module (fp32 NHWC activations, fp32 weights, v_mfma_f32_32x32x2_f32)
 struct ConvF32Args {
     const float* src0; const float* src1;   // up to two NHWC fp32 sources concatenated along channels

@@ -228,8 +228,37 @@ struct FreeU {
 // blocks selected by UNet::pag_mask a perturbed sample's self-attention map is the identity (pag.hip); everything else is untouched
 enum { PAG_NONE = 0x7fffffff };
 
+// LoRA (runtime_lora.cpp; DESIGN.md "LoRA").  A target is one diffusers conv / linear module: a block of rows of one packed weight.  The
+// concatenated weights (qkv, kv2, temb_all) hold one target per member module, the GEGLU projection is one target with the interleaved
+// row map.  Adapters keep their factors on the device in fp32; set_adapters re-merges every touched block from the pristine copy of its
+// packed weight (taken the first time an adapter touches it), so weights never move and nothing drifts.
+struct LoraTarget {
+    std::string name;                       // diffusers module name, e.g. down_blocks.0.attentions.0.transformer_blocks.0.attn1.to_q
+    DConv* cv = nullptr;                    // the packed weight the block lives in
+    int row0 = 0, rows = 0, geglu_half = 0; // block of rows (kernels.h LoraMergeArgs)
+    XfBlock* xf = nullptr; int packed = 0;  // 1 / 2: the block's attn2.to_out.0 / ff.net.2, which the fused sub-blocks read re-packed
+};
+struct LoraFactor { int rank = 0; float alpha = 0.f; const float* up = nullptr; const float* down = nullptr; };
+struct LoraAdapter {
+    std::string name;
+    float* dev = nullptr;                   // one allocation: every factor of the adapter
+    std::unordered_map<int, LoraFactor> f;  // target index -> factors
+    ~LoraAdapter();
+};
+
 struct UNet {
     UNetCfg cfg;
+    std::vector<LoraTarget> lora_targets; std::unordered_map<std::string, int> lora_index;
+    std::vector<std::unique_ptr<LoraAdapter>> lora_adapters;
+    std::vector<std::pair<std::string, float>> lora_active;       // the active set, in merge order
+    std::unordered_map<const h16*, h16*> lora_base;               // live packed weight -> its pristine copy (in `pool`)
+    unsigned* lora_cnt = nullptr;                                 // device [lora_targets.size()]: non-finite results of the last merge, per target
+    void build_lora_targets();                                    // end of load(): the vectors of blocks no longer move
+    void lora_load(const std::string& name, const WeightStore& ws);
+    void lora_delete(const std::string& name);
+    // throws std::runtime_error (nothing changed, or -- non-finite results -- the previous set merged back)
+    void lora_set(const std::vector<std::pair<std::string, float>>& set, hipStream_t st);
+    long long export_weight(const std::string& key, float* host_out, long long cap);
     FreeU freeu;
     // pag_applied_layers (ladi_unet_set_pag_layers, sticky): bit i = transformer block i in execution order -- down_blocks.{0,1,2}
     // .attentions.{0..L-1}, mid_block, up_blocks.{1,2,3}.attentions.{0..L}; pag_layer_count() bits.  The default is the mid block, as in

@@ -96,6 +96,7 @@ void UNet::load(const UNetCfg& c, const WeightStore& ws) {
     norm_out = load_norm(pool, ws, "conv_norm_out");
     conv_out = load_conv(pool, ws, "conv_out");
     temb_all = load_linear_cat(pool, ws, temb_names, true);
+    build_lora_targets();
 }
 
 UNet::~UNet() {

@@ -123,6 +123,7 @@ class NativeUNet(_Base):
         self._ctx_key = None
         self._ctx_keepalive = None
         self.freeu = None             # (s1, s2, b1, b2) while FreeU is on
+        self._lora_disabled = None    # the active set disable_lora() put aside for enable_lora()
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -156,6 +157,93 @@ class NativeUNet(_Base):
     def pag_applied_layers(self):
         """the mask of selected transformer blocks, bit i = block i in execution order"""
         return int(self.lib.ladi_unet_pag_layers(self.h))
+
+    # ---- LoRA (lora.py, include/ladi_native.h "LoRA adapters"): merged onto the device weights, which keep their addresses
+    def lora_target_modules(self):
+        """the diffusers names of the modules a LoRA factor pair may be attached to: every conv and linear of this UNet"""
+        from . import lora
+        return lora.target_modules(self.cfg)
+
+    def load_lora_adapter(self, state_dict, adapter_name="default"):
+        """Load a LoRA state dict (PEFT, legacy diffusers or kohya keys: lora.normalize_state_dict) under adapter_name.  Everything is checked
+        before anything changes.  Loading does not activate: set_adapters does.  Returns the keys that belong to a text encoder (not applied)."""
+        from . import lora
+        norm = lora.normalize_state_dict(state_dict, self.lora_target_modules())
+        with _Weights(lora.to_library_keys(norm)) as w:
+            check(self.lib.ladi_unet_lora_load(self.h, str(adapter_name).encode(), w.h), "ladi_unet_lora_load")
+        return list(norm.text_encoder_keys)
+
+    def set_adapters(self, names, weights=None):
+        """diffusers' set_adapters: the active adapters, merged in this order at these weights (default 1.0 each); [] restores the plain
+        weights bit for bit.  Every touched weight is re-merged from its pristine copy (no drift), on the device.  Raises, with the previous
+        set back in place, when a merged weight leaves the fp16 range."""
+        names = [names] if isinstance(names, str) else list(names)
+        if weights is None:
+            weights = [1.0] * len(names)
+        elif isinstance(weights, (int, float)):
+            weights = [float(weights)] * len(names)
+        weights = [float(x) for x in weights]
+        if len(weights) != len(names):
+            raise ValueError("%d adapter names but %d weights" % (len(names), len(weights)))
+        n = len(names)
+        na = (ctypes.c_char_p * max(n, 1))(*[str(s).encode() for s in names])
+        wa = (c_float * max(n, 1))(*weights)
+        self._ctx_key = None           # whatever happens next, the cross-attention K/V cache no longer belongs to these weights
+        check(self.lib.ladi_unet_set_adapters(self.h, na, wa, n, stream_ptr()), "ladi_unet_set_adapters")
+        self._lora_disabled = None
+
+    def disable_lora(self):
+        """the plain weights, bit for bit; enable_lora() brings the set that was active back"""
+        saved = self.active_adapters
+        self.set_adapters([])
+        self._lora_disabled = saved
+
+    def enable_lora(self):
+        if self._lora_disabled:
+            saved = self._lora_disabled
+            self.set_adapters([s[0] for s in saved], [s[1] for s in saved])
+
+    def delete_adapters(self, names):
+        """free adapters; refused for one that is active"""
+        for s in ([names] if isinstance(names, str) else list(names)):
+            check(self.lib.ladi_unet_lora_delete(self.h, str(s).encode()), "ladi_unet_lora_delete")
+            if self._lora_disabled:
+                self._lora_disabled = [a for a in self._lora_disabled if a[0] != s] or None
+        self._ctx_key = None
+
+    @property
+    def active_adapters(self):
+        """[(name, weight), ..] in merge order"""
+        na, wa = (ctypes.c_char_p * 8)(), (c_float * 8)()
+        n = self.lib.ladi_unet_lora_active(self.h, na, wa, 8)
+        if n < 0:
+            raise NativeError("ladi_unet_lora_active failed: " + _lib.last_error())
+        return [(na[i].decode(), float(wa[i])) for i in range(n)]
+
+    def list_adapters(self):
+        """the names of the loaded adapters, in load order"""
+        n = self.lib.ladi_unet_lora_count(self.h)
+        return [self.lib.ladi_unet_lora_name(self.h, i).decode() for i in range(n)]
+
+    def export_weight(self, key):
+        """the live value of a diffusers `.weight` key of a conv / linear, in diffusers shape (float32 holding fp16 values)"""
+        n = self.lib.ladi_unet_export_weight(self.h, key.encode(), None, 0)
+        if n < 0:
+            raise NativeError("ladi_unet_export_weight(%s) failed: %s" % (key, _lib.last_error()))
+        out = torch.empty(n, dtype=torch.float32)
+        if self.lib.ladi_unet_export_weight(self.h, key.encode(), c_void_p(out.data_ptr()), n) != n:
+            raise NativeError("ladi_unet_export_weight(%s) failed: %s" % (key, _lib.last_error()))
+        from . import configs
+        return out.reshape(configs.unet_shapes(self.cfg)[key])
+
+    def export_state_dict(self, base=None):
+        """the live `.weight` of every conv and linear (the merged weights while adapters are active: a fused checkpoint).  base: a state dict
+        whose other entries (norms, biases), which LoRA never touches, are carried over so that the result is a whole checkpoint"""
+        from collections import OrderedDict
+        out = OrderedDict((k, v) for k, v in base.items()) if base is not None else OrderedDict()
+        for m in self.lora_target_modules():
+            out[m + ".weight"] = self.export_weight(m + ".weight")
+        return out
 
     def enable_xformers_memory_efficient_attention(self, *a, **k):
         return None  # attention is always fused (flash-style) in the native kernels

@@ -286,6 +286,56 @@ class StableDiffusionTryOnePipeline:
             raise ValueError("`disable_freeu` needs a UNet with disable_freeu (NativeUNet), the pipeline holds %s." % type(self.unet).__name__)
         self.unet.disable_freeu()
 
+    # ---- LoRA: the state lives in the UNet (NativeUNet.load_lora_adapter / set_adapters), these are diffusers' pipeline-level names
+    def _lora_unet(self, what):
+        if not hasattr(self.unet, "load_lora_adapter"):
+            raise ValueError("`%s` needs the native UNet (NativeUNet), the pipeline holds %s." % (what, type(self.unet).__name__))
+        return self.unet
+
+    def load_lora_weights(self, state_dict_or_path, adapter_name="default"):
+        """diffusers' pipe.load_lora_weights: a LoRA state dict (PEFT, legacy diffusers or kohya keys) or a path to one (.safetensors where
+        that module is installed, else a torch.save file).  The adapter is loaded and, as in diffusers, activated at weight 1.0 together
+        with what was already active (after disable_lora(): together with the set that was put aside, which is enabled again).
+        Text-encoder keys are not applied."""
+        unet = self._lora_unet("load_lora_weights")
+        sd = state_dict_or_path
+        if not hasattr(sd, "items"):
+            from . import lora
+            sd = lora.load_file(sd)
+        unet.load_lora_adapter(sd, adapter_name)
+        # after disable_lora() the set that was put aside counts as "already active": loading re-enables it together with the new adapter
+        # (set_adapters forgets the put-aside set, so it must not be lost here)
+        active = unet.active_adapters or list(getattr(unet, "_lora_disabled", None) or [])
+        try:
+            unet.set_adapters([a[0] for a in active] + [adapter_name], [a[1] for a in active] + [1.0])
+        except Exception:
+            unet.delete_adapters(adapter_name)
+            raise
+
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        self._lora_unet("set_adapters").set_adapters(adapter_names, adapter_weights)
+
+    def disable_lora(self):
+        self._lora_unet("disable_lora").disable_lora()
+
+    def enable_lora(self):
+        self._lora_unet("enable_lora").enable_lora()
+
+    def delete_adapters(self, adapter_names):
+        self._lora_unet("delete_adapters").delete_adapters(adapter_names)
+
+    def unload_lora_weights(self):
+        """the plain weights back, every adapter freed"""
+        unet = self._lora_unet("unload_lora_weights")
+        unet.set_adapters([])
+        unet.delete_adapters(unet.list_adapters())
+
+    def get_active_adapters(self):
+        return [a[0] for a in self._lora_unet("get_active_adapters").active_adapters]
+
+    def get_list_adapters(self):
+        return {"unet": self._lora_unet("get_list_adapters").list_adapters()}
+
     @property
     def shallow_evals(self):
         """how many evaluations of the last run ran shallow (`feature_cache=`), after promotion (fused: ladi_tryon_shallow_evals)"""
