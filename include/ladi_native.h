@@ -358,6 +358,14 @@ int ladi_tryon_cond_only_evals(ladi_tryon* t);
 int ladi_tryon_set_feature_cache(ladi_tryon* t, const unsigned char* full_flags_host, int count, int branch);
 /* how many evaluations of the last run ran shallow, after promotion */
 int ladi_tryon_shallow_evals(ladi_tryon* t);
+/* the per-evaluation plan ladi_tryon_run makes of a run with `evals` evaluations from the scalar guidance_scale and what
+ * ladi_tryon_set_guidance_schedule, _set_guidance_rescale, _set_pag and _set_feature_cache were given (a NULL table or a count of 0: not set).
+ * Host arithmetic only: needs no handle and never touches the GPU.  forms_out[i] (evals bytes) is the form of evaluation i: bit 0 cond-only,
+ * bit 1 shallow (after the promotion), bit 2 PAG.  Returns evals, or what the run would be refused with (-9, -10,
+ * LADI_TRYON_PAG_WITH_FEATURE_CACHE) with the run's message in ladi_last_error; first_step / steps only word that message. */
+int ladi_tryon_plan_forms(int evals, int first_step, int steps, float guidance_scale, const float* guidance_tab_host, int guidance_count,
+                          float phi, const float* pag_tab_host, int pag_count, const unsigned char* full_flags_host, int flag_count,
+                          unsigned char* forms_out);
 /* keep the unmasked region for the following runs (sticky per handle; (0, 0) = off, the state of a new handle: nothing is launched for it and
  * every result stays bit for bit).  mode_bits: bit 0 latents, bit 1 pixels.
  * Latents: diffusers' 4-channel inpaint rule.  After the scheduler update of evaluation i every KEEP latent pixel is replaced by

@@ -172,6 +172,8 @@ SIGNATURES = {
     "ladi_tryon_set_preserve": (c_int, [_P, c_int, c_float]),
     "ladi_sched_keep_coeffs": (c_int, [c_int, c_int, _P, c_int, POINTER(c_float), c_int]),
     "ladi_tryon_shallow_evals": (c_int, [_P]),
+    "ladi_tryon_plan_forms": (c_int, [c_int, c_int, c_int, c_float, POINTER(c_float), c_int, c_float, POINTER(c_float), c_int,
+                                      POINTER(ctypes.c_ubyte), c_int, POINTER(ctypes.c_ubyte)]),
     "ladi_tryon_set_step_callback": (c_int, [_P, STEP_CALLBACK, _P, c_int, _P]),
     "ladi_tryon_set_lanes": (c_int, [_P, c_int]),
     "ladi_tryon_lanes": (c_int, [_P]),

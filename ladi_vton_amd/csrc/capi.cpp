@@ -382,10 +382,9 @@ int ladi_unet_time_forward_lanes(ladi_unet* u, int n, int h, int w, int iters, i
         hipStream_t user = S(stream), st = nullptr;
         HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));      // the NULL stream cannot be captured
         hipEvent_t e0 = nullptr, e1 = nullptr, ein = nullptr;
-        hipGraph_t graph = nullptr; hipGraphExec_t gexec = nullptr;
+        GraphTable graphs;      // slot 0: the one forward
         auto cleanup = [&]() {
-            if (gexec) (void)hipGraphExecDestroy(gexec);
-            if (graph) (void)hipGraphDestroy(graph);
+            graphs.clear();
             if (e0) (void)hipEventDestroy(e0);
             if (e1) (void)hipEventDestroy(e1);
             if (ein) (void)hipEventDestroy(ein);
@@ -408,16 +407,12 @@ int ladi_unet_time_forward_lanes(ladi_unet* u, int n, int h, int w, int iters, i
             HIP_OK(hipMemsetAsync(x.p, 0, x.pixels() * 64 * sizeof(h16), st));
             LN.forward(U, st, false, false, x, eps, U.temb_table, nullptr);      // warm-up, lanes in sequence (tile measurement)
             if (use_graph) {
-                HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-                try { LN.forward(U, st, false, true, x, eps, U.temb_table, nullptr); }
-                catch (...) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(st, &g); if (g) (void)hipGraphDestroy(g); throw; }
-                HIP_OK(hipStreamEndCapture(st, &graph));
-                HIP_OK(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
-                HIP_OK(hipGraphLaunch(gexec, st));                              // one untimed replay
+                graphs.capture(0, st, [&]() { LN.forward(U, st, false, true, x, eps, U.temb_table, nullptr); });
+                HIP_OK(hipGraphLaunch(graphs.e[0], st));                        // one untimed replay
             } else LN.forward(U, st, false, true, x, eps, U.temb_table, nullptr);
             HIP_OK(hipEventRecord(e0, st));
             for (int i = 0; i < iters; ++i) {
-                if (use_graph) HIP_OK(hipGraphLaunch(gexec, st));
+                if (use_graph) HIP_OK(hipGraphLaunch(graphs.e[0], st));
                 else LN.forward(U, st, false, true, x, eps, U.temb_table, nullptr);
             }
             HIP_OK(hipEventRecord(e1, st));
@@ -880,6 +875,22 @@ int ladi_tryon_set_guidance_rescale(ladi_tryon* t, float phi) {
     return 0;
 }
 int ladi_tryon_cond_only_evals(ladi_tryon* t) { return t ? t->t.last_cond_only : -1; }
+int ladi_tryon_plan_forms(int evals, int first_step, int steps, float guidance, const float* guidance_tab_host, int guidance_count, float phi,
+                          const float* pag_tab_host, int pag_count, const unsigned char* full_flags_host, int flag_count, unsigned char* forms_out) {
+    if (evals < 1 || guidance_count < 0 || pag_count < 0 || flag_count < 0 || !forms_out) {
+        set_error("ladi_tryon_plan_forms: evals < 1, a negative count or no output");
+        return -1;
+    }
+    return guarded("ladi_tryon_plan_forms", [&]() {
+        EvalPlan p;
+        const std::vector<float> g(guidance_tab_host, guidance_tab_host + (guidance_tab_host ? guidance_count : 0));
+        const std::vector<float> pag(pag_tab_host, pag_tab_host + (pag_tab_host ? pag_count : 0));
+        const std::vector<unsigned char> fc(full_flags_host, full_flags_host + (full_flags_host ? flag_count : 0));
+        if (plan_evals(p, evals, first_step, steps, guidance, g, phi, pag, fc)) { set_error(p.error); return p.rc; }
+        std::memcpy(forms_out, p.form.data(), (size_t)evals);
+        return evals;
+    });
+}
 int ladi_tryon_set_feature_cache(ladi_tryon* t, const unsigned char* full_flags_host, int count, int branch) {
     if (!t || count < 0) { set_error("ladi_tryon_set_feature_cache: null handle or negative count"); return -1; }
     if (!full_flags_host || count == 0) { t->t.fc_plan.clear(); t->t.fc_branch = 0; return 0; }

@@ -5,6 +5,8 @@
 #include "kernels.h"
 #include <string>
 #include <vector>
+#include <functional>
+#include <cstring>
 #include <unordered_map>
 #include <memory>
 #include <stdexcept>
@@ -329,7 +331,9 @@ struct UNetLanes {
                  int sample0 = 0, const FeatCache* fc = nullptr, int pag_first = PAG_NONE);
     int sub_lanes(int n_sub) const { int g = G; while (g > 1 && (n_sub % g)) --g; return g; }   // the default rule: lowered until it divides
     void commit_plan();                     // after the dry pass: (re)allocate what grew; not capturable
-    unsigned long long key() const;         // part of the hipGraph key: lane count and every address a captured lane may touch
+    // part of the hipGraph key (GraphKey): lane count and every address a captured lane may touch, zero beyond G
+    struct Key { int G; const void* arena[MAXG]; const void* stats[MAXG]; };
+    void key(Key& k) const;
     ~UNetLanes();
 };
 
@@ -518,13 +522,71 @@ struct TryOnInputs {
 };
 enum { TRYON_PAG_WITH_CACHE = -12 };  // TryOn::run: a PAG table with a positive entry together with a feature-cache plan (LADI_TRYON_PAG_WITH_FEATURE_CACHE)
 enum { TRYON_CALLBACK_ABORT = -8 };   // TryOn::run: the step callback returned non-zero (LADI_TRYON_CALLBACK_ABORTED, include/ladi_native.h)
+// The forms of one evaluation of the fused loop: bit 0 cond-only, bit 1 shallow (feature cache), bit 2 PAG (never together with bit 1), so
+// 0 .. 5.  The form is the index of GraphTable and of EvalPlan::has_form.
+
+// The captured graphs of one owner, one slot per form
+struct GraphTable {
+    static constexpr int N = 6;
+    hipGraph_t g[N] = {}; hipGraphExec_t e[N] = {};
+    void clear();            // destroy every graph and executable (the owner's destructor; a changed GraphKey)
+    // capture fn's launches on st into slot f and instantiate them; a throw of fn ends the capture and is passed on.  A graph left in the slot
+    // by a capture whose instantiation failed is destroyed first
+    void capture(int f, hipStream_t st, const std::function<void()>& fn);
+};
+// What the captured graphs of a TryOn were captured with.  The rule: a value that a captured launch carries as an argument, or a pointer it
+// dereferences, is a field here.  Zeroed with memset before it is filled (so padding compares equal) and compared with memcmp: another key
+// drops every graph.  A field that means something only with a feature on is zero when it is off
+struct GraphKey {
+    const void* arena;                          // base of the run's activation arena: every transient address
+    int B, H, W, cfg, L, pose_ch, has_cloth;    // the shapes of every launch
+    unsigned guidance;                          // bits of the scalar guidance, when !guided (with a table the scalar is ignored: zero)
+    const void *temb_table, *kv_cache, *d_table, *stats;
+    const void *trace_eps, *trace_lat; int trace_cap;
+    const void* step_noise;
+    UNetLanes::Key lanes;
+    // a graph captured without the probe launches is never replayed with it, nor one that holds another probe's slots: the id is unique per
+    // Probe (0 = none), and within one Probe a name keeps its slot
+    unsigned long long probe;
+    // every form lives under one key, with the guidance table, the factor buffer and phi (its bits, when guided)
+    const void *guidance_tab, *factor; int guided; unsigned phi;
+    // ... and with the feature cache: its buffer, the branch and whether whole evaluations capture (a graph captured with capture on is never
+    // replayed for a plain run, nor the reverse); buffer and branch when fc_on
+    const void* fcache; int fc_on, fc_branch;
+    // ... and with the latent blend: its buffers, the coefficient table and the mode (when the latents bit is set)
+    const void *keep_x0, *keep_noise, *keep_mask, *keep_tab; int preserve_mode;
+    // ... and with FreeU: on / off and, when on, the bits of the four factors the captured launches carry as arguments
+    int freeu_on; unsigned freeu[4];
+    // ... and with PAG: whether the run has the third group, the scale table and the selected blocks (when pag_on); a graph captured with PAG
+    // is never replayed without it, nor the reverse
+    int pag_on; unsigned pag_mask; const void* pag_tab;
+};
+// The per-evaluation plan of one run: host arithmetic only (plan_evals; ladi_tryon_plan_forms runs it without a GPU)
+struct EvalPlan {
+    bool cfg = false;          // CFG-shaped: ANY evaluation's scale is > 1 (a set schedule replaces the scalar)
+    bool guided = false;       // the scales come from a device table (a schedule, or the scalar repeated for the rescale statistics)
+    bool use_factor = false;   // guided with phi > 0: the rescale statistics run
+    bool pag_on = false;       // PAG-shaped (a third sample group): ANY PAG scale is > 0
+    bool fc_on = false;        // some evaluation runs shallow, after promotion; else the plain run: capture stays off
+    int ng = 1, groups = 1;    // sample groups of a plain evaluation ([uncond ; cond] or [cond]); of the run: ng + pag_on
+    std::vector<float> gtab;   // scale of every evaluation
+    std::vector<unsigned char> form;   // form of every evaluation, after the feature cache's one promotion
+    bool has_form[GraphTable::N] = {};
+    int rc = 0; std::string error;     // a refusal: -9 (guidance / PAG table length), -10 (feature-cache plan), TRYON_PAG_WITH_CACHE
+};
+// first_step / steps: for the message of a length refusal only.  Returns p.rc
+int plan_evals(EvalPlan& p, int evals, int first_step, int steps, float guidance, const std::vector<float>& g_sched, float phi,
+               const std::vector<float>& pag_sched, const std::vector<unsigned char>& fc_plan);
+
 struct TryOn {
     UNet* unet = nullptr; VAE* vae = nullptr; EMASC* emasc = nullptr;
     Arena arena; float* stats = nullptr; size_t stats_cap = 0;
     DevPool pool;  // small persistent things
     StepTable* d_table = nullptr; int table_cap = 0; int* d_step = nullptr;
     int* sk_cnt = nullptr;   // split-K arrival counters of this handle's stream (Ctx::sk_cnt)
-    hipGraph_t graph = nullptr; hipGraphExec_t gexec = nullptr; unsigned long long graph_key = 0;
+    // the captured evaluation of every form, and what they were captured with (all bytes zero, padding included, until the first capture)
+    GraphTable graphs; GraphKey graph_key;
+    TryOn() { std::memset(&graph_key, 0, sizeof(graph_key)); }
     UNetLanes lanes; int lanes_override = 0;   // sample-group lanes of the denoising loop (0 = LADI_UNET_LANES / default)
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool ev_valid = false;
     int last_evals = 0;
@@ -540,27 +602,22 @@ struct TryOn {
     const float* init_src = nullptr; int init_hs = 0, init_ws = 0, init_first = 0, init_noisy = 0;
     // per-evaluation guidance (ladi_tryon_set_guidance_schedule, sticky; empty = in.guidance for every evaluation) and guidance rescale phi
     // (ladi_tryon_set_guidance_rescale).  A run is CFG-shaped (2B rows, both contexts) if any scale is > 1; inside such a run an evaluation
-    // whose scale is <= 1 runs the UNet over the conditional samples [B, 2B) only.  With a schedule or phi > 0 the scales come from the
-    // device table d_gtab, so the two captured graphs (full evaluation: gexec; cond-only evaluation: gexec_cond) serve every value
+    // whose scale is <= 1 runs the UNet over the conditional samples [B, 2B) only (form bit 0).  With a schedule or phi > 0 the scales come
+    // from the device table d_gtab, so the graphs of the full and of the cond-only form serve every value
     std::vector<float> g_sched; float phi = 0.f;
     float* d_gtab = nullptr; int gtab_cap = 0; float* d_factor = nullptr; int factor_cap = 0;
-    hipGraph_t graph_cond = nullptr; hipGraphExec_t gexec_cond = nullptr;
     int last_cond_only = 0;   // evaluations of the last run that ran cond-only (ladi_tryon_cond_only_evals)
     // deep-feature cache (ladi_tryon_set_feature_cache, sticky; empty plan = off): fc_plan holds one flag per evaluation, 1 = whole forward
-    // (which captures into fcache), 0 = shallow forward from fcache at fc_branch.  The loop then has up to four evaluation forms,
-    // {whole, shallow} x {2B samples, cond-only}: graph / gexec, graph_cond / gexec_cond and the two below, all under graph_key.  fcache is
-    // persistent (outside the per-evaluation arena region) and grow-only: fp16 [n][h][w][fc_channels]
+    // (which captures into fcache), 0 = shallow forward from fcache at fc_branch (form bit 1).  fcache is persistent (outside the
+    // per-evaluation arena region) and grow-only: fp16 [n][h][w][fc_channels]
     std::vector<unsigned char> fc_plan; int fc_branch = 0;
     h16* fcache = nullptr; size_t fcache_cap = 0;
-    hipGraph_t graph_sh[2] = {nullptr, nullptr}; hipGraphExec_t gexec_sh[2] = {nullptr, nullptr};   // shallow forms: [0] 2B samples, [1] cond-only
     // perturbed-attention guidance (ladi_tryon_set_pag, sticky; empty = off: nothing below is allocated or launched): one scale per
     // evaluation.  With any scale > 0 the run is PAG-shaped: unet_in, eps and the context grow by a third group of B samples behind the
     // cond group ([uncond ; cond ; perturbed], or [cond ; perturbed] without CFG), the scales go to the device table d_pag, and an evaluation
-    // with a scale > 0 runs the forward over the perturbed group too (form bit 2; never together with the feature cache, which run() refuses):
-    // graph_pag [0] all groups, [1] cond + perturbed (a cond-only evaluation of a guided run), under graph_key like the others
+    // with a scale > 0 runs the forward over the perturbed group too (form bit 2; never together with the feature cache, which run() refuses)
     std::vector<float> pag_sched;
     float* d_pag = nullptr; int pag_cap = 0;
-    hipGraph_t graph_pag[2] = {nullptr, nullptr}; hipGraphExec_t gexec_pag[2] = {nullptr, nullptr};
     int last_shallow = 0;     // evaluations of the last run that ran shallow, after promotion (ladi_tryon_shallow_evals)
     // preserve-unmasked (ladi_tryon_set_preserve, sticky; 0 = off: nothing below is allocated or launched).  Bit 0, latents: after every
     // scheduler update the keep pixels (1 - maxpool8x8 of the binarised mask) become k_x z0 + k_n noise at the next timestep, z0 = scaling *
@@ -579,6 +636,15 @@ struct TryOn {
     int stage_ms(float out[3]);
     // images_out: fp32 [B,H,W,3] in [0,1], or (images_u8) uint8 = round(image * 255)
     int run(const TryOnInputs& in, void* images_out, int images_u8, float* latents_out, hipStream_t st);
+    // the stages of run(), in its order, over the state of one run (runtime_tryon.cpp).  The int ones return a refusal code or 0
+    struct Run;
+    int enter(Run& r);              // stream fence, overflow poll
+    int plan(Run& r);               // geometry, scheduler tables (host), evaluation plan
+    int grow_tables(Run& r);        // grow-only device tables, step-noise buffer, events; last of all the feature cache
+    void upload_tables(Run& r);     // real pass: probes from zero, the tables' uploads, time embeddings (r.rc = -5)
+    void encode(Run& r);            // persistent buffers, preprocessing and VAE encodes, static UNet input (r.rc = -6)
+    void denoise(Run& r);           // the loop: eager, or graph replay by form; the callback point (r.cb_rc)
+    void decode(Run& r);            // VAE decode, composite, outputs
     ~TryOn();
 };
 

@@ -467,13 +467,12 @@ void UNetLanes::commit_plan() {
     }
 }
 
-unsigned long long UNetLanes::key() const {
-    unsigned long long h = 0x9e3779b97f4a7c15ULL * (unsigned long long)G;
-    for (int g = 0; g < G; ++g) {
-        h ^= (unsigned long long)(uintptr_t)arena[g].base + (h << 6) + (h >> 2);
-        h ^= (unsigned long long)(uintptr_t)stats[g] + (h << 6) + (h >> 2);
+void UNetLanes::key(Key& k) const {
+    k.G = G;
+    for (int g = 0; g < MAXG; ++g) {
+        k.arena[g] = g < G ? arena[g].base : nullptr;
+        k.stats[g] = g < G ? stats[g] : nullptr;
     }
-    return h;
 }
 
 UNetLanes::~UNetLanes() {
