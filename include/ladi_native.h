@@ -467,6 +467,50 @@ int ladi_unet_lora_count(const ladi_unet* u);
 const char* ladi_unet_lora_name(const ladi_unet* u, int i);
 int ladi_unet_lora_active(const ladi_unet* u, const char** names_out, float* weights_out, int cap);
 long long ladi_unet_export_weight(ladi_unet* u, const char* key, float* host_out, long long cap);
+/* ---- IP-Adapter image prompt (DESIGN.md "IP-Adapter"; diffusers load_ip_adapter / set_ip_adapter_scale / ip_adapter_image_embeds).  With an
+ * image context set, attn2 of every transformer block computes
+ *   to_out(softmax(q k_text^T / 8) v_text + s_block * softmax(q k_ip^T / 8) v_ip),  k_ip | v_ip = (to_k_ip | to_v_ip)(tokens)
+ * with tokens = LayerNorm(Linear(image_embeds)).reshape(n, N, cross_dim).  The image K/V are hoisted out of the denoising loop like the
+ * text K/V; the per-evaluation work is one launch per block (csrc/ip_adapter.hip) between the attention and to_out.
+ * ladi_unet_ip_adapter_load: `ws` holds image_proj.proj.weight [N * cross_dim, E], image_proj.proj.bias, image_proj.norm.weight / .bias and,
+ * for every transformer block, <block>.transformer_blocks.0.attn2.processor.to_k_ip.weight and ...to_v_ip.weight ([C, cross_dim], no bias),
+ * <block> = down_blocks.i.attentions.j, mid_block.attentions.0, up_blocks.i.attentions.j.  N comes from the projection's rows, E from its
+ * columns.  Everything is checked first -- every block present, the shapes, N in [1, 64], E % 8, no other key -- and on an error nothing has
+ * changed.  One adapter per UNet: a second load is refused until ladi_unet_ip_adapter_unload (which waits for the device and drops the
+ * weights, the scales and the image context).  Loading activates nothing.  The weights are fp16 on the device: about 51 MB of to_k_ip /
+ * to_v_ip at the released architecture, 8 MB of projection at N = 4; the image K/V are n * N rows of 2C halves per block, 3.2 MB for n = 16, N = 4.
+ * ladi_unet_ip_adapter_info: 1 with a loaded adapter (its N and E written), 0 without.
+ * ladi_unet_set_ip_scale: `count` == ladi_unet_pag_layer_count(u) floats, one per block in the execution order PAG's mask uses.  Sticky; a
+ * new adapter starts with every scale 1.0.  A block with scale 0 launches nothing for the image term.  A wrong count, a non-finite value or
+ * no loaded adapter returns -1 and changes nothing.  ladi_unet_ip_scale: the current scales (returns the block count).
+ * ladi_unet_set_ip_context: embeds_dev fp16 [n][E] -> the projection, the per-token LayerNorm (eps 1e-5) and one GEMM per block into that
+ * block's image K/V [n][N][2C], asynchronous on `stream`.  ladi_unet_set_ip_tokens: finished tokens fp16 [n][N][cross_dim] instead (adapter
+ * variants with another projection network); its N, 1 .. 64, may differ from the loaded projection's.  ladi_unet_clear_ip_context: no image
+ * context; the forward is then the plain one, launch for launch.
+ * A forward reads the image K/V rows of its own samples (sample0), as it reads the text K/V; an image context whose n is not the text
+ * context's fails with a "batch mismatch" error.  Under LADI_XF_FUSE a block with an image term takes the un-fused chain.  Shallow forwards
+ * of the feature cache skip the blocks they skip; PAG perturbs attn1 only.  ladi_unet_set_adapters (LoRA) leaves the image K/V alone: LoRA
+ * has no to_k_ip / to_v_ip target. */
+int ladi_unet_ip_adapter_load(ladi_unet* u, const ladi_weights* ws);
+int ladi_unet_ip_adapter_unload(ladi_unet* u);
+int ladi_unet_ip_adapter_info(const ladi_unet* u, int* tokens, int* embed_dim);
+int ladi_unet_set_ip_scale(ladi_unet* u, const float* scales, int count);
+int ladi_unet_ip_scale(ladi_unet* u, float* scales_out, int cap);
+int ladi_unet_set_ip_context(ladi_unet* u, const void* embeds_dev, int n, void* stream);
+int ladi_unet_set_ip_tokens(ladi_unet* u, const void* tokens_dev, int n, int N, void* stream);
+int ladi_unet_clear_ip_context(ladi_unet* u);
+/* measurement switch (tools/bench_ip_adapter.py): route 0 (default, shipped) computes the image term with csrc/ip_adapter.hip, route 1 with
+ * the kernels that existed before it -- the flash attention over the N image keys into a scratch tensor, then a scaled add (two roundings
+ * instead of one).  Sticky; -1 for another value. */
+int ladi_unet_set_ip_route(ladi_unet* u, int route);
+/* Image embeddings of the following runs (sticky per handle; the pointers are read by every run, on its stream): fp16 [B][E] each, E the
+ * loaded adapter's.  negative_embeds_dev NULL means zeros (diffusers' zeros_like; the projection still runs on them, so the unconditional
+ * tokens are LayerNorm(bias)).  embeds_dev NULL switches the image prompt off: the run clears the UNet's image context.  A run assembles
+ * [neg ; pos] (CFG-shaped), [neg ; pos ; pos] (with PAG) or [pos] into a buffer of its own and sets the UNet's image context right after the
+ * text context.  A run on a UNet without a loaded adapter fails with LADI_TRYON_IP_NO_ADAPTER before anything is launched; a run with every
+ * scale 0 is the plain run bit for bit.  The captured graphs are keyed on the image term: on / off, N, the image K/V and every scale. */
+#define LADI_TRYON_IP_NO_ADAPTER (-13)
+int ladi_tryon_set_ip_adapter(ladi_tryon* t, const void* embeds_dev, const void* negative_embeds_dev);
 /* PAG scales of the following runs (sticky per handle; copied): scales_host[i] = s_i of evaluation i.  NULL or count 0 switches it off; a
  * table of zeros is the plain run bit for bit (nothing is allocated or launched for it).  With any s_i > 0 the run has the third sample group
  * ([uncond ; cond ; perturbed], or [cond ; perturbed] without CFG; context [neg ; pe ; pe]) and the guided prediction of an evaluation with
@@ -691,6 +735,14 @@ int ladi_op_assemble_input(void* unet_in_dev, int ld, int B, int hw, int cfg, co
  * head h at column h * d of every row, any d <= 128 (d > 128: -1), out [n][ldo] */
 int ladi_op_attention_single_query(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int n, int heads,
                                    int d, int Nk, long long sk, long long sv, float scale, void* stream);
+/* the image-prompt term of a cross-attention on its own (csrc/ip_adapter.hip), in place on o:
+ *   o[s][t][h*64 + d] = fp16(float(o[s][t][h*64 + d]) + scale * sum_j softmax_j(0.125 <q[s][t][h], k[s][j][h]>) v[s][j][h*64 + d]),  j < N
+ * fp32 with the row maximum subtracted, one rounding per element; head dimension 64.  Row strides ldq / ldk / ldv / ldo and per-sample
+ * strides sq / sk / sv / so in elements (the kv_cache layout: k = kv, v = kv + C, ldk = ldv = 2C, sk = sv = N * 2C).  Rows t >= T and columns
+ * >= heads * 64 are never touched.  -1 with a message, nothing launched: N outside [1, 64], n / heads / T < 1, a null pointer, a row stride
+ * that is not a multiple of 8 or below heads * 64, a per-sample stride that is not a multiple of 8, a base that is not 16-byte aligned */
+int ladi_op_ip_attn_add(const void* q, int ldq, long long sq, const void* k, int ldk, long long sk, const void* v, int ldv, long long sv, void* o,
+                        int ldo, long long so, int n, int heads, int T, int N, float scale, void* stream);
 /* fp32 path of the warping module (TPS network and refinement UNet called with fp32 tensors): NHWC fp32 activations, fp32 weights
  * [Q][ksize * ksize * (C0 + C1)] tap-major / channel-minor (row stride ldw, 0 = K), out = act(conv + bias) (act: 0 none, 1 SiLU, 4 ReLU, 5 tanh).
  * batch > 1 runs `batch` problems bs_src0 / bs_w / bs_out elements apart (the correlation: the weight operand is a feature map).

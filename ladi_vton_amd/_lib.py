@@ -124,6 +124,18 @@ SIGNATURES = {
     "ladi_unet_lora_name": (c_char_p, [_P, c_int]),
     "ladi_unet_lora_active": (c_int, [_P, POINTER(c_char_p), POINTER(c_float), c_int]),
     "ladi_unet_export_weight": (c_longlong, [_P, c_char_p, _P, c_longlong]),
+    "ladi_unet_ip_adapter_load": (c_int, [_P, _P]),
+    "ladi_unet_ip_adapter_unload": (c_int, [_P]),
+    "ladi_unet_ip_adapter_info": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
+    "ladi_unet_set_ip_scale": (c_int, [_P, POINTER(c_float), c_int]),
+    "ladi_unet_ip_scale": (c_int, [_P, POINTER(c_float), c_int]),
+    "ladi_unet_set_ip_context": (c_int, [_P, _P, c_int, _P]),
+    "ladi_unet_set_ip_tokens": (c_int, [_P, _P, c_int, c_int, _P]),
+    "ladi_unet_clear_ip_context": (c_int, [_P]),
+    "ladi_unet_set_ip_route": (c_int, [_P, c_int]),
+    "ladi_tryon_set_ip_adapter": (c_int, [_P, _P, _P]),
+    "ladi_op_ip_attn_add": (c_int, [_P, c_int, c_longlong, _P, c_int, c_longlong, _P, c_int, c_longlong, _P, c_int, c_longlong, c_int, c_int,
+                                    c_int, c_int, c_float, _P]),
     "ladi_vae_create": (_P, [POINTER(VAEConfig), _P]),
     "ladi_vae_destroy": (None, [_P]),
     "ladi_vae_encode": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, POINTER(_P), _P]),

@@ -33,6 +33,7 @@ static void set_module_probe(Probe*& slot, ladi_probe* p) {
     if (slot) ++g_probe_refs[slot];
 }
 static_assert(TRYON_CALLBACK_ABORT == LADI_TRYON_CALLBACK_ABORTED, "callback abort code");
+static_assert(TRYON_IP_NO_ADAPTER == LADI_TRYON_IP_NO_ADAPTER, "IP-Adapter refusal code");
 
 static_assert(sizeof(ladi_igemm_desc) == sizeof(IGemmArgs), "public igemm descriptor must mirror IGemmArgs");
 static_assert(sizeof(ladi_conv_f32_desc) == sizeof(ConvF32Args), "public fp32 convolution descriptor must mirror ConvF32Args");
@@ -225,6 +226,73 @@ int ladi_op_lora_merge(const void* base, void* W, long long pitch, int cin, int 
         if (rc) throw std::runtime_error(std::string("launch refused or failed (rc = ") + std::to_string(rc) + (rc <= -1 && rc >= -7 ? std::string("): ") + why[-rc] : ")"));
         return 0;
     });
+}
+
+// ------------------------------------------------------------------------------------------------ IP-Adapter (runtime_unet.cpp)
+int ladi_unet_ip_adapter_load(ladi_unet* u, const ladi_weights* ws) {
+    return guarded("ladi_unet_ip_adapter_load", [&]() {
+        if (!u || !ws) throw std::runtime_error("null handle or weights");
+        u->u.ip_load(ws->ws);
+        return 0;
+    });
+}
+int ladi_unet_ip_adapter_unload(ladi_unet* u) {
+    return guarded("ladi_unet_ip_adapter_unload", [&]() {
+        if (!u) throw std::runtime_error("null handle");
+        HIP_OK(hipDeviceSynchronize());          // a forward still in flight may read the weights and the image K/V
+        u->u.ip_unload();
+        return 0;
+    });
+}
+int ladi_unet_ip_adapter_info(const ladi_unet* u, int* tokens, int* embed_dim) {
+    if (!u) { set_error("ladi_unet_ip_adapter_info: null handle"); return -1; }
+    if (tokens) *tokens = u->u.ip_N;
+    if (embed_dim) *embed_dim = u->u.ip_E;
+    return u->u.ip_loaded ? 1 : 0;
+}
+int ladi_unet_set_ip_scale(ladi_unet* u, const float* scales, int count) {
+    if (!u) { set_error("ladi_unet_set_ip_scale: null handle"); return -1; }
+    try { u->u.ip_set_scale(scales, count); }
+    catch (const std::exception& e) { set_error(std::string("ladi_unet_set_ip_scale: ") + e.what()); return -1; }
+    return 0;
+}
+int ladi_unet_ip_scale(ladi_unet* u, float* scales_out, int cap) {
+    if (!u || cap < 0 || (cap > 0 && !scales_out)) { set_error("ladi_unet_ip_scale: null handle, cap < 0 or null output"); return -1; }
+    auto blocks = u->u.xf_blocks();
+    for (int i = 0; i < (int)blocks.size() && i < cap; ++i) scales_out[i] = blocks[i].first->ip_scale;
+    return (int)blocks.size();
+}
+int ladi_unet_set_ip_context(ladi_unet* u, const void* embeds, int n, void* stream) {
+    return guarded("ladi_unet_set_ip_context", [&]() {
+        if (!u) throw std::runtime_error("null handle");
+        return u->u.set_ip_context(reinterpret_cast<const h16*>(embeds), n, S(stream));
+    });
+}
+int ladi_unet_set_ip_tokens(ladi_unet* u, const void* tokens, int n, int N, void* stream) {
+    return guarded("ladi_unet_set_ip_tokens", [&]() {
+        if (!u) throw std::runtime_error("null handle");
+        return u->u.set_ip_tokens(reinterpret_cast<const h16*>(tokens), n, N, S(stream));
+    });
+}
+int ladi_unet_clear_ip_context(ladi_unet* u) {
+    if (!u) { set_error("ladi_unet_clear_ip_context: null handle"); return -1; }
+    u->u.clear_ip_context();
+    return 0;
+}
+int ladi_unet_set_ip_route(ladi_unet* u, int route) {
+    if (!u || route < 0 || route > 1) { set_error("ladi_unet_set_ip_route: null handle or a route other than 0 / 1"); return -1; }
+    u->u.ip_route = route;
+    return 0;
+}
+int ladi_op_ip_attn_add(const void* q, int ldq, long long sq, const void* k, int ldk, long long sk, const void* v, int ldv, long long sv, void* o,
+                        int ldo, long long so, int n, int heads, int T, int N, float scale, void* stream) {
+    const int rc = ladi_launch_ip_attn_add(reinterpret_cast<const h16*>(q), ldq, sq, reinterpret_cast<const h16*>(k), ldk, sk,
+                                           reinterpret_cast<const h16*>(v), ldv, sv, reinterpret_cast<h16*>(o), ldo, so, n, heads, T, N, scale, S(stream));
+    if (rc == -1)
+        set_error("ladi_op_ip_attn_add: refused: a null pointer, n / heads / T < 1, N = " + std::to_string(N) + " outside [1, 64], a row stride that is "
+                  "not a multiple of 8 or below heads * 64, a per-sample stride that is not a multiple of 8, or a base that is not 16-byte aligned");
+    else if (rc) set_error("ladi_op_ip_attn_add: launch failed rc=" + std::to_string(rc));
+    return rc;
 }
 
 int ladi_unet_forward_pag(ladi_unet* u, const void* sample, int dtype, int n, int h, int w, float timestep, void* out, int out_dtype,
@@ -858,6 +926,12 @@ int ladi_tryon_set_guidance_schedule(ladi_tryon* t, const float* scales_host, in
             return -1;
         }
     return guarded("ladi_tryon_set_guidance_schedule", [&]() { t->t.g_sched.assign(scales_host, scales_host + count); return 0; });
+}
+int ladi_tryon_set_ip_adapter(ladi_tryon* t, const void* embeds, const void* negative_embeds) {
+    if (!t) { set_error("ladi_tryon_set_ip_adapter: null handle"); return -1; }
+    t->t.ip_pos = reinterpret_cast<const h16*>(embeds);
+    t->t.ip_neg = embeds ? reinterpret_cast<const h16*>(negative_embeds) : nullptr;
+    return 0;
 }
 int ladi_tryon_set_pag(ladi_tryon* t, const float* scales_host, int count) {
     if (!t || count < 0) { set_error("ladi_tryon_set_pag: null handle or negative count"); return -1; }

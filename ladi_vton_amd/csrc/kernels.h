@@ -273,6 +273,19 @@ int ladi_launch_freeu(h16* hidden, int ld_h, int C_h, float b, const h16* skip, 
 // on a refusal
 int ladi_launch_pag_identity(const h16* v, int ldv, h16* o, int ldo, long long rows, int C, hipStream_t st);
 
+// ---- ip_adapter.hip: the image-prompt term of a cross-attention (IP-Adapter), accumulated in place into the attention output:
+//   o[s][t][h*64 + d] = fp16(float(o[..]) + scale * sum_j softmax_j(0.125 <q[s][t][h*64 ..], k[s][j][h*64 ..]>) v[s][j][h*64 + d]),  j < N
+// fp32 with the row maximum subtracted, one rounding per element.  q / o: row strides ldq / ldo, per-sample strides sq / so; k / v: N rows
+// per sample (strides ldk / ldv, sk / sv; the kv_cache layout is k = kv, v = kv + C, ld 2C).  Only rows t < T and columns < heads * 64 of o
+// are written.  -1 (nothing launched): a null pointer, n / heads / T < 1, N outside [1, 64], ldq / ldk / ldv / ldo not a multiple of 8 or
+// below heads * 64, a per-sample stride that is not a multiple of 8, a base that is not 16-byte aligned
+int ladi_launch_ip_attn_add(const h16* q, int ldq, long long sq, const h16* k, int ldk, long long sk, const h16* v, int ldv, long long sv,
+                            h16* o, int ldo, long long so, int n, int heads, int T, int N, float scale, hipStream_t st);
+// o[row][0:C] = fp16(float(o) + scale * float(x)) over `rows` rows: the second half of the image term by the route that existed before the
+// kernel above (flash_attn64 over the N keys into a scratch tensor, then this), kept as the measured A/B arm (UNet::ip_route).  C and both
+// strides multiples of 8, bases 16-byte aligned, else -1
+int ladi_launch_ip_scaled_add(const h16* x, int ldx, h16* o, int ldo, long long rows, int C, float scale, hipStream_t st);
+
 // ---- lora.hip: LoRA merge of one block of rows of one packed weight, from the pristine copy `base` into the live weight `W` (both fp16
 // [rows of the weight][taps][cin_pad], row pitch `pitch` halves):
 //   W[map(o)][t][i] = fp16(float(base[map(o)][t][i]) + sum_a scale[a] * sum_r up[a][o][r] * down[a][r][t][i]),  o < rows, i < cin

@@ -191,6 +191,9 @@ struct XfBlock {
     h16* kv_cache = nullptr;  // [n][L][2C]
     // fused sub-blocks of the C = 320 level (xf_fused.hip): operands packed once at load (o2_packed, ff2_packed) / per context (kp, vt)
     h16* o2_packed = nullptr; h16* ff2_packed = nullptr; h16* kp_tiles = nullptr; h16* vt_tiles = nullptr;
+    // IP-Adapter (UNet::ip_load): attn2.processor.to_k_ip | to_v_ip packed like kv2, the image K/V of the image context [n][N][2C], and this
+    // block's scale (0: the block launches nothing for the image term)
+    DConv ip_kv; h16* ip_kv_cache = nullptr; float ip_scale = 1.f;
 };
 
 struct UNetCfg {
@@ -262,6 +265,28 @@ struct UNet {
     void lora_set(const std::vector<std::pair<std::string, float>>& set, hipStream_t st);
     long long export_weight(const std::string& key, float* host_out, long long cap);
     FreeU freeu;
+    // IP-Adapter image prompt (diffusers load_ip_adapter / set_ip_adapter_scale / ip_adapter_image_embeds; DESIGN.md "IP-Adapter").  One adapter
+    // per UNet: the image projection (Linear [N * cross_dim, E] + LayerNorm per token) and to_k_ip | to_v_ip of every transformer block, in
+    // their own pool.  An image context (set_ip_context / set_ip_tokens) is the hoisted image K/V of every block for n samples of ip_ctx_N
+    // tokens, in its own grow-only pool; with one set, attn2 of every block whose scale is not 0 adds scale * softmax(q k_ip^T / 8) v_ip to its
+    // attention output before to_out (ip_adapter.hip), reading the rows of this forward's samples (sample0) as kv_cache is read.  Without an
+    // image context the forward launches exactly the plain forward.  LoRA (lora_set) leaves all of it alone: no LoRA target is an image weight
+    bool ip_loaded = false; int ip_N = 0, ip_E = 0;           // tokens per image and embedding width of the loaded projection
+    std::unique_ptr<DevPool> ip_pool;
+    h16* ip_proj_w = nullptr; h16* ip_proj_b = nullptr; DNorm ip_norm;
+    int ip_ctx_n = 0, ip_ctx_N = 0; size_t ip_ctx_cap = 0;    // image context: samples (0 = none), tokens per sample; capacity in rows (n * N)
+    std::unique_ptr<DevPool> ip_ctx_pool; h16* ip_lin = nullptr; h16* ip_tok = nullptr;   // projection output / tokens [rows][cross_dim]
+    std::vector<std::pair<XfBlock*, std::string>> xf_blocks();   // every transformer block with its diffusers prefix, in execution order (PAG's bits)
+    void ip_load(const WeightStore& ws);                      // throws; everything is checked before anything changes
+    void ip_unload();
+    void ip_set_scale(const float* scales, int count);        // throws on a wrong count or a non-finite value, nothing changed
+    void ip_reserve(int n, int N);                            // host only: buffers for n samples of N tokens, and the context's shape (planning passes)
+    int set_ip_context(const h16* embeds, int n, hipStream_t st);          // fp16 [n][ip_E] -> projection, LayerNorm, one igemm per block
+    int set_ip_tokens(const h16* tokens, int n, int N, hipStream_t st);    // finished tokens fp16 [n][N][cross_dim]
+    void clear_ip_context() { ip_ctx_n = 0; }
+    // A/B switch of the image term (tools/bench_ip_adapter.py; ladi_unet_set_ip_route): 0 = ip_attn_add, the shipped route on every level
+    // (BASELINE.md "IP-Adapter"); 1 = flash_attn64 over the N image keys into a scratch tensor plus ip_scaled_add (two roundings)
+    int ip_route = 0;
     // pag_applied_layers (ladi_unet_set_pag_layers, sticky): bit i = transformer block i in execution order -- down_blocks.{0,1,2}
     // .attentions.{0..L-1}, mid_block, up_blocks.{1,2,3}.attentions.{0..L}; pag_layer_count() bits.  The default is the mid block, as in
     // diffusers.  Without perturbed samples in a forward (pag_first = PAG_NONE) the mask has no effect
@@ -521,6 +546,7 @@ struct TryOnInputs {
     const float* alphas_cumprod;  // optional [1000] host
 };
 enum { TRYON_PAG_WITH_CACHE = -12 };  // TryOn::run: a PAG table with a positive entry together with a feature-cache plan (LADI_TRYON_PAG_WITH_FEATURE_CACHE)
+enum { TRYON_IP_NO_ADAPTER = -13 };   // TryOn::run: image embeddings are set but the UNet has no IP-Adapter loaded (LADI_TRYON_IP_NO_ADAPTER)
 enum { TRYON_CALLBACK_ABORT = -8 };   // TryOn::run: the step callback returned non-zero (LADI_TRYON_CALLBACK_ABORTED, include/ladi_native.h)
 // The forms of one evaluation of the fused loop: bit 0 cond-only, bit 1 shallow (feature cache), bit 2 PAG (never together with bit 1), so
 // 0 .. 5.  The form is the index of GraphTable and of EvalPlan::has_form.
@@ -560,6 +586,10 @@ struct GraphKey {
     // ... and with PAG: whether the run has the third group, the scale table and the selected blocks (when pag_on); a graph captured with PAG
     // is never replayed without it, nor the reverse
     int pag_on; unsigned pag_mask; const void* pag_tab;
+    // ... and with the image prompt (IP-Adapter): on / off and, when on, the tokens per sample, the mid block's image K/V (every block's
+    // lives in the same pool) and the bits of the per-block scales, which the captured launches carry as arguments and which decide whether a
+    // block launches the image term at all
+    int ip_on, ip_N; const void* ip_kv; unsigned ip_scale[32];
 };
 // The per-evaluation plan of one run: host arithmetic only (plan_evals; ladi_tryon_plan_forms runs it without a GPU)
 struct EvalPlan {
@@ -618,6 +648,12 @@ struct TryOn {
     // with a scale > 0 runs the forward over the perturbed group too (form bit 2; never together with the feature cache, which run() refuses)
     std::vector<float> pag_sched;
     float* d_pag = nullptr; int pag_cap = 0;
+    // image prompt (ladi_tryon_set_ip_adapter, sticky; ip_pos null = off: the run clears the UNet's image context and launches the plain
+    // run).  The caller's fp16 [B][E] embeddings (ip_neg null: zeros, diffusers' zeros_like) are assembled per run into the runtime-owned
+    // ip_buf [groups * B][E] -- [neg ; pos], [neg ; pos ; pos] with PAG, [pos] without CFG -- on the run's stream, next to the prompt
+    // embeddings, and become the UNet's image context right after set_context
+    const h16* ip_pos = nullptr; const h16* ip_neg = nullptr;
+    h16* ip_buf = nullptr; size_t ip_buf_cap = 0;
     int last_shallow = 0;     // evaluations of the last run that ran shallow, after promotion (ladi_tryon_shallow_evals)
     // preserve-unmasked (ladi_tryon_set_preserve, sticky; 0 = off: nothing below is allocated or launched).  Bit 0, latents: after every
     // scheduler update the keep pixels (1 - maxpool8x8 of the binarised mask) become k_x z0 + k_n noise at the next timestep, z0 = scaling *

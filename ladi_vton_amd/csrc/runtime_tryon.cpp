@@ -31,6 +31,7 @@ TryOn::~TryOn() {
     if (fcache) (void)hipFree(fcache);
     if (stats) (void)hipFree(stats);
     if (step_noise_buf) (void)hipFree(step_noise_buf);
+    if (ip_buf) (void)hipFree(ip_buf);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     if (ev_in) (void)hipEventDestroy(ev_in);
     if (ev_out) (void)hipEventDestroy(ev_out);
@@ -191,6 +192,10 @@ int TryOn::plan(Run& r) {
     r.pose_ch = in.pose_channels;
     if (9 + r.pose_ch + (r.has_cloth ? 4 : 0) != unet->cfg.in_channels) { set_error("tryon: UNet in_channels does not match 9 + pose + cloth channels"); return -3; }
     r.L = in.L; r.D = unet->cfg.cross_dim;
+    if (ip_pos && !unet->ip_loaded) {
+        set_error("tryon: image embeddings are set (ladi_tryon_set_ip_adapter) but the UNet has no IP-Adapter loaded (ladi_unet_ip_adapter_load)");
+        return TRYON_IP_NO_ADAPTER;
+    }
     if (cfg_shaped(in.guidance, g_sched) && !in.negative_prompt_embeds) { set_error("tryon: negative_prompt_embeds required when guidance_scale > 1"); return -4; }
     // ---- scheduler tables (host)
     if (in.alphas_cumprod) r.ac.assign(in.alphas_cumprod, in.alphas_cumprod + 1000); else default_alphas_cumprod(r.ac);
@@ -237,6 +242,15 @@ int TryOn::grow_tables(Run& r) {
             step_noise_buf = nullptr; step_noise_cap = 0;
             HIP_OK(hipMalloc(reinterpret_cast<void**>(&step_noise_buf), r.step_noise_bytes));
             step_noise_cap = r.step_noise_bytes;
+        }
+    }
+    if (ip_pos) {
+        const size_t need = (size_t)r.n * unet->ip_E;
+        if (need > ip_buf_cap) {
+            if (ip_buf) HIP_OK_RC(hipFree(ip_buf));
+            ip_buf = nullptr; ip_buf_cap = 0;
+            HIP_OK_RC(hipMalloc(reinterpret_cast<void**>(&ip_buf), need * sizeof(h16)));
+            ip_buf_cap = need;
         }
     }
     // every argument check is behind us: only now grow the feature cache (a refused run leaves it, and the graphs that hold it, alone)
@@ -302,6 +316,9 @@ void TryOn::encode(Run& r) {
     float* keep_mask = r.keep_mask = keep_lat ? c.alloc_f32((size_t)B * hw) : nullptr;
     const size_t mk_persist = arena.mark();
 
+    // the image context's shape is part of what the planning pass of the forward sees (which blocks take the chain of projections)
+    if (!ip_pos) unet->clear_ip_context();
+    else if (c.dry()) unet->ip_reserve(n, unet->ip_N);
     if (!c.dry()) {
         if (stats_cap) HIP_OK(hipMemsetAsync(stats, 0, stats_cap * sizeof(float), st));
         // prompt embeddings [uncond ; cond] (tryon_pipe.py:620-628)
@@ -313,6 +330,18 @@ void TryOn::encode(Run& r) {
         // PAG: [neg ; pe ; pe] -- the perturbed group has the cond group's context
         if (p.pag_on) HIP_OK(hipMemcpyAsync(ehs + (size_t)p.ng * B * L * D, in.prompt_embeds, pe, hipMemcpyDeviceToDevice, st));
         if (unet->set_context(ehs, n, L, st)) { r.rc = -6; return; }
+        // image embeddings, the same groups: [neg ; pos], the perturbed group a copy of pos; a null negative is zeros
+        if (ip_pos) {
+            const size_t ie = (size_t)B * unet->ip_E;
+            for (int g = 0; g < p.groups; ++g) {
+                h16* dst = ip_buf + (size_t)g * ie;
+                if (p.cfg && g == 0) {
+                    if (ip_neg) HIP_OK(hipMemcpyAsync(dst, ip_neg, ie * sizeof(h16), hipMemcpyDeviceToDevice, st));
+                    else HIP_OK(hipMemsetAsync(dst, 0, ie * sizeof(h16), st));
+                } else HIP_OK(hipMemcpyAsync(dst, ip_pos, ie * sizeof(h16), hipMemcpyDeviceToDevice, st));
+            }
+            if (unet->set_ip_context(ip_buf, n, st)) { r.rc = -6; return; }
+        }
     }
     // ---------------- 4. mask / masked image / pose (tryon_pipe.py:630-636)
     Act masked_img = c.new_act(B, H, W, 64);
@@ -477,6 +506,11 @@ void TryOn::denoise(Run& r) {
         }
         if (p.pag_on) { key.pag_on = 1; key.pag_mask = unet->pag_mask; }
         key.pag_tab = sa.pag_tab;
+        if (unet->ip_ctx_n > 0) {
+            key.ip_on = 1; key.ip_N = unet->ip_ctx_N; key.ip_kv = unet->mid_xf.ip_kv_cache;
+            auto blocks = unet->xf_blocks();
+            for (size_t i = 0; i < blocks.size() && i < 32; ++i) std::memcpy(&key.ip_scale[i], &blocks[i].first->ip_scale, 4);
+        }
         if (std::memcmp(&key, &graph_key, sizeof(key))) { graphs.clear(); std::memcpy(&graph_key, &key, sizeof(key)); }
         // the host knows the schedule and picks the graph; the values come from the device table.  A form that this run has not yet
         // run eagerly and that has no graph runs eagerly once (see above), its next evaluation captures

@@ -7,6 +7,7 @@
 #include <new>
 #include <cstdlib>
 #include <cstdio>
+#include <cmath>
 
 namespace ladi {
 
@@ -167,6 +168,148 @@ int UNet::compute_temb(const float* ts_host, int count, hipStream_t st) {
     return rc;
 }
 
+// ------------------------------------------------------------------------------------------------
+// IP-Adapter image prompt (runtime.h UNet; ip_adapter.hip)
+// ------------------------------------------------------------------------------------------------
+std::vector<std::pair<XfBlock*, std::string>> UNet::xf_blocks() {
+    std::vector<std::pair<XfBlock*, std::string>> all;
+    const int L = cfg.layers_per_block;
+    for (int i = 0; i < (int)down_xf.size(); ++i)
+        all.emplace_back(&down_xf[i], "down_blocks." + std::to_string(i / L) + ".attentions." + std::to_string(i % L));
+    all.emplace_back(&mid_xf, "mid_block.attentions.0");
+    for (int i = 0; i < (int)up_xf.size(); ++i)
+        all.emplace_back(&up_xf[i], "up_blocks." + std::to_string(1 + i / (L + 1)) + ".attentions." + std::to_string(i % (L + 1)));
+    return all;
+}
+
+void UNet::ip_load(const WeightStore& ws) {
+    if (ip_loaded) throw std::runtime_error("an IP-Adapter is already loaded (ladi_unet_ip_adapter_unload first)");
+    auto shape_str = [](const HostTensor& t) { std::string s = "["; for (size_t i = 0; i < t.shape.size(); ++i) s += (i ? ", " : "") + std::to_string(t.shape[i]); return s + "]"; };
+    auto need = [&](const std::string& k) -> const HostTensor& {
+        if (!ws.has(k)) throw std::runtime_error("'" + k + "' is missing");
+        return ws.get(k);
+    };
+    // ---- validate everything; nothing of the UNet changes before the end of this block
+    const int D = cfg.cross_dim;
+    const HostTensor& pw = need("image_proj.proj.weight");
+    if (pw.shape.size() != 2 || pw.shape[0] < D || pw.shape[0] % D || pw.shape[1] < 1)
+        throw std::runtime_error("image_proj.proj.weight of shape " + shape_str(pw) + " is not [N * " + std::to_string(D) + ", E]");
+    const long long N = pw.shape[0] / D, E = pw.shape[1];
+    if (N < 1 || N > 64) throw std::runtime_error("image_proj.proj.weight gives " + std::to_string(N) + " image tokens, outside [1, 64]");
+    if (E % 8) throw std::runtime_error("the image embedding width " + std::to_string(E) + " is not a multiple of 8");
+    if ((long long)need("image_proj.proj.bias").numel() != N * D) throw std::runtime_error("image_proj.proj.bias does not have " + std::to_string(N * D) + " entries");
+    if ((long long)need("image_proj.norm.weight").numel() != D || (long long)need("image_proj.norm.bias").numel() != D)
+        throw std::runtime_error("image_proj.norm does not have " + std::to_string(D) + " channels");
+    auto blocks = xf_blocks();
+    size_t expected = 4;
+    for (auto& b : blocks) {
+        for (const char* nm : {"to_k_ip", "to_v_ip"}) {
+            const std::string k = b.second + ".transformer_blocks.0.attn2.processor." + nm + ".weight";
+            const HostTensor& w = need(k);
+            if (w.shape.size() != 2 || w.shape[0] != b.first->C || w.shape[1] != D)
+                throw std::runtime_error(k + " of shape " + shape_str(w) + " is not [" + std::to_string(b.first->C) + ", " + std::to_string(D) + "]");
+            ++expected;
+        }
+        if (ws.has(b.second + ".transformer_blocks.0.attn2.processor.to_k_ip.bias") || ws.has(b.second + ".transformer_blocks.0.attn2.processor.to_v_ip.bias"))
+            throw std::runtime_error(b.second + ": to_k_ip / to_v_ip have no bias");
+    }
+    if (ws.m.size() != expected) {
+        for (auto& kv : ws.m) {
+            const std::string& k = kv.first;
+            bool known = k == "image_proj.proj.weight" || k == "image_proj.proj.bias" || k == "image_proj.norm.weight" || k == "image_proj.norm.bias";
+            for (auto& b : blocks)
+                known = known || k == b.second + ".transformer_blocks.0.attn2.processor.to_k_ip.weight" ||
+                        k == b.second + ".transformer_blocks.0.attn2.processor.to_v_ip.weight";
+            if (!known) throw std::runtime_error("unexpected key '" + k + "'");
+        }
+    }
+    // ---- load
+    std::unique_ptr<DevPool> pool_(new DevPool());
+    h16* w = pool_->upload_h16(pw.data);
+    h16* bias = pool_->upload_h16(ws.get("image_proj.proj.bias").data);
+    DNorm nm = load_norm(*pool_, ws, "image_proj.norm");
+    std::vector<DConv> kv;
+    for (auto& b : blocks) {
+        const std::string p = b.second + ".transformer_blocks.0.attn2.processor.";
+        kv.push_back(load_linear_cat(*pool_, ws, {p + "to_k_ip", p + "to_v_ip"}, false));
+    }
+    HIP_OK(hipDeviceSynchronize());
+    for (size_t i = 0; i < blocks.size(); ++i) { blocks[i].first->ip_kv = kv[i]; blocks[i].first->ip_scale = 1.f; }
+    ip_pool = std::move(pool_);
+    ip_proj_w = w; ip_proj_b = bias; ip_norm = nm;
+    ip_N = (int)N; ip_E = (int)E; ip_loaded = true;
+    ip_ctx_n = 0;
+}
+
+void UNet::ip_unload() {
+    ip_ctx_n = 0; ip_ctx_N = 0; ip_ctx_cap = 0;
+    for (auto& b : xf_blocks()) { b.first->ip_kv = DConv(); b.first->ip_kv_cache = nullptr; b.first->ip_scale = 1.f; }
+    ip_lin = ip_tok = nullptr;
+    ip_ctx_pool.reset();
+    ip_pool.reset();
+    ip_proj_w = ip_proj_b = nullptr; ip_norm = DNorm();
+    ip_N = ip_E = 0; ip_loaded = false;
+}
+
+void UNet::ip_set_scale(const float* scales, int count) {
+    if (!ip_loaded) throw std::runtime_error("no IP-Adapter is loaded (ladi_unet_ip_adapter_load)");
+    if (!scales || count != pag_layer_count())
+        throw std::runtime_error("want " + std::to_string(pag_layer_count()) + " scales, one per transformer block, but got " + std::to_string(count));
+    for (int i = 0; i < count; ++i)
+        if (!std::isfinite(scales[i])) throw std::runtime_error("scale " + std::to_string(i) + " is not finite");
+    auto blocks = xf_blocks();
+    for (int i = 0; i < count; ++i) blocks[i].first->ip_scale = scales[i];
+}
+
+void UNet::ip_reserve(int n, int N) {
+    if (!ip_loaded) throw std::runtime_error("no IP-Adapter is loaded (ladi_unet_ip_adapter_load)");
+    if (n < 1 || N < 1 || N > 64) throw std::runtime_error("image context of " + std::to_string(n) + " samples x " + std::to_string(N) + " tokens: n >= 1 and N in [1, 64]");
+    const size_t rows = (size_t)n * N;
+    if (rows > ip_ctx_cap) {
+        ip_ctx_pool.reset(new DevPool());   // frees the previous (smaller) image K/V
+        const size_t D = (size_t)cfg.cross_dim;
+        ip_lin = reinterpret_cast<h16*>(ip_ctx_pool->alloc(rows * D * sizeof(h16)));
+        ip_tok = reinterpret_cast<h16*>(ip_ctx_pool->alloc(rows * D * sizeof(h16)));
+        for (auto& b : xf_blocks()) b.first->ip_kv_cache = reinterpret_cast<h16*>(ip_ctx_pool->alloc(rows * 2 * b.first->C * sizeof(h16)));
+        ip_ctx_cap = rows;
+    }
+    ip_ctx_n = n; ip_ctx_N = N;
+}
+
+// the image K/V of every block from the tokens in ip_tok: one igemm per block, as set_context's
+static int ip_project_kv(UNet& u, const h16* tok, hipStream_t st) {
+    const int rows = u.ip_ctx_n * u.ip_ctx_N;
+    for (auto& b : u.xf_blocks()) {
+        XfBlock* x = b.first;
+        IGemmArgs a; std::memset(&a, 0, sizeof(a));
+        a.src0 = tok; a.C0 = u.cfg.cross_dim; a.ld0 = u.cfg.cross_dim;
+        a.Hs = rows; a.Ws = 1; a.Ho = rows; a.Wo = 1; a.P = rows;
+        a.ksize = 1; a.stride = 1; a.pad = 0;
+        a.W = x->ip_kv.w; a.Q = x->ip_kv.cout; a.K = x->ip_kv.K();
+        a.out = x->ip_kv_cache; a.ldo = 2 * x->C; a.out_scale = 1.f;
+        const int rc = ladi_launch_igemm(a, 1, 0, st);
+        if (rc) { u.ip_ctx_n = 0; set_error("set_ip_context igemm rc=" + std::to_string(rc)); return rc; }
+    }
+    return 0;
+}
+
+int UNet::set_ip_context(const h16* embeds, int n, hipStream_t st) {
+    if (!embeds) throw std::runtime_error("null image embeddings");
+    ip_reserve(n, ip_N);
+    const int D = cfg.cross_dim;
+    // tokens = LayerNorm(Linear(embeds)).reshape(n, N, cross_dim): the projection's output row [N * D] is N token rows of D
+    int rc = ladi_launch_small_linear(embeds, 0, ip_E, ip_proj_w, ip_proj_b, nullptr, 0, n, ip_N * D, ip_E, LADI_ACT_NONE, 0, ip_lin, 0, ip_N * D, st);
+    if (!rc) rc = ladi_launch_layernorm(ip_lin, D, ip_norm.g, ip_norm.b, 1e-5f, n * ip_N, D, ip_tok, D, st);
+    if (rc) { ip_ctx_n = 0; set_error("set_ip_context image projection rc=" + std::to_string(rc)); return rc; }
+    return ip_project_kv(*this, ip_tok, st);
+}
+
+int UNet::set_ip_tokens(const h16* tokens, int n, int N, hipStream_t st) {
+    if (!tokens) throw std::runtime_error("null image tokens");
+    ip_reserve(n, N);
+    return ip_project_kv(*this, tokens, st);
+}
+
 namespace {
 
 struct Fwd {
@@ -241,8 +384,11 @@ struct Fwd {
         // MI355X (profiles/r05_xf_fused_ab.txt): parity-green and bit-reproducible, but at one wave per SIMD the fused chains expose the latency two
         // waves per SIMD hide in the separate launches -- attn2 85.7 us against the ~76 us of the three launches it replaces (forward
         // +0.05 ms), feed-forward 275 us against 109 + 57 us (forward +0.45 ms) -- so the DEFAULT IS OFF; the kernels stay selectable.
+        // an image context (IP-Adapter) with a non-zero scale for this block: the chain of projections, with the image term accumulated into
+        // the attention output before to_out
+        const bool ip = u.ip_ctx_n > 0 && b.ip_scale != 0.f;
         int fuse = 0;
-        if (b.o2_packed && b.kp_tiles && t1.ld == C && ladi_xf_fused_eligible(C, b.heads, T, u.ctx_L)) fuse = u.xf_fuse;
+        if (!ip && b.o2_packed && b.kp_tiles && t1.ld == C && ladi_xf_fused_eligible(C, b.heads, T, u.ctx_L)) fuse = u.xf_fuse;
         Act t2;
         if (fuse >= 1) {
             t2 = c.new_act(n, T, 1, C);
@@ -260,6 +406,17 @@ struct Fwd {
             Act q2 = conv2d(c, b.q2, t1, nullptr, oq2);
             const h16* kv = b.kv_cache + (size_t)sample0 * u.ctx_L * 2 * C;     // this lane's samples of the cached cross-attention K / V
             Act o2 = attn(q2.p, C, (long long)T * C, kv, kv + C, 2 * C, (long long)u.ctx_L * 2 * C, n, T, u.ctx_L, b.heads);
+            if (ip) {
+                const long long skv = (long long)u.ip_ctx_N * 2 * C;
+                const h16* ikv = b.ip_kv_cache + (size_t)sample0 * skv;           // this lane's samples of the image K / V
+                if (u.ip_route == 1) {
+                    Act oi = attn(q2.p, C, (long long)T * C, ikv, ikv + C, 2 * C, skv, n, T, u.ip_ctx_N, b.heads);
+                    if (!c.dry()) c.check(ladi_launch_ip_scaled_add(oi.p, oi.ld, o2.p, o2.ld, (long long)n * T, C, b.ip_scale, c.st), "ip_scaled_add");
+                } else if (!c.dry()) {
+                    c.check(ladi_launch_ip_attn_add(q2.p, q2.ld, (long long)T * q2.ld, ikv, 2 * C, skv, ikv + C, 2 * C, skv, o2.p, o2.ld, (long long)T * o2.ld,
+                                                    n, b.heads, T, u.ip_ctx_N, b.ip_scale, c.st), "ip_attn_add");
+                }
+            }
             ConvOpt or2; or2.res0 = &t1;
             t2 = conv2d(c, b.o2, o2, nullptr, or2);
         }
@@ -306,6 +463,8 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
         return a;
     };
     if ((eps_out ? sample0 + x.n > ctx_n : ctx_n != x.n) && !c.dry()) throw std::runtime_error("UNet::forward: set_context batch mismatch");
+    if (ip_ctx_n > 0 && ip_ctx_n != ctx_n && !c.dry())
+        throw std::runtime_error("UNet::forward: image context batch mismatch: " + std::to_string(ip_ctx_n) + " samples, set_context has " + std::to_string(ctx_n));
     if (pag_first != PAG_NONE && fmode != FeatCache::NONE) throw std::runtime_error("UNet::forward: perturbed samples together with a feature cache");
     Fwd f{c, *this, temb_row, temb_idx, sample0, pag_first};
     ProbeScope probe_scope(c, probe);

@@ -124,6 +124,8 @@ class NativeUNet(_Base):
         self._ctx_keepalive = None
         self.freeu = None             # (s1, s2, b1, b2) while FreeU is on
         self._lora_disabled = None    # the active set disable_lora() put aside for enable_lora()
+        self._ip_key = None           # the image context the library holds (the tensor is kept alive, as for _ctx_key)
+        self._ip_keepalive = None
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -245,6 +247,77 @@ class NativeUNet(_Base):
             out[m + ".weight"] = self.export_weight(m + ".weight")
         return out
 
+    # ---- IP-Adapter image prompt (ip_adapter.py, include/ladi_native.h "IP-Adapter image prompt")
+    def load_ip_adapter(self, state_dict_or_path):
+        """Load an IP-Adapter (diffusers' {"image_proj", "ip_adapter"} layout, nested or flat, numbered or module-named keys:
+        ip_adapter.load_state).  Everything is checked before anything changes; one adapter per UNet.  Loading activates nothing: an image
+        term appears in a forward that is given ip_image_embeds= / ip_tokens=.  A new adapter starts with every scale 1.0."""
+        from . import ip_adapter
+        sd = ip_adapter.load_state(state_dict_or_path, self.cfg["layers_per_block"])
+        with _Weights(sd) as w:
+            check(self.lib.ladi_unet_ip_adapter_load(self.h, w.h), "ladi_unet_ip_adapter_load")
+        self._ip_key = self._ip_keepalive = None
+
+    def unload_ip_adapter(self):
+        check(self.lib.ladi_unet_ip_adapter_unload(self.h), "ladi_unet_ip_adapter_unload")
+        self._ip_key = self._ip_keepalive = None
+
+    @property
+    def ip_adapter_info(self):
+        """None, or (tokens per image, embedding width) of the loaded adapter"""
+        n, e = c_int(0), c_int(0)
+        rc = self.lib.ladi_unet_ip_adapter_info(self.h, ctypes.byref(n), ctypes.byref(e))
+        if rc < 0:
+            raise NativeError("ladi_unet_ip_adapter_info failed: " + _lib.last_error())
+        return (n.value, e.value) if rc else None
+
+    def set_ip_adapter_scale(self, scale):
+        """diffusers' set_ip_adapter_scale: a number (every transformer block), or a dict / list of (name, scale) in the block names of
+        set_pag_applied_layers ("down", "up.block_1", "mid", ..), unnamed blocks 0 -- the layer-wise use of diffusers' dict form.  Sticky; a
+        block with scale 0 launches nothing for the image term."""
+        from . import ip_adapter
+        v = ip_adapter.scale_list(scale, self.cfg["layers_per_block"])
+        check(self.lib.ladi_unet_set_ip_scale(self.h, (c_float * len(v))(*v), len(v)), "ladi_unet_set_ip_scale")
+
+    @property
+    def ip_adapter_scale(self):
+        """the scale of every transformer block, in execution order"""
+        out = (c_float * 32)()
+        n = self.lib.ladi_unet_ip_scale(self.h, out, 32)
+        if n < 0:
+            raise NativeError("ladi_unet_ip_scale failed: " + _lib.last_error())
+        return [float(out[i]) for i in range(n)]
+
+    def set_ip_context(self, embeds=None, tokens=None):
+        """the image context of the following forwards: embeds [n, E] (or [n, 1, E]) through the adapter's projection, or finished tokens
+        [n, N, cross_dim]; both None: none.  The same tensor object passed again unmodified is not uploaded again."""
+        if embeds is not None and tokens is not None:
+            raise ValueError("`ip_image_embeds` and `ip_tokens` cannot both be given.")
+        t = embeds if embeds is not None else tokens
+        if t is None:
+            if self._ip_key != "none":
+                check(self.lib.ladi_unet_clear_ip_context(self.h), "ladi_unet_clear_ip_context")
+                self._ip_key, self._ip_keepalive = "none", None
+            return
+        info = self.ip_adapter_info
+        if info is None:
+            raise ValueError("an image prompt needs a loaded IP-Adapter (load_ip_adapter).")
+        key = (id(t), t._version, embeds is not None)
+        if self._ip_key == key and self._ip_keepalive is not None and self._ip_keepalive[0] is t:
+            return
+        if embeds is not None:
+            e = embeds[:, 0] if embeds.dim() == 3 and embeds.shape[1] == 1 else embeds
+            if e.dim() != 2 or e.shape[1] != info[1]:
+                raise ValueError("ip_image_embeds has shape %s, expected [n, %d] (the loaded adapter's embedding width)" % (tuple(embeds.shape), info[1]))
+            e = e.to(device=self.device, dtype=torch.float16).contiguous()
+            check(self.lib.ladi_unet_set_ip_context(self.h, ptr(e), e.shape[0], stream_ptr()), "ladi_unet_set_ip_context")
+        else:
+            if tokens.dim() != 3 or tokens.shape[2] != self.cfg["cross_attention_dim"] or not 1 <= tokens.shape[1] <= 64:
+                raise ValueError("ip_tokens has shape %s, expected [n, N <= 64, %d]" % (tuple(tokens.shape), self.cfg["cross_attention_dim"]))
+            e = tokens.to(device=self.device, dtype=torch.float16).contiguous()
+            check(self.lib.ladi_unet_set_ip_tokens(self.h, ptr(e), e.shape[0], e.shape[1], stream_ptr()), "ladi_unet_set_ip_tokens")
+        self._ip_key, self._ip_keepalive = key, (t, e)
+
     def enable_xformers_memory_efficient_attention(self, *a, **k):
         return None  # attention is always fused (flash-style) in the native kernels
 
@@ -261,8 +334,11 @@ class NativeUNet(_Base):
 
     FEATURE_CACHE_MODES = {None: 0, "capture": 1, "reuse": 2}
 
-    def __call__(self, sample, timestep, encoder_hidden_states=None, feature_cache=None, cache_branch=0, sample0=0, pag_first=None, **kw):
-        """pag_first: None, or the index in the encoder_hidden_states batch from which the samples are perturbed (perturbed-attention
+    def __call__(self, sample, timestep, encoder_hidden_states=None, feature_cache=None, cache_branch=0, sample0=0, pag_first=None,
+                 ip_image_embeds=None, ip_tokens=None, **kw):
+        """ip_image_embeds / ip_tokens: the image prompt of this forward (set_ip_context), one row per sample of the
+        encoder_hidden_states batch; neither: no image term, the plain forward.
+        pag_first: None, or the index in the encoder_hidden_states batch from which the samples are perturbed (perturbed-attention
         guidance: identity self-attention in the blocks of set_pag_applied_layers); not together with feature_cache.
         feature_cache: None, "capture" (the whole forward, which also caches the deep features of the full-resolution level) or "reuse"
         (the shallow forward from that cache: the outermost cache_branch + 1 layers only; ladi_unet_forward_cached).  sample0: the samples
@@ -274,6 +350,7 @@ class NativeUNet(_Base):
         if isinstance(cache_branch, bool) or not isinstance(cache_branch, int) or not 0 <= cache_branch <= self.cfg["layers_per_block"]:
             raise ValueError("cache_branch has to be in [0, %d] but is %r" % (self.cfg["layers_per_block"], cache_branch))
         self.set_context(encoder_hidden_states)
+        self.set_ip_context(ip_image_embeds, ip_tokens)
         x = sample.contiguous()
         n, C, h, w = x.shape
         if C != self.cfg["in_channels"]:

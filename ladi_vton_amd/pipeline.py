@@ -336,6 +336,24 @@ class StableDiffusionTryOnePipeline:
     def get_list_adapters(self):
         return {"unet": self._lora_unet("get_list_adapters").list_adapters()}
 
+    # ---- IP-Adapter image prompt: the state lives in the UNet (NativeUNet.load_ip_adapter / set_ip_adapter_scale)
+    def _ip_unet(self, what):
+        if not hasattr(self.unet, "load_ip_adapter"):
+            raise ValueError("`%s` needs the native UNet (NativeUNet), the pipeline holds %s." % (what, type(self.unet).__name__))
+        return self.unet
+
+    def load_ip_adapter(self, state_dict_or_path):
+        """diffusers' pipe.load_ip_adapter for the plain adapter: a state dict in diffusers' {"image_proj", "ip_adapter"} layout or a path
+        to one (ip_adapter.load_state).  The picture itself is not encoded here: pass `ip_adapter_image_embeds` to the call."""
+        self._ip_unet("load_ip_adapter").load_ip_adapter(state_dict_or_path)
+
+    def unload_ip_adapter(self):
+        self._ip_unet("unload_ip_adapter").unload_ip_adapter()
+
+    def set_ip_adapter_scale(self, scale):
+        """a number, or per-block scales as a dict / list in the names of set_pag_applied_layers (NativeUNet.set_ip_adapter_scale)"""
+        self._ip_unet("set_ip_adapter_scale").set_ip_adapter_scale(scale)
+
     @property
     def shallow_evals(self):
         """how many evaluations of the last run ran shallow (`feature_cache=`), after promotion (fused: ladi_tryon_shallow_evals)"""
@@ -463,7 +481,8 @@ class StableDiffusionTryOnePipeline:
                  negative_prompt_embeds=None, generator=None, latents=None, output_type="pil", return_dict=True, callback=None,
                  callback_steps=1, cloth_cond_rate=1.0, no_pose=False, cloth_input_type="warped", fused=True, noise=None,
                  use_graph=True, guidance_rescale=0.0, strength=1.0, init_image=None, init_latents=None, init_is_noisy=False,
-                 feature_cache=None, preserve_unmasked=None, mask_feather=0.0, pag_scale=0.0, pag_adaptive_scale=0.0):
+                 feature_cache=None, preserve_unmasked=None, mask_feather=0.0, pag_scale=0.0, pag_adaptive_scale=0.0,
+                 ip_adapter_image_embeds=None, negative_ip_adapter_image_embeds=None):
         """tryon_pipe.py's __call__.  `guidance_scale`: a float, a sequence with one scale per evaluation (len(scheduler.timesteps); PNDM: steps
         + 1) or a callable f(i, n_evals) -- see guidance_interval.  Classifier-free guidance is on if any scale is > 1; an evaluation whose scale
         is <= 1 then runs the UNet over the conditional samples only.  `guidance_rescale` (rescale_noise_cfg's phi, [0, 1]) acts on the CFG
@@ -501,7 +520,12 @@ class StableDiffusionTryOnePipeline:
         prediction becomes u + g (c - u) + s (c - p), or c + s (c - p) without classifier-free guidance; `guidance_rescale` acts on that
         sum.  `pag_adaptive_scale` > 0 lowers the scale with the timestep, s_i = max(pag_scale - pag_adaptive_scale * (1000 - t_i), 0); an
         evaluation with s_i = 0 runs without the perturbed samples.  Needs the native UNet; not together with `feature_cache`.  0 is the
-        plain run bit for bit."""
+        plain run bit for bit.
+
+        `ip_adapter_image_embeds` is the image prompt of a loaded IP-Adapter (load_ip_adapter): [B, E] or [B, 1, E] image embeddings, or
+        diffusers' one-element list holding [2B, 1, E] with the negatives first.  `negative_ip_adapter_image_embeds` defaults to zeros.  Every
+        cross-attention then adds scale * softmax(q k_ip^T / 8) v_ip over the projected image tokens (set_ip_adapter_scale; fused and modular
+        path alike).  None is the plain run; a raw `ip_adapter_image` is not taken (this package's vision encoder has no visual_projection)."""
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
@@ -552,6 +576,20 @@ class StableDiffusionTryOnePipeline:
         device = self._execution_device
         pe, neg = self._encode_prompt(prompt, device, num_images_per_prompt, do_cfg, negative_prompt, prompt_embeds, negative_prompt_embeds)
         B = pe.shape[0]
+        ip = None
+        if ip_adapter_image_embeds is not None:
+            from . import ip_adapter
+            info = self._ip_unet("ip_adapter_image_embeds").ip_adapter_info
+            if info is None:
+                raise ValueError("`ip_adapter_image_embeds` needs a loaded IP-Adapter (load_ip_adapter).")
+            ip_pos, ip_neg = ip_adapter.split_embeds(ip_adapter_image_embeds, negative_ip_adapter_image_embeds, B, do_cfg)
+            if ip_pos.shape[1] != info[1]:
+                raise ValueError("`ip_adapter_image_embeds` has width %d, the loaded adapter takes %d." % (ip_pos.shape[1], info[1]))
+            ip_pos = ip_pos.to(device=device, dtype=torch.float16).contiguous()
+            ip_neg = ip_neg.to(device=device, dtype=torch.float16).contiguous() if ip_neg is not None else torch.zeros_like(ip_pos)
+            ip = (ip_pos, ip_neg)
+        elif negative_ip_adapter_image_embeds is not None:
+            raise ValueError("`negative_ip_adapter_image_embeds` without `ip_adapter_image_embeds`.")
         self._validate_images(image, mask_image)
         h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
         # RNG draws in pipeline order (cloth posterior, initial latents, masked-image posterior)
@@ -585,7 +623,7 @@ class StableDiffusionTryOnePipeline:
                                      no_pose, use_graph, step_noise=step_noise, eta=ddim_eta, callback=callback,
                                      callback_steps=callback_steps, guidance_table=g_table, guidance_rescale=guidance_rescale,
                                      init_latents=init, first_step=first_step, init_is_noisy=init_is_noisy,
-                                     feature_cache=(fc_flags, fc_branch), preserve=preserve, pag_table=pag_table)
+                                     feature_cache=(fc_flags, fc_branch), preserve=preserve, pag_table=pag_table, ip=ip)
             # prepare_mask_and_masked_image binarises the caller's mask in place; keep that side effect
             mask_image[mask_image < 0.5] = 0
             mask_image[mask_image >= 0.5] = 1
@@ -595,7 +633,7 @@ class StableDiffusionTryOnePipeline:
                                        no_pose, eta, generator, callback, callback_steps, guidance_table=g_table,
                                        guidance_rescale=guidance_rescale, init_latents=init, first_step=first_step,
                                        init_is_noisy=init_is_noisy, feature_cache=(fc_flags, fc_branch), preserve=preserve,
-                                       pag_table=pag_table)
+                                       pag_table=pag_table, ip=ip)
         if output_type == "pil":
             images = numpy_to_pil(images)
         if not return_dict:
@@ -624,8 +662,9 @@ class StableDiffusionTryOnePipeline:
     def _run_fused(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose,
                    use_graph, return_device=False, out_uint8=False, lanes=None, step_noise=None, eta=0.0, callback=None, callback_steps=1,
                    guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0, init_is_noisy=False, feature_cache=None,
-                   preserve=None, pag_table=None):
-        """return_device: hand back the device tensor (no host copy); out_uint8: the batch as uint8 [B,H,W,3] = numpy_to_pil's
+                   preserve=None, pag_table=None, ip=None):
+        """ip: (embeds, negative embeds), fp16 [B, E] device tensors each (ladi_tryon_set_ip_adapter); None = no image prompt.
+        return_device: hand back the device tensor (no host copy); out_uint8: the batch as uint8 [B,H,W,3] = numpy_to_pil's
         (images * 255).round() computed by the decode epilogue (ladi_tryon_run_u8); lanes: sample-group lanes of the UNet forward;
         step_noise: fp32 [steps, B, 4, h, w], the per-step noise of EulerAncestralDiscreteScheduler and of DDIM with eta > 0
         (ladi_tryon_set_step_noise); eta: DDIM's eta (ladi_tryon_set_eta, DDIM only); guidance_table: one scale per evaluation, replaces
@@ -730,6 +769,13 @@ class StableDiffusionTryOnePipeline:
             check(lib.ladi_tryon_set_pag(self._tryon, None, 0), "ladi_tryon_set_pag")
         p_bits, p_sigma = preserve if preserve is not None else (0, 0.0)
         check(lib.ladi_tryon_set_preserve(self._tryon, int(p_bits), float(p_sigma)), "ladi_tryon_set_preserve")
+        if ip is not None:
+            for t in ip:
+                if t.dim() != 2 or t.shape[0] != B or t.dtype != torch.float16 or not t.is_contiguous():
+                    raise ValueError("image embeddings have shape %s (%s), expected a contiguous fp16 [%d, E]" % (tuple(t.shape), t.dtype, B))
+            check(lib.ladi_tryon_set_ip_adapter(self._tryon, ptr(ip[0]), ptr(ip[1])), "ladi_tryon_set_ip_adapter")
+        else:
+            check(lib.ladi_tryon_set_ip_adapter(self._tryon, None, None), "ladi_tryon_set_ip_adapter")
         self._shallow_evals = None
         cb_error = []
         cb_latents = trampoline = None
@@ -747,8 +793,9 @@ class StableDiffusionTryOnePipeline:
             trampoline = _lib.STEP_CALLBACK(_step)     # referenced until the callback is switched off below
             check(lib.ladi_tryon_set_step_callback(self._tryon, trampoline, None, int(callback_steps), ptr(cb_latents)),
                   "ladi_tryon_set_step_callback")
-        # the fused loop rewrites the UNet's cross-attention K/V cache behind the shim's back
+        # the fused loop rewrites the UNet's cross-attention K/V cache (and its image context) behind the shim's back
         self.unet._ctx_key = None
+        self.unet._ip_key = None
         if lanes is not None or self.lanes is not None:
             check(lib.ladi_tryon_set_lanes(self._tryon, int(lanes if lanes is not None else self.lanes)), "ladi_tryon_set_lanes")
         native_run = lib.ladi_tryon_run_u8 if out_uint8 else lib.ladi_tryon_run
@@ -821,7 +868,7 @@ class StableDiffusionTryOnePipeline:
     # -------------------------------------------------------------------------------------------------------
     def _run_modular(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose, eta,
                      generator, callback, callback_steps, guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0,
-                     init_is_noisy=False, feature_cache=None, preserve=None, pag_table=None):
+                     init_is_noisy=False, feature_cache=None, preserve=None, pag_table=None, ip=None):
         F = torch.nn.functional
         dev = self._execution_device
         do_cfg = neg is not None
@@ -829,6 +876,15 @@ class StableDiffusionTryOnePipeline:
         ehs = torch.cat([neg, pe]) if do_cfg else pe
         # PAG: the context of the whole run is [neg ; pe ; pe] (or [pe ; pe]); every evaluation runs its own rows of it
         ehs_pag = torch.cat([ehs, pe]) if pag_table is not None else None
+        # the image prompt follows the context row for row: [neg ; pos], [pos], with PAG one more pos
+        ip_c = ip_all = ip_pag = None
+        if ip is not None:
+            ip_c = ip[0]
+            ip_all = torch.cat([ip[1], ip[0]]) if do_cfg else ip[0]
+            ip_pag = torch.cat([ip_all, ip[0]])
+
+        def ipkw(t):
+            return {"ip_image_embeds": t} if ip is not None else {}
         mask_image[mask_image < 0.5] = 0
         mask_image[mask_image >= 0.5] = 1
         mask = mask_image.to(dev)
@@ -908,14 +964,16 @@ class StableDiffusionTryOnePipeline:
             x = torch.cat([p.float() for p in parts], dim=1)
             if pag_table is not None:
                 ng = 2 if do_cfg else 1
-                eps = self.unet(x, t, encoder_hidden_states=ehs_pag, sample0=B if do_cfg and not cfg_i else 0, pag_first=ng * B).sample.float()
+                eps = self.unet(x, t, encoder_hidden_states=ehs_pag, sample0=B if do_cfg and not cfg_i else 0, pag_first=ng * B,
+                                **ipkw(ip_pag)).sample.float()
                 if s_i > 0.0:
                     eps, ep = eps[:-B], eps[-B:]
             elif fc_flags is not None:
                 eps = self.unet(x, t, encoder_hidden_states=ehs, feature_cache="capture" if fc_flags[i] else "reuse", cache_branch=fc_branch,
-                                sample0=B if do_cfg and not cfg_i else 0).sample.float()
+                                sample0=B if do_cfg and not cfg_i else 0, **ipkw(ip_all)).sample.float()
             else:
-                eps = self.unet(x, t, encoder_hidden_states=ehs if cfg_i or not do_cfg else pe).sample.float()
+                whole = cfg_i or not do_cfg
+                eps = self.unet(x, t, encoder_hidden_states=ehs if whole else pe, **ipkw(ip_all if whole else ip_c)).sample.float()
             if cfg_i:
                 eu, et = eps.chunk(2)
                 eps = eu + g_i * (et - eu)
