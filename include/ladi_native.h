@@ -222,6 +222,39 @@ int ladi_tps_forward(ladi_tps* t, const void* input_a_dev, const void* input_b_d
  *   bits 8-9 solver_order (0 = 2, or 1..3), bit 10 solver_type heun (0 = midpoint), bit 11 lower_order_final off.
  * Any other bit, an option bit on another kind or an unknown kind is an error.  The DPM / Euler formulas are restated from the published
  * algorithms as diffusers 0.14 ships them, not pinned against diffusers itself (it is not installable here).
+ *
+ * Few-step sampling (distilled weights: LCM / LCM-LoRA, TCD, Turbo, Lightning, Hyper-SD).  Two more kinds and two more option fields:
+ *   7 = LCM, 8 = TCD (kinds 6, 9 and 15 stay unknown);
+ *   bit 6 = trailing timestep spacing, valid on kinds 0 (DDIM), 4 (Euler) and 5 (Euler-ancestral) only;
+ *   bits 12-21 = original_inference_steps of LCM / TCD, 1..1000 (0 = 50), valid on kinds 7 and 8 only.
+ * num_inference_steps N: [1, original_inference_steps] for kinds 7 and 8, [1, 1000] with the trailing bit, [2, 1000] for the plain codes 0-5.
+ * The arithmetic below is restated from the published algorithms as diffusers ships them, from memory like the other schedulers here; THIS
+ * TEXT IS THE CONTRACT.  a(t) = alphas_cumprod[t], T = 1000, every coefficient is computed in double and the rows are held in fp32; the
+ * timesteps of the evaluations i = 0..N-1:
+ *   LCM / TCD : O = original_inference_steps, k = T / O (integer division), t_i = (O - floor(i * (O / N))) * k - 1 with i * (O / N) evaluated
+ *               in double as numpy.linspace(0, O, N, endpoint=False) evaluates it (O = 50: N = 4 gives 999, 759, 499, 259; N = 1 gives 999).
+ *   trailing  : t_i = round_half_even(T - i * (T / N)) - 1 (N = 4: 999, 749, 499, 249; N = 3: 999, 666, 332).  This closed form is the
+ *               contract.  It equals np.round(np.arange(T, 0, -T/N)) - 1 for every N <= 47; from N = 48 on, numpy's arange sometimes
+ *               differs in a value or returns one element too many.  It gives no duplicate and no negative timestep for any N in 1..1000.
+ * With x0 = (x - sqrt(1 - a_t) eps) / sqrt(a_t), the updates, all linear in (x, eps, noise_i) and therefore rows of the table below:
+ *   LCM       : s = 10 t (timestep_scaling 10, sigma_data 0.5), c_skip = 0.25 / (s^2 + 0.25), c_out = s / sqrt(s^2 + 0.25),
+ *               den = c_out x0 + c_skip x; x' = sqrt(a_p) den + sqrt(1 - a_p) noise_i with a_p = a(t_{i+1}); the last evaluation x' = den
+ *               (c_n = 0).  Row: c_x = sqrt(a_p) (c_out / sqrt(a_t) + c_skip), c_e w0 = -sqrt(a_p) c_out sqrt(1 - a_t) / sqrt(a_t),
+ *               c_n = sqrt(1 - a_p), sqrt(a_p) replaced by 1 in the last row.
+ *   TCD       : gamma = eta in [0, 1]; t_prev = t_{i+1}, or 0 after the last timestep; t_s = floor((1 - gamma) t_prev);
+ *               x_s = sqrt(a_s) x0 + sqrt(1 - a_s) eps; gamma > 0 and not the last evaluation: x' = sqrt(a_prev / a_s) x_s +
+ *               sqrt(1 - a_prev / a_s) noise_i; otherwise x' = x_s.  gamma = 0 is the deterministic DDIM jump t_i -> t_{i+1}, the last to t = 0.
+ *   trailing DDIM : DDIM's row (with or without eta) over the trailing timesteps with diffusers' prev = t - T / N (integer division; N = 3:
+ *               666, 333, -1, not the next timestep); prev < 0 uses alphas_cumprod[0].
+ *   trailing Euler / Euler-ancestral : their rows over sigma_i = sqrt((1 - a(t_i)) / a(t_i)) held in fp32, with a trailing 0;
+ *               init_noise_sigma is the largest sigma (14.6146 at t = 999 with the default betas); a one-step Euler-ancestral row has
+ *               sigma_up = 0.
+ * The rules generic over kinds cover kinds 7 and 8 like DDIM: a tail (first_step, strength) is the tail of the N-step list and starts from
+ * sqrt(a) init + sqrt(1 - a) noise at its first timestep (not diffusers' set_timesteps(strength=)); the latent blend's coefficients are
+ * sqrt(a), sqrt(1 - a) at timesteps[i + 1]; the cloth cut-off counts evaluations.  Step noise: a run whose table has a stochastic term needs
+ * one slab per evaluation; LCM, and TCD with eta > 0, never read the last slab (its row has c_n = 0), and a run of one evaluation needs none.
+ * Not covered: guidance-embedded UNets (time_cond_proj_dim / timestep_cond), trailing spacing on PNDM, LMS and DPM-Solver++,
+ * timestep_scaling != 10, v-prediction, custom timestep lists.
  * ------------------------------------------------------------------------------------------------------------- */
 #define LADI_SCHED_DDIM 0
 #define LADI_SCHED_PNDM 1
@@ -229,11 +262,16 @@ int ladi_tps_forward(ladi_tps* t, const void* input_a_dev, const void* input_b_d
 #define LADI_SCHED_DPMPP 3
 #define LADI_SCHED_EULER 4
 #define LADI_SCHED_EULER_ANCESTRAL 5
+#define LADI_SCHED_LCM 7
+#define LADI_SCHED_TCD 8
+#define LADI_SCHED_TRAILING (1 << 6)           /* kinds 0, 4 and 5 */
+#define LADI_SCHED_ORIGINAL_STEPS(o) ((o) << 12)     /* kinds 7 and 8; o in 1..1000, 0 = 50 */
 #define LADI_SCHED_DPM_ORDER(o) ((o) << 8)     /* o in 1..3 */
 #define LADI_SCHED_DPM_HEUN (1 << 10)
 #define LADI_SCHED_DPM_NO_LOWER_ORDER_FINAL (1 << 11)
-/* host helper: writes the N (DDIM, DPMSolverMultistep) or N+1 (PNDM) integer timesteps; returns their count, or negative on error.
- * LMSDiscrete / Euler / Euler-ancestral (fractional timesteps) are refused: use ladi_sched_lms, whose timesteps and sigmas all three share.
+/* host helper: writes the N (DDIM, DPMSolverMultistep, LCM, TCD, any trailing code) or N+1 (PNDM) integer timesteps; returns their count,
+ * or negative on error.  LMSDiscrete / Euler / Euler-ancestral without the trailing bit (fractional timesteps) are refused: use
+ * ladi_sched_lms, whose timesteps and sigmas all three share.
  * DPMSolverMultistep refuses step counts whose rounded timesteps repeat (N = 1000), on which diffusers 0.14 fails. */
 int ladi_sched_timesteps(int kind, int num_inference_steps, int* timesteps_out, int cap);
 /* host helper (tests): the per-evaluation step table of any scheduler code, 10 floats per evaluation:
@@ -243,8 +281,9 @@ int ladi_sched_timesteps(int kind, int num_inference_steps, int* timesteps_out, 
  * Returns the evaluation count (or negative on error; cap = capacity in evaluations). */
 int ladi_sched_table(int kind, int num_inference_steps, const float* alphas_cumprod_host, double* timesteps_out, float* rows_out, int cap);
 /* the same table for DDIMScheduler.step(eta = ...) (diffusers 0.14): std = eta sqrt(max((1 - a_p) / (1 - a_t) (1 - a_t / a_p), 0)), the eps
- * direction sqrt(max(1 - a_p - std^2, 0)), c_n = std.  eta == 0 gives ladi_sched_table's rows bit for bit; eta < 0, a non-finite eta, or a
- * non-zero eta with any kind but DDIM is an error (the other schedulers' step() takes no eta). */
+ * direction sqrt(max(1 - a_p - std^2, 0)), c_n = std.  eta == 0 gives ladi_sched_table's rows bit for bit.  TCD's gamma travels as eta too
+ * (diffusers' TCDScheduler.step takes it under that name) and has to be in [0, 1].  eta < 0, a non-finite eta, or a non-zero eta with any
+ * kind but DDIM and TCD is an error (the other schedulers' step() takes no eta). */
 int ladi_sched_table_eta(int kind, int num_inference_steps, const float* alphas_cumprod_host, float eta, double* timesteps_out, float* rows_out,
                          int cap);
 /* the table of a run that starts at step first_step of the num_inference_steps-step schedule (strength; ladi_tryon_set_init): the evaluations of
@@ -289,8 +328,10 @@ typedef struct {
     int num_inference_steps;
     float guidance_scale;
     int scheduler;                     /* scheduler code (see "Scheduler" above): 0 DDIM, 1 PNDM, 2 LMSDiscrete, 3 DPMSolverMultistep
-                                        * (+ option bits), 4 EulerDiscrete, 5 EulerAncestralDiscrete (needs ladi_tryon_set_step_noise);
-                                        * DDIM's eta is set with ladi_tryon_set_eta */
+                                        * (+ option bits), 4 EulerDiscrete, 5 EulerAncestralDiscrete (needs ladi_tryon_set_step_noise),
+                                        * 7 LCM (step noise when it has more than one evaluation), 8 TCD (step noise with eta > 0),
+                                        * + LADI_SCHED_TRAILING / LADI_SCHED_ORIGINAL_STEPS; DDIM's eta and TCD's gamma are set with
+                                        * ladi_tryon_set_eta.  num_inference_steps may be 1 for kinds 7 and 8 and with the trailing bit */
     int cloth_zero_from_eval;          /* first evaluation index i that sees zero cloth latents: the smallest i with
                                         * i >= num_inference_steps - (1 - cloth_cond_rate) * num_inference_steps, evaluated by the CALLER in
                                         * float64 exactly like tryon_pipe.py:654,718 (a float32 rate crossing the ABI shifts the cut-off by
@@ -313,7 +354,8 @@ int ladi_tryon_run_u8(ladi_tryon* t, const ladi_tryon_inputs* in, unsigned char*
  * and the updated latents of evaluation i to *_trace_dev[i] (fp32 [B, h*w, 4] each) for i < cap_evals; NULL pointers switch it off.
  * Buffers are caller-owned and must outlive the runs. */
 int ladi_tryon_set_trace(ladi_tryon* t, float* eps_trace_dev, float* latents_trace_dev, int cap_evals);
-/* per-step noise of EulerAncestralDiscrete and of DDIM with eta > 0 (the randn draw of their step(), one per evaluation): fp32
+/* per-step noise of EulerAncestralDiscrete, of DDIM with eta > 0, of LCM and of TCD with eta > 0 (the randn draw of their step(), one slab
+ * per evaluation; LCM and TCD draw at every evaluation but the last, whose slab is never read and may hold anything): fp32
  * [steps][B][4][h][w] on the device.  Each run copies the first `evaluations` steps on its stream into a runtime-owned buffer before the loop,
  * so the captured graph never reads the caller's buffer (which, like the run's other inputs, must stay valid until the run's work on the stream
  * has started); such a run with no noise, or fewer steps than evaluations, fails.  Runs without a stochastic term ignore it.  NULL = off. */
@@ -330,8 +372,9 @@ int ladi_tryon_set_step_noise(ladi_tryon* t, const float* noise_dev, int steps);
  * the run's scheduler and step count, or a guidance schedule / step-noise count that does not match the tail, fails the run before anything is
  * launched; hs or ws < 1 or first_step < 0 is refused here. */
 int ladi_tryon_set_init(ladi_tryon* t, const float* init_latents_dev, int hs, int ws, int first_step, int noisy);
-/* DDIMScheduler.step's eta for the following runs (sticky per handle, default 0): > 0 adds the stochastic term std * noise[i], which needs
- * ladi_tryon_set_step_noise.  Only DDIM reads it: a run of any other scheduler with a non-zero eta fails.  eta < 0 or non-finite: error. */
+/* DDIMScheduler.step's eta, or TCDScheduler.step's eta (its gamma, [0, 1]), for the following runs (sticky per handle, default 0): > 0 adds
+ * the stochastic term c_n * noise[i], which needs ladi_tryon_set_step_noise.  Only DDIM (kind 0, trailing or not) and TCD (kind 8) read it:
+ * a run of any other scheduler with a non-zero eta fails, and so does a TCD run with eta > 1.  eta < 0 or non-finite: error. */
 int ladi_tryon_set_eta(ladi_tryon* t, float eta);
 /* per-evaluation guidance scale for the following runs (sticky per handle; copied): scales_host[i] is the scale of evaluation i and
  * in->guidance_scale is ignored while a schedule is set.  NULL or count 0 switches it off.  A run whose evaluation count is not `count`

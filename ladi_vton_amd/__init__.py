@@ -11,7 +11,7 @@ from .modules import (NativeEMASC, NativeInversionAdapter, NativeUNet, NativeVAE
 from .pipeline import StableDiffusionTryOnePipeline, feature_cache_plan, guidance_interval, preserve_spec, strength_first_step  # noqa: F401
 from .probe import RangeProbe  # noqa: F401
 from .schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler,  # noqa: F401
-                         LMSDiscreteScheduler, PNDMScheduler)
+                         LCMScheduler, LMSDiscreteScheduler, PNDMScheduler, TCDScheduler)
 from .text import NativeCLIPTextEncoder, encode_text_word_embedding  # noqa: F401
 from .vision import NativeCLIPVisionEncoder  # noqa: F401
 from .warp import NativeRefinementUNet, NativeTPS, clip_preprocess, grid_sample_border, resize_antialias, warp_cloth  # noqa: F401

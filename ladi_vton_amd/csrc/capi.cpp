@@ -775,10 +775,11 @@ int ladi_tps_forward(ladi_tps* t, const void* a, const void* b, int dtype, int B
 // ------------------------------------------------------------------------------------------------ scheduler helpers
 int ladi_sched_timesteps(int kind, int steps, int* out, int cap) {
     return guarded("ladi_sched_timesteps", [&]() {
-        if (steps < 2 || steps > 1000) throw std::runtime_error("num_inference_steps out of range");
         std::vector<float> ac; default_alphas_cumprod(ac);
-        const int k = decode_sched_code(kind).kind;
-        if (k == SCHED_LMS || k == SCHED_EULER || k == SCHED_EULER_A)
+        const SchedCode sc = decode_sched_code(kind);
+        const int k = sc.kind;
+        // (the step-count range is the table builder's: it depends on the code; trailing Euler timesteps are integers)
+        if (!sc.trailing && (k == SCHED_LMS || k == SCHED_EULER || k == SCHED_EULER_A))
             throw std::runtime_error("LMSDiscrete / EulerDiscrete / EulerAncestralDiscrete timesteps are fractional: use ladi_sched_lms");
         std::vector<double> ts; std::vector<StepTable> tb;
         build_step_table(kind, steps, ac.data(), 1 << 30, ts, tb);
@@ -870,7 +871,8 @@ static int tryon_run_any(ladi_tryon* t, const ladi_tryon_inputs* in, void* image
         ti.steps = in->num_inference_steps; ti.guidance = in->guidance_scale; ti.scheduler = in->scheduler;
         ti.cloth_zero_from = in->cloth_zero_from_eval; ti.no_pose = in->no_pose; ti.use_graph = in->use_graph;
         ti.alphas_cumprod = in->alphas_cumprod_host;
-        if (ti.steps < 2 || ti.steps > 1000) throw std::runtime_error("num_inference_steps out of range");
+        // (the lower bound per scheduler code, 2 or 1, is the step-table builder's)
+        if (ti.steps < 1 || ti.steps > 1000) throw std::runtime_error("num_inference_steps out of range");
         if (!ti.image || !ti.mask_image || !ti.pose_map || !ti.prompt_embeds || !ti.noise_latents || !ti.noise_masked) throw std::runtime_error("missing input");
         if (ti.warped_cloth && !ti.noise_cloth) throw std::runtime_error("noise_cloth required with warped_cloth");
         return t->t.run(ti, images, images_u8, latents, S(stream));
@@ -1413,7 +1415,7 @@ static int sched_run_any(const char* name, int kind, int steps, const float* ac_
         build_step_table(kind, steps, ac.data(), 1 << 30, ts, tb, nullptr, eta);
         if (evals > (int)tb.size()) throw std::runtime_error("evals exceeds scheduler length");
         if (table_needs_step_noise(tb) && (!step_noise || noise_steps < evals))
-            throw std::runtime_error("EulerAncestralDiscrete / DDIM with eta > 0 need step noise for every evaluation run");
+            throw std::runtime_error("EulerAncestralDiscrete / DDIM with eta > 0 / LCM / TCD with eta > 0 need step noise for every evaluation run");
         char* buf = nullptr;
         const size_t plane = (size_t)B * hw * 4 * sizeof(float);
         const size_t tb_bytes = (tb.size() * sizeof(StepTable) + 255) & ~(size_t)255;
@@ -1482,7 +1484,7 @@ static int sched_run_guided_any(const char* name, int kind, int steps, const flo
         build_step_table(kind, steps, ac.data(), 1 << 30, ts, tb, nullptr, eta);
         if (evals > (int)tb.size()) throw std::runtime_error("evals exceeds scheduler length");
         if (table_needs_step_noise(tb) && (!step_noise || noise_steps < evals))
-            throw std::runtime_error("EulerAncestralDiscrete / DDIM with eta > 0 need step noise for every evaluation run");
+            throw std::runtime_error("EulerAncestralDiscrete / DDIM with eta > 0 / LCM / TCD with eta > 0 need step noise for every evaluation run");
         char* buf = nullptr;
         const size_t plane = (size_t)B * hw * 4 * sizeof(float);
         const size_t tb_bytes = (tb.size() * sizeof(StepTable) + 255) & ~(size_t)255;

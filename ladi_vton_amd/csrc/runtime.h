@@ -625,7 +625,7 @@ struct TryOn {
     // runtime-owned step_noise_buf that the captured graph reads
     const float* step_noise_src = nullptr; int step_noise_steps = 0;
     float* step_noise_buf = nullptr; size_t step_noise_cap = 0;
-    float eta = 0.f;   // DDIM's eta (ladi_tryon_set_eta), sticky; other kinds refuse a non-zero one
+    float eta = 0.f;   // DDIM's eta / TCD's gamma (ladi_tryon_set_eta), sticky; other kinds refuse a non-zero one
     // start from given latents at step init_first of the schedule (ladi_tryon_set_init, sticky; null or init_first = 0: off): the caller's fp32
     // NCHW [B][4][init_hs][init_ws], read once by init_latents_kernel on the run's stream before the loop (never inside the captured graph),
     // which resamples it to the run's latent size and mixes it with noise_latents (init_noisy: taken as the loop's latents unchanged)
@@ -689,9 +689,11 @@ struct TryOn {
 // 3 = DPMSolverMultistep (dpmsolver++), 4 = EulerDiscrete, 5 = EulerAncestralDiscrete (LMS's timesteps and sigmas).
 // The scheduler code (ladi_tryon_inputs.scheduler, include/ladi_native.h) carries the kind in bits 0-3 and the DPM-Solver++ options in
 // bits 8-11: bits 8-9 solver_order (0 = the default 2, else 1..3), bit 10 solver_type heun (0 = midpoint), bit 11 lower_order_final off.
+// 7 = LCM and 8 = TCD (few-step sampling of distilled weights; kinds 6, 9 and 15 stay unknown).  Bit 6: trailing timestep spacing (DDIM, Euler
+// and Euler-ancestral only); bits 12-21: original_inference_steps of LCM / TCD (1..1000, 0 = 50; those two kinds only).
 // Any other bit, an option bit on another kind, or an unknown kind is rejected.
-enum { SCHED_DDIM = 0, SCHED_PNDM = 1, SCHED_LMS = 2, SCHED_DPMPP = 3, SCHED_EULER = 4, SCHED_EULER_A = 5 };
-struct SchedCode { int kind = 0, order = 2, heun = 0, lower_order_final = 1; };
+enum { SCHED_DDIM = 0, SCHED_PNDM = 1, SCHED_LMS = 2, SCHED_DPMPP = 3, SCHED_EULER = 4, SCHED_EULER_A = 5, SCHED_LCM = 7, SCHED_TCD = 8 };
+struct SchedCode { int kind = 0, order = 2, heun = 0, lower_order_final = 1, trailing = 0, original_steps = 50; };
 SchedCode decode_sched_code(int code);
 void default_alphas_cumprod(std::vector<float>& ac);
 struct SchedInfo {
@@ -705,7 +707,9 @@ struct SchedInfo {
     float start_kx = 0.f, start_kn = 1.f;
 };
 // cloth_zero_from: first evaluation index that must see zero cloth latents (tryon_pipe.py:718), computed by the caller in float64;
-// code: the scheduler code above; eta: DDIMScheduler.step's eta (DDIM only, >= 0; > 0 puts the stochastic term into c_n).
+// code: the scheduler code above; eta: DDIMScheduler.step's eta (>= 0; > 0 puts the stochastic term into c_n) or TCDScheduler.step's gamma
+// ([0, 1]; > 0 re-noises every update but the last); a non-zero eta with any other kind is refused.
+// Step counts: [2, 1000] for the plain codes 0-5, [1, 1000] with the trailing bit, [1, original_inference_steps] for LCM / TCD.
 // first_step > 0 builds the tail of the `steps`-step schedule (strength): the evaluations of steps first_step .. with their own timesteps and
 // sigmas, indexed from 0 (cloth_zero_from too).  Multistep history starts empty there: LMS and DPM-Solver++ warm up again (orders 1, 2, ..),
 // lower_order_final acts where it does in the whole run, and PNDM restarts as a fresh PLMS run over the tail's step timesteps u0 > u1 > ..
@@ -720,7 +724,8 @@ void build_keep_coeffs(int code, int steps, const float* alphas_cumprod, int fir
 // the same from the timesteps and SchedInfo a build_step_table(code, .., first_step) call returned
 void keep_coeffs_of(int code, const std::vector<double>& timesteps, const SchedInfo& info, const float* alphas_cumprod, int first_step,
                     std::vector<float>& out);
-// true if the table has a stochastic term (some c_n != 0: Euler-ancestral, DDIM with eta > 0), i.e. a run of it needs step noise
+// true if the table has a stochastic term (some c_n != 0: Euler-ancestral, DDIM with eta > 0, LCM and TCD with eta > 0 of more than one
+// evaluation), i.e. a run of it needs step noise
 bool table_needs_step_noise(const std::vector<StepTable>& table);
 
 }  // namespace ladi

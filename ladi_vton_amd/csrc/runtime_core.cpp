@@ -463,14 +463,25 @@ static double lms_basis_integral(const double* s, int order, int j, double lo, d
 
 SchedCode decode_sched_code(int code) {
     SchedCode sc;
-    if (code < 0 || (code & ~0xF0F) != 0)
-        throw std::runtime_error("scheduler code " + std::to_string(code) + ": unknown bits (kind: bits 0-3, DPM-Solver++ options: bits 8-11)");
+    if (code < 0 || (code & ~0x3FFF4F) != 0)
+        throw std::runtime_error("scheduler code " + std::to_string(code) + ": unknown bits (kind: bits 0-3, trailing spacing: bit 6, "
+                                 "DPM-Solver++ options: bits 8-11, LCM / TCD original_inference_steps: bits 12-21)");
     sc.kind = code & 15;
-    if (sc.kind > SCHED_EULER_A)
+    if (sc.kind > SCHED_EULER_A && sc.kind != SCHED_LCM && sc.kind != SCHED_TCD)
         throw std::runtime_error("scheduler kind " + std::to_string(sc.kind) + " unknown: 0 DDIM, 1 PNDM, 2 LMSDiscrete, 3 DPMSolverMultistep, "
-                                 "4 EulerDiscrete, 5 EulerAncestralDiscrete");
+                                 "4 EulerDiscrete, 5 EulerAncestralDiscrete, 7 LCM, 8 TCD");
     const int opt = (code >> 8) & 15;
     if (sc.kind != SCHED_DPMPP && opt) throw std::runtime_error("scheduler code " + std::to_string(code) + ": option bits 8-11 are DPM-Solver++ only");
+    sc.trailing = (code >> 6) & 1;
+    if (sc.trailing && sc.kind != SCHED_DDIM && sc.kind != SCHED_EULER && sc.kind != SCHED_EULER_A)
+        throw std::runtime_error("scheduler code " + std::to_string(code) + ": trailing spacing (bit 6) is DDIM, EulerDiscrete and "
+                                 "EulerAncestralDiscrete only");
+    const int orig = (code >> 12) & 0x3FF;
+    const bool few_step = sc.kind == SCHED_LCM || sc.kind == SCHED_TCD;
+    if (orig && !few_step)
+        throw std::runtime_error("scheduler code " + std::to_string(code) + ": original_inference_steps (bits 12-21) is LCM and TCD only");
+    if (orig > 1000) throw std::runtime_error("scheduler code " + std::to_string(code) + ": original_inference_steps " + std::to_string(orig) + " out of range [1, 1000]");
+    if (few_step && orig) sc.original_steps = orig;
     if (sc.kind == SCHED_DPMPP) {
         sc.order = (opt & 3) ? (opt & 3) : 2;
         sc.heun = (opt >> 2) & 1;
@@ -481,13 +492,23 @@ SchedCode decode_sched_code(int code) {
 
 // diffusers 0.14 LMSDiscreteScheduler.set_timesteps (EulerDiscrete / EulerAncestralDiscrete use the same): timesteps = linspace(0, T-1, n)[::-1];
 // sigma = interp(t, arange(T), sqrt((1 - a) / a)) held in fp32, trailing 0
-static void lms_sigmas(int steps, const float* ac, std::vector<double>& timesteps, std::vector<float>& sig) {
+// trailing spacing (timestep_spacing = "trailing"): t_i = round_half_even(T - i (T / n)) - 1, T / n in double.  This closed form is the
+// contract; it equals np.round(np.arange(T, 0, -T / n)) - 1 for every n <= 47 (from n = 48 on numpy's arange sometimes differs in a value
+// or returns one element too many).  No duplicate and no negative timestep for any n in 1..1000
+static int trailing_timestep(int i, int steps) {
+    const int T = 1000;
+    return (int)std::nearbyint((double)T - (double)i * ((double)T / (double)steps)) - 1;
+}
+
+// trailing: the integer timesteps above, sigma = sqrt((1 - a) / a) at them held in fp32, trailing 0
+static void lms_sigmas(int steps, const float* ac, std::vector<double>& timesteps, std::vector<float>& sig, bool trailing) {
     const int T = 1000;
     sig.assign((size_t)steps + 1, 0.f);
     for (int i = 0; i < steps; ++i) {
         // numpy.linspace: arange(n) * ((stop - start) / (n - 1)) + start, last element set to stop exactly
         const int k = steps - 1 - i;
-        const double t = k == steps - 1 ? (double)(T - 1) : (double)k * ((double)(T - 1) / (double)(steps - 1));
+        const double t = trailing ? (double)trailing_timestep(i, steps)
+                                  : k == steps - 1 ? (double)(T - 1) : (double)k * ((double)(T - 1) / (double)(steps - 1));
         timesteps.push_back(t);
         const int lo = std::min((int)t, T - 1), hi = std::min(lo + 1, T - 1);
         const double slo = (double)(float)std::sqrt((1.0 - (double)ac[lo]) / (double)ac[lo]);
@@ -515,17 +536,27 @@ static std::vector<int> dpm_timesteps(int steps) {
 void build_step_table(int code, int steps, const float* ac, int cloth_zero_from, std::vector<double>& timesteps,
                       std::vector<StepTable>& table, SchedInfo* info, double eta, int first_step) {
     const int T = 1000;
-    if (steps < 2 || steps > T) throw std::runtime_error("num_inference_steps out of range [2, 1000]");   // ts[steps - 2] below
     const SchedCode sc = decode_sched_code(code);
     const int kind = sc.kind;
+    const bool few_step = kind == SCHED_LCM || kind == SCHED_TCD;
+    // one step: the few-step kinds and trailing spacing only (the plain codes keep [2, 1000]: ts[steps - 2], linspace's n - 1 below)
+    if (few_step) {
+        if (steps < 1 || steps > sc.original_steps)
+            throw std::runtime_error("num_inference_steps out of range [1, " + std::to_string(sc.original_steps) + "] (original_inference_steps)");
+    } else if (sc.trailing) {
+        if (steps < 1 || steps > T) throw std::runtime_error("num_inference_steps out of range [1, 1000]");
+    } else if (steps < 2 || steps > T) throw std::runtime_error("num_inference_steps out of range [2, 1000]");
     // a tail needs one step, a PNDM tail two (its second evaluation averages with the first)
     const int max_first = kind == SCHED_PNDM ? steps - 2 : steps - 1;
     if (first_step < 0 || first_step > max_first)
         throw std::runtime_error("first_step " + std::to_string(first_step) + " out of range [0, " + std::to_string(max_first) + "] for " +
                                  std::to_string(steps) + " steps" + (kind == SCHED_PNDM ? " (a PNDM tail needs at least 2 steps)" : ""));
     if (!(eta >= 0.0) || !std::isfinite(eta)) throw std::runtime_error("eta must be finite and >= 0, got " + std::to_string(eta));
-    // only DDIMScheduler.step takes eta; the other schedulers ignore it, and a table that silently did the same would diverge from the caller's intent
-    if (eta != 0.0 && kind != SCHED_DDIM) throw std::runtime_error("eta > 0 is DDIM only (scheduler kind " + std::to_string(kind) + ")");
+    // only DDIMScheduler.step and TCDScheduler.step (its gamma) take eta; the other schedulers ignore it, and a table that silently did the
+    // same would diverge from the caller's intent
+    if (eta != 0.0 && kind != SCHED_DDIM && kind != SCHED_TCD)
+        throw std::runtime_error("eta > 0 is DDIM only, and TCD's gamma (scheduler kind " + std::to_string(kind) + ")");
+    if (kind == SCHED_TCD && eta > 1.0) throw std::runtime_error("TCD: eta (gamma) must be in [0, 1], got " + std::to_string(eta));
     const int ratio = T / steps;
     const double final_ac = ac[0];  // set_alpha_to_one = False
     timesteps.clear(); table.clear();
@@ -533,7 +564,7 @@ void build_step_table(int code, int steps, const float* ac, int cloth_zero_from,
     const bool sigma_kind = kind == SCHED_LMS || kind == SCHED_EULER || kind == SCHED_EULER_A;
     std::vector<float> sig;
     if (sigma_kind) {
-        lms_sigmas(steps, ac, timesteps, sig);
+        lms_sigmas(steps, ac, timesteps, sig, sc.trailing != 0);
         float smax = 0.f;
         for (float s : sig) smax = std::max(smax, s);
         if (info) {
@@ -625,8 +656,47 @@ void build_step_table(int code, int steps, const float* ac, int cloth_zero_from,
             e.in_scale_next = 1.f;
             table.push_back(e);
         }
+    } else if (few_step) {
+        // LCMScheduler / TCDScheduler as diffusers ships them, restated from the published algorithms (include/ladi_native.h is the contract).
+        // Timesteps: O = original_inference_steps, k = T // O, t_i = (O - floor(i (O / n))) k - 1 with i (O / n) in double, as
+        // numpy.linspace(0, O, n, endpoint=False) evaluates it.  Both updates are linear in (x, eps, noise):
+        // x0 = (x - sqrt(1 - a_t) eps) / sqrt(a_t)
+        const int O = sc.original_steps, k = T / O;
+        const double stride = (double)O / (double)steps;
+        for (int i = 0; i < steps; ++i) timesteps.push_back((double)((O - (int)std::floor((double)i * stride)) * k - 1));
+        for (int i = first_step; i < steps; ++i) {
+            const bool last = i == steps - 1;
+            const int t = (int)timesteps[i];
+            const double a_t = ac[t], sa_t = std::sqrt(a_t), sb_t = std::sqrt(1.0 - a_t);
+            StepTable e; std::memset(&e, 0, sizeof(e));
+            e.w[0] = 1.f;
+            if (kind == SCHED_LCM) {
+                // boundary condition (timestep_scaling 10, sigma_data 0.5): s = 10 t, c_skip = 0.25 / (s^2 + 0.25), c_out = s / sqrt(s^2 + 0.25);
+                // denoised = c_out x0 + c_skip x; x' = sqrt(a_p) denoised + sqrt(1 - a_p) noise_i at a_p = a(t_{i+1}), the last x' = denoised
+                const double s = 10.0 * (double)t, c_skip = 0.25 / (s * s + 0.25), c_out = s / std::sqrt(s * s + 0.25);
+                const double a_p = last ? 1.0 : (double)ac[(int)timesteps[i + 1]], sa_p = std::sqrt(a_p);
+                e.c_x = (float)(sa_p * (c_out / sa_t + c_skip));
+                e.c_e = (float)(-sa_p * c_out * sb_t / sa_t);
+                e.c_n = last ? 0.f : (float)std::sqrt(1.0 - a_p);
+            } else {
+                // gamma = eta: t_prev = t_{i+1} (0 after the last timestep), t_s = floor((1 - gamma) t_prev);
+                // x_s = sqrt(a_s) x0 + sqrt(1 - a_s) eps; gamma > 0 and not the last evaluation: x' = sqrt(a_prev / a_s) x_s +
+                // sqrt(1 - a_prev / a_s) noise_i, else x' = x_s
+                const int t_prev = last ? 0 : (int)timesteps[i + 1];
+                const int t_s = (int)std::floor((1.0 - eta) * (double)t_prev);
+                const double a_s = ac[t_s], a_prev = ac[t_prev];
+                const double kx = std::sqrt(a_s) / sa_t, ke = std::sqrt(1.0 - a_s) - std::sqrt(a_s) * sb_t / sa_t;
+                const bool renoise = eta > 0.0 && !last;
+                const double r = renoise ? std::sqrt(a_prev / a_s) : 1.0;
+                e.c_x = (float)(r * kx);
+                e.c_e = (float)(r * ke);
+                e.c_n = renoise ? (float)std::sqrt(std::max(1.0 - a_prev / a_s, 0.0)) : 0.f;
+            }
+            table.push_back(e);
+        }
     } else if (kind == 0) {
-        for (int i = steps - 1; i >= 0; --i) timesteps.push_back(i * ratio + 1);
+        // trailing spacing keeps diffusers' prev = t - T // n (n = 3: 666, 333, -1, not the next timestep)
+        for (int i = steps - 1; i >= 0; --i) timesteps.push_back(sc.trailing ? trailing_timestep(steps - 1 - i, steps) : i * ratio + 1);
         for (int i = first_step; i < steps; ++i) {
             const int t = (int)timesteps[i], tp = t - ratio;
             const double a_t = ac[t], a_p = tp >= 0 ? (double)ac[tp] : final_ac;

@@ -225,12 +225,15 @@ int TryOn::grow_tables(Run& r) {
     if (p.use_factor && B > factor_cap) { d_factor = reinterpret_cast<float*>(pool.alloc((size_t)B * sizeof(float))); factor_cap = B; }
     if (r.keep_lat && evals > keep_tab_cap) { d_keep_tab = reinterpret_cast<float*>(pool.alloc((size_t)evals * 2 * sizeof(float))); keep_tab_cap = evals; }
     if (!ev[0]) for (auto& e : ev) HIP_OK(hipEventCreate(&e));
-    // a table with a stochastic term (Euler-ancestral, DDIM with eta > 0): the caller's per-step noise is copied into a runtime-owned buffer
-    // (upload_tables, on the run's stream) so that the pointer the captured graph holds stays valid after the caller frees theirs
+    // a table with a stochastic term (Euler-ancestral, DDIM with eta > 0, LCM, TCD with eta > 0): the caller's per-step noise is copied into
+    // a runtime-owned buffer (upload_tables, on the run's stream) so that the pointer the captured graph holds stays valid after the caller
+    // frees theirs.  One slab per evaluation, whichever rows read theirs (the last row of LCM and TCD has c_n = 0: its slab is never read)
     r.use_step_noise = table_needs_step_noise(r.table);
     r.step_noise_bytes = r.use_step_noise ? (size_t)evals * B * 4 * r.hw * sizeof(float) : 0;
     if (r.use_step_noise) {
-        const char* noisy = decode_sched_code(r.in.scheduler).kind == SCHED_EULER_A ? "EulerAncestralDiscrete" : "DDIM with eta > 0";
+        const int kind = decode_sched_code(r.in.scheduler).kind;
+        const char* noisy = kind == SCHED_EULER_A ? "EulerAncestralDiscrete" : kind == SCHED_LCM ? "LCM" : kind == SCHED_TCD ? "TCD with eta > 0"
+                                                                                                                         : "DDIM with eta > 0";
         if (!step_noise_src) { set_error(std::string("tryon: ") + noisy + " needs per-step noise (ladi_tryon_set_step_noise)"); return -7; }
         if (step_noise_steps < evals) {
             set_error(std::string("tryon: ") + noisy + " needs " + std::to_string(evals) + " steps of noise, ladi_tryon_set_step_noise gave " +

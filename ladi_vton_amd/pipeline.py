@@ -18,11 +18,11 @@ from . import _lib
 from ._lib import TryOnInputs, check, dtype_code, ptr, stream_ptr
 from .modules import NativeEMASC, NativeUNet, NativeVAE, mask_features
 from .schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler,
-                         LMSDiscreteScheduler, PNDMScheduler)
+                         LCMScheduler, LMSDiscreteScheduler, PNDMScheduler, TCDScheduler)
 
 # the schedulers the fused native loop runs (ladi_tryon_run): the native step table of each is the mirror's arithmetic
 FUSED_SCHEDULERS = (DDIMScheduler, PNDMScheduler, LMSDiscreteScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler,
-                    EulerAncestralDiscreteScheduler)
+                    EulerAncestralDiscreteScheduler, LCMScheduler, TCDScheduler)
 
 
 def guidance_interval(n_evals, scale, start=0.0, stop=1.0):
@@ -497,7 +497,14 @@ class StableDiffusionTryOnePipeline:
         noise of `latents=` / RNG draw #2; `init_is_noisy=True` takes the init as the loop's latents at that timestep unchanged (resume).
         Everything indexed per evaluation (a guidance schedule, the callback's i, scheduler.timesteps, the cloth cut-off of `cloth_cond_rate`)
         refers to the tail.  PNDM restarts as a fresh PLMS run over the tail (tail steps + 1 evaluations, at least 2 steps).  strength = 1.0
-        ignores a given init and is the plain run.
+        ignores a given init and is the plain run.  LCMScheduler and TCDScheduler run the tail of their N-step list too, like every other
+        scheduler here; diffusers' set_timesteps(strength=), which spaces the N steps anew over the shortened range, is not used.
+
+        `eta` goes to DDIMScheduler.step and, as its gamma, to TCDScheduler.step (there it has to be in [0, 1]); no other scheduler reads it.
+        Few-step sampling: LCMScheduler / TCDScheduler (1 .. original_inference_steps evaluations) and timestep_spacing="trailing" on
+        DDIM, Euler and Euler-ancestral (1 .. 1000).  Their step() draws one batch-shaped fp32 tensor at every evaluation but the last (TCD
+        with eta = 0: none), after the pipeline's three draws; the fused path makes exactly those draws up front, so both paths agree for a
+        seed.
 
         `feature_cache` (DeepCache on the full-resolution level; None = off): an int N (every N-th evaluation runs the whole UNet, the others
         only its outermost layers on the deep features the last whole one cached), a dict {"interval": N, "branch": k} (k = 0, 1, 2: how many
@@ -540,6 +547,8 @@ class StableDiffusionTryOnePipeline:
         # can run are image batches that already hold B * k samples -- the same rule applies here (shape checks below)
         if not isinstance(num_images_per_prompt, int) or num_images_per_prompt < 1:
             raise ValueError("num_images_per_prompt must be a positive integer")
+        if isinstance(self.scheduler, TCDScheduler) and not 0.0 <= float(eta) <= 1.0:
+            raise ValueError("`eta` is TCDScheduler's gamma and has to be in [0, 1] but is %r." % (eta,))
         first_step = strength_first_step(strength, num_inference_steps)
         preserve = preserve_spec(preserve_unmasked, mask_feather)
         if init_image is not None and init_latents is not None:
@@ -604,18 +613,26 @@ class StableDiffusionTryOnePipeline:
             self._range_probe.reset()
         init = self._prepare_init(init_image, init_latents, B, device) if first_step > 0 else None
         native = isinstance(self.unet, NativeUNet) and isinstance(self.vae, NativeVAE) and (self.emasc is None or isinstance(self.emasc, NativeEMASC))
-        # only DDIMScheduler.step takes eta (the modular path passes it to no other scheduler); a negative one stays on the modular path
-        ddim_eta = float(eta) if isinstance(self.scheduler, DDIMScheduler) else 0.0
+        # only DDIMScheduler.step and TCDScheduler.step (its gamma) take eta (the modular path passes it to no other scheduler); a negative
+        # one stays on the modular path
+        ddim_eta = float(eta) if isinstance(self.scheduler, (DDIMScheduler, TCDScheduler)) else 0.0
         can_fuse = (fused and native and isinstance(self.scheduler, FUSED_SCHEDULERS) and ddim_eta >= 0.0
                     and (not self.emasc or list(self.emasc_int_layers or []) == [1, 2, 3, 4, 5]))
         if can_fuse:
             # Euler / Euler-ancestral / DDIM with eta > 0 step() draw one batch-shaped fp32 noise tensor per step after the three draws above:
             # the fused path makes the same draws up front, in the same generator order (Euler's are unused, as in diffusers without churn)
             step_noise = None
-            if isinstance(self.scheduler, (EulerDiscreteScheduler, EulerAncestralDiscreteScheduler)) or ddim_eta > 0.0:
+            few_step = isinstance(self.scheduler, (LCMScheduler, TCDScheduler))
+            if isinstance(self.scheduler, (EulerDiscreteScheduler, EulerAncestralDiscreteScheduler)) or (ddim_eta > 0.0 and not few_step):
                 draws = [self._draw((B, 4, h, w), generator, torch.float32, device) for _ in range(int(num_inference_steps) - first_step)]
                 if not isinstance(self.scheduler, EulerDiscreteScheduler):
                     step_noise = torch.stack(draws).contiguous()
+            elif isinstance(self.scheduler, LCMScheduler) or (isinstance(self.scheduler, TCDScheduler) and ddim_eta > 0.0):
+                # LCM / TCD with eta > 0 draw at every evaluation but the last: exactly those evaluations - 1 draws, and one slab per
+                # evaluation for the runtime, the last zero-filled and not drawn (its table row has c_n = 0: never read)
+                draws = [self._draw((B, 4, h, w), generator, torch.float32, device) for _ in range(int(num_inference_steps) - first_step - 1)]
+                if draws:
+                    step_noise = torch.stack(draws + [torch.zeros_like(draws[0])]).contiguous()
             if callback is not None:
                 self.scheduler.set_timesteps(num_inference_steps, device=device, **ts_kw)    # the callback's t, as on the modular path
             images = self._run_fused(image, mask_image, pose_map, warped_cloth if cloth_input_type == "warped" else None, pe, neg,
@@ -667,8 +684,8 @@ class StableDiffusionTryOnePipeline:
         return_device: hand back the device tensor (no host copy); out_uint8: the batch as uint8 [B,H,W,3] = numpy_to_pil's
         (images * 255).round() computed by the decode epilogue (ladi_tryon_run_u8); lanes: sample-group lanes of the UNet forward;
         step_noise: fp32 [steps, B, 4, h, w], the per-step noise of EulerAncestralDiscreteScheduler and of DDIM with eta > 0
-        (ladi_tryon_set_step_noise); eta: DDIM's eta (ladi_tryon_set_eta, DDIM only); guidance_table: one scale per evaluation, replaces
-        `guidance` (ladi_tryon_set_guidance_schedule; None = off); guidance_rescale: phi of ladi_tryon_set_guidance_rescale;
+        (ladi_tryon_set_step_noise; LCM and TCD with eta > 0 too, their last slab unread); eta: DDIM's eta or TCD's gamma
+        (ladi_tryon_set_eta); guidance_table: one scale per evaluation, replaces `guidance` (ladi_tryon_set_guidance_schedule; None = off); guidance_rescale: phi of ladi_tryon_set_guidance_rescale;
         callback / callback_steps: called as callback(i, self.scheduler.timesteps[i], latents) after every evaluation i with
         i % callback_steps == 0, latents an fp32 [B, 4, h, w] device tensor whose in-place edits the loop takes over
         (ladi_tryon_set_step_callback).  An exception in the callback aborts the run and is re-raised here.  When the decode's fp16-range

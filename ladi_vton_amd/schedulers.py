@@ -9,6 +9,10 @@ EulerAncestralDiscreteScheduler, mirrored here with the same SD2-inpainting conf
 epsilon prediction).  Their formulas are restated from the published algorithms as diffusers 0.14 ships them, from memory: diffusers is
 not installable here, so they are not pinned against it (like the other three).
 
+Few-step sampling of distilled weights: LCMScheduler and TCDScheduler (1 .. original_inference_steps evaluations), and
+timestep_spacing="trailing" on DDIMScheduler, EulerDiscreteScheduler and EulerAncestralDiscreteScheduler (1 .. 1000), restated the same way;
+the scheduler block of include/ladi_native.h is the contract for their timesteps and updates.
+
 The fused native loop (ladi_tryon_run) does not call .step(): it consumes the same tables on the device.  .step() here serves
 the module-by-module drop-in path and operates on small [B,4,h,w] tensors.
 """
@@ -20,6 +24,20 @@ import torch
 from . import _lib
 
 DDIM, PNDM, LMS, DPMPP, EULER, EULER_ANCESTRAL = 0, 1, 2, 3, 4, 5
+LCM, TCD = 7, 8
+# option bits of the scheduler code (include/ladi_native.h): bit 6 trailing timestep spacing (DDIM, Euler, Euler-ancestral), bits 12-21
+# original_inference_steps of LCM / TCD (0 = 50)
+TRAILING = 1 << 6
+
+
+def _spacing_bit(cls_name, timestep_spacing, default):
+    """timestep_spacing of DDIM / Euler / Euler-ancestral: the class's diffusers default or "trailing" (Turbo, Lightning, Hyper-SD weights)"""
+    if timestep_spacing == default:
+        return 0
+    if timestep_spacing == "trailing":
+        return TRAILING
+    raise NotImplementedError("%s: timestep_spacing=%r is not implemented (only %r, the default, and 'trailing')"
+                              % (cls_name, timestep_spacing, default))
 
 
 def _alphas_cumprod():
@@ -92,7 +110,14 @@ def _step_noise(shape, dtype, generator, device):
 
 
 class DDIMScheduler(_SchedulerBase):
+    """timestep_spacing="trailing": t_i = round_half_even(1000 - i * (1000 / n)) - 1 and, as in diffusers, prev = t - 1000 // n (n = 3: 666,
+    333, -1: not the next timestep); one step is allowed then (the default "leading" keeps n >= 2)"""
     kind = DDIM
+
+    def __init__(self, timestep_spacing="leading"):
+        super().__init__()
+        self.kind = DDIM | _spacing_bit("DDIMScheduler", timestep_spacing, "leading")
+        self.config.timestep_spacing = timestep_spacing
 
     def set_timesteps(self, num_inference_steps, device=None, first_step=0):
         """first_step > 0 (strength): the timesteps of steps first_step .. of the schedule"""
@@ -257,8 +282,10 @@ class _SigmaScheduler(_SchedulerBase):
     scale_model_input = sample / sqrt(sigma^2 + 1).  The tables come from the native builder (ladi_sched_lms), i.e. they are the very
     numbers the fused device loop uses."""
 
-    def __init__(self):
+    def __init__(self, timestep_spacing="linspace"):
         super().__init__()
+        self.kind = type(self).kind | _spacing_bit(type(self).__name__, timestep_spacing, "linspace")
+        self.config.timestep_spacing = timestep_spacing
         self.sigmas = None
         self.init_noise_sigma = float(((1 - self.alphas_cumprod) / self.alphas_cumprod).sqrt().max())   # as diffusers before set_timesteps
 
@@ -266,6 +293,18 @@ class _SigmaScheduler(_SchedulerBase):
         import ctypes
         n = int(num_inference_steps)
         first_step = self._check_first_step(n, first_step)
+        if self.kind & TRAILING:
+            # timestep_spacing="trailing": integer timesteps t_i = round_half_even(1000 - i * (1000 / n)) - 1 from the native builder,
+            # sigma = sqrt((1 - a) / a) at them in float64, held in fp32 (the builder's arithmetic), trailing 0; one step is allowed
+            tl = self._native_timesteps(n)
+            ac = [float(self.alphas_cumprod[t]) for t in tl]
+            sg = [float(torch.tensor(math.sqrt((1.0 - a) / a), dtype=torch.float32)) for a in ac] + [0.0]
+            self.num_inference_steps = n
+            self.timesteps = torch.tensor([float(t) for t in tl][first_step:], dtype=torch.float64, device=device)
+            self.sigmas = torch.tensor(sg[first_step:], dtype=torch.float32)
+            self._ts = [float(t) for t in tl][first_step:]
+            self.init_noise_sigma = float(max(sg))
+            return None
         ts = (ctypes.c_double * n)()
         sg = (ctypes.c_float * (n + 1))()
         cf = (ctypes.c_float * (4 * n))()
@@ -341,6 +380,9 @@ class LMSDiscreteScheduler(_SigmaScheduler):
     are the very numbers the fused device loop uses."""
     kind = LMS
 
+    def __init__(self):
+        super().__init__()      # (no timestep_spacing: trailing spacing is DDIM, Euler and Euler-ancestral only)
+
     def set_timesteps(self, num_inference_steps, device=None, first_step=0):
         """first_step > 0 (strength): steps first_step .. with the multistep weights of a history that starts empty there (orders 1, 2, ..)"""
         cf = self._set_sigma_tables(num_inference_steps, device, first_step)
@@ -362,3 +404,90 @@ class LMSDiscreteScheduler(_SigmaScheduler):
         for c, d in zip(self._coeffs[i][:min(i + 1, 4)], reversed(self.derivatives)):
             prev = prev + c * d
         return SimpleNamespace(prev_sample=prev.to(sample.dtype))
+
+
+class _FewStepScheduler(_SchedulerBase):
+    """what LCMScheduler and TCDScheduler share: the timesteps of a distilled model.  With O = original_inference_steps and k = 1000 // O,
+    t_i = (O - floor(i * (O / n))) * k - 1, i * (O / n) evaluated as numpy.linspace(0, O, n, endpoint=False) does (O = 50, n = 4: 999, 759,
+    499, 259); 1 <= n <= O.  They come from the native builder (ladi_sched_timesteps), i.e. they are the fused loop's.  first_step > 0
+    (strength) runs the tail of the n-step list like every other scheduler here -- not diffusers' set_timesteps(strength=), which spaces
+    the n steps anew over the shortened range.  Restated from the published algorithms as diffusers ships them, from memory: not pinned
+    against diffusers."""
+    _kind = None
+
+    def __init__(self, original_inference_steps=50):
+        o = int(original_inference_steps)
+        if not 1 <= o <= 1000:
+            raise ValueError("original_inference_steps must be in [1, 1000], got %r" % (original_inference_steps,))
+        super().__init__()
+        self.config.original_inference_steps = o
+        # scheduler code (include/ladi_native.h): bits 12-21 original_inference_steps, 0 = the default 50
+        self.kind = self._kind | ((o if o != 50 else 0) << 12)
+
+    def set_timesteps(self, num_inference_steps, device=None, first_step=0):
+        n = int(num_inference_steps)
+        first_step = self._check_first_step(n, first_step)
+        self.num_inference_steps = n
+        self._ts = self._native_timesteps(n)[first_step:]
+        self.timesteps = torch.tensor(self._ts, dtype=torch.int64, device=device)
+
+    def _at(self, timestep):
+        """-> (index of the timestep in this run, is it the last, a_t)"""
+        t = int(timestep)
+        i = self._ts.index(t)
+        return i, i == len(self._ts) - 1, float(self.alphas_cumprod[t])
+
+
+class LCMScheduler(_FewStepScheduler):
+    """diffusers LCMScheduler (latent consistency models), epsilon prediction, timestep_scaling 10, sigma_data 0.5: with s = 10 t,
+    c_skip = 0.25 / (s^2 + 0.25), c_out = s / sqrt(s^2 + 0.25) and x0 = (x - sqrt(1 - a_t) eps) / sqrt(a_t), denoised = c_out x0 + c_skip x;
+    every evaluation but the last returns sqrt(a_p) denoised + sqrt(1 - a_p) noise at a_p = alphas_cumprod[t_{i+1}] with one batch-shaped
+    fp32 draw from `generator`, the last returns denoised and draws nothing.  The fused loop takes the same evaluations - 1 draws, made up
+    front in the same generator order (ladi_tryon_set_step_noise; the last slab is zeros and never read)."""
+    _kind = LCM
+
+    def __init__(self, original_inference_steps=50, timestep_scaling=10.0):
+        if float(timestep_scaling) != 10.0:
+            raise NotImplementedError("LCMScheduler: only timestep_scaling = 10 is implemented, got %r" % (timestep_scaling,))
+        super().__init__(original_inference_steps)
+        self.config.timestep_scaling = 10.0
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, **kw):
+        i, last, a_t = self._at(timestep)
+        s = 10.0 * int(timestep)
+        c_skip, c_out = 0.25 / (s * s + 0.25), s / math.sqrt(s * s + 0.25)
+        x, e = sample.float(), model_output.float()
+        x0 = (x - math.sqrt(1.0 - a_t) * e) / math.sqrt(a_t)
+        denoised = c_out * x0 + c_skip * x
+        prev = denoised
+        if not last:
+            a_p = float(self.alphas_cumprod[self._ts[i + 1]])
+            noise = _step_noise(tuple(model_output.shape), torch.float32, generator, sample.device)
+            prev = math.sqrt(a_p) * denoised + math.sqrt(1.0 - a_p) * noise
+        return SimpleNamespace(prev_sample=prev.to(sample.dtype), denoised=denoised.to(sample.dtype))
+
+
+class TCDScheduler(_FewStepScheduler):
+    """diffusers TCDScheduler (trajectory consistency distillation), epsilon prediction; step()'s `eta` is the paper's gamma in [0, 1]:
+    t_prev = t_{i+1} (0 after the last timestep), t_s = floor((1 - gamma) t_prev), x_s = sqrt(a_s) x0 + sqrt(1 - a_s) eps with
+    x0 = (x - sqrt(1 - a_t) eps) / sqrt(a_t); with gamma > 0 every evaluation but the last returns sqrt(a_prev / a_s) x_s +
+    sqrt(1 - a_prev / a_s) noise with one batch-shaped fp32 draw from `generator`; otherwise x_s, and nothing is drawn (gamma = 0 is a
+    deterministic DDIM jump between the scheduler's own timesteps, the last one to t = 0).  The fused loop reads gamma from
+    ladi_tryon_set_eta, in fp32 as the C ABI carries it: step() rounds it the same way."""
+    _kind = TCD
+
+    def step(self, model_output, timestep, sample, eta=0.3, generator=None, return_dict=True, **kw):
+        gamma = float(torch.tensor(float(eta), dtype=torch.float32))
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError("TCDScheduler.step: eta (gamma) has to be in [0, 1] but is %r." % (eta,))
+        i, last, a_t = self._at(timestep)
+        t_prev = 0 if last else self._ts[i + 1]
+        t_s = int(math.floor((1.0 - gamma) * t_prev))
+        a_s, a_prev = float(self.alphas_cumprod[t_s]), float(self.alphas_cumprod[t_prev])
+        x, e = sample.float(), model_output.float()
+        x0 = (x - math.sqrt(1.0 - a_t) * e) / math.sqrt(a_t)
+        prev = math.sqrt(a_s) * x0 + math.sqrt(1.0 - a_s) * e
+        if gamma > 0.0 and not last:
+            noise = _step_noise(tuple(model_output.shape), torch.float32, generator, sample.device)
+            prev = math.sqrt(a_prev / a_s) * prev + math.sqrt(max(1.0 - a_prev / a_s, 0.0)) * noise
+        return SimpleNamespace(prev_sample=prev.to(sample.dtype), pred_noised_sample=prev.to(sample.dtype))
