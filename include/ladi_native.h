@@ -865,6 +865,59 @@ int ladi_op_lora_merge(const void* base, void* W, long long pitch, int cin, int 
                        int n_adapters, const float* const* up, const float* const* down, const int* rank, const float* scale,
                        unsigned* nonfinite, void* stream);
 
+/* ---- Token merging (DESIGN.md "Token merging"; tomesd.apply_patch, bipartite_soft_matching_random2d) ----
+ * In the transformer blocks of the first max_downsample levels of the UNet (1: the full-resolution level, down_blocks.0 and up_blocks.3; 2:
+ * also the half-resolution level) the selected sub-layers run over T - r rows, r = min(int(T * ratio), Ns).  The T = h w tokens of a block
+ * are split into one dst token per full sy x sx cell -- at in-cell offset 0, or with use_rand at splitmix64(seed * 2^32 + cell) mod (sx sy),
+ * computed on the host, the same for every block of a level and every evaluation (tomesd redraws per block and evaluation) -- and Ns src
+ * tokens (every other token, leftover rows and columns of an odd side included).  Every src is matched to the dst with the largest cosine
+ * similarity of the block's token input (the output of proj_in; fp16 unit rows, fp32 accumulation; ties to the lower dst), the r src with
+ * the largest score (ties to the lower src, NaN as -inf) are averaged into their dst (fp32, ascending src order, one rounding), and a merged
+ * sub-layer is x = u(f(m(norm x))) + x over the rows [unmerged src, ascending ; dst]: attn1 with merge_attn, attn2 (its queries, and the
+ * IP-Adapter image term's) with merge_crossattn, the feed-forward with merge_mlp, one plan per block.  Sticky per UNet, off by default;
+ * holds for the stand-alone forwards, the cached forms and the fused loop (whose graphs are keyed on it).  cfg NULL or ratio 0 switches it
+ * off: the forward then launches exactly the plain forward.  A block whose level gives r = 0 runs the plain path.
+ * Refused with a message (-1, nothing changed): ratio outside [0, 1) or not finite, sx or sy other than 2, max_downsample other than 1 or 2,
+ * all three merge flags off with ratio > 0.  A forward refuses (with a message) a level of more than 4096 dst tokens or a block width that
+ * is no multiple of 64 or above 960, and perturbed (PAG) samples in a block that merges. */
+typedef struct {
+    double ratio;
+    int max_downsample, sx, sy, use_rand;
+    unsigned seed;
+    int merge_attn, merge_crossattn, merge_mlp;
+} ladi_tome_config;
+int ladi_tome_config_check(const ladi_tome_config* cfg);                    /* host only: 0, or -1 with the refusal as the last error */
+int ladi_unet_set_token_merging(ladi_unet* u, const ladi_tome_config* cfg);
+int ladi_unet_token_merging(const ladi_unet* u, ladi_tome_config* cfg_out);  /* 1 on, 0 off (cfg_out then holds the defaults), -1 null handle */
+/* the merged transformer blocks, in execution order; blocks_out (may be NULL) receives their indices in PAG's block numbering */
+int ladi_unet_tome_block_count(const ladi_unet* u, int* blocks_out, int cap);
+/* out_row of merged block `block` (0 .. count - 1) as the last forward left it: n * T ints for the n samples of the context batch, entry
+ * [s][p] the row of the merged sequence that token p of sample s reads (its own row for an unmerged src, Nu + j for dst j and every src
+ * merged into it) -- also what a visualisation of the merges needs.  Synchronises the device.  Returns n * T (copied when cap is at least
+ * that), 0 when the block merges nothing at the last size, < 0 on error. */
+int ladi_unet_tome_read_plan(ladi_unet* u, int block, int* out_row_host, int cap);
+/* host only: the partition of h x w tokens.  Returns Nd = (h / sy) * (w / sx) and, with both pointers given and cap >= max(Nd, h w - Nd),
+ * the token positions of the src (h w - Nd of them) and of the dst tokens, each ascending; -1 on a refusal. */
+int ladi_tome_tables(int h, int w, int sx, int sy, int use_rand, unsigned seed, int* src_pos, int* dst_pos, int cap);
+int ladi_tome_merge_count(int T, int Ns, double ratio);                     /* host only: r, or -1 for a ratio outside [0, 1) */
+/* the kernels on their own (csrc/tome.hip).  Tables and plans are device int32; n samples of T = Ns + Nd tokens, rows of C halves.
+ * match: prep + match over the metric x (row stride ld, per-sample stride sx elements): score[n][Ns] fp32, node[n][Ns]; C % 64 == 0, C <= 960;
+ *   workspace of ladi_op_tome_match_workspace_bytes(n, Ns, Nd, C) bytes, 16-byte aligned.
+ * plan: out_row[n][T] and plan[n][ladi_op_tome_plan_ints(Ns, Nd, r)] = seg_off (Nd + 1) | unm_pos (Ns - r) | seg_src (r) | scratch (r);
+ *   1 <= r <= Ns, Nd <= 4096.
+ * merge: y[n][T - r] from x with such a plan (r = 0 allowed: a permutation); unmerge_add: out[s][p] = fp16(y[s][out_row[s][p]] + res[s][p]).
+ * C % 8 == 0, strides multiples of 8 and >= C, 16-byte aligned bases: anything else is refused with a message and nothing is launched. */
+long long ladi_op_tome_match_workspace_bytes(int n, int Ns, int Nd, int C);
+long long ladi_op_tome_plan_ints(int Ns, int Nd, int r);
+int ladi_op_tome_match(const void* x, int ld, long long sx, const int* src_pos, const int* dst_pos, int n, int T, int Ns, int Nd, int C,
+                       void* workspace, float* score, int* node, void* stream);
+int ladi_op_tome_plan(const float* score, const int* node, const int* src_pos, const int* dst_pos, int n, int T, int Ns, int Nd, int r,
+                      int* out_row, int* plan, void* stream);
+int ladi_op_tome_merge(const void* x, int ldx, long long sx, const int* dst_pos, const int* plan, int n, int T, int Ns, int Nd, int r, int C,
+                       void* y, int ldy, long long sy, void* stream);
+int ladi_op_tome_unmerge_add(const void* y, int ldy, long long sy, const void* res, int ldr, long long sr, const int* out_row, int n, int T,
+                             int Tm, int C, void* out, int ldo, long long so, void* stream);
+
 /* ---- fp16 range probe (opt-in; with no probe attached nothing changes: same launches, same captured graph, same bits) ----
  * A probe records, for every named activation of the modules it is attached to, the largest finite |x| and the number of inf / NaN
  * elements the fp16 tensor held (one extra read of the tensor per point; values accumulate -- max / sum -- until ladi_probe_reset).

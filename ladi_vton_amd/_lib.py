@@ -67,6 +67,11 @@ class TryOnInputs(Structure):
                 ("no_pose", c_int), ("use_graph", c_int), ("alphas_cumprod_host", c_void_p)]
 
 
+class ToMeConfig(Structure):
+    _fields_ = [("ratio", ctypes.c_double), ("max_downsample", c_int), ("sx", c_int), ("sy", c_int), ("use_rand", c_int),
+                ("seed", ctypes.c_uint), ("merge_attn", c_int), ("merge_crossattn", c_int), ("merge_mlp", c_int)]
+
+
 class IGemmDesc(Structure):
     _fields_ = [("src0", c_void_p), ("src1", c_void_p), ("C0", c_int), ("C1", c_int), ("ld0", c_int), ("ld1", c_int),
                 ("Hs", c_int), ("Ws", c_int), ("Ho", c_int), ("Wo", c_int), ("P", c_int), ("ksize", c_int), ("stride", c_int),
@@ -136,6 +141,19 @@ SIGNATURES = {
     "ladi_tryon_set_ip_adapter": (c_int, [_P, _P, _P]),
     "ladi_op_ip_attn_add": (c_int, [_P, c_int, c_longlong, _P, c_int, c_longlong, _P, c_int, c_longlong, _P, c_int, c_longlong, c_int, c_int,
                                     c_int, c_int, c_float, _P]),
+    "ladi_tome_config_check": (c_int, [POINTER(ToMeConfig)]),
+    "ladi_unet_set_token_merging": (c_int, [_P, POINTER(ToMeConfig)]),
+    "ladi_unet_token_merging": (c_int, [_P, POINTER(ToMeConfig)]),
+    "ladi_unet_tome_block_count": (c_int, [_P, POINTER(c_int), c_int]),
+    "ladi_unet_tome_read_plan": (c_int, [_P, c_int, _P, c_int]),
+    "ladi_tome_tables": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.c_uint, _P, _P, c_int]),
+    "ladi_tome_merge_count": (c_int, [c_int, c_int, ctypes.c_double]),
+    "ladi_op_tome_match_workspace_bytes": (c_longlong, [c_int, c_int, c_int, c_int]),
+    "ladi_op_tome_plan_ints": (c_longlong, [c_int, c_int, c_int]),
+    "ladi_op_tome_match": (c_int, [_P, c_int, c_longlong, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "ladi_op_tome_plan": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "ladi_op_tome_merge": (c_int, [_P, c_int, c_longlong, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_longlong, _P]),
+    "ladi_op_tome_unmerge_add": (c_int, [_P, c_int, c_longlong, _P, c_int, c_longlong, _P, c_int, c_int, c_int, c_int, _P, c_int, c_longlong, _P]),
     "ladi_vae_create": (_P, [POINTER(VAEConfig), _P]),
     "ladi_vae_destroy": (None, [_P]),
     "ladi_vae_encode": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, POINTER(_P), _P]),

@@ -150,6 +150,107 @@ int ladi_unet_set_pag_layers(ladi_unet* u, unsigned layer_mask) {
 }
 unsigned ladi_unet_pag_layers(const ladi_unet* u) { return u ? u->u.pag_mask : 0u; }
 
+// ------------------------------------------------------------------------------------------------ token merging (runtime.h ToMe, tome.hip)
+static ToMeCfg tome_from(const ladi_tome_config& c) {
+    ToMeCfg t;
+    t.ratio = c.ratio; t.max_downsample = c.max_downsample; t.sx = c.sx; t.sy = c.sy; t.use_rand = c.use_rand; t.seed = c.seed;
+    t.merge_attn = c.merge_attn; t.merge_crossattn = c.merge_crossattn; t.merge_mlp = c.merge_mlp;
+    return t;
+}
+int ladi_tome_config_check(const ladi_tome_config* cfg) {
+    if (!cfg) { set_error("ladi_tome_config_check: null configuration"); return -1; }
+    const std::string e = tome_cfg_error(tome_from(*cfg));
+    if (!e.empty()) { set_error("ladi_tome_config_check: " + e); return -1; }
+    return 0;
+}
+int ladi_unet_set_token_merging(ladi_unet* u, const ladi_tome_config* cfg) {
+    if (!u) { set_error("ladi_unet_set_token_merging: null handle"); return -1; }
+    try {
+        if (cfg) { const ToMeCfg t = tome_from(*cfg); u->u.tome_set(&t); }
+        else u->u.tome_set(nullptr);
+    } catch (const std::exception& e) { set_error(std::string("ladi_unet_set_token_merging: ") + e.what()); return -1; }
+    return 0;
+}
+int ladi_unet_token_merging(const ladi_unet* u, ladi_tome_config* cfg_out) {
+    if (!u) { set_error("ladi_unet_token_merging: null handle"); return -1; }
+    if (cfg_out) {
+        const ToMeCfg& t = u->u.tome.cfg;
+        cfg_out->ratio = t.ratio; cfg_out->max_downsample = t.max_downsample; cfg_out->sx = t.sx; cfg_out->sy = t.sy; cfg_out->use_rand = t.use_rand;
+        cfg_out->seed = t.seed; cfg_out->merge_attn = t.merge_attn; cfg_out->merge_crossattn = t.merge_crossattn; cfg_out->merge_mlp = t.merge_mlp;
+    }
+    return u->u.tome.on ? 1 : 0;
+}
+int ladi_unet_tome_block_count(const ladi_unet* u, int* blocks_out, int cap) {
+    if (!u) { set_error("ladi_unet_tome_block_count: null handle"); return -1; }
+    const std::vector<int> b = u->u.tome_blocks();
+    for (int i = 0; blocks_out && i < (int)b.size() && i < cap; ++i) blocks_out[i] = b[i];
+    return (int)b.size();
+}
+int ladi_unet_tome_read_plan(ladi_unet* u, int block, int* out_row_host, int cap) {
+    return guarded("ladi_unet_tome_read_plan", [&]() {
+        if (!u) throw std::runtime_error("null handle");
+        const std::vector<int> b = u->u.tome_blocks();
+        if (block < 0 || block >= (int)b.size()) throw std::runtime_error("block " + std::to_string(block) + " is outside the " + std::to_string(b.size()) + " merged blocks");
+        const ToMeLevel& l = u->u.tome.lv[u->u.xf_level(b[block])];
+        const int* src = u->u.tome.out_row[b[block]];
+        if (!src || l.r == 0) return 0;
+        const int n = u->u.ctx_n < l.cap_n ? u->u.ctx_n : l.cap_n;
+        const long long cnt = (long long)n * l.T;
+        if (cnt > 0x7fffffffLL) throw std::runtime_error("the plan has more than 2^31 entries");
+        if (out_row_host && cap >= cnt && cnt > 0) {
+            HIP_OK(hipDeviceSynchronize());
+            HIP_OK(hipMemcpy(out_row_host, src, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost));
+        }
+        return (int)cnt;
+    });
+}
+int ladi_tome_tables(int h, int w, int sx, int sy, int use_rand, unsigned seed, int* src_pos, int* dst_pos, int cap) {
+    const int rc = ladi_tome_tables_host(h, w, sx, sy, use_rand, seed, src_pos, dst_pos, cap);
+    if (rc < 0) set_error("ladi_tome_tables: refused: h or w < 1, sx or sy other than 2, one table pointer without the other, or cap below max(Nd, h w - Nd)");
+    return rc;
+}
+int ladi_tome_merge_count(int T, int Ns, double ratio) {
+    const int rc = ladi_tome_count_host(T, Ns, ratio);
+    if (rc < 0) set_error("ladi_tome_merge_count: T < 1, Ns < 0 or a ratio outside [0, 1)");
+    return rc;
+}
+static int tome_op_rc(const char* what, int rc) {
+    if (rc == -1) set_error(std::string(what) + ": refused: a null pointer or a bad count (n, T, Ns + Nd != T, r)");
+    else if (rc == -2) set_error(std::string(what) + ": refused: the channel count C (match: a multiple of 64 up to 960; merge / unmerge: a multiple of 8)");
+    else if (rc == -3) set_error(std::string(what) + ": refused: a row stride below C or not a multiple of 8, a sample stride that is not a multiple of 8, or a base that is not 16-byte aligned");
+    else if (rc == -4) set_error(std::string(what) + ": refused: more than 4096 dst tokens");
+    else if (rc) set_error(std::string(what) + ": launch failed rc=" + std::to_string(rc));
+    return rc;
+}
+long long ladi_op_tome_match_workspace_bytes(int n, int Ns, int Nd, int C) {
+    if (n < 1 || Ns < 1 || Nd < 1 || C < 1) return -1;
+    return (long long)n * ((long long)ladi_tome_pad_src(Ns) + ladi_tome_pad_dst(Nd)) * C * (long long)sizeof(h16);
+}
+long long ladi_op_tome_plan_ints(int Ns, int Nd, int r) { return ladi_tome_plan_ints(Ns, Nd, r); }
+int ladi_op_tome_match(const void* x, int ld, long long sx, const int* src_pos, const int* dst_pos, int n, int T, int Ns, int Nd, int C,
+                       void* workspace, float* score, int* node, void* stream) {
+    if (!workspace || n < 1 || Ns < 1 || C < 1) return tome_op_rc("ladi_op_tome_match", -1);
+    h16* A = reinterpret_cast<h16*>(workspace);
+    h16* B = A + (size_t)n * ladi_tome_pad_src(Ns) * C;
+    int rc = ladi_launch_tome_prep(reinterpret_cast<const h16*>(x), ld, sx, src_pos, dst_pos, n, T, Ns, Nd, C, A, B, S(stream));
+    if (!rc) rc = score && node ? ladi_launch_tome_match(A, B, n, Ns, Nd, C, score, node, S(stream)) : -1;
+    return tome_op_rc("ladi_op_tome_match", rc);
+}
+int ladi_op_tome_plan(const float* score, const int* node, const int* src_pos, const int* dst_pos, int n, int T, int Ns, int Nd, int r,
+                      int* out_row, int* plan, void* stream) {
+    return tome_op_rc("ladi_op_tome_plan", ladi_launch_tome_plan(score, node, src_pos, dst_pos, n, T, Ns, Nd, r, out_row, plan, S(stream)));
+}
+int ladi_op_tome_merge(const void* x, int ldx, long long sx, const int* dst_pos, const int* plan, int n, int T, int Ns, int Nd, int r, int C,
+                       void* y, int ldy, long long sy, void* stream) {
+    return tome_op_rc("ladi_op_tome_merge", ladi_launch_tome_merge(reinterpret_cast<const h16*>(x), ldx, sx, dst_pos, plan, n, T, Ns, Nd, r, C,
+                                                                   reinterpret_cast<h16*>(y), ldy, sy, S(stream)));
+}
+int ladi_op_tome_unmerge_add(const void* y, int ldy, long long sy, const void* res, int ldr, long long sr, const int* out_row, int n, int T,
+                             int Tm, int C, void* out, int ldo, long long so, void* stream) {
+    return tome_op_rc("ladi_op_tome_unmerge_add", ladi_launch_tome_unmerge_add(reinterpret_cast<const h16*>(y), ldy, sy, reinterpret_cast<const h16*>(res),
+                                                                               ldr, sr, out_row, n, T, Tm, C, reinterpret_cast<h16*>(out), ldo, so, S(stream)));
+}
+
 // ------------------------------------------------------------------------------------------------ LoRA (runtime_lora.cpp)
 int ladi_unet_lora_load(ladi_unet* u, const char* name, const ladi_weights* ws) {
     return guarded("ladi_unet_lora_load", [&]() {

@@ -286,6 +286,33 @@ int ladi_launch_ip_attn_add(const h16* q, int ldq, long long sq, const h16* k, i
 // strides multiples of 8, bases 16-byte aligned, else -1
 int ladi_launch_ip_scaled_add(const h16* x, int ldx, h16* o, int ldo, long long rows, int C, float scale, hipStream_t st);
 
+// ---- tome.hip: token merging (ToMe).  Tables: src_pos[Ns] / dst_pos[Nd], token positions in ascending order (ladi_tome_tables_host, which
+// returns Nd; both pointers null: only the count; -1: a size < 1, sx / sy other than 2 or cap too small).  Panels: fp16 src [n][pad_src(Ns)][C]
+// and dst [n][pad_dst(Nd)][C], normalised rows, zero rows behind Ns / Nd.  Plan buffer: plan_ints(Ns, Nd, r) ints per sample,
+// [seg_off (Nd + 1) | unm_pos (Ns - r) | seg_src (r) | scratch (r)] (positions are token positions, seg_off offsets into seg_src).
+// Refusals (nothing launched): -1 a null pointer or a bad count (Ns + Nd != T, r outside [1, Ns] -- merge accepts r = 0 --, n > 65535 where
+// n is a grid dimension); -2 the channel count (prep / match: C % 64, C <= 960; merge / unmerge: C % 8); -3 a row stride below C or not a
+// multiple of 8, a per-sample stride that is not a multiple of 8, a base that is not 16-byte aligned; -4 plan: Nd > 4096
+int ladi_tome_tables_host(int h, int w, int sx, int sy, int use_rand, unsigned seed, int* src_pos, int* dst_pos, int cap);
+int ladi_tome_count_host(int T, int Ns, double ratio);      // r = min(int(T * ratio), Ns); -1: ratio outside [0, 1) or not finite
+int ladi_tome_pad_src(int Ns);
+int ladi_tome_pad_dst(int Nd);
+long long ladi_tome_plan_ints(int Ns, int Nd, int r);
+// x: the metric, [n][T] rows of C halves (row stride ld, per-sample stride sx)
+int ladi_launch_tome_prep(const h16* x, int ld, long long sx, const int* src_pos, const int* dst_pos, int n, int T, int Ns, int Nd, int C,
+                          h16* A, h16* B, hipStream_t st);
+// score[n][Ns] = max_j <a_i, b_j> (fp32 accumulation on MFMA), node[n][Ns] = the lowest j that reaches it
+int ladi_launch_tome_match(const h16* A, const h16* B, int n, int Ns, int Nd, int C, float* score, int* node, hipStream_t st);
+// the r src with the largest score (ties to the lower src, NaN as -inf) are merged into dst node[i]: out_row[n][T] and the plan buffer
+int ladi_launch_tome_plan(const float* score, const int* node, const int* src_pos, const int* dst_pos, int n, int T, int Ns, int Nd, int r,
+                          int* out_row, int* plan, hipStream_t st);
+// y[n][T - r]: unmerged src rows (copies), then (x[dst_j] + sum of its merged src in ascending order) / (1 + count), fp32, one rounding
+int ladi_launch_tome_merge(const h16* x, int ldx, long long sx, const int* dst_pos, const int* plan, int n, int T, int Ns, int Nd, int r, int C,
+                           h16* y, int ldy, long long sy, hipStream_t st);
+// out[s][p] = fp16(float(y[s][out_row[s][p]]) + float(res[s][p])); an out_row entry outside [0, Tm) leaves its row unwritten
+int ladi_launch_tome_unmerge_add(const h16* y, int ldy, long long sy, const h16* res, int ldr, long long sr, const int* out_row, int n, int T,
+                                 int Tm, int C, h16* out, int ldo, long long so, hipStream_t st);
+
 // ---- lora.hip: LoRA merge of one block of rows of one packed weight, from the pristine copy `base` into the live weight `W` (both fp16
 // [rows of the weight][taps][cin_pad], row pitch `pitch` halves):
 //   W[map(o)][t][i] = fp16(float(base[map(o)][t][i]) + sum_a scale[a] * sum_r up[a][o][r] * down[a][r][t][i]),  o < rows, i < cin

@@ -233,6 +233,33 @@ struct FreeU {
 // blocks selected by UNet::pag_mask a perturbed sample's self-attention map is the identity (pag.hip); everything else is untouched
 enum { PAG_NONE = 0x7fffffff };
 
+// Token merging (tomesd.apply_patch; ladi_unet_set_token_merging, sticky, off by default; tome.hip, DESIGN.md "Token merging").  In the
+// transformer blocks of the first max_downsample levels the selected sub-layers run over T - r rows: one plan per block and forward, from
+// the block's token input (the output of proj_in), reused by all its merged sub-layers.  Level state (the dst / src tables, one persistent
+// out_row buffer per block of the level) is built by a planning pass when the configuration, the level's size or the sample capacity is
+// first seen -- never by a real pass, so never inside a capture -- and `gen` counts the rebuilds: a captured graph is keyed on the
+// configuration and on gen.  r = 0 (ratio 0, or a level of a single row or column): the block runs the plain path launch for launch
+struct ToMeCfg {
+    double ratio = 0.0;
+    int max_downsample = 1, sx = 2, sy = 2, use_rand = 0;
+    unsigned seed = 0;
+    int merge_attn = 1, merge_crossattn = 0, merge_mlp = 0;
+};
+struct ToMeLevel {
+    int h = 0, w = 0, T = 0, Ns = 0, Nd = 0, r = 0, cap_n = 0;
+    int* src_pos = nullptr; int* dst_pos = nullptr;       // device tables
+    void* mem = nullptr;                                  // one allocation: the tables and the level's out_row buffers (freed by the UNet)
+};
+struct ToMe {
+    bool on = false;
+    ToMeCfg cfg;
+    ToMeLevel lv[2];
+    int* out_row[32] = {};                                // per transformer block (PAG's bit numbering): [cap_n][T] of its level
+    unsigned long long gen = 0;
+};
+// the refusal of a configuration, or an empty string (ratio 0 is valid: off)
+std::string tome_cfg_error(const ToMeCfg& c);
+
 // LoRA (runtime_lora.cpp; DESIGN.md "LoRA").  A target is one diffusers conv / linear module: a block of rows of one packed weight.  The
 // concatenated weights (qkv, kv2, temb_all) hold one target per member module, the GEGLU projection is one target with the interleaved
 // row map.  Adapters keep their factors on the device in fp32; set_adapters re-merges every touched block from the pristine copy of its
@@ -292,6 +319,14 @@ struct UNet {
     // diffusers.  Without perturbed samples in a forward (pag_first = PAG_NONE) the mask has no effect
     unsigned pag_mask = 0;
     int pag_layer_count() const { return 6 * cfg.layers_per_block + 4; }
+    // token merging (ToMe above).  xf_level: 0 .. 3, the resolution level of transformer block `bit`; tome_blocks: the bits of the blocks
+    // the configuration merges, in execution order; tome_prepare: the level state for a forward of samples [0, need_n) at h x w -- a
+    // planning pass builds it (synchronises the device and bumps gen when something is freed), a real pass only checks it and throws
+    ToMe tome;
+    void tome_set(const ToMeCfg* c);                          // throws on a refused configuration, nothing changed; null / ratio 0: off
+    int xf_level(int bit) const;
+    std::vector<int> tome_blocks() const;
+    const ToMeLevel* tome_prepare(int level, int h, int w, int need_n, bool dry);
     DevPool pool;
     DConv conv_in, conv_out, time_l1, time_l2, temb_all;
     DNorm norm_out;
@@ -590,6 +625,9 @@ struct GraphKey {
     // lives in the same pool) and the bits of the per-block scales, which the captured launches carry as arguments and which decide whether a
     // block launches the image term at all
     int ip_on, ip_N; const void* ip_kv; unsigned ip_scale[32];
+    // ... and with token merging: on / off and, when on, every field of the configuration (the ratio by its bits) and the generation of the
+    // UNet's level state, whose tables and out_row buffers the captured launches address
+    int tome_on; int tome_opts[8]; unsigned long long tome_ratio, tome_gen;
 };
 // The per-evaluation plan of one run: host arithmetic only (plan_evals; ladi_tryon_plan_forms runs it without a GPU)
 struct EvalPlan {

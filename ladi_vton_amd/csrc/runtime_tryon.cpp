@@ -514,6 +514,12 @@ void TryOn::denoise(Run& r) {
             auto blocks = unet->xf_blocks();
             for (size_t i = 0; i < blocks.size() && i < 32; ++i) std::memcpy(&key.ip_scale[i], &blocks[i].first->ip_scale, 4);
         }
+        if (unet->tome.on) {
+            const ToMeCfg& tc = unet->tome.cfg;
+            const int opts[8] = {tc.max_downsample, tc.sx, tc.sy, tc.use_rand, (int)tc.seed, tc.merge_attn, tc.merge_crossattn, tc.merge_mlp};
+            key.tome_on = 1; std::memcpy(key.tome_opts, opts, sizeof(opts));
+            std::memcpy(&key.tome_ratio, &tc.ratio, sizeof(double)); key.tome_gen = unet->tome.gen;
+        }
         if (std::memcmp(&key, &graph_key, sizeof(key))) { graphs.clear(); std::memcpy(&graph_key, &key, sizeof(key)); }
         // the host knows the schedule and picks the graph; the values come from the device table.  A form that this run has not yet
         // run eagerly and that has no graph runs eagerly once (see above), its next evaluation captures

@@ -105,6 +105,89 @@ UNet::~UNet() {
     if (stats) (void)hipFree(stats);
     if (in_buf) (void)hipFree(in_buf);
     if (fc_buf) (void)hipFree(fc_buf);
+    for (auto& l : tome.lv) if (l.mem) (void)hipFree(l.mem);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Token merging (runtime.h ToMe; tome.hip)
+// ------------------------------------------------------------------------------------------------
+std::string tome_cfg_error(const ToMeCfg& c) {
+    if (!std::isfinite(c.ratio) || c.ratio < 0.0 || c.ratio >= 1.0) return "ratio " + std::to_string(c.ratio) + " is outside [0, 1) or not finite";
+    if (c.sx != 2 || c.sy != 2) return "sx = " + std::to_string(c.sx) + ", sy = " + std::to_string(c.sy) + ": only 2 x 2 cells are supported";
+    if (c.max_downsample != 1 && c.max_downsample != 2) return "max_downsample " + std::to_string(c.max_downsample) + " is not 1 or 2";
+    if (c.ratio > 0.0 && !c.merge_attn && !c.merge_crossattn && !c.merge_mlp) return "merge_attn, merge_crossattn and merge_mlp are all off with ratio > 0";
+    return std::string();
+}
+
+void UNet::tome_set(const ToMeCfg* c) {
+    ToMeCfg n;
+    if (c) {
+        const std::string e = tome_cfg_error(*c);
+        if (!e.empty()) throw std::runtime_error(e);
+        n = *c;
+        n.use_rand = c->use_rand ? 1 : 0; n.merge_attn = c->merge_attn ? 1 : 0; n.merge_crossattn = c->merge_crossattn ? 1 : 0; n.merge_mlp = c->merge_mlp ? 1 : 0;
+    }
+    // a forward still in flight reads the tables and writes the out_row buffers
+    if (tome.lv[0].mem || tome.lv[1].mem) HIP_OK(hipDeviceSynchronize());
+    for (auto& l : tome.lv) { if (l.mem) (void)hipFree(l.mem); l = ToMeLevel(); }
+    for (auto& p : tome.out_row) p = nullptr;
+    tome.cfg = n;
+    tome.on = c && n.ratio > 0.0;
+    ++tome.gen;
+}
+
+int UNet::xf_level(int bit) const {
+    const int L = cfg.layers_per_block;
+    if (bit < 3 * L) return bit / L;
+    if (bit == 3 * L) return 3;
+    return 2 - (bit - 3 * L - 1) / (L + 1);
+}
+
+std::vector<int> UNet::tome_blocks() const {
+    std::vector<int> v;
+    if (!tome.on) return v;
+    for (int b = 0; b < pag_layer_count(); ++b)
+        if (xf_level(b) < tome.cfg.max_downsample) v.push_back(b);
+    return v;
+}
+
+const ToMeLevel* UNet::tome_prepare(int level, int h, int w, int need_n, bool dry) {
+    ToMeLevel& l = tome.lv[level];
+    if (l.h == h && l.w == w && l.cap_n >= need_n) return &l;
+    if (!dry) throw std::runtime_error("token merging: no planning pass has seen " + std::to_string(need_n) + " samples of " + std::to_string(h) + " x " +
+                                       std::to_string(w) + " tokens on level " + std::to_string(level));
+    const ToMeCfg& c = tome.cfg;
+    ToMeLevel nl;
+    nl.h = h; nl.w = w; nl.T = h * w; nl.cap_n = need_n;
+    nl.Nd = ladi_tome_tables_host(h, w, c.sx, c.sy, c.use_rand, c.seed, nullptr, nullptr, 0);
+    if (nl.Nd < 0) throw std::runtime_error("token merging: " + std::to_string(h) + " x " + std::to_string(w) + " tokens cannot be partitioned");
+    nl.Ns = nl.T - nl.Nd;
+    nl.r = nl.Nd > 0 ? ladi_tome_count_host(nl.T, nl.Ns, c.ratio) : 0;
+    if (nl.r > 0 && nl.Nd > 4096)
+        throw std::runtime_error("token merging: " + std::to_string(h) + " x " + std::to_string(w) + " tokens give " + std::to_string(nl.Nd) +
+                                 " dst tokens, the plan kernel holds at most 4096");
+    std::vector<int> bits;
+    for (int b = 0; b < pag_layer_count() && b < 32; ++b) if (xf_level(b) == level) bits.push_back(b);
+    if (l.mem) { HIP_OK(hipDeviceSynchronize()); (void)hipFree(l.mem); }
+    l = ToMeLevel();
+    for (int b : bits) tome.out_row[b] = nullptr;
+    ++tome.gen;
+    if (nl.r > 0) {
+        auto up = [](size_t ints) { return (ints * sizeof(int) + 255) & ~(size_t)255; };
+        const size_t tab = up((size_t)nl.Ns) + up((size_t)nl.Nd), rows = up((size_t)need_n * nl.T);
+        HIP_OK(hipMalloc(&nl.mem, tab + rows * bits.size()));
+        char* p = reinterpret_cast<char*>(nl.mem);
+        nl.src_pos = reinterpret_cast<int*>(p); nl.dst_pos = reinterpret_cast<int*>(p + up((size_t)nl.Ns));
+        std::vector<int> sp((size_t)nl.T), dp((size_t)nl.T);
+        (void)ladi_tome_tables_host(h, w, c.sx, c.sy, c.use_rand, c.seed, sp.data(), dp.data(), nl.T);
+        hipError_t e = hipMemcpy(nl.src_pos, sp.data(), (size_t)nl.Ns * sizeof(int), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(nl.dst_pos, dp.data(), (size_t)nl.Nd * sizeof(int), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(p + tab, 0, rows * bits.size());
+        if (e != hipSuccess) { (void)hipFree(nl.mem); throw std::runtime_error(std::string("token merging: table upload: ") + hipGetErrorString(e)); }
+        for (size_t k = 0; k < bits.size(); ++k) tome.out_row[bits[k]] = reinterpret_cast<int*>(p + tab + rows * k);
+    }
+    l = nl;
+    return &l;
 }
 
 int UNet::set_context(const h16* ehs, int n, int L, hipStream_t st) {
@@ -353,14 +436,65 @@ struct Fwd {
         c.check(ladi_launch_flash_attn64(a, c.st), "flash_attn64");
         return o;
     }
-    // bit: the block's index in execution order (UNet::pag_mask)
-    Act xf(const XfBlock& b, const Act& x, int bit) {
+    // Token merging of one block (runtime.h ToMe): the plan from the block's token input t0 -- prep, match, plan into the block's persistent
+    // out_row rows of this forward's samples and into a plan buffer of the arena, which lives until the block releases its mark
+    struct Merge { const ToMeLevel* l = nullptr; const int* plan = nullptr; const int* out_row = nullptr; int Tm = 0; };
+    Merge tome_plan(const ToMeLevel* l, const Act& t0, int bit) {
+        const int n = t0.n, C = t0.c;
+        if (C % 64 || C > 960) throw std::runtime_error("token merging: " + std::to_string(C) + " channels (the match kernel takes multiples of 64 up to 960)");
+        Merge m; m.l = l; m.Tm = l->T - l->r;
+        const long long ps = ladi_tome_plan_ints(l->Ns, l->Nd, l->r);
+        int* plan = reinterpret_cast<int*>(c.ar->alloc((size_t)n * ps * sizeof(int)));
+        h16* A = c.alloc_h16((size_t)n * ladi_tome_pad_src(l->Ns) * C);
+        h16* B = c.alloc_h16((size_t)n * ladi_tome_pad_dst(l->Nd) * C);
+        float* score = c.alloc_f32((size_t)n * l->Ns);
+        int* node = reinterpret_cast<int*>(c.ar->alloc((size_t)n * l->Ns * sizeof(int)));
+        m.plan = plan;
+        if (c.dry()) return m;
+        int* orow = u.tome.out_row[bit];
+        if (!orow) throw std::runtime_error("token merging: block " + std::to_string(bit) + " has no out_row buffer");
+        orow += (size_t)sample0 * l->T;
+        m.out_row = orow;
+        c.check(ladi_launch_tome_prep(t0.p, t0.ld, (long long)l->T * t0.ld, l->src_pos, l->dst_pos, n, l->T, l->Ns, l->Nd, C, A, B, c.st), "tome_prep");
+        c.check(ladi_launch_tome_match(A, B, n, l->Ns, l->Nd, C, score, node, c.st), "tome_match");
+        c.check(ladi_launch_tome_plan(score, node, l->src_pos, l->dst_pos, n, l->T, l->Ns, l->Nd, l->r, orow, plan, c.st), "tome_plan");
+        return m;
+    }
+    // m(LayerNorm(t)): the LayerNorm the following projection fuses on the plain path is its own launch in front of the merge
+    Act tome_merge(const Merge& m, const DNorm& ln, const Act& t) {
+        Act a = layer_norm(c, ln, t, 1e-5f);
+        Act y = c.new_act(t.n, m.Tm, 1, t.c);
+        if (!c.dry())
+            c.check(ladi_launch_tome_merge(a.p, a.ld, (long long)m.l->T * a.ld, m.l->dst_pos, m.plan, t.n, m.l->T, m.l->Ns, m.l->Nd, m.l->r, t.c,
+                                           y.p, y.ld, (long long)m.Tm * y.ld, c.st), "tome_merge");
+        return y;
+    }
+    // u(y) + res
+    Act tome_unmerge(const Merge& m, const Act& y, const Act& res) {
+        Act o = c.new_act(res.n, res.h, res.w, res.c);
+        if (!c.dry())
+            c.check(ladi_launch_tome_unmerge_add(y.p, y.ld, (long long)m.Tm * y.ld, res.p, res.ld, (long long)m.l->T * res.ld, m.out_row, res.n, m.l->T,
+                                                 m.Tm, res.c, o.p, o.ld, (long long)m.l->T * o.ld, c.st), "tome_unmerge_add");
+        return o;
+    }
+    // bit: the block's index in execution order (UNet::pag_mask); level: its resolution level (UNet::xf_level)
+    Act xf(const XfBlock& b, const Act& x, int bit, int level) {
         const int n = x.n, T = x.h * x.w, C = b.C;
         int np = 0;
         if (pag_first != PAG_NONE && ((u.pag_mask >> bit) & 1u)) {
             const int lead = pag_first - sample0;                       // leading unperturbed samples of this forward
             np = n - (lead < 0 ? 0 : lead > n ? n : lead);
         }
+        const ToMeLevel* tl = nullptr;
+        if (u.tome.on && level < u.tome.cfg.max_downsample) {
+            // a planning pass sizes the buffers for the whole context batch at once (the lanes and the sub-batch forms plan one after the other)
+            const int need = c.dry() && u.ctx_n > sample0 + n ? u.ctx_n : sample0 + n;
+            tl = u.tome_prepare(level, x.h, x.w, need, c.dry());
+            if (tl->r == 0) tl = nullptr;
+            else if (np > 0) throw std::runtime_error("UNet::forward: perturbed samples in a transformer block that merges tokens");
+        }
+        const ToMeCfg& tc = u.tome.cfg;
+        const bool m1 = tl && tc.merge_attn, m2 = tl && tc.merge_crossattn, m3 = tl && tc.merge_mlp;
         Act out = new_act_with_stats(c, x.n, x.h, x.w, C);
         const size_t mk = c.ar->mark();
         // GroupNorm (no activation) -> proj_in: the normalisation's affine is applied to proj_in's register panel where the X-stationary
@@ -374,11 +508,21 @@ struct Fwd {
         tok.h = T; tok.w = 1;  // tokens view [n][T][C]
         tok.st_part = nullptr; tok.st_px = 0;
         Act t0 = conv2d(c, b.proj_in, tok, nullptr, op);
-        ConvOpt oq; oq.ln = &b.ln1;                  // LayerNorm fused into the K = 320 / 640 projections (X-stationary kernel), else a launch
-        Act qkv = conv2d(c, b.qkv, t0, nullptr, oq);
-        Act o1 = attn(qkv.p, 3 * C, (long long)T * 3 * C, qkv.p + C, qkv.p + 2 * C, 3 * C, (long long)T * 3 * C, n, T, T, b.heads, np);
-        ConvOpt or1; or1.res0 = &t0;
+        // token merging: one plan per block from t0; a merged sub-layer is u(f(m(LayerNorm(t)))) + t, its output projection without the fused
+        // residual, which the unmerge kernel adds
+        Merge mg;
+        if (tl) mg = tome_plan(tl, t0, bit);
+        const int T1 = m1 ? mg.Tm : T;
+        Act qkv;
+        if (m1) { ConvOpt oq; qkv = conv2d(c, b.qkv, tome_merge(mg, b.ln1, t0), nullptr, oq); }
+        else {
+            ConvOpt oq; oq.ln = &b.ln1;              // LayerNorm fused into the K = 320 / 640 projections (X-stationary kernel), else a launch
+            qkv = conv2d(c, b.qkv, t0, nullptr, oq);
+        }
+        Act o1 = attn(qkv.p, 3 * C, (long long)T1 * 3 * C, qkv.p + C, qkv.p + 2 * C, 3 * C, (long long)T1 * 3 * C, n, T1, T1, b.heads, np);
+        ConvOpt or1; if (!m1) or1.res0 = &t0;
         Act t1 = conv2d(c, b.o1, o1, nullptr, or1);
+        if (m1) t1 = tome_unmerge(mg, t1, t0);
         // attn2 and the feed-forward as ONE kernel each on the C = 320 level (xf_fused.hip; LADI_XF_FUSE=0 / =1 / =2: none / attn2 only / both,
         // latched at UNet::load), else the chain of projections.  Measured on
         // MI355X (profiles/r05_xf_fused_ab.txt): parity-green and bit-reproducible, but at one wave per SIMD the fused chains expose the latency two
@@ -390,7 +534,7 @@ struct Fwd {
         int fuse = 0;
         if (!ip && b.o2_packed && b.kp_tiles && t1.ld == C && ladi_xf_fused_eligible(C, b.heads, T, u.ctx_L)) fuse = u.xf_fuse;
         Act t2;
-        if (fuse >= 1) {
+        if (fuse >= 1 && !m2) {                      // a sub-layer that merges runs the chain of projections
             t2 = c.new_act(n, T, 1, C);
             if (!c.dry()) {
                 XAttnBlockArgs xa;
@@ -402,26 +546,29 @@ struct Fwd {
                 c.check(ladi_launch_xattn_block(xa, c.st), "xattn_block");
             }
         } else {
-            ConvOpt oq2; oq2.ln = &b.ln2;
-            Act q2 = conv2d(c, b.q2, t1, nullptr, oq2);
+            const int T2 = m2 ? mg.Tm : T;             // merged: the queries (and the image term's) are the T - r merged rows
+            Act q2;
+            if (m2) { ConvOpt oq2; q2 = conv2d(c, b.q2, tome_merge(mg, b.ln2, t1), nullptr, oq2); }
+            else { ConvOpt oq2; oq2.ln = &b.ln2; q2 = conv2d(c, b.q2, t1, nullptr, oq2); }
             const h16* kv = b.kv_cache + (size_t)sample0 * u.ctx_L * 2 * C;     // this lane's samples of the cached cross-attention K / V
-            Act o2 = attn(q2.p, C, (long long)T * C, kv, kv + C, 2 * C, (long long)u.ctx_L * 2 * C, n, T, u.ctx_L, b.heads);
+            Act o2 = attn(q2.p, C, (long long)T2 * C, kv, kv + C, 2 * C, (long long)u.ctx_L * 2 * C, n, T2, u.ctx_L, b.heads);
             if (ip) {
                 const long long skv = (long long)u.ip_ctx_N * 2 * C;
                 const h16* ikv = b.ip_kv_cache + (size_t)sample0 * skv;           // this lane's samples of the image K / V
                 if (u.ip_route == 1) {
-                    Act oi = attn(q2.p, C, (long long)T * C, ikv, ikv + C, 2 * C, skv, n, T, u.ip_ctx_N, b.heads);
-                    if (!c.dry()) c.check(ladi_launch_ip_scaled_add(oi.p, oi.ld, o2.p, o2.ld, (long long)n * T, C, b.ip_scale, c.st), "ip_scaled_add");
+                    Act oi = attn(q2.p, C, (long long)T2 * C, ikv, ikv + C, 2 * C, skv, n, T2, u.ip_ctx_N, b.heads);
+                    if (!c.dry()) c.check(ladi_launch_ip_scaled_add(oi.p, oi.ld, o2.p, o2.ld, (long long)n * T2, C, b.ip_scale, c.st), "ip_scaled_add");
                 } else if (!c.dry()) {
-                    c.check(ladi_launch_ip_attn_add(q2.p, q2.ld, (long long)T * q2.ld, ikv, 2 * C, skv, ikv + C, 2 * C, skv, o2.p, o2.ld, (long long)T * o2.ld,
-                                                    n, b.heads, T, u.ip_ctx_N, b.ip_scale, c.st), "ip_attn_add");
+                    c.check(ladi_launch_ip_attn_add(q2.p, q2.ld, (long long)T2 * q2.ld, ikv, 2 * C, skv, ikv + C, 2 * C, skv, o2.p, o2.ld, (long long)T2 * o2.ld,
+                                                    n, b.heads, T2, u.ip_ctx_N, b.ip_scale, c.st), "ip_attn_add");
                 }
             }
-            ConvOpt or2; or2.res0 = &t1;
+            ConvOpt or2; if (!m2) or2.res0 = &t1;
             t2 = conv2d(c, b.o2, o2, nullptr, or2);
+            if (m2) t2 = tome_unmerge(mg, t2, t1);
         }
         Act t3;
-        if (fuse >= 2) {
+        if (fuse >= 2 && !m3) {
             t3 = c.new_act(n, T, 1, C);
             if (!c.dry()) {
                 FFBlockArgs fa;
@@ -430,10 +577,13 @@ struct Fwd {
                 c.check(ladi_launch_ff_block(fa, c.st), "ff_block");
             }
         } else {
-            ConvOpt og; og.act = LADI_ACT_GEGLU; og.ln = &b.ln3;
-            Act gg = conv2d(c, b.ff1, t2, nullptr, og);
-            ConvOpt or3; or3.res0 = &t2;
+            ConvOpt og; og.act = LADI_ACT_GEGLU;
+            Act gg;
+            if (m3) gg = conv2d(c, b.ff1, tome_merge(mg, b.ln3, t2), nullptr, og);
+            else { og.ln = &b.ln3; gg = conv2d(c, b.ff1, t2, nullptr, og); }
+            ConvOpt or3; if (!m3) or3.res0 = &t2;
             t3 = conv2d(c, b.ff2, gg, nullptr, or3);
+            if (m3) t3 = tome_unmerge(mg, t3, t2);
         }
         Act xin = x; xin.h = T; xin.w = 1;
         Act outv = out; outv.h = T; outv.w = 1;
@@ -486,7 +636,7 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
             if (shallow && (i > 0 || j >= fbranch)) { ++ri; if (i < 3) ++xi; continue; }
             h = f.res(down_res[ri++], h, nullptr);
             pp(h, "down_blocks.%d.resnets.%d", i, j);
-            if (i < 3) { h = f.xf(down_xf[xi], h, xi); ++xi; pp(h, "down_blocks.%d.attentions.%d", i, j); }
+            if (i < 3) { h = f.xf(down_xf[xi], h, xi, i); ++xi; pp(h, "down_blocks.%d.attentions.%d", i, j); }
             skips.push_back(h);
         }
         if (i < 3 && !shallow) {
@@ -499,7 +649,7 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
     if (!shallow) {
         h = f.res(mid_res[0], h, nullptr);
         pp(h, "mid_block.resnets.0");
-        h = f.xf(mid_xf, h, 3 * L);
+        h = f.xf(mid_xf, h, 3 * L, 3);
         pp(h, "mid_block.attentions.0");
         h = f.res(mid_res[1], h, nullptr);
         pp(h, "mid_block.resnets.1");
@@ -537,7 +687,7 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
             }
             h = f.res(up_res[ri++], h, &sk);
             pp(h, "up_blocks.%d.resnets.%d", i, j);
-            if (i > 0) { h = f.xf(up_xf[xi], h, 3 * L + 1 + xi); ++xi; pp(h, "up_blocks.%d.attentions.%d", i, j); }
+            if (i > 0) { h = f.xf(up_xf[xi], h, 3 * L + 1 + xi, 3 - i); ++xi; pp(h, "up_blocks.%d.attentions.%d", i, j); }
         }
         if (i < 3 && !shallow) {
             ConvOpt ou; ou.ups = 1; ou.stats = true;

@@ -318,6 +318,55 @@ class NativeUNet(_Base):
             check(self.lib.ladi_unet_set_ip_tokens(self.h, ptr(e), e.shape[0], e.shape[1], stream_ptr()), "ladi_unet_set_ip_tokens")
         self._ip_key, self._ip_keepalive = key, (t, e)
 
+    # ---- token merging (tome.py, include/ladi_native.h "Token merging")
+    def set_token_merging(self, ratio=0.5, **kw):
+        """tomesd.apply_patch for this UNet: the transformer blocks of the first max_downsample levels run the selected sub-layers over
+        T - int(T * ratio) rows (tome.config's keywords: max_downsample, sx, sy, use_rand, seed, merge_attn, merge_crossattn, merge_mlp).
+        ratio None or 0: off, the plain forward launch for launch.  Sticky, for every later forward, stand-alone or in the fused loop."""
+        from . import tome
+        if ratio is None:
+            check(self.lib.ladi_unet_set_token_merging(self.h, None), "ladi_unet_set_token_merging")
+            return
+        cfg = tome.config(ratio, **kw)
+        c = _lib.ToMeConfig(**{k: (int(v) if isinstance(v, bool) else v) for k, v in cfg.items()})
+        check(self.lib.ladi_unet_set_token_merging(self.h, ctypes.byref(c)), "ladi_unet_set_token_merging")
+
+    def remove_token_merging(self):
+        self.set_token_merging(None)
+
+    @property
+    def token_merging(self):
+        """None while off, else the configuration as a dict"""
+        c = _lib.ToMeConfig()
+        rc = self.lib.ladi_unet_token_merging(self.h, ctypes.byref(c))
+        if rc < 0:
+            raise NativeError("ladi_unet_token_merging failed: " + _lib.last_error())
+        if not rc:
+            return None
+        return dict(ratio=c.ratio, max_downsample=c.max_downsample, sx=c.sx, sy=c.sy, use_rand=bool(c.use_rand), seed=int(c.seed),
+                    merge_attn=bool(c.merge_attn), merge_crossattn=bool(c.merge_crossattn), merge_mlp=bool(c.merge_mlp))
+
+    def token_merging_blocks(self):
+        """the merged transformer blocks, as indices in execution order (the numbering of the PAG layer mask)"""
+        out = (c_int * 32)()
+        n = self.lib.ladi_unet_tome_block_count(self.h, out, 32)
+        if n < 0:
+            raise NativeError("ladi_unet_tome_block_count failed: " + _lib.last_error())
+        return [int(out[i]) for i in range(n)]
+
+    def token_merging_plan(self, block):
+        """out_row of the block-th merged block as the last forward left it: a flat int32 tensor of n * T entries, entry s * T + p the row of the
+        merged sequence token p of sample s reads (tokens that share a value were merged); None when the block merged nothing"""
+        n = self.lib.ladi_unet_tome_read_plan(self.h, int(block), None, 0)
+        if n < 0:
+            raise NativeError("ladi_unet_tome_read_plan failed: " + _lib.last_error())
+        if n == 0:
+            return None
+        out = torch.empty(n, dtype=torch.int32)
+        if self.lib.ladi_unet_tome_read_plan(self.h, int(block), c_void_p(out.data_ptr()), n) != n:
+            raise NativeError("ladi_unet_tome_read_plan failed: " + _lib.last_error())
+        return out
+
     def enable_xformers_memory_efficient_attention(self, *a, **k):
         return None  # attention is always fused (flash-style) in the native kernels
 

@@ -286,6 +286,27 @@ class StableDiffusionTryOnePipeline:
             raise ValueError("`disable_freeu` needs a UNet with disable_freeu (NativeUNet), the pipeline holds %s." % type(self.unet).__name__)
         self.unet.disable_freeu()
 
+    # ---- token merging: the state lives in the UNet (NativeUNet.set_token_merging); the fused and the modular path both run it
+    def apply_token_merging(self, ratio=0.5, max_downsample=1, sx=2, sy=2, use_rand=False, seed=0, merge_attn=True, merge_crossattn=False,
+                            merge_mlp=False):
+        """tomesd.apply_patch(pipe, ratio=...): in the transformer blocks of the first max_downsample levels the selected sub-layers run over
+        T - int(T * ratio) tokens.  Holds for every later call until remove_token_merging(); ratio 0 is off.  use_rand draws the dst
+        position of every 2 x 2 cell once per configuration from `seed` (tomesd redraws per block and evaluation)."""
+        if not hasattr(self.unet, "set_token_merging"):
+            raise ValueError("`apply_token_merging` needs the native UNet (NativeUNet), the pipeline holds %s." % type(self.unet).__name__)
+        self.unet.set_token_merging(ratio, max_downsample=max_downsample, sx=sx, sy=sy, use_rand=use_rand, seed=seed, merge_attn=merge_attn,
+                                    merge_crossattn=merge_crossattn, merge_mlp=merge_mlp)
+
+    def remove_token_merging(self):
+        if not hasattr(self.unet, "remove_token_merging"):
+            raise ValueError("`remove_token_merging` needs the native UNet (NativeUNet), the pipeline holds %s." % type(self.unet).__name__)
+        self.unet.remove_token_merging()
+
+    @property
+    def token_merging(self):
+        """None while off, else the configuration as a dict"""
+        return getattr(self.unet, "token_merging", None)
+
     # ---- LoRA: the state lives in the UNet (NativeUNet.load_lora_adapter / set_adapters), these are diffusers' pipeline-level names
     def _lora_unet(self, what):
         if not hasattr(self.unet, "load_lora_adapter"):
@@ -574,6 +595,9 @@ class StableDiffusionTryOnePipeline:
                 raise ValueError("`pag_scale` needs the native UNet (NativeUNet), the pipeline holds %s." % type(self.unet).__name__)
             if feature_cache is not None:
                 raise ValueError("`pag_scale` > 0 and `feature_cache` cannot be combined (the cache has no third sample group).")
+            if getattr(self.unet, "token_merging", None):
+                from . import tome
+                tome.check_pag_layers(self.unet.token_merging, self.unet.pag_applied_layers, self.unet.cfg["layers_per_block"])
             n_evals()
             pag_table = pag_plan(pag_scale, pag_adaptive_scale, self.scheduler.timesteps)
             if not any(s > 0.0 for s in pag_table):
