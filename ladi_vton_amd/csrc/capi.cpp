@@ -73,6 +73,33 @@ Act op_view(const void* p, int n, int HW, int C) {
 }
 }  // namespace
 
+// The body of the stand-alone forward entries (ladi_unet_forward, _forward_pag, _forward_cached_rows): null pointers are refused, then
+// `checks` -- the entry's own refusals and preparation, by throwing --, the time embedding, and in the UNet's own arena NCHW -> NHWC,
+// UNet::forward into an output view, NHWC -> NCHW; `done` is the entry's own bookkeeping after everything was queued
+template <typename Checks, typename Done>
+static int unet_forward_entry(const char* where, ladi_unet* u, const void* sample, int dtype, int n, int h, int w, float timestep, void* out,
+                              int out_dtype, FwdOpt o, void* stream, Checks&& checks, Done&& done) {
+    return guarded(where, [&]() {
+        if (!u) throw std::runtime_error("null handle");
+        if (!sample || !out) throw std::runtime_error("null argument");
+        UNet& U = u->u;
+        hipStream_t st = S(stream);
+        checks(U);
+        if (U.compute_temb(&timestep, 1, st)) return -1;
+        const int eps_ld = (U.cfg.out_channels + 3) / 4 * 4;
+        run_planned(U.arena, st, [&](Ctx& c) {
+            Act x = c.new_act(n, h, w, 64);
+            Act eo = c.new_act(n, h, w, U.cfg.out_channels, eps_ld);
+            o.eps_out = &eo;
+            if (!c.dry()) c.check(ladi_launch_nchw_to_nhwc(sample, dtype == LADI_F32, n, U.cfg.in_channels, h, w, x.p, 64, st), "nchw_to_nhwc");
+            Act eps = U.forward(c, x, U.temb_table, nullptr, o);
+            if (!c.dry()) c.check(ladi_launch_nhwc_to_nchw(eps.p, eps.ld, n, U.cfg.out_channels, h, w, out, out_dtype == LADI_F32, st), "nhwc_to_nchw");
+        }, &U.stats, &U.stats_cap);
+        done(U);
+        return 0;
+    });
+}
+
 extern "C" {
 
 const char* ladi_last_error(void) { return last_error(); }
@@ -191,7 +218,7 @@ int ladi_unet_tome_read_plan(ladi_unet* u, int block, int* out_row_host, int cap
         if (!u) throw std::runtime_error("null handle");
         const std::vector<int> b = u->u.tome_blocks();
         if (block < 0 || block >= (int)b.size()) throw std::runtime_error("block " + std::to_string(block) + " is outside the " + std::to_string(b.size()) + " merged blocks");
-        const ToMeLevel& l = u->u.tome.lv[u->u.xf_level(b[block])];
+        const ToMeLevel& l = u->u.tome.lv[u->u.xf[b[block]].level];
         const int* src = u->u.tome.out_row[b[block]];
         if (!src || l.r == 0) return 0;
         const int n = u->u.ctx_n < l.cap_n ? u->u.ctx_n : l.cap_n;
@@ -359,9 +386,8 @@ int ladi_unet_set_ip_scale(ladi_unet* u, const float* scales, int count) {
 }
 int ladi_unet_ip_scale(ladi_unet* u, float* scales_out, int cap) {
     if (!u || cap < 0 || (cap > 0 && !scales_out)) { set_error("ladi_unet_ip_scale: null handle, cap < 0 or null output"); return -1; }
-    auto blocks = u->u.xf_blocks();
-    for (int i = 0; i < (int)blocks.size() && i < cap; ++i) scales_out[i] = blocks[i].first->ip_scale;
-    return (int)blocks.size();
+    for (auto& b : u->u.xf) if (b.bit < cap) scales_out[b.bit] = b.ip_scale;
+    return (int)u->u.xf.size();
 }
 int ladi_unet_set_ip_context(ladi_unet* u, const void* embeds, int n, void* stream) {
     return guarded("ladi_unet_set_ip_context", [&]() {
@@ -398,49 +424,28 @@ int ladi_op_ip_attn_add(const void* q, int ldq, long long sq, const void* k, int
 
 int ladi_unet_forward_pag(ladi_unet* u, const void* sample, int dtype, int n, int h, int w, float timestep, void* out, int out_dtype,
                           int sample0, int pag_first, void* stream) {
-    return guarded("ladi_unet_forward_pag", [&]() {
-        if (!u || !sample || !out) throw std::runtime_error("null argument");
-        UNet& U = u->u;
-        hipStream_t st = S(stream);
+    FwdOpt o; o.sample0 = sample0; o.pag_first = pag_first;
+    return unet_forward_entry("ladi_unet_forward_pag", u, sample, dtype, n, h, w, timestep, out, out_dtype, o, stream, [&](UNet& U) {
         if (n < 1 || h < 1 || w < 1 || sample0 < 0 || sample0 + n > U.ctx_n)
             throw std::runtime_error("samples [" + std::to_string(sample0) + ", " + std::to_string(sample0 + n) + ") are not inside the context batch of " +
                                      std::to_string(U.ctx_n) + " (ladi_unet_set_context)");
         if (pag_first < 0) throw std::runtime_error("pag_first " + std::to_string(pag_first) + " is negative");
-        if (U.compute_temb(&timestep, 1, st)) return -1;
-        const int eps_ld = (U.cfg.out_channels + 3) / 4 * 4;
-        run_planned(U.arena, st, [&](Ctx& c) {
-            Act x = c.new_act(n, h, w, 64);
-            Act eo = c.new_act(n, h, w, U.cfg.out_channels, eps_ld);
-            if (!c.dry()) c.check(ladi_launch_nchw_to_nhwc(sample, dtype == LADI_F32, n, U.cfg.in_channels, h, w, x.p, 64, st), "nchw_to_nhwc");
-            Act eps = U.forward(c, x, U.temb_table, nullptr, &eo, sample0, nullptr, pag_first);
-            if (!c.dry()) c.check(ladi_launch_nhwc_to_nchw(eps.p, eps.ld, n, U.cfg.out_channels, h, w, out, out_dtype == LADI_F32, st), "nhwc_to_nchw");
-        }, &U.stats, &U.stats_cap);
-        return 0;
-    });
+    }, [](UNet&) {});
 }
 
 int ladi_unet_forward(ladi_unet* u, const void* sample, int dtype, int n, int h, int w, float timestep, void* out, int out_dtype,
                       void* stream) {
-    return guarded("ladi_unet_forward", [&]() {
-        UNet& U = u->u;
-        hipStream_t st = S(stream);
-        if (U.compute_temb(&timestep, 1, st)) return -1;
-        run_planned(U.arena, st, [&](Ctx& c) {
-            Act x = c.new_act(n, h, w, 64);
-            if (!c.dry()) c.check(ladi_launch_nchw_to_nhwc(sample, dtype == LADI_F32, n, U.cfg.in_channels, h, w, x.p, 64, st), "nchw_to_nhwc");
-            Act eps = U.forward(c, x, U.temb_table, nullptr);
-            if (!c.dry()) c.check(ladi_launch_nhwc_to_nchw(eps.p, eps.ld, n, U.cfg.out_channels, h, w, out, out_dtype == LADI_F32, st), "nhwc_to_nchw");
-        }, &U.stats, &U.stats_cap);
-        return 0;
-    });
+    return unet_forward_entry("ladi_unet_forward", u, sample, dtype, n, h, w, timestep, out, out_dtype, FwdOpt(), stream, [&](UNet& U) {
+        // the whole context batch: with an output view UNet::forward itself only asks for samples inside it
+        if (n != U.ctx_n) throw std::runtime_error("UNet::forward: set_context batch mismatch");
+    }, [](UNet&) {});
 }
 
 int ladi_unet_forward_cached_rows(ladi_unet* u, const void* sample, int dtype, int n, int h, int w, float timestep, void* out, int out_dtype,
                                   int mode, int branch, int sample0, void* stream) {
-    return guarded("ladi_unet_forward_cached", [&]() {
-        if (!u) throw std::runtime_error("null handle");
-        UNet& U = u->u;
-        hipStream_t st = S(stream);
+    FeatCache fc; fc.mode = mode; fc.branch = branch;
+    FwdOpt o; o.sample0 = sample0; o.fc = mode ? &fc : nullptr;
+    return unet_forward_entry("ladi_unet_forward_cached", u, sample, dtype, n, h, w, timestep, out, out_dtype, o, stream, [&](UNet& U) {
         if (mode < 0 || mode > 2) throw std::runtime_error("mode " + std::to_string(mode) + " unknown: 0 plain, 1 whole + capture, 2 shallow");
         if (mode && (branch < 0 || branch > U.cfg.layers_per_block))
             throw std::runtime_error("branch " + std::to_string(branch) + " out of range [0, " + std::to_string(U.cfg.layers_per_block) + "]");
@@ -469,18 +474,9 @@ int ladi_unet_forward_cached_rows(ladi_unet* u, const void* sample, int dtype, i
             }
             U.fc_h = h; U.fc_w = w; U.fc_branch = branch;
         }
-        if (U.compute_temb(&timestep, 1, st)) return -1;
-        FeatCache fc; fc.mode = mode; fc.branch = branch; fc.buf = U.fc_buf;
-        const int eps_ld = (U.cfg.out_channels + 3) / 4 * 4;
-        run_planned(U.arena, st, [&](Ctx& c) {
-            Act x = c.new_act(n, h, w, 64);
-            Act eo = c.new_act(n, h, w, U.cfg.out_channels, eps_ld);
-            if (!c.dry()) c.check(ladi_launch_nchw_to_nhwc(sample, dtype == LADI_F32, n, U.cfg.in_channels, h, w, x.p, 64, st), "nchw_to_nhwc");
-            Act eps = U.forward(c, x, U.temb_table, nullptr, &eo, sample0, mode ? &fc : nullptr);
-            if (!c.dry()) c.check(ladi_launch_nhwc_to_nchw(eps.p, eps.ld, n, U.cfg.out_channels, h, w, out, out_dtype == LADI_F32, st), "nhwc_to_nchw");
-        }, &U.stats, &U.stats_cap);
+        fc.buf = U.fc_buf;
+    }, [&](UNet& U) {
         if (mode == FeatCache::CAPTURE) for (int i = 0; i < n; ++i) U.fc_rows[sample0 + i] = 1;
-        return 0;
     });
 }
 
@@ -508,7 +504,7 @@ static int time_forward_any(const char* name, ladi_unet* u, int n, int h, int w,
             HIP_OK(hipMemsetAsync(scratch.p, 0, bytes, st));
             fcs.buf = scratch.p;
         }
-        const FeatCache* fc = mode ? &fcs : nullptr;
+        FwdOpt fo; fo.fc = mode ? &fcs : nullptr;
         float t0 = 500.f;
         if (U.compute_temb(&t0, 1, st)) return -1;
         hipEvent_t e0, e1;
@@ -518,12 +514,12 @@ static int time_forward_any(const char* name, ladi_unet* u, int n, int h, int w,
             if (!c.dry()) HIP_OK(hipMemsetAsync(x.p, 0, x.pixels() * 64 * sizeof(h16), st));
             const size_t mk = c.ar->mark();
             // warm-up
-            c.stats_off = 0; (void)U.forward(c, x, U.temb_table, nullptr, nullptr, 0, fc); c.ar->release(mk);
+            c.stats_off = 0; (void)U.forward(c, x, U.temb_table, nullptr, fo); c.ar->release(mk);
             if (!c.dry()) HIP_OK(hipEventRecord(e0, st));
             for (int i = 0; i < (c.dry() ? 1 : iters); ++i) {
                 c.stats_off = 0;
                 if (!c.dry() && c.stats_cap) HIP_OK(hipMemsetAsync(c.stats, 0, c.stats_cap * sizeof(float), st));
-                (void)U.forward(c, x, U.temb_table, nullptr, nullptr, 0, fc);
+                (void)U.forward(c, x, U.temb_table, nullptr, fo);
                 c.ar->release(mk);
             }
             if (!c.dry()) HIP_OK(hipEventRecord(e1, st));

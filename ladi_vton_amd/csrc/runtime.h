@@ -188,6 +188,9 @@ struct ResBlock {
 };
 struct XfBlock {
     DNorm gn, ln1, ln2, ln3; DConv proj_in, qkv, o1, q2, kv2, o2, ff1, ff2, proj_out; int C = 0, heads = 0;
+    // the block's place in the UNet (UNet::xf, filled by UNet::load): its index in execution order -- the bit of UNet::pag_mask, the slot of
+    // ToMe::out_row, the position of its IP-Adapter scale --, its resolution level 0 .. 3 and its diffusers prefix (down_blocks.0.attentions.1)
+    int bit = 0, level = 0; std::string prefix;
     h16* kv_cache = nullptr;  // [n][L][2C]
     // fused sub-blocks of the C = 320 level (xf_fused.hip): operands packed once at load (o2_packed, ff2_packed) / per context (kp, vt)
     h16* o2_packed = nullptr; h16* ff2_packed = nullptr; h16* kp_tiles = nullptr; h16* vt_tiles = nullptr;
@@ -232,6 +235,15 @@ struct FreeU {
 // Perturbed-attention guidance (diffusers PAGMixin): the context index from which a forward's samples are perturbed.  In the transformer
 // blocks selected by UNet::pag_mask a perturbed sample's self-attention map is the identity (pag.hip); everything else is untouched
 enum { PAG_NONE = 0x7fffffff };
+
+// The optional arguments of UNet::forward and UNetLanes::forward (which sets eps_out per lane itself)
+// eps_out: pre-allocated output view (rows of a shared buffer); sample0: index of x's first sample in the context batch
+// fc: deep-feature cache mode of this forward (FeatCache); null or mode NONE launches exactly the plain forward
+// pag_first: samples whose index in the context batch (the numbering of sample0) is >= pag_first are perturbed; a forward's own count of
+// leading unperturbed samples is clamp(pag_first - sample0, 0, n), every lane clamps it to its own samples.  Arena use does not depend on it
+struct FwdOpt {
+    const Act* eps_out = nullptr; int sample0 = 0; const FeatCache* fc = nullptr; int pag_first = PAG_NONE;
+};
 
 // Token merging (tomesd.apply_patch; ladi_unet_set_token_merging, sticky, off by default; tome.hip, DESIGN.md "Token merging").  In the
 // transformer blocks of the first max_downsample levels the selected sub-layers run over T - r rows: one plan per block and forward, from
@@ -303,7 +315,6 @@ struct UNet {
     h16* ip_proj_w = nullptr; h16* ip_proj_b = nullptr; DNorm ip_norm;
     int ip_ctx_n = 0, ip_ctx_N = 0; size_t ip_ctx_cap = 0;    // image context: samples (0 = none), tokens per sample; capacity in rows (n * N)
     std::unique_ptr<DevPool> ip_ctx_pool; h16* ip_lin = nullptr; h16* ip_tok = nullptr;   // projection output / tokens [rows][cross_dim]
-    std::vector<std::pair<XfBlock*, std::string>> xf_blocks();   // every transformer block with its diffusers prefix, in execution order (PAG's bits)
     void ip_load(const WeightStore& ws);                      // throws; everything is checked before anything changes
     void ip_unload();
     void ip_set_scale(const float* scales, int count);        // throws on a wrong count or a non-finite value, nothing changed
@@ -314,24 +325,25 @@ struct UNet {
     // A/B switch of the image term (tools/bench_ip_adapter.py; ladi_unet_set_ip_route): 0 = ip_attn_add, the shipped route on every level
     // (BASELINE.md "IP-Adapter"); 1 = flash_attn64 over the N image keys into a scratch tensor plus ip_scaled_add (two roundings)
     int ip_route = 0;
-    // pag_applied_layers (ladi_unet_set_pag_layers, sticky): bit i = transformer block i in execution order -- down_blocks.{0,1,2}
+    // pag_applied_layers (ladi_unet_set_pag_layers, sticky): bit i = transformer block i in execution order (xf[i].bit) -- down_blocks.{0,1,2}
     // .attentions.{0..L-1}, mid_block, up_blocks.{1,2,3}.attentions.{0..L}; pag_layer_count() bits.  The default is the mid block, as in
     // diffusers.  Without perturbed samples in a forward (pag_first = PAG_NONE) the mask has no effect
     unsigned pag_mask = 0;
-    int pag_layer_count() const { return 6 * cfg.layers_per_block + 4; }
-    // token merging (ToMe above).  xf_level: 0 .. 3, the resolution level of transformer block `bit`; tome_blocks: the bits of the blocks
-    // the configuration merges, in execution order; tome_prepare: the level state for a forward of samples [0, need_n) at h x w -- a
-    // planning pass builds it (synchronises the device and bumps gen when something is freed), a real pass only checks it and throws
+    int pag_layer_count() const { return (int)xf.size(); }
+    // token merging (ToMe above).  tome_blocks: the bits of the blocks the configuration merges, in execution order; tome_prepare: the
+    // level state for a forward of samples [0, need_n) at h x w -- a planning pass builds it (synchronises the device and bumps gen when
+    // something is freed), a real pass only checks it and throws
     ToMe tome;
     void tome_set(const ToMeCfg* c);                          // throws on a refused configuration, nothing changed; null / ratio 0: off
-    int xf_level(int bit) const;
     std::vector<int> tome_blocks() const;
     const ToMeLevel* tome_prepare(int level, int h, int w, int need_n, bool dry);
     DevPool pool;
     DConv conv_in, conv_out, time_l1, time_l2, temb_all;
     DNorm norm_out;
     std::vector<ResBlock> down_res, up_res; ResBlock mid_res[2];
-    std::vector<XfBlock> down_xf, up_xf; XfBlock mid_xf;
+    // every transformer block in execution order: down 0 .. 2, mid, up 1 .. 3.  Filled by load() and never moved afterwards (LoraTarget
+    // points into it); each block knows its own bit, level and prefix
+    std::vector<XfBlock> xf;
     DConv down_samp[3], up_samp[3];
     int temb_total = 0;
     int xf_fuse = 0;                        // LADI_XF_FUSE, latched at load(): fused attn2 / feed-forward kernels of the C = 320 level (default off)
@@ -349,12 +361,19 @@ struct UNet {
     int set_context(const h16* ehs, int n, int L, hipStream_t st);
     int compute_temb(const float* timesteps_host, int count, hipStream_t st);  // fills temb_table rows [0,count)
     // x: [n,h,w,64] padded NHWC input; returns eps Act [n,h,w,4(ld 4)]
-    // eps_out (optional): pre-allocated output view (rows of a shared buffer); sample0: index of x's first sample in the context batch
-    // fc (optional): deep-feature cache mode of this forward (FeatCache); null or mode NONE launches exactly the plain forward
-    // pag_first: samples whose index in the context batch (the numbering of sample0) is >= pag_first are perturbed; this forward's own
-    // count of leading unperturbed samples is clamp(pag_first - sample0, 0, n).  Arena use does not depend on it
-    Act forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_idx, const Act* eps_out = nullptr, int sample0 = 0,
-                const FeatCache* fc = nullptr, int pag_first = PAG_NONE);
+    Act forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_idx, const FwdOpt& o = FwdOpt());
+    // The UNet's part of the hipGraph key (GraphKey, whose rule it follows): every value a captured forward carries as an argument and one
+    // representative pointer of every pool it dereferences (a pool's buffers are allocated together).  Plain data; key() fills a ZEROED Key,
+    // and what belongs to a feature that is off stays zero.  perturbed: the run has perturbed samples -- only then does pag_mask reach a launch
+    struct Key {
+        const void *temb_table, *kv_cache;
+        unsigned long long probe;                   // Probe::id (0 = none): a graph captured with a probe's launches is replayed only with that probe
+        int freeu_on; unsigned freeu[4];            // s1, s2, b1, b2 by their bits
+        unsigned pag_mask;
+        int ip_on, ip_N; const void* ip_kv; unsigned ip_scale[32];     // tokens per sample, the image K/V, every block's scale by its bits
+        int tome_on; int tome_opts[8]; unsigned long long tome_ratio, tome_gen;   // every configuration field and the generation of the level state
+    };
+    void key(Key& k, bool perturbed) const;
     int fc_channels(int branch) const { return cfg.boc[branch >= cfg.layers_per_block ? 1 : 0]; }   // channels of the cached tensor
     // cache of the stand-alone entry ladi_unet_forward_cached: grow-only buffer over the context batch, the geometry it was captured at and
     // which sample rows hold a capture made since the last set_context
@@ -386,9 +405,8 @@ struct UNetLanes {
     // a quiet chip)
     // sub-group form (cond-only evaluations of a CFG-shaped run): x / eps hold x.n < n samples that start at index sample0 of the context
     // batch, and run on sub_lanes(x.n) of the configured lanes, in their arenas (planned by a dry pass of this form too)
-    // pag_first: as UNet::forward's, in the context batch's numbering; every lane clamps it to its own samples (a lane may hold both kinds)
     void forward(UNet& u, hipStream_t main_st, bool dry, bool concurrent, const Act& x, const Act& eps, const float* temb, const int* tidx,
-                 int sample0 = 0, const FeatCache* fc = nullptr, int pag_first = PAG_NONE);
+                 const FwdOpt& o = FwdOpt());
     int sub_lanes(int n_sub) const { int g = G; while (g > 1 && (n_sub % g)) --g; return g; }   // the default rule: lowered until it divides
     void commit_plan();                     // after the dry pass: (re)allocate what grew; not capturable
     // part of the hipGraph key (GraphKey): lane count and every address a captured lane may touch, zero beyond G
@@ -602,13 +620,13 @@ struct GraphKey {
     const void* arena;                          // base of the run's activation arena: every transient address
     int B, H, W, cfg, L, pose_ch, has_cloth;    // the shapes of every launch
     unsigned guidance;                          // bits of the scalar guidance, when !guided (with a table the scalar is ignored: zero)
-    const void *temb_table, *kv_cache, *d_table, *stats;
+    const void *d_table, *stats;
     const void *trace_eps, *trace_lat; int trace_cap;
     const void* step_noise;
     UNetLanes::Key lanes;
-    // a graph captured without the probe launches is never replayed with it, nor one that holds another probe's slots: the id is unique per
-    // Probe (0 = none), and within one Probe a name keeps its slot
-    unsigned long long probe;
+    // what the forward itself carries and dereferences: time-embedding table, cross-attention K/V, probe, FreeU, the PAG layers of a run with
+    // perturbed samples, the image context, token merging (UNet::key)
+    UNet::Key unet;
     // every form lives under one key, with the guidance table, the factor buffer and phi (its bits, when guided)
     const void *guidance_tab, *factor; int guided; unsigned phi;
     // ... and with the feature cache: its buffer, the branch and whether whole evaluations capture (a graph captured with capture on is never
@@ -616,18 +634,9 @@ struct GraphKey {
     const void* fcache; int fc_on, fc_branch;
     // ... and with the latent blend: its buffers, the coefficient table and the mode (when the latents bit is set)
     const void *keep_x0, *keep_noise, *keep_mask, *keep_tab; int preserve_mode;
-    // ... and with FreeU: on / off and, when on, the bits of the four factors the captured launches carry as arguments
-    int freeu_on; unsigned freeu[4];
-    // ... and with PAG: whether the run has the third group, the scale table and the selected blocks (when pag_on); a graph captured with PAG
-    // is never replayed without it, nor the reverse
-    int pag_on; unsigned pag_mask; const void* pag_tab;
-    // ... and with the image prompt (IP-Adapter): on / off and, when on, the tokens per sample, the mid block's image K/V (every block's
-    // lives in the same pool) and the bits of the per-block scales, which the captured launches carry as arguments and which decide whether a
-    // block launches the image term at all
-    int ip_on, ip_N; const void* ip_kv; unsigned ip_scale[32];
-    // ... and with token merging: on / off and, when on, every field of the configuration (the ratio by its bits) and the generation of the
-    // UNet's level state, whose tables and out_row buffers the captured launches address
-    int tome_on; int tome_opts[8]; unsigned long long tome_ratio, tome_gen;
+    // ... and with PAG: whether the run has the third group and its scale table; a graph captured with PAG is never replayed without it,
+    // nor the reverse
+    int pag_on; const void* pag_tab;
 };
 // The per-evaluation plan of one run: host arithmetic only (plan_evals; ladi_tryon_plan_forms runs it without a GPU)
 struct EvalPlan {

@@ -26,7 +26,8 @@ void UNet::build_lora_targets() {
         if (r.has_sc) add(p + ".conv_shortcut", r.sc);
         add(p + ".time_emb_proj", temb_all, r.temb_off, r.cout);
     };
-    auto add_xf = [&](XfBlock& x, const std::string& p) {
+    auto add_xf = [&](XfBlock& x) {
+        const std::string& p = x.prefix;
         const std::string b = p + ".transformer_blocks.0";
         const int C = x.C;
         add(p + ".proj_in", x.proj_in);
@@ -47,19 +48,19 @@ void UNet::build_lora_targets() {
         const std::string p = "down_blocks." + std::to_string(i);
         for (int j = 0; j < L; ++j) {
             add_res(down_res[ri++], p + ".resnets." + std::to_string(j));
-            if (i < 3) add_xf(down_xf[xi++], p + ".attentions." + std::to_string(j));
+            if (i < 3) add_xf(xf[xi++]);
         }
         if (i < 3) add(p + ".downsamplers.0.conv", down_samp[i]);
     }
     add_res(mid_res[0], "mid_block.resnets.0");
-    add_xf(mid_xf, "mid_block.attentions.0");
+    add_xf(xf[xi++]);
     add_res(mid_res[1], "mid_block.resnets.1");
-    ri = 0; xi = 0;
+    ri = 0;
     for (int i = 0; i < 4; ++i) {
         const std::string p = "up_blocks." + std::to_string(i);
         for (int j = 0; j < L + 1; ++j) {
             add_res(up_res[ri++], p + ".resnets." + std::to_string(j));
-            if (i > 0) add_xf(up_xf[xi++], p + ".attentions." + std::to_string(j));
+            if (i > 0) add_xf(xf[xi++]);
         }
         if (i < 3) add(p + ".upsamplers.0.conv", up_samp[i]);
     }

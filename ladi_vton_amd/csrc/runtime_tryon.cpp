@@ -450,7 +450,8 @@ void TryOn::denoise(Run& r) {
         Act xs = unet_in, es = eps;
         xs.n = ns; xs.p = unet_in.p + (size_t)s0 * hw * unet_in.ld;
         es.n = ns; es.p = eps.p + (size_t)s0 * hw * eps.ld;
-        lanes.forward(*unet, st, c.dry(), concurrent, xs, es, unet->temb_table, d_step, s0, p.fc_on ? &fcs : nullptr, pg ? p.ng * B : (int)PAG_NONE);
+        FwdOpt fo; fo.sample0 = s0; fo.fc = p.fc_on ? &fcs : nullptr; fo.pag_first = pg ? p.ng * B : (int)PAG_NONE;
+        lanes.forward(*unet, st, c.dry(), concurrent, xs, es, unet->temb_table, d_step, fo);
         if (c.dry()) return;
         sa.eps = eps.p; sa.ld_eps = eps.ld;
         if (p.use_factor && !cond)
@@ -493,33 +494,17 @@ void TryOn::denoise(Run& r) {
         GraphKey key; std::memset(&key, 0, sizeof(key));
         key.arena = arena.base; key.B = B; key.H = r.H; key.W = r.W; key.cfg = cfgf; key.L = r.L; key.pose_ch = r.pose_ch; key.has_cloth = r.has_cloth;
         if (!p.guided) std::memcpy(&key.guidance, &in.guidance, 4);
-        key.temb_table = unet->temb_table; key.kv_cache = unet->mid_xf.kv_cache; key.d_table = d_table; key.stats = stats;
+        key.d_table = d_table; key.stats = stats;
         key.trace_eps = trace_eps; key.trace_lat = trace_lat; key.trace_cap = trace_cap;
         key.step_noise = sa.step_noise;
         lanes.key(key.lanes);
-        key.probe = unet->probe ? unet->probe->id : 0ULL;
+        unet->key(key.unet, p.pag_on);
         key.guidance_tab = sa.guidance_tab; key.factor = sa.factor; key.guided = p.guided;
         if (p.guided) std::memcpy(&key.phi, &phi, 4);
         if (p.fc_on) { key.fcache = fcache; key.fc_on = 1; key.fc_branch = fc_branch; }
         key.keep_x0 = sa.keep_x0; key.keep_noise = sa.keep_noise; key.keep_mask = sa.keep_mask; key.keep_tab = sa.keep_tab;
         if (r.keep_lat) key.preserve_mode = preserve_mode;
-        if (unet->freeu.on) {
-            const float fv[4] = {unet->freeu.s1, unet->freeu.s2, unet->freeu.b1, unet->freeu.b2};
-            key.freeu_on = 1; std::memcpy(key.freeu, fv, sizeof(fv));
-        }
-        if (p.pag_on) { key.pag_on = 1; key.pag_mask = unet->pag_mask; }
-        key.pag_tab = sa.pag_tab;
-        if (unet->ip_ctx_n > 0) {
-            key.ip_on = 1; key.ip_N = unet->ip_ctx_N; key.ip_kv = unet->mid_xf.ip_kv_cache;
-            auto blocks = unet->xf_blocks();
-            for (size_t i = 0; i < blocks.size() && i < 32; ++i) std::memcpy(&key.ip_scale[i], &blocks[i].first->ip_scale, 4);
-        }
-        if (unet->tome.on) {
-            const ToMeCfg& tc = unet->tome.cfg;
-            const int opts[8] = {tc.max_downsample, tc.sx, tc.sy, tc.use_rand, (int)tc.seed, tc.merge_attn, tc.merge_crossattn, tc.merge_mlp};
-            key.tome_on = 1; std::memcpy(key.tome_opts, opts, sizeof(opts));
-            std::memcpy(&key.tome_ratio, &tc.ratio, sizeof(double)); key.tome_gen = unet->tome.gen;
-        }
+        key.pag_on = p.pag_on ? 1 : 0; key.pag_tab = sa.pag_tab;
         if (std::memcmp(&key, &graph_key, sizeof(key))) { graphs.clear(); std::memcpy(&graph_key, &key, sizeof(key)); }
         // the host knows the schedule and picks the graph; the values come from the device table.  A form that this run has not yet
         // run eagerly and that has no graph runs eagerly once (see above), its next evaluation captures

@@ -63,7 +63,6 @@ void UNet::load(const UNetCfg& c, const WeightStore& ws) {
     // see the same one (it used to be a getenv in every block of every pass)
     { const char* e = getenv("LADI_XF_FUSE"); xf_fuse = e ? atoi(e) : 0; }
     const int L = c.layers_per_block;
-    pag_mask = 1u << (3 * L);               // pag_applied_layers defaults to the mid block
     conv_in = load_conv(pool, ws, "conv_in", c.in_channels);
     time_l1 = load_conv(pool, ws, "time_embedding.linear_1");
     time_l2 = load_conv(pool, ws, "time_embedding.linear_2");
@@ -75,22 +74,31 @@ void UNet::load(const UNetCfg& c, const WeightStore& ws) {
         temb_names.push_back(p + ".time_emb_proj");
         if (vec) vec->push_back(r); else *single = r;
     };
+    // the transformer blocks are loaded in execution order: this is the one place that says which block has which bit, level and prefix.
+    // A second load() starts the table again.  The reserve is a hint only: nothing points into the table before build_lora_targets()
+    xf.clear(); xf.reserve(6 * L + 4);
+    auto add_xf = [&](const std::string& p, int level) {
+        XfBlock x = load_xf(pool, ws, p, c.heads[level], xf_fuse > 0);
+        x.bit = (int)xf.size(); x.level = level; x.prefix = p;
+        xf.push_back(std::move(x));
+    };
     for (int i = 0; i < 4; ++i) {
         for (int j = 0; j < L; ++j) {
             const std::string p = "down_blocks." + std::to_string(i);
             add_res(&down_res, nullptr, p + ".resnets." + std::to_string(j));
-            if (i < 3) down_xf.push_back(load_xf(pool, ws, p + ".attentions." + std::to_string(j), c.heads[i], xf_fuse > 0));
+            if (i < 3) add_xf(p + ".attentions." + std::to_string(j), i);
         }
         if (i < 3) down_samp[i] = load_conv(pool, ws, "down_blocks." + std::to_string(i) + ".downsamplers.0.conv");
     }
     add_res(nullptr, &mid_res[0], "mid_block.resnets.0");
-    mid_xf = load_xf(pool, ws, "mid_block.attentions.0", c.heads[3], xf_fuse > 0);
+    add_xf("mid_block.attentions.0", 3);
+    pag_mask = 1u << xf.back().bit;         // pag_applied_layers defaults to the mid block
     add_res(nullptr, &mid_res[1], "mid_block.resnets.1");
     for (int i = 0; i < 4; ++i) {
         for (int j = 0; j < L + 1; ++j) {
             const std::string p = "up_blocks." + std::to_string(i);
             add_res(&up_res, nullptr, p + ".resnets." + std::to_string(j));
-            if (i > 0) up_xf.push_back(load_xf(pool, ws, p + ".attentions." + std::to_string(j), c.heads[3 - i], xf_fuse > 0));
+            if (i > 0) add_xf(p + ".attentions." + std::to_string(j), 3 - i);
         }
         if (i < 3) up_samp[i] = load_conv(pool, ws, "up_blocks." + std::to_string(i) + ".upsamplers.0.conv");
     }
@@ -136,18 +144,11 @@ void UNet::tome_set(const ToMeCfg* c) {
     ++tome.gen;
 }
 
-int UNet::xf_level(int bit) const {
-    const int L = cfg.layers_per_block;
-    if (bit < 3 * L) return bit / L;
-    if (bit == 3 * L) return 3;
-    return 2 - (bit - 3 * L - 1) / (L + 1);
-}
-
 std::vector<int> UNet::tome_blocks() const {
     std::vector<int> v;
     if (!tome.on) return v;
-    for (int b = 0; b < pag_layer_count(); ++b)
-        if (xf_level(b) < tome.cfg.max_downsample) v.push_back(b);
+    for (auto& b : xf)
+        if (b.level < tome.cfg.max_downsample) v.push_back(b.bit);
     return v;
 }
 
@@ -167,7 +168,7 @@ const ToMeLevel* UNet::tome_prepare(int level, int h, int w, int need_n, bool dr
         throw std::runtime_error("token merging: " + std::to_string(h) + " x " + std::to_string(w) + " tokens give " + std::to_string(nl.Nd) +
                                  " dst tokens, the plan kernel holds at most 4096");
     std::vector<int> bits;
-    for (int b = 0; b < pag_layer_count() && b < 32; ++b) if (xf_level(b) == level) bits.push_back(b);
+    for (auto& b : xf) if (b.level == level && b.bit < 32) bits.push_back(b.bit);
     if (l.mem) { HIP_OK(hipDeviceSynchronize()); (void)hipFree(l.mem); }
     l = ToMeLevel();
     for (int b : bits) tome.out_row[b] = nullptr;
@@ -193,34 +194,30 @@ const ToMeLevel* UNet::tome_prepare(int level, int h, int w, int need_n, bool dr
 int UNet::set_context(const h16* ehs, int n, int L, hipStream_t st) {
     // cross-attention K/V of every transformer block depend only on encoder_hidden_states: hoisted out of the
     // denoising loop (SURVEY.md §8d "step-invariant work")
-    std::vector<XfBlock*> all;
-    for (auto& x : down_xf) all.push_back(&x);
-    all.push_back(&mid_xf);
-    for (auto& x : up_xf) all.push_back(&x);
     if (n * L > ctx_cap_n || n > ctx_cap_samples) {
         ctx_pool.reset(new DevPool());   // frees the previous (smaller) K/V cache
-        for (auto* x : all) {
-            x->kv_cache = reinterpret_cast<h16*>(ctx_pool->alloc((size_t)n * L * 2 * x->C * sizeof(h16)));
-            if (x->o2_packed) {
-                x->kp_tiles = reinterpret_cast<h16*>(ctx_pool->alloc(ladi_xf_kp_elems(n) * sizeof(h16)));
-                x->vt_tiles = reinterpret_cast<h16*>(ctx_pool->alloc(ladi_xf_vt_elems(n) * sizeof(h16)));
+        for (auto& x : xf) {
+            x.kv_cache = reinterpret_cast<h16*>(ctx_pool->alloc((size_t)n * L * 2 * x.C * sizeof(h16)));
+            if (x.o2_packed) {
+                x.kp_tiles = reinterpret_cast<h16*>(ctx_pool->alloc(ladi_xf_kp_elems(n) * sizeof(h16)));
+                x.vt_tiles = reinterpret_cast<h16*>(ctx_pool->alloc(ladi_xf_vt_elems(n) * sizeof(h16)));
             }
         }
         ctx_cap_n = n * L; ctx_cap_samples = n;
     }
     ctx_n = n; ctx_L = L;
     fc_rows.assign((size_t)n, 0);            // the stand-alone entry's deep-feature cache belongs to the context it was captured under
-    for (auto* x : all) {
+    for (auto& x : xf) {
         IGemmArgs a; std::memset(&a, 0, sizeof(a));
         a.src0 = ehs; a.C0 = cfg.cross_dim; a.ld0 = cfg.cross_dim;
         a.Hs = n * L; a.Ws = 1; a.Ho = n * L; a.Wo = 1; a.P = n * L;
         a.ksize = 1; a.stride = 1; a.pad = 0;
-        a.W = x->kv2.w; a.Q = x->kv2.cout; a.K = x->kv2.K();
-        a.out = x->kv_cache; a.ldo = 2 * x->C; a.out_scale = 1.f;
+        a.W = x.kv2.w; a.Q = x.kv2.cout; a.K = x.kv2.K();
+        a.out = x.kv_cache; a.ldo = 2 * x.C; a.out_scale = 1.f;
         int rc = ladi_launch_igemm(a, 1, 0, st);
         if (rc) { set_error("set_context igemm rc=" + std::to_string(rc)); return rc; }
-        if (x->kp_tiles && ladi_xf_fused_eligible(x->C, x->heads, 128, L)) {      // the fused attn2 reads per-(sample, head) tiles
-            rc = ladi_launch_pack_kv_tiles(x->kv_cache, n, L, x->C, x->kp_tiles, x->vt_tiles, st);
+        if (x.kp_tiles && ladi_xf_fused_eligible(x.C, x.heads, 128, L)) {      // the fused attn2 reads per-(sample, head) tiles
+            rc = ladi_launch_pack_kv_tiles(x.kv_cache, n, L, x.C, x.kp_tiles, x.vt_tiles, st);
             if (rc) { set_error("set_context pack_kv_tiles rc=" + std::to_string(rc)); return rc; }
         }
     }
@@ -254,17 +251,6 @@ int UNet::compute_temb(const float* ts_host, int count, hipStream_t st) {
 // ------------------------------------------------------------------------------------------------
 // IP-Adapter image prompt (runtime.h UNet; ip_adapter.hip)
 // ------------------------------------------------------------------------------------------------
-std::vector<std::pair<XfBlock*, std::string>> UNet::xf_blocks() {
-    std::vector<std::pair<XfBlock*, std::string>> all;
-    const int L = cfg.layers_per_block;
-    for (int i = 0; i < (int)down_xf.size(); ++i)
-        all.emplace_back(&down_xf[i], "down_blocks." + std::to_string(i / L) + ".attentions." + std::to_string(i % L));
-    all.emplace_back(&mid_xf, "mid_block.attentions.0");
-    for (int i = 0; i < (int)up_xf.size(); ++i)
-        all.emplace_back(&up_xf[i], "up_blocks." + std::to_string(1 + i / (L + 1)) + ".attentions." + std::to_string(i % (L + 1)));
-    return all;
-}
-
 void UNet::ip_load(const WeightStore& ws) {
     if (ip_loaded) throw std::runtime_error("an IP-Adapter is already loaded (ladi_unet_ip_adapter_unload first)");
     auto shape_str = [](const HostTensor& t) { std::string s = "["; for (size_t i = 0; i < t.shape.size(); ++i) s += (i ? ", " : "") + std::to_string(t.shape[i]); return s + "]"; };
@@ -283,26 +269,25 @@ void UNet::ip_load(const WeightStore& ws) {
     if ((long long)need("image_proj.proj.bias").numel() != N * D) throw std::runtime_error("image_proj.proj.bias does not have " + std::to_string(N * D) + " entries");
     if ((long long)need("image_proj.norm.weight").numel() != D || (long long)need("image_proj.norm.bias").numel() != D)
         throw std::runtime_error("image_proj.norm does not have " + std::to_string(D) + " channels");
-    auto blocks = xf_blocks();
     size_t expected = 4;
-    for (auto& b : blocks) {
+    for (auto& b : xf) {
         for (const char* nm : {"to_k_ip", "to_v_ip"}) {
-            const std::string k = b.second + ".transformer_blocks.0.attn2.processor." + nm + ".weight";
+            const std::string k = b.prefix + ".transformer_blocks.0.attn2.processor." + nm + ".weight";
             const HostTensor& w = need(k);
-            if (w.shape.size() != 2 || w.shape[0] != b.first->C || w.shape[1] != D)
-                throw std::runtime_error(k + " of shape " + shape_str(w) + " is not [" + std::to_string(b.first->C) + ", " + std::to_string(D) + "]");
+            if (w.shape.size() != 2 || w.shape[0] != b.C || w.shape[1] != D)
+                throw std::runtime_error(k + " of shape " + shape_str(w) + " is not [" + std::to_string(b.C) + ", " + std::to_string(D) + "]");
             ++expected;
         }
-        if (ws.has(b.second + ".transformer_blocks.0.attn2.processor.to_k_ip.bias") || ws.has(b.second + ".transformer_blocks.0.attn2.processor.to_v_ip.bias"))
-            throw std::runtime_error(b.second + ": to_k_ip / to_v_ip have no bias");
+        if (ws.has(b.prefix + ".transformer_blocks.0.attn2.processor.to_k_ip.bias") || ws.has(b.prefix + ".transformer_blocks.0.attn2.processor.to_v_ip.bias"))
+            throw std::runtime_error(b.prefix + ": to_k_ip / to_v_ip have no bias");
     }
     if (ws.m.size() != expected) {
         for (auto& kv : ws.m) {
             const std::string& k = kv.first;
             bool known = k == "image_proj.proj.weight" || k == "image_proj.proj.bias" || k == "image_proj.norm.weight" || k == "image_proj.norm.bias";
-            for (auto& b : blocks)
-                known = known || k == b.second + ".transformer_blocks.0.attn2.processor.to_k_ip.weight" ||
-                        k == b.second + ".transformer_blocks.0.attn2.processor.to_v_ip.weight";
+            for (auto& b : xf)
+                known = known || k == b.prefix + ".transformer_blocks.0.attn2.processor.to_k_ip.weight" ||
+                        k == b.prefix + ".transformer_blocks.0.attn2.processor.to_v_ip.weight";
             if (!known) throw std::runtime_error("unexpected key '" + k + "'");
         }
     }
@@ -312,12 +297,12 @@ void UNet::ip_load(const WeightStore& ws) {
     h16* bias = pool_->upload_h16(ws.get("image_proj.proj.bias").data);
     DNorm nm = load_norm(*pool_, ws, "image_proj.norm");
     std::vector<DConv> kv;
-    for (auto& b : blocks) {
-        const std::string p = b.second + ".transformer_blocks.0.attn2.processor.";
+    for (auto& b : xf) {
+        const std::string p = b.prefix + ".transformer_blocks.0.attn2.processor.";
         kv.push_back(load_linear_cat(*pool_, ws, {p + "to_k_ip", p + "to_v_ip"}, false));
     }
     HIP_OK(hipDeviceSynchronize());
-    for (size_t i = 0; i < blocks.size(); ++i) { blocks[i].first->ip_kv = kv[i]; blocks[i].first->ip_scale = 1.f; }
+    for (auto& b : xf) { b.ip_kv = kv[b.bit]; b.ip_scale = 1.f; }
     ip_pool = std::move(pool_);
     ip_proj_w = w; ip_proj_b = bias; ip_norm = nm;
     ip_N = (int)N; ip_E = (int)E; ip_loaded = true;
@@ -326,7 +311,7 @@ void UNet::ip_load(const WeightStore& ws) {
 
 void UNet::ip_unload() {
     ip_ctx_n = 0; ip_ctx_N = 0; ip_ctx_cap = 0;
-    for (auto& b : xf_blocks()) { b.first->ip_kv = DConv(); b.first->ip_kv_cache = nullptr; b.first->ip_scale = 1.f; }
+    for (auto& b : xf) { b.ip_kv = DConv(); b.ip_kv_cache = nullptr; b.ip_scale = 1.f; }
     ip_lin = ip_tok = nullptr;
     ip_ctx_pool.reset();
     ip_pool.reset();
@@ -340,8 +325,7 @@ void UNet::ip_set_scale(const float* scales, int count) {
         throw std::runtime_error("want " + std::to_string(pag_layer_count()) + " scales, one per transformer block, but got " + std::to_string(count));
     for (int i = 0; i < count; ++i)
         if (!std::isfinite(scales[i])) throw std::runtime_error("scale " + std::to_string(i) + " is not finite");
-    auto blocks = xf_blocks();
-    for (int i = 0; i < count; ++i) blocks[i].first->ip_scale = scales[i];
+    for (auto& b : xf) b.ip_scale = scales[b.bit];
 }
 
 void UNet::ip_reserve(int n, int N) {
@@ -353,7 +337,7 @@ void UNet::ip_reserve(int n, int N) {
         const size_t D = (size_t)cfg.cross_dim;
         ip_lin = reinterpret_cast<h16*>(ip_ctx_pool->alloc(rows * D * sizeof(h16)));
         ip_tok = reinterpret_cast<h16*>(ip_ctx_pool->alloc(rows * D * sizeof(h16)));
-        for (auto& b : xf_blocks()) b.first->ip_kv_cache = reinterpret_cast<h16*>(ip_ctx_pool->alloc(rows * 2 * b.first->C * sizeof(h16)));
+        for (auto& b : xf) b.ip_kv_cache = reinterpret_cast<h16*>(ip_ctx_pool->alloc(rows * 2 * b.C * sizeof(h16)));
         ip_ctx_cap = rows;
     }
     ip_ctx_n = n; ip_ctx_N = N;
@@ -362,14 +346,13 @@ void UNet::ip_reserve(int n, int N) {
 // the image K/V of every block from the tokens in ip_tok: one igemm per block, as set_context's
 static int ip_project_kv(UNet& u, const h16* tok, hipStream_t st) {
     const int rows = u.ip_ctx_n * u.ip_ctx_N;
-    for (auto& b : u.xf_blocks()) {
-        XfBlock* x = b.first;
+    for (auto& x : u.xf) {
         IGemmArgs a; std::memset(&a, 0, sizeof(a));
         a.src0 = tok; a.C0 = u.cfg.cross_dim; a.ld0 = u.cfg.cross_dim;
         a.Hs = rows; a.Ws = 1; a.Ho = rows; a.Wo = 1; a.P = rows;
         a.ksize = 1; a.stride = 1; a.pad = 0;
-        a.W = x->ip_kv.w; a.Q = x->ip_kv.cout; a.K = x->ip_kv.K();
-        a.out = x->ip_kv_cache; a.ldo = 2 * x->C; a.out_scale = 1.f;
+        a.W = x.ip_kv.w; a.Q = x.ip_kv.cout; a.K = x.ip_kv.K();
+        a.out = x.ip_kv_cache; a.ldo = 2 * x.C; a.out_scale = 1.f;
         const int rc = ladi_launch_igemm(a, 1, 0, st);
         if (rc) { u.ip_ctx_n = 0; set_error("set_ip_context igemm rc=" + std::to_string(rc)); return rc; }
     }
@@ -477,9 +460,22 @@ struct Fwd {
                                                  m.Tm, res.c, o.p, o.ld, (long long)m.l->T * o.ld, c.st), "tome_unmerge_add");
         return o;
     }
-    // bit: the block's index in execution order (UNet::pag_mask); level: its resolution level (UNet::xf_level)
-    Act xf(const XfBlock& b, const Act& x, int bit, int level) {
-        const int n = x.n, T = x.h * x.w, C = b.C;
+    // One residual sub-layer of a transformer block over the tokens t [n][T][C]: t + last(core(first(LayerNorm(t)))).  Plain (m null): the
+    // LayerNorm is fused into `first` (K = 320 / 640, X-stationary kernel; else its own launch) and the residual into `last`.  Merged:
+    // u(last(core(first(m(LayerNorm(t)))))) + t -- the LayerNorm is its own launch in front of the merge and the unmerge kernel adds the residual.
+    // core(a, rows) maps the projected tokens a [n][rows][.] to the input of `last`; rows is T, or T - r when merged
+    template <typename Core>
+    Act sublayer(const Merge* m, const DNorm& ln, const DConv& first, ConvOpt of, const DConv& last, const Act& t, int T, Core&& core) {
+        Act a;
+        if (m) a = conv2d(c, first, tome_merge(*m, ln, t), nullptr, of);
+        else { of.ln = &ln; a = conv2d(c, first, t, nullptr, of); }
+        Act y = core(a, m ? m->Tm : T);
+        ConvOpt ol; if (!m) ol.res0 = &t;
+        Act o = conv2d(c, last, y, nullptr, ol);
+        return m ? tome_unmerge(*m, o, t) : o;
+    }
+    Act xf(const XfBlock& b, const Act& x) {
+        const int n = x.n, T = x.h * x.w, C = b.C, bit = b.bit, level = b.level;
         int np = 0;
         if (pag_first != PAG_NONE && ((u.pag_mask >> bit) & 1u)) {
             const int lead = pag_first - sample0;                       // leading unperturbed samples of this forward
@@ -512,17 +508,9 @@ struct Fwd {
         // residual, which the unmerge kernel adds
         Merge mg;
         if (tl) mg = tome_plan(tl, t0, bit);
-        const int T1 = m1 ? mg.Tm : T;
-        Act qkv;
-        if (m1) { ConvOpt oq; qkv = conv2d(c, b.qkv, tome_merge(mg, b.ln1, t0), nullptr, oq); }
-        else {
-            ConvOpt oq; oq.ln = &b.ln1;              // LayerNorm fused into the K = 320 / 640 projections (X-stationary kernel), else a launch
-            qkv = conv2d(c, b.qkv, t0, nullptr, oq);
-        }
-        Act o1 = attn(qkv.p, 3 * C, (long long)T1 * 3 * C, qkv.p + C, qkv.p + 2 * C, 3 * C, (long long)T1 * 3 * C, n, T1, T1, b.heads, np);
-        ConvOpt or1; if (!m1) or1.res0 = &t0;
-        Act t1 = conv2d(c, b.o1, o1, nullptr, or1);
-        if (m1) t1 = tome_unmerge(mg, t1, t0);
+        Act t1 = sublayer(m1 ? &mg : nullptr, b.ln1, b.qkv, ConvOpt(), b.o1, t0, T, [&](const Act& qkv, int T1) {
+            return attn(qkv.p, 3 * C, (long long)T1 * 3 * C, qkv.p + C, qkv.p + 2 * C, 3 * C, (long long)T1 * 3 * C, n, T1, T1, b.heads, np);
+        });
         // attn2 and the feed-forward as ONE kernel each on the C = 320 level (xf_fused.hip; LADI_XF_FUSE=0 / =1 / =2: none / attn2 only / both,
         // latched at UNet::load), else the chain of projections.  Measured on
         // MI355X (profiles/r05_xf_fused_ab.txt): parity-green and bit-reproducible, but at one wave per SIMD the fused chains expose the latency two
@@ -546,13 +534,11 @@ struct Fwd {
                 c.check(ladi_launch_xattn_block(xa, c.st), "xattn_block");
             }
         } else {
-            const int T2 = m2 ? mg.Tm : T;             // merged: the queries (and the image term's) are the T - r merged rows
-            Act q2;
-            if (m2) { ConvOpt oq2; q2 = conv2d(c, b.q2, tome_merge(mg, b.ln2, t1), nullptr, oq2); }
-            else { ConvOpt oq2; oq2.ln = &b.ln2; q2 = conv2d(c, b.q2, t1, nullptr, oq2); }
-            const h16* kv = b.kv_cache + (size_t)sample0 * u.ctx_L * 2 * C;     // this lane's samples of the cached cross-attention K / V
-            Act o2 = attn(q2.p, C, (long long)T2 * C, kv, kv + C, 2 * C, (long long)u.ctx_L * 2 * C, n, T2, u.ctx_L, b.heads);
-            if (ip) {
+            // merged: the queries (and the image term's) are the T - r merged rows
+            t2 = sublayer(m2 ? &mg : nullptr, b.ln2, b.q2, ConvOpt(), b.o2, t1, T, [&](const Act& q2, int T2) {
+                const h16* kv = b.kv_cache + (size_t)sample0 * u.ctx_L * 2 * C;     // this lane's samples of the cached cross-attention K / V
+                Act o2 = attn(q2.p, C, (long long)T2 * C, kv, kv + C, 2 * C, (long long)u.ctx_L * 2 * C, n, T2, u.ctx_L, b.heads);
+                if (!ip) return o2;
                 const long long skv = (long long)u.ip_ctx_N * 2 * C;
                 const h16* ikv = b.ip_kv_cache + (size_t)sample0 * skv;           // this lane's samples of the image K / V
                 if (u.ip_route == 1) {
@@ -562,10 +548,8 @@ struct Fwd {
                     c.check(ladi_launch_ip_attn_add(q2.p, q2.ld, (long long)T2 * q2.ld, ikv, 2 * C, skv, ikv + C, 2 * C, skv, o2.p, o2.ld, (long long)T2 * o2.ld,
                                                     n, b.heads, T2, u.ip_ctx_N, b.ip_scale, c.st), "ip_attn_add");
                 }
-            }
-            ConvOpt or2; if (!m2) or2.res0 = &t1;
-            t2 = conv2d(c, b.o2, o2, nullptr, or2);
-            if (m2) t2 = tome_unmerge(mg, t2, t1);
+                return o2;
+            });
         }
         Act t3;
         if (fuse >= 2 && !m3) {
@@ -578,12 +562,7 @@ struct Fwd {
             }
         } else {
             ConvOpt og; og.act = LADI_ACT_GEGLU;
-            Act gg;
-            if (m3) gg = conv2d(c, b.ff1, tome_merge(mg, b.ln3, t2), nullptr, og);
-            else { og.ln = &b.ln3; gg = conv2d(c, b.ff1, t2, nullptr, og); }
-            ConvOpt or3; if (!m3) or3.res0 = &t2;
-            t3 = conv2d(c, b.ff2, gg, nullptr, or3);
-            if (m3) t3 = tome_unmerge(mg, t3, t2);
+            t3 = sublayer(m3 ? &mg : nullptr, b.ln3, b.ff1, og, b.ff2, t2, T, [](const Act& gg, int) { return gg; });
         }
         Act xin = x; xin.h = T; xin.w = 1;
         Act outv = out; outv.h = T; outv.w = 1;
@@ -597,8 +576,9 @@ struct Fwd {
 
 }  // namespace
 
-Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_idx, const Act* eps_out, int sample0, const FeatCache* fc,
-                  int pag_first) {
+Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_idx, const FwdOpt& opt) {
+    const Act* eps_out = opt.eps_out; const FeatCache* fc = opt.fc;
+    const int sample0 = opt.sample0, pag_first = opt.pag_first;
     // deep-feature cache (runtime.h FeatCache): `shallow` skips every layer outside the 64x48 level's outermost `branch` layers; the layer
     // sequence below stays the only one -- a skipped layer only advances the weight indices
     const int L = cfg.layers_per_block;
@@ -630,13 +610,13 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
     Act h = conv2d(c, conv_in, x, nullptr, o);
     pp(h, "conv_in");
     skips.push_back(h);
-    int ri = 0, xi = 0;
+    int ri = 0, xi = 0;     // xi walks UNet::xf once, down to up: every transformer block, run or skipped, advances it
     for (int i = 0; i < 4; ++i) {
         for (int j = 0; j < L; ++j) {
             if (shallow && (i > 0 || j >= fbranch)) { ++ri; if (i < 3) ++xi; continue; }
             h = f.res(down_res[ri++], h, nullptr);
             pp(h, "down_blocks.%d.resnets.%d", i, j);
-            if (i < 3) { h = f.xf(down_xf[xi], h, xi, i); ++xi; pp(h, "down_blocks.%d.attentions.%d", i, j); }
+            if (i < 3) { h = f.xf(xf[xi++], h); pp(h, "down_blocks.%d.attentions.%d", i, j); }
             skips.push_back(h);
         }
         if (i < 3 && !shallow) {
@@ -649,15 +629,16 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
     if (!shallow) {
         h = f.res(mid_res[0], h, nullptr);
         pp(h, "mid_block.resnets.0");
-        h = f.xf(mid_xf, h, 3 * L, 3);
+        h = f.xf(xf[xi], h);
         pp(h, "mid_block.attentions.0");
         h = f.res(mid_res[1], h, nullptr);
         pp(h, "mid_block.resnets.1");
     }
+    ++xi;
     // diffusers' `forward_upsample_size`: when a latent side is not a multiple of 2^3 (three upsamplers), the down path rounded a level up
     // (ceil(H / 2)) and every upsampler stretches to the size of the skip it is concatenated with; else each one doubles
     const bool ups_to_skip = (x.h % 8) || (x.w % 8);
-    ri = 0; xi = 0;
+    ri = 0;
     for (int i = 0; i < 4; ++i) {
         for (int j = 0; j < L + 1; ++j) {
             // the cache point: the hidden state that enters up_blocks.3.resnets.(L - branch), before the concatenation with its skip
@@ -687,7 +668,7 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
             }
             h = f.res(up_res[ri++], h, &sk);
             pp(h, "up_blocks.%d.resnets.%d", i, j);
-            if (i > 0) { h = f.xf(up_xf[xi], h, 3 * L + 1 + xi, 3 - i); ++xi; pp(h, "up_blocks.%d.attentions.%d", i, j); }
+            if (i > 0) { h = f.xf(xf[xi++], h); pp(h, "up_blocks.%d.attentions.%d", i, j); }
         }
         if (i < 3 && !shallow) {
             ConvOpt ou; ou.ups = 1; ou.stats = true;
@@ -704,6 +685,27 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
     Act out = conv2d(c, conv_out, g, nullptr, oc);
     pp(out, "conv_out");
     return out;
+}
+
+void UNet::key(Key& k, bool perturbed) const {
+    if (xf.empty()) throw std::runtime_error("UNet::key: the UNet is not loaded");
+    k.temb_table = temb_table; k.kv_cache = xf.front().kv_cache;
+    k.probe = probe ? probe->id : 0ULL;
+    if (freeu.on) {
+        const float fv[4] = {freeu.s1, freeu.s2, freeu.b1, freeu.b2};
+        k.freeu_on = 1; std::memcpy(k.freeu, fv, sizeof(fv));
+    }
+    if (perturbed) k.pag_mask = pag_mask;
+    if (ip_ctx_n > 0) {
+        k.ip_on = 1; k.ip_N = ip_ctx_N; k.ip_kv = xf.front().ip_kv_cache;
+        for (auto& b : xf) if (b.bit < 32) std::memcpy(&k.ip_scale[b.bit], &b.ip_scale, 4);
+    }
+    if (tome.on) {
+        const ToMeCfg& tc = tome.cfg;
+        const int opts[8] = {tc.max_downsample, tc.sx, tc.sy, tc.use_rand, (int)tc.seed, tc.merge_attn, tc.merge_crossattn, tc.merge_mlp};
+        k.tome_on = 1; std::memcpy(k.tome_opts, opts, sizeof(opts));
+        std::memcpy(&k.tome_ratio, &tc.ratio, sizeof(double)); k.tome_gen = tome.gen;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -741,7 +743,7 @@ void UNetLanes::configure(int n, int g) {
 }
 
 void UNetLanes::forward(UNet& u, hipStream_t main_st, bool dry, bool concurrent, const Act& x, const Act& eps, const float* temb, const int* tidx,
-                        int sample0, const FeatCache* fc, int pag_first) {
+                        const FwdOpt& o) {
     const int Gu = sub_lanes(x.n);          // the configured count when it divides x.n (always, for the whole batch)
     const int ng = x.n / Gu;
     const bool par = concurrent && !dry && Gu > 1;
@@ -754,7 +756,8 @@ void UNetLanes::forward(UNet& u, hipStream_t main_st, bool dry, bool concurrent,
         if (!dry && stats_cap[g]) HIP_OK_L(hipMemsetAsync(stats[g], 0, stats_cap[g] * sizeof(float), sg));
         Act xg = x; xg.n = ng; xg.p = x.p + (size_t)g * ng * x.h * x.w * x.ld;
         Act eg = eps; eg.n = ng; eg.p = eps.p + (size_t)g * ng * eps.h * eps.w * eps.ld; eg.st_part = nullptr; eg.st_px = 0;
-        (void)u.forward(c, xg, temb, tidx, &eg, sample0 + g * ng, fc, pag_first);
+        FwdOpt og = o; og.eps_out = &eg; og.sample0 = o.sample0 + g * ng;
+        (void)u.forward(c, xg, temb, tidx, og);
         if (dry) { peak[g] = arena[g].peak; if (c.stats_peak > stats_peak[g]) stats_peak[g] = c.stats_peak; }
         if (par && g > 0) { HIP_OK_L(hipEventRecord(join[g], sg)); HIP_OK_L(hipStreamWaitEvent(main_st, join[g], 0)); }
     }

@@ -298,6 +298,8 @@ def tiny():
     mods = dict(unet=L.NativeUNet(ucfg, sds["unet"]), vae=L.NativeVAE(vcfg, sds["vae"]), emasc=L.NativeEMASC(ecfg, sds["emasc"]))
     yield dict(ucfg=ucfg, vcfg=vcfg, ecfg=ecfg, sd=sds, mod=mods, ref={}, run={}, fwd={})
     mods["unet"].remove_token_merging()
+    if mods["unet"].ip_adapter_info is not None:            # loaded by _adapter for the +ip cases
+        mods["unet"].unload_ip_adapter()
 
 
 @pytest.fixture(autouse=True)
@@ -308,6 +310,8 @@ def _off_between_tests(request):
         u = request.getfixturevalue("tiny")["mod"]["unet"]
         u.remove_token_merging()
         u.set_pag_applied_layers("mid")
+        if u.ip_adapter_info is not None:
+            u.set_ip_adapter_scale(1.0)
 
 
 def _fwd_inputs(tiny, hw, seed=11):
@@ -318,6 +322,24 @@ def _fwd_inputs(tiny, hw, seed=11):
         ehs = torch.randn((2, 8, tiny["ucfg"]["cross_attention_dim"]), generator=g).half().float()
         tiny["fwd"][key] = (x, ehs, x.to(U.dev()), ehs.to(U.dev()))
     return tiny["fwd"][key]
+
+
+IP_SCALES = [1.0] * 16
+IP_SCALES[1] = 0.0                    # down_blocks.0.attentions.1: a block that merges and skips the image term
+
+
+def _adapter(tiny):
+    """the IP-Adapter of tests/ip_adapter_ref.py, loaded once into the UNet the module shares (without an image context the forward is the
+    plain one), with IP_SCALES set -> (sd_ip, embeds [2, E], tokens [2, N, cross_dim])"""
+    from tests import ip_adapter_ref as IR
+    unet = tiny["mod"]["unet"]
+    if "ip" not in tiny:
+        sd_ip = IR.make_adapter(tiny["ucfg"])
+        unet.load_ip_adapter(dict(sd_ip))
+        emb = torch.randn((2, 64), generator=torch.Generator().manual_seed(77)).half().float()
+        tiny["ip"] = (sd_ip, emb, IR.image_proj(sd_ip, emb))
+    assert _lib.load().ladi_unet_set_ip_scale(unet.h, (ctypes.c_float * 16)(*IP_SCALES), 16) == 0, _lib.last_error()
+    return tiny["ip"]
 
 
 def _device_plans(unet, tcfg, hw, n):
@@ -387,26 +409,31 @@ FWD_CASES = {
 
 
 @pytest.mark.parametrize("hw", [(8, 6), (5, 3)])
-@pytest.mark.parametrize("case", list(FWD_CASES))
+@pytest.mark.parametrize("case", list(FWD_CASES) + ["attn+ip", "all+ip"])
 def test_forward_with_forced_plans(tiny, case, hw):
     """NativeUNet tiny, B = 2, t = 481: every merged block's plan is read back and forced into tome_ref's forward; thresholds of
-    tests/test_gpu_pag.py's forward comparison (rel-L2 <= 5e-3, PSNR >= 55 dB)"""
+    tests/test_gpu_pag.py's forward comparison (rel-L2 <= 5e-3, PSNR >= 55 dB).  +ip: with an IP-Adapter image context set (one block at
+    scale 0), the image term from the merged rows where the cross-attention merges; "plain" is then the unmerged forward with that context"""
     from ladi_vton_amd import tome
     unet = tiny["mod"]["unet"]
     x, ehs, xd, ed = _fwd_inputs(tiny, hw)
-    tcfg = tome.config(**FWD_CASES[case])
-    plain = unet(xd, T0, encoder_hidden_states=ed).sample.float().cpu()
-    unet.set_token_merging(**FWD_CASES[case])
-    got = unet(xd, T0, encoder_hidden_states=ed).sample.float().cpu()
+    kw, ip = {}, None
+    if case.endswith("+ip"):
+        sd_ip, emb, tok = _adapter(tiny)
+        kw, ip = dict(ip_image_embeds=emb.to(U.dev())), (sd_ip, tok, IP_SCALES)
+    tcfg = tome.config(**FWD_CASES[case.split("+")[0]])
+    plain = unet(xd, T0, encoder_hidden_states=ed, **kw).sample.float().cpu()
+    unet.set_token_merging(**FWD_CASES[case.split("+")[0]])
+    got = unet(xd, T0, encoder_hidden_states=ed, **kw).sample.float().cpu()
     forced = _device_plans(unet, tcfg, hw, 2)
     assert forced, "nothing merged"
-    ref = R.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, tcfg, forced)
+    ref = R.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, tcfg, forced, ip=ip)
     ps, rl = U.psnr(got, ref), U.rel_l2(got, ref)
     print("ToMe forward %s %dx%d: PSNR %.2f dB, rel-L2 %.3g; against plain %.2f dB" % ((case,) + hw + (ps, rl, U.psnr(got, plain))))
     U.record_parity("tome_forward_tiny_%s_%dx%d" % ((case,) + hw), dict(psnr_db=round(ps, 2), rel_l2=rl))
     assert torch.isfinite(got).all() and rl <= REL_L2 and ps >= PSNR_DB, (ps, rl)
     assert not torch.equal(got, plain)
-    assert torch.equal(unet(xd, T0, encoder_hidden_states=ed).sample.float().cpu(), got)           # and it is reproducible
+    assert torch.equal(unet(xd, T0, encoder_hidden_states=ed, **kw).sample.float().cpu(), got)     # and it is reproducible
 
 
 def wiring_shares(sd, ucfg, x, ehs, tcfg):
@@ -546,10 +573,10 @@ def test_graph_equals_eager_and_runs_repeat_bitwise(tiny):
     assert torch.equal(a[1], b[1]) and torch.equal(a[0], b[0]) and torch.equal(a[1], lat_g)
 
 
-@pytest.mark.parametrize("what", ["feature_cache", "pag_mid", "lcm2"])
+@pytest.mark.parametrize("what", ["feature_cache", "pag_mid", "lcm2", "ip"])
 def test_loop_with_other_switches(tiny, what):
-    """token merging together with feature_cache = 2, PAG on the mid block and a 2-step LCM run: the graph run is finite, equals the eager
-    run bit for bit and differs from the same run without merging"""
+    """token merging together with feature_cache = 2, PAG on the mid block, a 2-step LCM run and an IP-Adapter image prompt (one block at
+    scale 0): the graph run is finite, equals the eager run bit for bit and differs from the same run without merging"""
     import ladi_vton_amd as L
     kw, steps, sched = {}, STEPS, None
     if what == "feature_cache":
@@ -558,6 +585,8 @@ def test_loop_with_other_switches(tiny, what):
         kw = dict(pag_scale=3.0)
     elif what == "lcm2":
         steps, sched = 2, L.LCMScheduler()
+    elif what == "ip":
+        kw = dict(ip_adapter_image_embeds=_adapter(tiny)[1].to(U.dev()))
     pipe = _pipe(tiny, sched)
 
     def call(**k):                                                      # LCM draws step noise: every call gets its own seeded generator

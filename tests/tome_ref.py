@@ -137,10 +137,12 @@ def plan_diff(a, b):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the block and the UNet
-def transformer2d(sd, p, x, ehs, heads, groups, tcfg=None, forced=None, record=None, metric="proj_in"):
+def transformer2d(sd, p, x, ehs, heads, groups, tcfg=None, forced=None, record=None, metric="proj_in", ip=None):
     """oracle.models.transformer2d with token merging.  tcfg: the configuration dict or None; forced: a plan per sample (else the plan is
     computed here, in x's dtype); record(p, t0, plans): a hook.  metric: "proj_in" (the contract), or a mis-wiring "norm1" / "input" the
-    wiring test measures against"""
+    wiring test measures against.  ip: None or (sd_ip, tokens [n, N, cross_dim], scales per block in execution order), the IP-Adapter image
+    term of tests/ip_adapter_ref.py: scale * attention(q2, to_k_ip(tokens), to_v_ip(tokens)) added to the attn2 output before to_out, q2 from
+    the merged rows when merge_crossattn is on; a block whose scale is 0 has no image term"""
     n, C, h, w = x.shape
     res = x
     g = M.group_norm(sd, p + ".norm", x, groups, 1e-6).permute(0, 2, 3, 1).reshape(n, h * w, C)
@@ -169,8 +171,15 @@ def transformer2d(sd, p, x, ehs, heads, groups, tcfg=None, forced=None, record=N
     t = (u(o) if on("merge_attn") else o) + t
     a = M.layer_norm(sd, b + ".norm2", t)
     a = m(a) if on("merge_crossattn") else a
-    o = M.linear(sd, b + ".attn2.to_out.0", M.attention(M.linear(sd, b + ".attn2.to_q", a), M.linear(sd, b + ".attn2.to_k", ehs),
-                                                        M.linear(sd, b + ".attn2.to_v", ehs), heads))
+    q2 = M.linear(sd, b + ".attn2.to_q", a)
+    o = M.attention(q2, M.linear(sd, b + ".attn2.to_k", ehs), M.linear(sd, b + ".attn2.to_v", ehs), heads)
+    if ip is not None:
+        sd_ip, tokens, scales = ip
+        scale = float(scales[block_prefixes().index(p)])
+        if scale != 0.0:
+            proc = p + ".transformer_blocks.0.attn2.processor."
+            o = o + scale * M.attention(q2, F.linear(tokens, sd_ip[proc + "to_k_ip.weight"]), F.linear(tokens, sd_ip[proc + "to_v_ip.weight"]), heads)
+    o = M.linear(sd, b + ".attn2.to_out.0", o)
     t = (u(o) if on("merge_crossattn") else o) + t
     a = M.layer_norm(sd, b + ".norm3", t)
     a = m(a) if on("merge_mlp") else a
@@ -191,16 +200,16 @@ def merged_prefixes(tcfg, L=2):
     return [p for p in block_prefixes(L) if level_of(p, L) < tcfg["max_downsample"]]
 
 
-def unet_forward(sd, cfg, sample, timestep, ehs, tcfg=None, forced=None, record=None, metric="proj_in"):
+def unet_forward(sd, cfg, sample, timestep, ehs, tcfg=None, forced=None, record=None, metric="proj_in", ip=None):
     """the whole forward (any latent size) with token merging in the blocks of the first max_downsample levels.  forced: dict prefix -> a
-    plan per sample"""
+    plan per sample; ip: as transformer2d's"""
     boc, heads, L = cfg["block_out_channels"], cfg["num_heads"], cfg["layers_per_block"]
     G_, eps = cfg["norm_num_groups"], cfg["norm_eps"]
     n = sample.shape[0]
 
     def xf(p, x, hd):
         on = tcfg is not None and tcfg["ratio"] > 0 and level_of(p, L) < tcfg["max_downsample"]
-        return transformer2d(sd, p, x, ehs, hd, G_, tcfg if on else None, forced.get(p) if forced else None, record, metric)
+        return transformer2d(sd, p, x, ehs, hd, G_, tcfg if on else None, forced.get(p) if forced else None, record, metric, ip)
     forward_upsample_size = any(s % 8 != 0 for s in sample.shape[-2:])
     t = torch.as_tensor(timestep, dtype=torch.float32).reshape(-1).expand(n)
     temb = M.timestep_embedding(t, boc[0])
