@@ -1,4 +1,4 @@
-"""Any latent size on the host (no GPU): the restatement in tests/anysize_ref.py is oracle.models.unet_forward bit for bit wherever diffusers
+"""Any latent size on the host (no GPU): the reference forward in tests/ref_unet.py is oracle.models.unet_forward bit for bit wherever diffusers
 does not set `forward_upsample_size`, it stretches to the skips' sizes where it does, and its statement of the nearest-index rule (the one
 the igemm gather implements) is F.interpolate(size=..., mode="nearest")."""
 import pytest
@@ -7,7 +7,7 @@ import torch.nn.functional as F
 
 from oracle import configs as C
 from oracle import models as M
-from tests import anysize_ref as R
+from tests import ref_unet as R
 
 
 @pytest.fixture(scope="module")
@@ -28,8 +28,11 @@ def test_restatement_is_the_oracle_at_multiples_of_8(tiny_unet, hw):
     ucfg, sd = tiny_unet
     x, ehs = _inputs(ucfg, 2, *hw)
     ref, probe_ref = M.unet_forward(sd, ucfg, x, 481, ehs, return_probe=True)
-    got, probe = R.unet_forward(sd, ucfg, x, 481, ehs, return_probe=True)
-    assert torch.equal(got, ref) and torch.equal(probe, probe_ref)
+    seen = {}
+    got = R.unet_forward(sd, ucfg, x, 481, ehs, observe=seen.__setitem__)
+    assert torch.equal(got, ref) and torch.equal(seen["mid_block.resnets.1"], probe_ref)
+    tome0 = dict(ratio=0.0, max_downsample=2, use_rand=False, seed=0, merge_attn=True, merge_crossattn=True, merge_mlp=True)
+    assert torch.equal(R.unet_forward(sd, ucfg, x, 481, ehs, tome=(tome0, None, None, "proj_in")), ref)           # token merging at ratio 0
 
 
 @pytest.mark.parametrize("hw", [(17, 15), (9, 7), (12, 16)])

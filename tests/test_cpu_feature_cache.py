@@ -11,7 +11,8 @@ from oracle import configs as C
 from oracle import models as M
 from oracle import pipeline as P
 from tests import feature_cache_ref as R
-from tests import strength_ref as SR
+from tests import ref_tryon as RT
+from tests import ref_unet as RU
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -35,9 +36,9 @@ def _unet_case(tiny, hw=(16, 8), n=2, seed=3):
 def test_reference_whole_forward_is_the_oracle_forward(tiny):
     x, ehs = _unet_case(tiny)
     want = M.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs)
-    assert torch.equal(R.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs), want)
+    assert torch.equal(RU.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs), want)
     for k in (0, 1, 2):
-        out, cap = R.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs, "capture", k)
+        out, cap = RU.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs, cache=("capture", k))
         assert torch.equal(out, want)
         assert cap.shape == (2, tiny["ucfg"]["block_out_channels"][1 if k == 2 else 0], 16, 8)
 
@@ -46,22 +47,22 @@ def test_reference_whole_forward_is_the_oracle_forward(tiny):
 def test_reference_shallow_at_the_captured_input_is_the_whole_forward(tiny, k):
     """the same layers on the same tensors: exactly equal; at another input and timestep it is another function (the comparison sees it)"""
     x, ehs = _unet_case(tiny)
-    want, cap = R.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs, "capture", k)
-    assert torch.equal(R.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs, "shallow", k, cap), want)
+    want, cap = RU.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs, cache=("capture", k))
+    assert torch.equal(RU.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs, cache=("shallow", k, cap)), want)
     x1, _ = _unet_case(tiny, seed=4)
-    other = R.unet_forward(tiny["unet"], tiny["ucfg"], x1, 461, ehs, "shallow", k, cap)
+    other = RU.unet_forward(tiny["unet"], tiny["ucfg"], x1, 461, ehs, cache=("shallow", k, cap))
     whole1 = M.unet_forward(tiny["unet"], tiny["ucfg"], x1, 461, ehs)
     assert not torch.equal(other, whole1) and not torch.equal(other, want) and torch.isfinite(other).all()
 
 
 def test_reference_cache_point_differs_per_branch_and_runs_odd_sizes(tiny):
     x, ehs = _unet_case(tiny, hw=(13, 10))
-    caps = [R.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs, "capture", k)[1] for k in (0, 1, 2)]
+    caps = [RU.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs, cache=("capture", k))[1] for k in (0, 1, 2)]
     assert all(c.shape[-2:] == (13, 10) for c in caps)
     assert not torch.equal(caps[0], caps[1]) and not torch.equal(caps[1], caps[2])
-    want = R.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs)
+    want = RU.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs)
     for k in (0, 1, 2):
-        assert torch.equal(R.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs, "shallow", k, caps[k]), want)
+        assert torch.equal(RU.unet_forward(tiny["unet"], tiny["ucfg"], x, 481, ehs, cache=("shallow", k, caps[k])), want)
 
 
 # ------------------------------------------------------------------------------------------------------------------ the plan
@@ -173,19 +174,26 @@ def _loop_inputs(tiny, B=1, H=64, W=64):
 
 
 def _loop(tiny, inp, interval, branch=0, steps=4, sched="ddim", table=None, counts=None):
-    return R.tryon_reference(tiny["unet"], tiny["ucfg"], tiny["vae"], tiny["vcfg"], tiny["emasc"], inp, interval, branch, steps, sched,
-                             table=table, counts=counts)
+    return RT.tryon_reference(tiny["unet"], tiny["ucfg"], tiny["vae"], tiny["vcfg"], tiny["emasc"], inp, steps, sched, table=table,
+                              feature_cache=(interval, branch), info=counts)
 
 
 @pytest.mark.parametrize("sched", ["ddim", "pndm"])
 def test_reference_loop_with_an_all_true_plan_is_the_plain_loop(tiny, sched):
+    """with the oracle's own scheduler the plain loop is oracle.pipeline.tryon_pipeline; with the package's mirror it is the loop with every
+    option off"""
     inp = _loop_inputs(tiny)
-    img0, lat0 = SR.tryon_reference(tiny["unet"], tiny["ucfg"], tiny["vae"], tiny["vcfg"], tiny["emasc"], inp, None, 0, 4, sched)
+    a = (tiny["unet"], tiny["ucfg"], tiny["vae"], tiny["vcfg"], tiny["emasc"], inp)
+    img_o, lat_o = P.tryon_pipeline(*a, num_inference_steps=4, guidance_scale=7.5, scheduler=sched)
+    img0, lat0 = RT.tryon_reference(*a, 4, sched)
     n = 5 if sched == "pndm" else 4
     for interval in (None, 1, [1] * n):
         c = {}
         img, lat = _loop(tiny, inp, interval, steps=4, sched=sched, counts=c)
         assert torch.equal(lat, lat0) and torch.equal(img, img0)
+        assert c["shallow"] == 0 and c["evals"] == n
+        img, lat = _loop(tiny, inp, interval, steps=4, sched=P.make_scheduler(sched), counts=c)
+        assert torch.equal(lat, lat_o) and torch.equal(img, img_o)
         assert c["shallow"] == 0 and c["evals"] == n
 
 

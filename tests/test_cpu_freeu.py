@@ -9,6 +9,7 @@ import torch
 from oracle import configs as C
 from oracle import models as M
 from tests import freeu_ref as R
+from tests import ref_unet as RU
 from tests import util as U
 
 FREEU = (0.9, 0.2, 1.4, 1.6)          # diffusers' recommendation for SD 2.1: s1, s2, b1, b2
@@ -38,7 +39,7 @@ def tiny():
     g = torch.Generator().manual_seed(11)
     x = torch.randn((2, 31, 32, 24), generator=g).half().float()
     ehs = torch.randn((2, 8, cfg["cross_attention_dim"]), generator=g).half().float()
-    run = lambda fu: R.unet_forward(sd, cfg, x, 481, ehs, fu)
+    run = lambda fu: RU.unet_forward(sd, cfg, x, 481, ehs, freeu=fu)
     return dict(cfg=cfg, sd=sd, x=x, ehs=ehs, run=run, plain=M.unet_forward(sd, cfg, x, 481, ehs), on=run(FREEU))
 
 

@@ -1,4 +1,4 @@
-"""Guidance schedule, CFG cut-off and guidance rescale, host side: the reference restatement (tests/guidance_ref.py) is pinned to the
+"""Guidance schedule, CFG cut-off and guidance rescale, host side: the reference loop (tests/ref_tryon.py) is pinned to the
 oracle pipeline before anything is compared with it; the guidance_interval helper; the Python-side validation; the ABI declarations."""
 import math
 import os
@@ -11,6 +11,8 @@ import torch
 from oracle import configs as C
 from oracle import pipeline as P
 from tests import guidance_ref as G
+from tests import ip_adapter_ref as IP
+from tests import ref_tryon as RT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["ladi_tryon_set_guidance_schedule", "ladi_tryon_set_guidance_rescale", "ladi_tryon_cond_only_evals", "ladi_op_sched_run_guided",
@@ -27,27 +29,40 @@ def tiny():
     return dict(ucfg=ucfg, vcfg=vcfg, sd=sd, inp=inp)
 
 
+def _counts(info):
+    return {k: info[k] for k in ("full", "cond_only")}
+
+
 @pytest.mark.parametrize("scheduler,steps,evals", [("ddim", 3, 3), ("pndm", 3, 4)])
 @pytest.mark.parametrize("scale", [7.5, 1.0])
 def test_reference_constant_schedule_is_the_oracle_pipeline(tiny, scheduler, steps, evals, scale):
     """tryon_reference with a constant schedule and phi = 0 IS oracle.pipeline.tryon_pipeline: equal, not close (scale 1.0: the run without
-    CFG); the forward counts are what the schedule implies"""
+    CFG); the forward counts are what the schedule implies.  So is the loop with each feature at its off value"""
     a = (tiny["sd"]["unet"], tiny["ucfg"], tiny["sd"]["vae"], tiny["vcfg"], tiny["sd"]["emasc"], tiny["inp"])
     ref_img, ref_lat = P.tryon_pipeline(*a, num_inference_steps=steps, guidance_scale=scale, scheduler=scheduler)
     counts = {}
-    img, lat = G.tryon_reference(*a, [scale] * evals, 0.0, num_inference_steps=steps, scheduler=scheduler, counts=counts)
+    img, lat = RT.tryon_reference(*a, steps, P.make_scheduler(scheduler), table=[scale] * evals, info=counts)
     assert torch.equal(lat, ref_lat) and torch.equal(img, ref_img)
-    assert counts == (dict(full=evals, cond_only=0) if scale > 1 else dict(full=0, cond_only=evals))
+    assert _counts(counts) == (dict(full=evals, cond_only=0) if scale > 1 else dict(full=0, cond_only=evals))
+    # every other option at its off value is that same run
+    sd_ip = IP.make_adapter(tiny["ucfg"])
+    tome0 = dict(ratio=0.0, max_downsample=1, use_rand=False, seed=0, merge_attn=True, merge_crossattn=False, merge_mlp=False)
+    off = dict(cache_none=dict(feature_cache=(None, 0)), cache_1=dict(feature_cache=(1, 0)), cache_flags=dict(feature_cache=([True] * evals, 1)),
+               pag_0=dict(pag=(0.0, 0.0, ("mid",))), ip_zero=dict(ip=(sd_ip, torch.ones(1, 64), None, [0.0] * 16)), tome_0=dict(tome=(tome0, None)),
+               preserve_none=dict(preserve=(None, 0.0)), first_step_0=dict(first_step=0, init_latents=torch.ones(1, 4, 16, 16)), freeu_none=dict(freeu=None))
+    for name, kw in off.items():
+        img, lat = RT.tryon_reference(*a, steps, P.make_scheduler(scheduler), table=[scale] * evals, **kw)
+        assert torch.equal(lat, ref_lat) and torch.equal(img, ref_img), name
 
 
 def test_reference_cut_off_and_rescale_change_the_result(tiny):
     """the restatement's two new branches do something: a cut-off run differs from the constant one and counts its cond-only forwards; phi
     rescales the guided prediction to the conditional one's standard deviation (phi = 1: equal stds)"""
     a = (tiny["sd"]["unet"], tiny["ucfg"], tiny["sd"]["vae"], tiny["vcfg"], tiny["sd"]["emasc"], tiny["inp"])
-    _, lat_c = G.tryon_reference(*a, [7.5] * 3, 0.0, num_inference_steps=3)
+    _, lat_c = RT.tryon_reference(*a, 3, P.make_scheduler("ddim"), table=[7.5] * 3)
     counts = {}
-    _, lat_i = G.tryon_reference(*a, [7.5, 1.0, 7.5], 0.0, num_inference_steps=3, counts=counts)
-    assert counts == dict(full=2, cond_only=1) and not torch.equal(lat_c, lat_i)
+    _, lat_i = RT.tryon_reference(*a, 3, P.make_scheduler("ddim"), table=[7.5, 1.0, 7.5], info=counts)
+    assert _counts(counts) == dict(full=2, cond_only=1) and not torch.equal(lat_c, lat_i)
     g = torch.Generator().manual_seed(3)
     eu, ec = torch.randn((3, 4, 5, 7), generator=g, dtype=torch.float64), torch.randn((3, 4, 5, 7), generator=g, dtype=torch.float64) * 0.5
     e1 = G.guided_eps(eu, ec, 7.5, 1.0)

@@ -8,10 +8,13 @@ import torch
 
 from ladi_vton_amd import ip_adapter as IPA
 from oracle import configs as C
+from oracle import models as M
 from oracle import pipeline as P
 from tests import ip_adapter_cases as IC
 from tests import ip_adapter_ref as R
 from tests import pag_ref as PG
+from tests import ref_tryon as RT
+from tests import ref_unet as RU
 from tests import util as U
 
 CFG = C.UNET_TINY
@@ -35,7 +38,7 @@ def test_numbered_order_is_pinned():
     assert len(order) == 16 and order[-1] == "mid_block.attentions.0" and 2 * 15 + 1 == 31
     assert order[:6] == ["down_blocks.%d.attentions.%d" % (i, j) for i in range(3) for j in range(2)]
     assert order[6:15] == ["up_blocks.%d.attentions.%d" % (i, j) for i in (1, 2, 3) for j in range(3)]
-    assert IPA.block_prefixes(2) == PG.block_prefixes(2) and sorted(order) == sorted(IPA.block_prefixes(2))
+    assert IPA.block_prefixes(2) == RU.block_prefixes(2) and sorted(order) == sorted(IPA.block_prefixes(2))
 
 
 @pytest.mark.parametrize("numbered", [True, False])
@@ -150,42 +153,49 @@ def test_operator_bound(c):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the reference
-def test_reference_off_is_the_plain_reference(tiny):
+def test_reference_off_is_the_oracle_forward(tiny):
+    """no image prompt, and one whose scales are all 0: oracle.models.unet_forward's bits; under PAG the zero scales change nothing either"""
     x, ehs = torch.cat([tiny["x"], tiny["x"]]), torch.cat([tiny["ehs"], tiny["ehs"]])
     tok = R.image_proj(tiny["ip"], torch.cat([tiny["emb"], tiny["emb"]]))
     assert tok.shape == (4, 4, CFG["cross_attention_dim"])
-    plain = PG.unet_forward(tiny["sd"], CFG, x, 481, ehs)
-    assert torch.equal(R.unet_forward(tiny["sd"], CFG, x, 481, ehs), plain)
-    assert torch.equal(R.unet_forward(tiny["sd"], CFG, x, 481, ehs, ip=(tiny["ip"], tok, [0.0] * 16)), plain)
-    pag = PG.unet_forward(tiny["sd"], CFG, x, 481, ehs, PG.layer_prefixes("mid"), 2)
-    assert torch.equal(R.unet_forward(tiny["sd"], CFG, x, 481, ehs, PG.layer_prefixes("mid"), 2, ip=(tiny["ip"], tok, [0.0] * 16)), pag)
+    plain = M.unet_forward(tiny["sd"], CFG, x, 481, ehs)
+    assert torch.equal(RU.unet_forward(tiny["sd"], CFG, x, 481, ehs, ip=None), plain)
+    assert torch.equal(RU.unet_forward(tiny["sd"], CFG, x, 481, ehs, ip=(tiny["ip"], tok, [0.0] * 16)), plain)
+    pag = RU.unet_forward(tiny["sd"], CFG, x, 481, ehs, pag=(PG.layer_prefixes("mid"), 2))
+    assert not torch.equal(pag, plain)
+    assert torch.equal(RU.unet_forward(tiny["sd"], CFG, x, 481, ehs, pag=(PG.layer_prefixes("mid"), 2), ip=(tiny["ip"], tok, [0.0] * 16)), pag)
 
 
 def test_reference_image_term_is_visible(tiny):
     """scale 1 in every block: below the 55 dB the GPU forward test asks against the reference; the mid block alone too is another function"""
     x, ehs = tiny["x"], tiny["ehs"]
     tok = R.image_proj(tiny["ip"], tiny["emb"])
-    plain = PG.unet_forward(tiny["sd"], CFG, x, 481, ehs)
-    on = R.unet_forward(tiny["sd"], CFG, x, 481, ehs, ip=(tiny["ip"], tok, [1.0] * 16))
-    mid = R.unet_forward(tiny["sd"], CFG, x, 481, ehs, ip=(tiny["ip"], tok, [0.0] * 6 + [1.0] + [0.0] * 9))
+    plain = M.unet_forward(tiny["sd"], CFG, x, 481, ehs)
+    on = RU.unet_forward(tiny["sd"], CFG, x, 481, ehs, ip=(tiny["ip"], tok, [1.0] * 16))
+    mid = RU.unet_forward(tiny["sd"], CFG, x, 481, ehs, ip=(tiny["ip"], tok, [0.0] * 6 + [1.0] + [0.0] * 9))
     p, pm = U.psnr(on, plain), U.psnr(mid, plain)
     print("reference forward with the image term against plain: %.1f dB (mid block alone %.1f dB)" % (p, pm))
     assert torch.isfinite(on).all() and p < 55.0, p
     assert pm < 55.0 and not torch.equal(mid, on), pm
     # the tokens matter, not only the adapter: other embeddings give another output
-    other = R.unet_forward(tiny["sd"], CFG, x, 481, ehs, ip=(tiny["ip"], R.image_proj(tiny["ip"], -tiny["emb"]), [1.0] * 16))
+    other = RU.unet_forward(tiny["sd"], CFG, x, 481, ehs, ip=(tiny["ip"], R.image_proj(tiny["ip"], -tiny["emb"]), [1.0] * 16))
     assert U.psnr(other, on) < 55.0
 
 
 def test_reference_loop_is_not_the_plain_loop(tiny):
-    """4 DDIM steps at 64x48: the latents are below the 40 dB the GPU loop test asks against the reference"""
+    """4 DDIM steps at 64x48: the latents are below the 40 dB the GPU loop test asks against the reference; with all scales 0 the loop is
+    the one without an image prompt, and with the oracle's own scheduler, at a size the oracle runs, that is oracle.pipeline.tryon_pipeline"""
     vcfg = C.VAE_TINY
     vsd = C.synth_state_dict(C.vae_shapes(vcfg), "vae.")
     inp = P.synthetic_inputs(2, 64, 48, L=8, D=CFG["cross_attention_dim"])
-    _, plain = R.tryon_reference(tiny["sd"], CFG, vsd, vcfg, None, inp, 4, "ddim")
+    _, plain = RT.tryon_reference(tiny["sd"], CFG, vsd, vcfg, None, inp, 4, "ddim")
     counts = {}
-    _, on = R.tryon_reference(tiny["sd"], CFG, vsd, vcfg, None, inp, 4, "ddim", ip=(tiny["ip"], tiny["emb"], None, [1.0] * 16), counts=counts)
-    _, zero = R.tryon_reference(tiny["sd"], CFG, vsd, vcfg, None, inp, 4, "ddim", ip=(tiny["ip"], tiny["emb"], None, [0.0] * 16))
+    _, on = RT.tryon_reference(tiny["sd"], CFG, vsd, vcfg, None, inp, 4, "ddim", ip=(tiny["ip"], tiny["emb"], None, [1.0] * 16), info=counts)
+    _, zero = RT.tryon_reference(tiny["sd"], CFG, vsd, vcfg, None, inp, 4, "ddim", ip=(tiny["ip"], tiny["emb"], None, [0.0] * 16))
+    inp8 = P.synthetic_inputs(2, 64, 64, L=8, D=CFG["cross_attention_dim"])          # latents 8x8: a size the oracle runs
+    img_o, lat_o = P.tryon_pipeline(tiny["sd"], CFG, vsd, vcfg, None, inp8, num_inference_steps=4, guidance_scale=7.5, scheduler="ddim")
+    img_z, lat_z = RT.tryon_reference(tiny["sd"], CFG, vsd, vcfg, None, inp8, 4, P.make_scheduler("ddim"), ip=(tiny["ip"], tiny["emb"], None, [0.0] * 16))
+    assert torch.equal(lat_z, lat_o) and torch.equal(img_z, img_o)
     p = U.psnr(on, plain)
     print("reference loop with the image term against plain: latents %.1f dB" % p)
     assert counts["evals"] == 4 and torch.isfinite(on).all() and p < 40.0, p

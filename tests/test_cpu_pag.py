@@ -10,6 +10,7 @@ import torch
 from oracle import configs as C
 from oracle import models as M
 from tests import pag_ref as R
+from tests import ref_unet as RU
 from tests import util as U
 
 
@@ -26,11 +27,11 @@ def tiny():
 
 def test_reference_off_is_the_oracle_forward(tiny):
     plain = M.unet_forward(tiny["sd"], tiny["cfg"], tiny["x"], 481, tiny["ehs"])
-    assert torch.equal(R.unet_forward(tiny["sd"], tiny["cfg"], tiny["x"], 481, tiny["ehs"]), plain)
-    every = set(R.block_prefixes(2))
-    assert torch.equal(R.unet_forward(tiny["sd"], tiny["cfg"], tiny["x"], 481, tiny["ehs"], every, None), plain)
-    assert torch.equal(R.unet_forward(tiny["sd"], tiny["cfg"], tiny["x"], 481, tiny["ehs"], every, 4), plain)
-    assert torch.equal(R.unet_forward(tiny["sd"], tiny["cfg"], tiny["x"], 481, tiny["ehs"], (), 2), plain)
+    assert torch.equal(RU.unet_forward(tiny["sd"], tiny["cfg"], tiny["x"], 481, tiny["ehs"]), plain)
+    every = set(RU.block_prefixes(2))
+    assert torch.equal(RU.unet_forward(tiny["sd"], tiny["cfg"], tiny["x"], 481, tiny["ehs"], pag=(every, None)), plain)
+    assert torch.equal(RU.unet_forward(tiny["sd"], tiny["cfg"], tiny["x"], 481, tiny["ehs"], pag=(every, 4)), plain)
+    assert torch.equal(RU.unet_forward(tiny["sd"], tiny["cfg"], tiny["x"], 481, tiny["ehs"], pag=((), 2)), plain)
 
 
 @pytest.mark.parametrize("names", ["mid", ["down.block_0.attentions_1", "up.block_3"], ["down.block_1", "up.block_2"], ["down", "mid", "up"]])
@@ -38,7 +39,7 @@ def test_reference_perturbs_only_the_samples_from_pag_first(tiny, names):
     """samples 2, 3 are copies of 0, 1: with pag_first = 2 the first two keep the plain forward's bits and the last two are another function
     of the same inputs (below the 55 dB of the GPU forward test)"""
     plain = M.unet_forward(tiny["sd"], tiny["cfg"], tiny["x"], 481, tiny["ehs"])
-    out = R.unet_forward(tiny["sd"], tiny["cfg"], tiny["x"], 481, tiny["ehs"], R.layer_prefixes(names), 2)
+    out = RU.unet_forward(tiny["sd"], tiny["cfg"], tiny["x"], 481, tiny["ehs"], pag=(R.layer_prefixes(names), 2))
     p = U.psnr(out[2:], plain[2:])
     print("%s: perturbed samples %.1f dB from plain" % (names, p))
     assert torch.allclose(out[:2], plain[:2], rtol=0, atol=1e-5)

@@ -9,6 +9,7 @@ from ladi_vton_amd import _lib
 from ladi_vton_amd import tome
 from oracle import configs as C
 from oracle import models as M
+from tests import ref_unet as RU
 from tests import tome_ref as R
 from tests import util as U
 
@@ -94,9 +95,9 @@ def test_config_round_trip(lib):
 
 def test_merged_blocks_and_the_pag_overlap_rule():
     from ladi_vton_amd.pipeline import pag_layer_mask
-    pre = R.block_prefixes(2)
+    pre = RU.block_prefixes(2)
     for md in (1, 2):
-        assert [pre[b] for b in tome.merged_blocks(md, 2)] == R.merged_prefixes(dict(max_downsample=md), 2)
+        assert [pre[b] for b in tome.merged_blocks(md, 2)] == RU.merged_prefixes(dict(max_downsample=md), 2)
     assert tome.merged_blocks(1, 2) == [0, 1, 13, 14, 15]
     cfg = tome.config(0.5)
     tome.check_pag_layers(cfg, pag_layer_mask("mid", 2), 2)                              # the default layer is fine
@@ -167,8 +168,8 @@ def test_block_with_nothing_merged_is_the_oracle_block():
     none = R.make_plan(torch.zeros(len(sp), dtype=torch.bool), torch.zeros(len(sp), dtype=torch.long), sp, dp)
     for flags in (dict(merge_attn=True, merge_crossattn=False, merge_mlp=False), dict(merge_attn=True, merge_crossattn=True, merge_mlp=True)):
         tc = dict(ratio=0.5, max_downsample=1, use_rand=False, seed=0, **flags)
-        got = R.transformer2d(sd, p, x, ehs, cfg["num_heads"][0], cfg["norm_num_groups"], tc, [none, none])
+        got = RU.transformer2d(sd, p, x, ehs, cfg["num_heads"][0], cfg["norm_num_groups"], tome=(tc, [none, none], None, "proj_in"))
         assert U.rel_l2(got, ref) < 1e-12
-        on = R.transformer2d(sd, p, x, ehs, cfg["num_heads"][0], cfg["norm_num_groups"], tc)
+        on = RU.transformer2d(sd, p, x, ehs, cfg["num_heads"][0], cfg["norm_num_groups"], tome=(tc, None, None, "proj_in"))
         assert U.rel_l2(on, ref) > 1e-4                                      # and merging is visible
-    assert torch.equal(R.transformer2d(sd, p, x, ehs, cfg["num_heads"][0], cfg["norm_num_groups"]), ref)
+    assert torch.equal(RU.transformer2d(sd, p, x, ehs, cfg["num_heads"][0], cfg["norm_num_groups"]), ref)

@@ -1,6 +1,6 @@
 """Image sizes divisible by 8 whose latent is not a multiple of 8 (640x480, 136x120, ...): the size-mapped nearest upsample folded into the
 implicit-GEMM gather and stride-2 convolutions on odd sides, both through the C ABI (ladi_op_igemm); the UNet forward of the tiny and the
-full-size model against tests/anysize_ref.py (diffusers' `forward_upsample_size` arithmetic); the fused and modular try-on loops of the tiny
+full-size model against tests/ref_unet.py (diffusers' `forward_upsample_size` arithmetic); the fused and modular try-on loops of the tiny
 model against the oracle pipeline running that forward."""
 import ctypes
 import math
@@ -14,7 +14,7 @@ from ladi_vton_amd._lib import ptr, stream_ptr
 from oracle import configs as C
 from oracle import models as M
 from oracle import pipeline as P
-from tests import anysize_ref as R
+from tests import ref_unet as R
 from tests import util as U
 
 pytestmark = pytest.mark.gpu

@@ -1,6 +1,6 @@
 """Deep-feature cache (DeepCache on the full-resolution level) on the device: the capturing and the shallow forward of the stand-alone UNet
 entry against tests/feature_cache_ref.py, the rows of the cache, then the tiny model end to end (fused hipGraph, fused eager, modular, lanes)
-against feature_cache_ref.tryon_reference, the bit-equalities the feature promises, its combinations, and one case at the released size."""
+against ref_tryon.tryon_reference, the bit-equalities the feature promises, its combinations, and one case at the released size."""
 import ctypes
 
 import pytest
@@ -11,7 +11,8 @@ from ladi_vton_amd._lib import dtype_code, ptr, stream_ptr
 from oracle import configs as C
 from oracle import models as M
 from oracle import pipeline as P
-from tests import feature_cache_ref as R
+from tests import ref_tryon as RT
+from tests import ref_unet as RU
 from tests import strength_ref as SR
 from tests import util as U
 
@@ -71,8 +72,8 @@ def _op_case(tiny, hw, n=2):
         sd, cfg = tiny["sd"]["unet"], tiny["ucfg"]
         c = dict(x0=x0, x1=x1, ehs=ehs, cap={}, shallow={})
         for k in (0, 1, 2):
-            c["whole"], c["cap"][k] = R.unet_forward(sd, cfg, x0, T0, ehs, "capture", k)
-            c["shallow"][k] = R.unet_forward(sd, cfg, x1, T1, ehs, "shallow", k, c["cap"][k])
+            c["whole"], c["cap"][k] = RU.unet_forward(sd, cfg, x0, T0, ehs, cache=("capture", k))
+            c["shallow"][k] = RU.unet_forward(sd, cfg, x1, T1, ehs, cache=("shallow", k, c["cap"][k]))
         tiny["op"][key] = c
     return tiny["op"][key]
 
@@ -138,9 +139,9 @@ def test_cache_rows_and_staleness(tiny):
     xa, xb, xc = [torch.randn((n, 31) + hw, generator=g).half().float() for _ in range(3)]
     ehs = torch.randn((n, 8, tiny["ucfg"]["cross_attention_dim"]), generator=g).half().float()
     sd, cfg = tiny["sd"]["unet"], tiny["ucfg"]
-    _, cap_a = R.unet_forward(sd, cfg, xa, T0, ehs, "capture", k)
-    out_b_ref, cap_b = R.unet_forward(sd, cfg, xb[2:], 441, ehs[2:], "capture", k)
-    ref = R.unet_forward(sd, cfg, xc, T1, ehs, "shallow", k, torch.cat([cap_a[:2], cap_b]))
+    _, cap_a = RU.unet_forward(sd, cfg, xa, T0, ehs, cache=("capture", k))
+    out_b_ref, cap_b = RU.unet_forward(sd, cfg, xb[2:], 441, ehs[2:], cache=("capture", k))
+    ref = RU.unet_forward(sd, cfg, xc, T1, ehs, cache=("shallow", k, torch.cat([cap_a[:2], cap_b])))
     unet = tiny["mod"]["unet"]
     unet.set_context(ehs.to(U.dev()))
     _fwd(unet, xa, T0, 1, k)
@@ -150,7 +151,7 @@ def test_cache_rows_and_staleness(tiny):
     ps, rl = U.psnr(got, ref), U.rel_l2(got, ref)
     print("mixed rows: PSNR %.2f dB, rel-L2 %.3g" % (ps, rl))
     assert ps >= 55.0 and rl <= 5e-3, (ps, rl)
-    stale = R.unet_forward(sd, cfg, xc, T1, ehs, "shallow", k, cap_a)
+    stale = RU.unet_forward(sd, cfg, xc, T1, ehs, cache=("shallow", k, cap_a))
     assert U.psnr(got[2:], stale[2:]) < 55.0 and U.psnr(got[:2], stale[:2]) >= 55.0      # rows [2, 4) came from the second capture
     # a sub-batch shallow forward reads its own rows
     sub = _fwd(unet, xc[2:], T1, 2, k, sample0=2)
@@ -220,12 +221,12 @@ def _call(tiny, pipe, feature_cache, fused=True, graph=True, steps=STEPS, guidan
 
 
 def _ref(tiny, key, sched, interval, branch, steps=STEPS, **kw):
-    """feature_cache_ref.tryon_reference once per case -> (img, latents, counts)"""
+    """ref_tryon.tryon_reference once per case -> (img, latents, counts)"""
     if key not in tiny["ref"]:
         inp, H, W = _tiny_inputs(tiny)
         counts = {}
-        img, lat = R.tryon_reference(tiny["sd"]["unet"], tiny["ucfg"], tiny["sd"]["vae"], tiny["vcfg"], tiny["sd"]["emasc"], inp, interval, branch,
-                                     steps, sched, counts=counts, **kw)
+        img, lat = RT.tryon_reference(tiny["sd"]["unet"], tiny["ucfg"], tiny["sd"]["vae"], tiny["vcfg"], tiny["sd"]["emasc"], inp, steps, sched,
+                                      feature_cache=(interval, branch), info=counts, **kw)
         tiny["ref"][key] = (img, lat, counts)
     return tiny["ref"][key]
 

@@ -1,6 +1,6 @@
 """FreeU on the device: the one-launch-per-site kernel against tests/freeu_ref.py element by element (strided views in poisoned buffers, in
 place and out of place), the native UNet's forward with FreeU against the reference forward, then the tiny model end to end (fused hipGraph,
-fused eager, modular, lanes, with the feature cache) against freeu_ref.tryon_reference, and the graph key.  There is no case at the released
+fused eager, modular, lanes, with the feature cache) against ref_tryon.tryon_reference, and the graph key.  There is no case at the released
 width here: building a UNET_FULL and its reference forward costs ten seconds (the operator cases cover C = 256 | 128: several channel chunks)."""
 import pytest
 import torch
@@ -10,6 +10,8 @@ from ladi_vton_amd._lib import stream_ptr
 from oracle import configs as C
 from oracle import pipeline as P
 from tests import freeu_ref as R
+from tests import ref_tryon as RT
+from tests import ref_unet as RU
 from tests import util as U
 
 pytestmark = pytest.mark.gpu
@@ -142,7 +144,7 @@ def _forward_case(unet, sd, cfg, n, hw, seed, L_=8):
     on = run()
     unet.disable_freeu()
     assert unet.freeu is None
-    return plain, on, run(), R.unet_forward(sd, cfg, x, T0, ehs, FREEU)
+    return plain, on, run(), RU.unet_forward(sd, cfg, x, T0, ehs, freeu=FREEU)
 
 
 @pytest.mark.parametrize("hw", [(32, 24), (26, 19)])
@@ -206,12 +208,12 @@ def _call(tiny, pipe, freeu, fused=True, graph=True, feature_cache=None):
 
 
 def _ref(tiny, freeu, interval=None):
-    """freeu_ref.tryon_reference once per case -> (img, latents, counts)"""
+    """ref_tryon.tryon_reference once per case -> (img, latents, counts)"""
     key = (freeu, interval)
     if key not in tiny["ref"]:
         counts = {}
-        img, lat = R.tryon_reference(tiny["sd"]["unet"], tiny["ucfg"], tiny["sd"]["vae"], tiny["vcfg"], tiny["sd"]["emasc"], _tiny_inputs(tiny),
-                                     freeu, STEPS, "ddim", interval=interval, counts=counts)
+        img, lat = RT.tryon_reference(tiny["sd"]["unet"], tiny["ucfg"], tiny["sd"]["vae"], tiny["vcfg"], tiny["sd"]["emasc"], _tiny_inputs(tiny),
+                                      STEPS, "ddim", freeu=freeu, feature_cache=(interval, 0), info=counts)
         tiny["ref"][key] = (img, lat, counts)
     return tiny["ref"][key]
 

@@ -1,6 +1,6 @@
 """Guidance schedule, CFG cut-off and guidance rescale on the device: the statistics kernel (ladi_op_cfg_stats) and the guided step kernel
 (ladi_op_sched_run_guided) against tests/guidance_ref.py, then the tiny model end to end (fused hipGraph, fused eager, modular) against
-guidance_ref.tryon_reference, the bit-equalities the feature promises, and its misuse."""
+ref_tryon.tryon_reference, the bit-equalities the feature promises, and its misuse."""
 import ctypes
 
 import pytest
@@ -11,6 +11,7 @@ from ladi_vton_amd._lib import ptr, stream_ptr
 from oracle import configs as C
 from oracle import pipeline as P
 from tests import guidance_ref as G
+from tests import ref_tryon as RT
 from tests import util as U
 
 pytestmark = pytest.mark.gpu
@@ -227,8 +228,8 @@ def _tiny_ref(tiny, sched, case):
         table = gs if isinstance(gs, list) else [gs] * _n_evals(sched)
         inp, H, W = _tiny_inputs(tiny)
         counts = {}
-        img, lat = G.tryon_reference(tiny["sd"]["unet"], tiny["ucfg"], tiny["sd"]["vae"], tiny["vcfg"], tiny["sd"]["emasc"], inp, table, phi,
-                                     num_inference_steps=STEPS, scheduler=sched, counts=counts)
+        img, lat = RT.tryon_reference(tiny["sd"]["unet"], tiny["ucfg"], tiny["sd"]["vae"], tiny["vcfg"], tiny["sd"]["emasc"], inp, STEPS,
+                                      P.make_scheduler(sched), table=table, phi=phi, info=counts)     # the oracle's own scheduler
         tiny["ref"][(sched, case)] = (img, lat, counts)
     return tiny["ref"][(sched, case)]
 

@@ -8,11 +8,12 @@ import torch
 
 from ladi_vton_amd import _lib
 from ladi_vton_amd._lib import stream_ptr
-from oracle import configs as C
 from tests import ip_adapter_cases as IC
 from tests import ip_adapter_ref as R
 from tests import pag_ref as PG
-from tests import test_gpu_pag as TP
+from tests import ref_tryon as RT
+from tests import ref_unet as RU
+from tests import tiny_tryon as TT
 from tests import util as U
 
 pytestmark = pytest.mark.gpu
@@ -96,19 +97,15 @@ MID2 = [0.0] * 6 + [2.0] + [0.0] * 9
 
 @pytest.fixture(scope="module")
 def tiny():
-    import ladi_vton_amd as L
-    ucfg, vcfg = C.UNET_TINY, C.VAE_TINY
-    ecfg = C.emasc_for_vae(vcfg)
-    sds = dict(unet=C.synth_state_dict(C.unet_shapes(ucfg), "unet."), vae=C.synth_state_dict(C.vae_shapes(vcfg), "vae."),
-               emasc=C.synth_state_dict(C.emasc_shapes(ecfg), "emasc."))
-    mods = dict(unet=L.NativeUNet(ucfg, sds["unet"]), vae=L.NativeVAE(vcfg, sds["vae"]), emasc=L.NativeEMASC(ecfg, sds["emasc"]))
-    sd_ip = R.make_adapter(ucfg, N_TOK, E)
-    assert mods["unet"].ip_adapter_info is None
-    mods["unet"].load_ip_adapter(R.to_diffusers(sd_ip, 2, numbered=True))       # diffusers' nested layout with numbered keys
+    t = TT.build()
+    sd_ip = R.make_adapter(t["ucfg"], N_TOK, E)
+    assert t["mod"]["unet"].ip_adapter_info is None
+    t["mod"]["unet"].load_ip_adapter(R.to_diffusers(sd_ip, 2, numbered=True))       # diffusers' nested layout with numbered keys
     g = torch.Generator().manual_seed(77)
     emb = torch.randn((2, E), generator=g).half().float()
     neg = (torch.randn((2, E), generator=g) * 0.5).half().float()
-    yield dict(ucfg=ucfg, vcfg=vcfg, ecfg=ecfg, sd=sds, mod=mods, ip=sd_ip, emb=emb, neg=neg, ref={}, run={}, fwd={})
+    t.update(ip=sd_ip, emb=emb, neg=neg)
+    yield t
 
 
 @pytest.fixture(autouse=True)
@@ -128,7 +125,7 @@ def _fwd_inputs(tiny, hw):
     if ("ip",) + hw not in tiny["fwd"]:
         emb4 = torch.cat([tiny["emb"], tiny["neg"]])
         tiny["fwd"][("ip",) + hw] = (emb4, emb4.to(U.dev()))
-    return TP._fwd_inputs(tiny, hw) + tiny["fwd"][("ip",) + hw]
+    return TT.unet_inputs(tiny, hw) + tiny["fwd"][("ip",) + hw]
 
 
 def _close(what, got, ref, key=None):
@@ -142,7 +139,7 @@ def _close(what, got, ref, key=None):
 
 @pytest.mark.parametrize("hw", [(32, 24), (26, 19)])
 def test_forward_vs_reference(tiny, hw):
-    """NativeUNet tiny, n = 4, t = 481, thresholds of test_unet_forward_tiny (PSNR >= 55 dB, rel-L2 <= 5e-3) against ip_adapter_ref.unet_forward:
+    """NativeUNet tiny, n = 4, t = 481, thresholds of test_unet_forward_tiny (PSNR >= 55 dB, rel-L2 <= 5e-3) against ref_unet.unet_forward:
     every block at scale 1, the mid block alone at scale 2; both are another function than the plain forward; scale 0, no image context and
     a cleared context are the plain forward bit for bit"""
     unet = tiny["mod"]["unet"]
@@ -152,7 +149,7 @@ def test_forward_vs_reference(tiny, hw):
     assert unet.ip_adapter_info == (N_TOK, E) and unet.ip_adapter_scale == ONES
     on = run(ip_image_embeds=embd)
     tok = R.image_proj(tiny["ip"], emb)
-    ref = R.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, ip=(tiny["ip"], tok, ONES))
+    ref = RU.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, ip=(tiny["ip"], tok, ONES))
     _close("IP forward %dx%d" % hw, on, ref, "ip_forward_tiny_%dx%d" % hw)
     pp = U.psnr(on, plain)
     print("IP forward %dx%d against plain: %.2f dB" % (hw + (pp,)))
@@ -161,7 +158,7 @@ def test_forward_vs_reference(tiny, hw):
     unet.set_ip_adapter_scale({"mid": 2.0})
     assert unet.ip_adapter_scale == MID2
     mid = run(ip_image_embeds=embd)
-    _close("IP forward %dx%d, mid block alone" % hw, mid, R.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, ip=(tiny["ip"], tok, MID2)),
+    _close("IP forward %dx%d, mid block alone" % hw, mid, RU.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, ip=(tiny["ip"], tok, MID2)),
            "ip_forward_tiny_mid_%dx%d" % hw)
     pm = U.psnr(mid, plain)
     assert pm < 55.0 and not torch.equal(mid, on), pm
@@ -183,13 +180,13 @@ def test_forward_tokens_and_pag(tiny):
     x, ehs, xd, ed, emb, embd = _fwd_inputs(tiny, hw)
     tok16 = torch.randn((4, 16, tiny["ucfg"]["cross_attention_dim"]), generator=torch.Generator().manual_seed(5)).half().float()
     got = unet(xd, T0, encoder_hidden_states=ed, ip_tokens=tok16.to(U.dev())).sample.float().cpu()
-    _close("IP forward, 16 given tokens", got, R.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, ip=(tiny["ip"], tok16, ONES)),
+    _close("IP forward, 16 given tokens", got, RU.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, ip=(tiny["ip"], tok16, ONES)),
            "ip_forward_tiny_tokens16")
     names = ["down.block_1", "mid", "up.block_2"]
     unet.set_pag_applied_layers(names)
     tok = R.image_proj(tiny["ip"], emb)
     both = unet(xd, T0, encoder_hidden_states=ed, pag_first=2, ip_image_embeds=embd).sample.float().cpu()
-    ref = R.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, PG.layer_prefixes(names), 2, ip=(tiny["ip"], tok, ONES))
+    ref = RU.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, pag=(PG.layer_prefixes(names), 2), ip=(tiny["ip"], tok, ONES))
     _close("IP + PAG forward", both, ref, "ip_forward_tiny_pag")
     sub = unet(xd[2:].contiguous(), T0, encoder_hidden_states=ed, sample0=2, pag_first=2, ip_image_embeds=embd).sample.float().cpu()
     _close("IP + PAG forward, rows [2, 4)", sub, ref[2:])
@@ -207,7 +204,7 @@ def test_forward_measurement_route(tiny, lib):
         alt = run()
     finally:
         assert lib.ladi_unet_set_ip_route(unet.h, 0) == 0
-    ref = R.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, ip=(tiny["ip"], R.image_proj(tiny["ip"], emb), ONES))
+    ref = RU.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, ip=(tiny["ip"], R.image_proj(tiny["ip"], emb), ONES))
     _close("IP forward by flash + add", alt, ref)
     assert torch.equal(run(), on)
 
@@ -236,7 +233,8 @@ def test_forward_misuse(tiny, lib):
 
 
 # ------------------------------------------------------------------------------------------------------------------ tiny model, end to end
-STEPS = TP.STEPS
+STEPS = 4
+CUTOFF = [7.5, 7.5, 1.0, 1.0]
 LAYERS = ("down.block_1", "up.block_2")
 CASES = {
     "plain": dict(ip=False),
@@ -244,11 +242,15 @@ CASES = {
     "half": dict(scales=0.5),
     "pndm": dict(scheduler="pndm", neg=True),
     "nocfg": dict(guidance=1.0),
-    "cutoff": dict(table=TP.CUTOFF, neg=True),
+    "cutoff": dict(table=CUTOFF, neg=True),
     "feature_cache": dict(feature_cache=2),
     "pag": dict(pag_scale=3.0, layers=LAYERS),
-    "callback": dict(callback=lambda i, lat: TP._edit(lat)),
+    "callback": dict(callback=lambda i, lat: _edit(lat)),
 }
+
+
+def _edit(lat):
+    return lat * 0.8
 
 
 def _scales(kw):
@@ -260,42 +262,35 @@ def _ref(tiny, case):
         kw = dict(CASES[case])
         ip = (tiny["ip"], tiny["emb"], tiny["neg"] if kw.get("neg") else None, _scales(kw)) if kw.get("ip", True) else None
         counts = {}
-        a = (tiny["sd"]["unet"], tiny["ucfg"], tiny["sd"]["vae"], tiny["vcfg"], tiny["sd"]["emasc"], TP._inputs(tiny))
-        if kw.get("feature_cache"):
-            img, lat = R.tryon_reference_cached(*a, kw["feature_cache"], 0, STEPS, "ddim", ip, counts=counts)
-        else:
-            img, lat = R.tryon_reference(*a, STEPS, kw.get("scheduler", "ddim"), ip=ip, pag_scale=kw.get("pag_scale", 0.0),
-                                         layers=kw.get("layers", ("mid",)), guidance=kw.get("guidance", 7.5), table=kw.get("table"),
-                                         callback=kw.get("callback"), counts=counts)
+        a = (tiny["sd"]["unet"], tiny["ucfg"], tiny["sd"]["vae"], tiny["vcfg"], tiny["sd"]["emasc"], TT.inputs(tiny, 2, 64, 48))
+        img, lat = RT.tryon_reference(*a, STEPS, kw.get("scheduler", "ddim"), ip=ip, pag=(kw.get("pag_scale", 0.0), 0.0, kw.get("layers", ("mid",))),
+                                      guidance=kw.get("guidance", 7.5), table=kw.get("table"), callback=kw.get("callback"),
+                                      feature_cache=(kw.get("feature_cache"), 0), cloth_cond_rate=None, info=counts)
         tiny["ref"][case] = (img, lat, counts)
     return tiny["ref"][case]
 
 
 def _call(tiny, pipe, case, fused=True, graph=True, **over):
     kw = dict(CASES[case])
-    inp, d = TP._inputs(tiny), U.dev()
+    inp, d = TT.inputs(tiny, 2, 64, 48), U.dev()
     pipe.set_pag_applied_layers(list(kw.get("layers", ("mid",))))
     pipe.set_ip_adapter_scale(kw.get("scales", 1.0))
     cb = None
     if kw.get("callback"):
         def cb(i, t, lat):
-            lat.copy_(TP._edit(lat))
+            lat.copy_(_edit(lat))
     args = dict(guidance_scale=kw.get("table", kw.get("guidance", 7.5)), pag_scale=kw.get("pag_scale", 0.0), feature_cache=kw.get("feature_cache"),
                 callback=cb)
     if kw.get("ip", True):
         args.update(ip_adapter_image_embeds=tiny["emb"].to(d), negative_ip_adapter_image_embeds=tiny["neg"].to(d) if kw.get("neg") else None)
     args.update(over)
-    out = pipe(image=inp["image"].to(d), mask_image=inp["mask_image"].clone().to(d), pose_map=inp["pose_map"].to(d),
-               warped_cloth=inp["warped_cloth"].to(d), prompt_embeds=inp["prompt_embeds"].to(d),
-               negative_prompt_embeds=inp["negative_prompt_embeds"].to(d), height=64, width=48, num_inference_steps=STEPS,
-               output_type="np", fused=fused, use_graph=graph, noise=(inp["noise_cloth"], inp["noise_latents"], inp["noise_masked"]), **args)
-    return torch.from_numpy(out.images), pipe.last_latents.float().cpu()
+    return TT.call(tiny, pipe, inp, fused, graph, num_inference_steps=STEPS, **args)
 
 
 def _run(tiny, case, arm):
     """one run per (case, arm) on a fresh pipeline (a fresh native handle), shared by the tests below"""
     if (case, arm) not in tiny["run"]:
-        pipe = TP._pipe(tiny, CASES[case].get("scheduler", "ddim"))
+        pipe = TT.pipe(tiny, CASES[case].get("scheduler", "ddim"))
         img, lat = _call(tiny, pipe, case, fused=arm != "modular", graph=arm == "graph")
         tiny["run"][(case, arm)] = (img, lat, pipe.cond_only_evals() if arm != "modular" else None)
     return tiny["run"][(case, arm)]
@@ -303,11 +298,11 @@ def _run(tiny, case, arm):
 
 @pytest.mark.parametrize("arm", ["graph", "eager", "modular"])
 def test_loop_vs_reference(tiny, arm):
-    """thresholds of test_tryon_pipeline_tiny (latents >= 40 dB, image >= 35 dB) against ip_adapter_ref.tryon_reference, a NULL negative
+    """thresholds of test_tryon_pipeline_tiny (latents >= 40 dB, image >= 35 dB) against ref_tryon.tryon_reference, a NULL negative
     (zeros through the projection); below 40 dB against the plain reference"""
     ref_img, ref_lat, _ = _ref(tiny, "base")
     img, lat, _ = _run(tiny, "base", arm)
-    p_img, p_lat = TP._assert_close("tiny IP %s" % arm, img, lat, ref_img, ref_lat)
+    p_img, p_lat = TT.assert_close("tiny IP %s" % arm, img, lat, ref_img, ref_lat)
     U.record_parity("ip_tiny_ddim_%s" % arm, dict(image_db=round(p_img, 2), latents_db=round(p_lat, 2)))
     p = U.psnr(lat, _ref(tiny, "plain")[1])
     print("tiny IP %s against the plain reference: latents %.2f dB" % (arm, p))
@@ -327,7 +322,7 @@ def test_loop_cases_vs_reference(tiny, case, arm):
     group with the cond group's image tokens); a callback that edits the latents"""
     ref_img, ref_lat, counts = _ref(tiny, case)
     img, lat, n_cond = _run(tiny, case, arm)
-    p_img, p_lat = TP._assert_close("tiny IP %s %s" % (case, arm), img, lat, ref_img, ref_lat)
+    p_img, p_lat = TT.assert_close("tiny IP %s %s" % (case, arm), img, lat, ref_img, ref_lat)
     U.record_parity("ip_tiny_%s_%s" % (case, arm), dict(image_db=round(p_img, 2), latents_db=round(p_lat, 2)))
     if arm == "graph":
         assert n_cond == counts["cond_only"], (n_cond, counts)
@@ -344,7 +339,7 @@ def test_loop_cases_vs_reference(tiny, case, arm):
 def test_lanes_match_single_lane(tiny):
     """two sample-group lanes against one: latents >= 45 dB, the threshold of test_unet_lanes_match_single_lane"""
     _, lat_1, _ = _run(tiny, "base", "graph")
-    pipe = TP._pipe(tiny)
+    pipe = TT.pipe(tiny)
     pipe.lanes = 2
     _, lat_2 = _call(tiny, pipe, "base")
     assert pipe.lib_lanes() == 2
@@ -357,22 +352,22 @@ def test_lanes_match_single_lane(tiny):
 def test_no_stale_graph(tiny):
     """one pipeline with use_graph: plain -> scale 1 -> scale 0.5 -> scale 0 -> image prompt off.  Every image run meets its own reference
     and equals the eager run of a fresh pipeline bit for bit, the two are further apart than the threshold, scale 0 and off are the plain run"""
-    pipe = TP._pipe(tiny)
+    pipe = TT.pipe(tiny)
     img_1, lat_1 = _call(tiny, pipe, "plain")
     img_2, lat_2 = _call(tiny, pipe, "base")
     img_3, lat_3 = _call(tiny, pipe, "half")
     img_4, lat_4 = _call(tiny, pipe, "base", ip_adapter_image_embeds=tiny["emb"].to(U.dev()))
     pipe.set_ip_adapter_scale(0.0)
-    inp, d = TP._inputs(tiny), U.dev()
+    inp, d = TT.inputs(tiny, 2, 64, 48), U.dev()
     zero = pipe(image=inp["image"].to(d), mask_image=inp["mask_image"].clone().to(d), pose_map=inp["pose_map"].to(d),
                 warped_cloth=inp["warped_cloth"].to(d), prompt_embeds=inp["prompt_embeds"].to(d),
                 negative_prompt_embeds=inp["negative_prompt_embeds"].to(d), height=64, width=48, num_inference_steps=STEPS, output_type="np",
                 noise=(inp["noise_cloth"], inp["noise_latents"], inp["noise_masked"]), ip_adapter_image_embeds=tiny["emb"].to(d))
     lat_0 = pipe.last_latents.float().cpu()
     img_5, lat_5 = _call(tiny, pipe, "plain")
-    TP._assert_close("plain", img_1, lat_1, *_ref(tiny, "plain")[:2])
-    TP._assert_close("IP 1.0", img_2, lat_2, *_ref(tiny, "base")[:2])
-    TP._assert_close("IP 0.5", img_3, lat_3, *_ref(tiny, "half")[:2])
+    TT.assert_close("plain", img_1, lat_1, *_ref(tiny, "plain")[:2])
+    TT.assert_close("IP 1.0", img_2, lat_2, *_ref(tiny, "base")[:2])
+    TT.assert_close("IP 0.5", img_3, lat_3, *_ref(tiny, "half")[:2])
     assert torch.equal(lat_2, _run(tiny, "base", "eager")[1]) and torch.equal(lat_3, _run(tiny, "half", "eager")[1])
     assert torch.equal(lat_4, lat_2) and torch.equal(img_4, img_2)
     p = U.psnr(lat_2, lat_3)
@@ -385,7 +380,7 @@ def test_no_stale_graph(tiny):
 def test_misuse_fails_before_anything_is_launched(tiny, lib):
     """wrong E, wrong batch, negatives alone, and -- at the C boundary -- a run on a UNet without a loaded adapter: an error with a message,
     and the next plain run on the same handle is the plain run.  Then the adapter is loaded again, from module-named keys"""
-    pipe, unet = TP._pipe(tiny), tiny["mod"]["unet"]
+    pipe, unet = TT.pipe(tiny), tiny["mod"]["unet"]
     img_1, lat_1 = _call(tiny, pipe, "plain")
     d = U.dev()
     with pytest.raises(ValueError, match="width %d" % (E + 8)):
@@ -411,7 +406,7 @@ def test_misuse_fails_before_anything_is_launched(tiny, lib):
             _call_plain_after_unload(tiny, pipe, ip_adapter_image_embeds=tiny["emb"].to(d))
         with pytest.raises(ValueError, match="load_ip_adapter"):
             unet(fwd[2], T0, encoder_hidden_states=fwd[3], ip_image_embeds=fwd[5])
-        inp = TP._inputs(tiny)
+        inp = TT.inputs(tiny, 2, 64, 48)
         a = (inp["image"], inp["mask_image"].clone(), inp["pose_map"], inp["warped_cloth"], inp["prompt_embeds"].to(d),
              inp["negative_prompt_embeds"].to(d), inp["noise_cloth"], inp["noise_latents"], inp["noise_masked"], 64, 48, STEPS, 7.5, 1.0, False, True)
         e16 = tiny["emb"].to(d).half().contiguous()
@@ -430,7 +425,7 @@ def test_misuse_fails_before_anything_is_launched(tiny, lib):
 
 def _call_plain_after_unload(tiny, pipe, **over):
     """the plain case without touching the (unloaded) adapter's scales"""
-    inp, d = TP._inputs(tiny), U.dev()
+    inp, d = TT.inputs(tiny, 2, 64, 48), U.dev()
     out = pipe(image=inp["image"].to(d), mask_image=inp["mask_image"].clone().to(d), pose_map=inp["pose_map"].to(d),
                warped_cloth=inp["warped_cloth"].to(d), prompt_embeds=inp["prompt_embeds"].to(d),
                negative_prompt_embeds=inp["negative_prompt_embeds"].to(d), height=64, width=48, num_inference_steps=STEPS, output_type="np",

@@ -1,7 +1,7 @@
 """Perturbed-attention guidance on the device: the identity-attention copy kernel on strided views in poisoned buffers, the step and
 statistics kernels with the third sample group against tests/pag_ref.py, the native UNet's forward with perturbed samples against the
 reference forward, then the tiny model end to end (fused hipGraph, fused eager, modular, lanes, with the other sampler switches) against
-pag_ref.tryon_reference, the graph key and the misuse."""
+ref_tryon.tryon_reference, the graph key and the misuse."""
 import ctypes
 
 import pytest
@@ -9,10 +9,12 @@ import torch
 
 from ladi_vton_amd import _lib
 from ladi_vton_amd._lib import ptr, stream_ptr
-from oracle import configs as C
 from oracle import pipeline as P
 from tests import guidance_ref as G
 from tests import pag_ref as R
+from tests import ref_tryon as RT
+from tests import ref_unet as RU
+from tests import tiny_tryon as TT
 from tests import util as U
 from tests.test_gpu_guidance import SHAPES
 
@@ -229,15 +231,10 @@ LAYER_SETS = {"mid": "mid", "outer": ["down.block_0.attentions_1", "up.block_3"]
 
 @pytest.fixture(scope="module")
 def tiny():
-    import ladi_vton_amd as L
-    ucfg, vcfg = C.UNET_TINY, C.VAE_TINY
-    ecfg = C.emasc_for_vae(vcfg)
-    sds = dict(unet=C.synth_state_dict(C.unet_shapes(ucfg), "unet."), vae=C.synth_state_dict(C.vae_shapes(vcfg), "vae."),
-               emasc=C.synth_state_dict(C.emasc_shapes(ecfg), "emasc."))
-    mods = dict(unet=L.NativeUNet(ucfg, sds["unet"]), vae=L.NativeVAE(vcfg, sds["vae"]), emasc=L.NativeEMASC(ecfg, sds["emasc"]))
-    yield dict(ucfg=ucfg, vcfg=vcfg, ecfg=ecfg, sd=sds, mod=mods, ref={}, run={}, fwd={})
-    mods["unet"].set_pag_applied_layers("mid")
-    mods["unet"].disable_freeu()
+    t = TT.build()
+    yield t
+    t["mod"]["unet"].set_pag_applied_layers("mid")
+    t["mod"]["unet"].disable_freeu()
 
 
 @pytest.fixture(autouse=True)
@@ -250,35 +247,21 @@ def _defaults_between_tests(request):
         u.disable_freeu()
 
 
-def _fwd_inputs(tiny, hw, n=4):
-    """n = 4: samples 2, 3 are copies of samples 0, 1, inputs and context alike; n = 3: three different samples"""
-    key = (hw, n)
-    if key not in tiny["fwd"]:
-        g = torch.Generator().manual_seed(11 + hw[0])
-        m = 2 if n == 4 else n
-        x = torch.randn((m, 31) + hw, generator=g).half().float()
-        ehs = torch.randn((m, 8, tiny["ucfg"]["cross_attention_dim"]), generator=g).half().float()
-        if n == 4:
-            x, ehs = torch.cat([x, x]), torch.cat([ehs, ehs])
-        tiny["fwd"][key] = (x, ehs, x.to(U.dev()), ehs.to(U.dev()))
-    return tiny["fwd"][key]
-
-
 @pytest.mark.parametrize("hw", [(32, 24), (26, 19)])
 @pytest.mark.parametrize("which", list(LAYER_SETS))
 def test_forward_vs_reference(tiny, which, hw):
     """NativeUNet tiny, n = 4, t = 481, pag_first = 2.  Thresholds of test_unet_forward_tiny (PSNR >= 55 dB, rel-L2 <= 5e-3) against
-    pag_ref.unet_forward; samples 0, 1 keep the plain forward's bits (one attention workgroup per (sample, head, query tile)); samples 2, 3
+    ref_unet.unet_forward; samples 0, 1 keep the plain forward's bits (one attention workgroup per (sample, head, query tile)); samples 2, 3
     are another function than the plain forward; the default layers give the earlier bits again"""
     unet, names = tiny["mod"]["unet"], LAYER_SETS[which]
-    x, ehs, xd, ed = _fwd_inputs(tiny, hw)
+    x, ehs, xd, ed = TT.unet_inputs(tiny, hw)
     run = lambda **kw: unet(xd, T0, encoder_hidden_states=ed, **kw).sample.float().cpu()
     plain = run()
     mid_before = run(pag_first=2)
     unet.set_pag_applied_layers(names)
     assert unet.pag_applied_layers == R.mask_of(R.layer_prefixes(names))
     on = run(pag_first=2)
-    ref = R.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, R.layer_prefixes(names), 2)
+    ref = RU.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, pag=(R.layer_prefixes(names), 2))
     ps, rl, pp = U.psnr(on, ref), U.rel_l2(on, ref), U.psnr(on[2:], plain[2:])
     print("PAG forward %s %dx%d: PSNR %.2f dB, rel-L2 %.3g; perturbed samples against plain %.2f dB" % ((which,) + hw + (ps, rl, pp)))
     U.record_parity("pag_forward_tiny_%s_%dx%d" % ((which,) + hw), dict(psnr_db=round(ps, 2), rel_l2=rl, vs_plain_db=round(pp, 2)))
@@ -297,10 +280,10 @@ def test_forward_vs_reference(tiny, which, hw):
 def test_forward_other_splits(tiny, n, first):
     """pag_first = 0: every sample perturbed, the selected blocks launch no self-attention; pag_first = 1 of n = 3: an odd split"""
     unet, names = tiny["mod"]["unet"], LAYER_SETS["all"]
-    x, ehs, xd, ed = _fwd_inputs(tiny, (32, 24), n)
+    x, ehs, xd, ed = TT.unet_inputs(tiny, (32, 24), n)
     unet.set_pag_applied_layers(names)
     on = unet(xd, T0, encoder_hidden_states=ed, pag_first=first).sample.float().cpu()
-    ref = R.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, R.layer_prefixes(names), first)
+    ref = RU.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, pag=(R.layer_prefixes(names), first))
     ps, rl = U.psnr(on, ref), U.rel_l2(on, ref)
     print("PAG forward all blocks n = %d, pag_first = %d: PSNR %.2f dB, rel-L2 %.3g" % (n, first, ps, rl))
     U.record_parity("pag_forward_tiny_all_n%d_first%d" % (n, first), dict(psnr_db=round(ps, 2), rel_l2=rl))
@@ -321,7 +304,7 @@ def test_layer_setter_misuse(tiny, lib):
     with pytest.raises(ValueError):
         unet.set_pag_applied_layers("down.block_3")
     assert unet.pag_applied_layers == 1 << 6
-    x, ehs, xd, ed = _fwd_inputs(tiny, (32, 24))
+    x, ehs, xd, ed = TT.unet_inputs(tiny, (32, 24))
     with pytest.raises(ValueError, match="feature_cache"):
         unet(xd, T0, encoder_hidden_states=ed, pag_first=2, feature_cache="capture")
     with pytest.raises(ValueError, match="pag_first"):
@@ -340,7 +323,7 @@ def _edit(lat):
     return lat * 0.8
 
 
-# the keywords of one case: the reference's (pag_ref.tryon_reference) and, under "pipe", what the pipeline call gets instead
+# the keywords of one case: the reference's (_ref hands them to ref_tryon.tryon_reference) and, under "pipe", what the pipeline call gets instead
 CASES = {
     "plain": dict(pag_scale=0.0),
     "base": dict(pag_scale=3.0),
@@ -358,31 +341,16 @@ CASES = {
 }
 
 
-def _inputs(tiny, size=(64, 48)):
-    key = ("inp",) + size
-    if key not in tiny:
-        inp = P.synthetic_inputs(2, size[0], size[1], L=8, D=tiny["ucfg"]["cross_attention_dim"])
-        for k in ("prompt_embeds", "negative_prompt_embeds"):
-            inp[k] = inp[k].half().float()
-        tiny[key] = inp
-    return tiny[key]
-
-
-def _pipe(tiny, scheduler="ddim"):
-    import ladi_vton_amd as L
-    return L.StableDiffusionTryOnePipeline(vae=tiny["mod"]["vae"], text_encoder=None, tokenizer=None, unet=tiny["mod"]["unet"],
-                                           scheduler=L.PNDMScheduler() if scheduler == "pndm" else L.DDIMScheduler(), emasc=tiny["mod"]["emasc"],
-                                           emasc_int_layers=[1, 2, 3, 4, 5])
-
-
 def _ref(tiny, case):
     if case not in tiny["ref"]:
         kw = dict(CASES[case])
         size = kw.pop("size", (64, 48))
         kw.setdefault("layers", LAYERS)
         counts = {}
-        img, lat = R.tryon_reference(tiny["sd"]["unet"], tiny["ucfg"], tiny["sd"]["vae"], tiny["vcfg"], tiny["sd"]["emasc"], _inputs(tiny, size),
-                                     STEPS, kw.pop("scheduler", "ddim"), counts=counts, **kw)
+        pag = (kw.pop("pag_scale"), kw.pop("pag_adaptive_scale", 0.0), kw.pop("layers"))
+        preserve = ("latents", 0.0) if kw.pop("preserve_latents", False) else None
+        img, lat = RT.tryon_reference(tiny["sd"]["unet"], tiny["ucfg"], tiny["sd"]["vae"], tiny["vcfg"], tiny["sd"]["emasc"], TT.inputs(tiny, 2, *size),
+                                      STEPS, kw.pop("scheduler", "ddim"), pag=pag, preserve=preserve, cloth_cond_rate=None, info=counts, **kw)
         tiny["ref"][case] = (img, lat, counts)
     return tiny["ref"][case]
 
@@ -391,7 +359,7 @@ def _call(tiny, pipe, case, fused=True, graph=True, **over):
     """one run of a case through the pipeline -> (images, latents)"""
     kw = dict(CASES[case])
     size = kw.pop("size", (64, 48))
-    inp, d = _inputs(tiny, size), U.dev()
+    inp = TT.inputs(tiny, 2, *size)
     pipe.set_pag_applied_layers(list(kw.get("layers", LAYERS)))
     if kw.get("freeu"):
         pipe.enable_freeu(*kw["freeu"])
@@ -405,36 +373,23 @@ def _call(tiny, pipe, case, fused=True, graph=True, **over):
                 pag_adaptive_scale=kw.get("pag_adaptive_scale", 0.0), preserve_unmasked="latents" if kw.get("preserve_latents") else None,
                 callback=cb)
     args.update(over)
-    out = pipe(image=inp["image"].to(d), mask_image=inp["mask_image"].clone().to(d), pose_map=inp["pose_map"].to(d),
-               warped_cloth=inp["warped_cloth"].to(d), prompt_embeds=inp["prompt_embeds"].to(d),
-               negative_prompt_embeds=inp["negative_prompt_embeds"].to(d), height=size[0], width=size[1], num_inference_steps=STEPS,
-               output_type="np", fused=fused, use_graph=graph, noise=(inp["noise_cloth"], inp["noise_latents"], inp["noise_masked"]), **args)
-    return torch.from_numpy(out.images), pipe.last_latents.float().cpu()
+    return TT.call(tiny, pipe, inp, fused, graph, num_inference_steps=STEPS, **args)
 
 
 def _run(tiny, case, arm):
     """one run per (case, arm) on a fresh pipeline (a fresh native handle), shared by the tests below"""
     if (case, arm) not in tiny["run"]:
-        pipe = _pipe(tiny, CASES[case].get("scheduler", "ddim"))
+        pipe = TT.pipe(tiny, CASES[case].get("scheduler", "ddim"))
         img, lat = _call(tiny, pipe, case, fused=arm != "modular", graph=arm == "graph")
         tiny["run"][(case, arm)] = (img, lat, pipe.cond_only_evals() if arm != "modular" else None)
     return tiny["run"][(case, arm)]
-
-
-def _assert_close(what, img, lat, ref_img, ref_lat):
-    """thresholds of test_tryon_pipeline_tiny: latents >= 40 dB, image >= 35 dB on [0, 1]"""
-    p_img, p_lat = U.psnr(img, ref_img, peak=1.0), U.psnr(lat, ref_lat)
-    print("%s: image %.2f dB, latents %.2f dB" % (what, p_img, p_lat))
-    assert img.shape == ref_img.shape and torch.isfinite(lat).all()
-    assert p_lat >= 40.0 and p_img >= 35.0, (what, p_img, p_lat)
-    return p_img, p_lat
 
 
 @pytest.mark.parametrize("arm", ["graph", "eager", "modular"])
 def test_loop_vs_reference(tiny, arm):
     ref_img, ref_lat, counts = _ref(tiny, "base")
     img, lat, _ = _run(tiny, "base", arm)
-    p_img, p_lat = _assert_close("tiny PAG %s" % arm, img, lat, ref_img, ref_lat)
+    p_img, p_lat = TT.assert_close("tiny PAG %s" % arm, img, lat, ref_img, ref_lat)
     U.record_parity("pag_tiny_ddim_%s" % arm, dict(image_db=round(p_img, 2), latents_db=round(p_lat, 2)))
     assert counts["pag"] == STEPS
     p = U.psnr(lat, _ref(tiny, "plain")[1])
@@ -456,7 +411,7 @@ def test_loop_cases_vs_reference(tiny, case, arm):
     re-import reaches the perturbed group); the default layer at 128x96"""
     ref_img, ref_lat, counts = _ref(tiny, case)
     img, lat, n_cond = _run(tiny, case, arm)
-    p_img, p_lat = _assert_close("tiny PAG %s %s" % (case, arm), img, lat, ref_img, ref_lat)
+    p_img, p_lat = TT.assert_close("tiny PAG %s %s" % (case, arm), img, lat, ref_img, ref_lat)
     U.record_parity("pag_tiny_%s_%s" % (case, arm), dict(image_db=round(p_img, 2), latents_db=round(p_lat, 2)))
     if arm == "graph":
         assert n_cond == counts["cond_only"], (n_cond, counts)
@@ -474,7 +429,7 @@ def test_lanes_match_single_lane(tiny):
     """two sample-group lanes (n = 6: the second holds one cond and both perturbed samples) against one: latents >= 45 dB, the threshold of
     test_unet_lanes_match_single_lane"""
     _, lat_1, _ = _run(tiny, "base", "graph")
-    pipe = _pipe(tiny)
+    pipe = TT.pipe(tiny)
     pipe.lanes = 2
     _, lat_2 = _call(tiny, pipe, "base")
     assert pipe.lib_lanes() == 2
@@ -487,25 +442,25 @@ def test_lanes_match_single_lane(tiny):
 def test_no_stale_graph(tiny):
     """one pipeline with use_graph: plain -> PAG 3.0 -> PAG 1.0 -> other layers -> pag_scale = 0.0.  The first and the last run are
     bit-equal (and equal a fresh plain run), every PAG run meets its own reference, and they are further apart than the threshold"""
-    pipe = _pipe(tiny)
+    pipe = TT.pipe(tiny)
     img_1, lat_1 = _call(tiny, pipe, "plain")
     img_2, lat_2 = _call(tiny, pipe, "base")
     img_3, lat_3 = _call(tiny, pipe, "scale1")
     img_4, lat_4 = _call(tiny, pipe, "layers_b")
     img_5, lat_5 = _call(tiny, pipe, "base", pag_scale=0.0)
     assert torch.equal(lat_5, lat_1) and torch.equal(img_5, img_1)
-    _assert_close("plain", img_1, lat_1, *_ref(tiny, "plain")[:2])
-    _assert_close("PAG 3.0", img_2, lat_2, *_ref(tiny, "base")[:2])
-    _assert_close("PAG 1.0", img_3, lat_3, *_ref(tiny, "scale1")[:2])
-    _assert_close("PAG 3.0, other layers", img_4, lat_4, *_ref(tiny, "layers_b")[:2])
+    TT.assert_close("plain", img_1, lat_1, *_ref(tiny, "plain")[:2])
+    TT.assert_close("PAG 3.0", img_2, lat_2, *_ref(tiny, "base")[:2])
+    TT.assert_close("PAG 1.0", img_3, lat_3, *_ref(tiny, "scale1")[:2])
+    TT.assert_close("PAG 3.0, other layers", img_4, lat_4, *_ref(tiny, "layers_b")[:2])
     for a, b, what in ((lat_2, lat_3, "3.0 / 1.0"), (lat_2, lat_4, "layers"), (lat_3, lat_4, "1.0 / layers")):
         p = U.psnr(a, b)
         print("PAG runs %s: latents %.2f dB apart" % (what, p))
         assert p < 40.0, (what, p)
     assert torch.equal(lat_2, _run(tiny, "base", "graph")[1])           # a fresh pipeline gives the same PAG run
     # the plain run of a pipeline that never saw PAG, through the keyword-less call
-    inp, d = _inputs(tiny), U.dev()
-    out = _pipe(tiny)(image=inp["image"].to(d), mask_image=inp["mask_image"].clone().to(d), pose_map=inp["pose_map"].to(d),
+    inp, d = TT.inputs(tiny, 2, 64, 48), U.dev()
+    out = TT.pipe(tiny)(image=inp["image"].to(d), mask_image=inp["mask_image"].clone().to(d), pose_map=inp["pose_map"].to(d),
                       warped_cloth=inp["warped_cloth"].to(d), prompt_embeds=inp["prompt_embeds"].to(d),
                       negative_prompt_embeds=inp["negative_prompt_embeds"].to(d), height=64, width=48, num_inference_steps=STEPS,
                       output_type="np", noise=(inp["noise_cloth"], inp["noise_latents"], inp["noise_masked"]))
@@ -515,9 +470,9 @@ def test_no_stale_graph(tiny):
 def test_misuse_fails_before_anything_is_launched(tiny, lib):
     """a PAG table of the wrong length, PAG together with a feature-cache plan, a bad table entry: an error with a message, and the next
     plain run on the same handle is the plain run"""
-    pipe = _pipe(tiny)
+    pipe = TT.pipe(tiny)
     img_1, lat_1 = _call(tiny, pipe, "plain")
-    inp, d = _inputs(tiny), U.dev()
+    inp, d = TT.inputs(tiny, 2, 64, 48), U.dev()
     a = (inp["image"], inp["mask_image"].clone(), inp["pose_map"], inp["warped_cloth"], inp["prompt_embeds"].to(d),
          inp["negative_prompt_embeds"].to(d), inp["noise_cloth"], inp["noise_latents"], inp["noise_masked"], 64, 48, STEPS, 7.5, 1.0, False, True)
     with pytest.raises(_lib.NativeError, match="PAG table has 3 entries, this run has 4 evaluations"):

@@ -1,6 +1,6 @@
 """Keeping the unmasked region (`preserve_unmasked`) on the device: the four new kernels through the C ABI (ladi_op_mask_pool8,
 ladi_op_mask_feather, ladi_op_image_composite, ladi_op_sched_run_keep) between poisoned rows against tests/preserve_ref.py, then the tiny model
-end to end (fused hipGraph, fused eager, modular) against preserve_ref.tryon_reference for all six schedulers, the bit-level guarantees outside
+end to end (fused hipGraph, fused eager, modular) against ref_tryon.tryon_reference for all six schedulers, the bit-level guarantees outside
 the mask, degenerate masks, stale state and the interplay with strength, the feature cache and a guidance schedule."""
 import ctypes
 
@@ -13,6 +13,7 @@ from ladi_vton_amd._lib import ptr, stream_ptr
 from oracle import configs as C
 from oracle import pipeline as P
 from tests import preserve_ref as R
+from tests import ref_tryon as RT
 from tests import strength_ref as SR
 from tests import util as U
 
@@ -456,12 +457,13 @@ def _call(tiny, pipe, fused=True, graph=True, mask="ragged", prompt=None, **kw):
     return torch.from_numpy(out.images), pipe.last_latents.float().cpu()
 
 
-def _ref(tiny, sched, key, mode="both", mask="ragged", **kw):
+def _ref(tiny, sched, key, mode="both", mask="ragged", feather_sigma=0.0, interval=None, **kw):
     key = (sched, key)
     if key not in tiny["ref"]:
         sd = tiny["sd"]
-        tiny["ref"][key] = R.tryon_reference(sd["unet"], tiny["ucfg"], sd["vae"], tiny["vcfg"], sd["emasc"], _inputs(tiny, mask), mode, STEPS, sched,
-                                             generator=torch.Generator().manual_seed(NOISE_SEED), **kw)
+        tiny["ref"][key] = RT.tryon_reference(sd["unet"], tiny["ucfg"], sd["vae"], tiny["vcfg"], sd["emasc"], _inputs(tiny, mask), STEPS, sched,
+                                              preserve=(mode, feather_sigma), feature_cache=(interval, 0),
+                                              generator=torch.Generator().manual_seed(NOISE_SEED), **kw)
     return tiny["ref"][key]
 
 
@@ -494,7 +496,7 @@ def _post(image):
 @pytest.mark.parametrize("arm", list(ARMS))
 @pytest.mark.parametrize("sched", R.SCHEDULERS)
 def test_tryon_tiny_both_vs_reference(tiny, sched, arm):
-    """B = 2, 256x192, 8 steps, a ragged mask, "both": fused hipGraph, fused eager and modular against preserve_ref.tryon_reference; the
+    """B = 2, 256x192, 8 steps, a ragged mask, "both": fused hipGraph, fused eager and modular against ref_tryon.tryon_reference; the
     thresholds tests/test_gpu_strength.py applies to the same arms (latents >= 40 dB, image >= 35 dB on [0, 1])"""
     ref_img, ref_lat = _ref(tiny, sched, "both")
     img, lat = _run(tiny, sched, arm)

@@ -1,5 +1,5 @@
 """Starting the fused loop from an image or latents (`strength`) on the device: the start-latents kernel (ladi_op_init_latents) against
-tests/strength_ref.py, then the tiny model end to end (fused hipGraph, fused eager, modular) against strength_ref.tryon_reference for all six
+tests/strength_ref.py, then the tiny model end to end (fused hipGraph, fused eager, modular) against ref_tryon.tryon_reference for all six
 schedulers, the tail identity that pins the mechanism (a run resumed from the latents after evaluation k - 1 reproduces the whole run bit for
 bit), the two-pass recipe, stale state, and the interplay with the per-evaluation interfaces."""
 import ctypes
@@ -11,6 +11,7 @@ from ladi_vton_amd import _lib
 from ladi_vton_amd._lib import ptr, stream_ptr
 from oracle import configs as C
 from oracle import pipeline as P
+from tests import ref_tryon as RT
 from tests import strength_ref as R
 from tests import util as U
 
@@ -142,9 +143,9 @@ def _ref(tiny, sched, init=None, first_step=FIRST, key=None, **kw):
     key = (sched, key or "synthetic")
     if key not in tiny["ref"]:
         sd = tiny["sd"]
-        tiny["ref"][key] = R.tryon_reference(sd["unet"], tiny["ucfg"], sd["vae"], tiny["vcfg"], sd["emasc"], _inputs(tiny),
-                                             _init(tiny) if init is None else init, first_step, STEPS, sched,
-                                             generator=torch.Generator().manual_seed(NOISE_SEED), **kw)
+        tiny["ref"][key] = RT.tryon_reference(sd["unet"], tiny["ucfg"], sd["vae"], tiny["vcfg"], sd["emasc"], _inputs(tiny), STEPS, sched,
+                                              init_latents=_init(tiny) if init is None else init, first_step=first_step,
+                                              generator=torch.Generator().manual_seed(NOISE_SEED), **kw)
     return tiny["ref"][key]
 
 

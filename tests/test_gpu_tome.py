@@ -11,6 +11,8 @@ from ladi_vton_amd import _lib
 from ladi_vton_amd._lib import ptr, stream_ptr
 from oracle import configs as C
 from oracle import pipeline as P
+from tests import ref_tryon as RT
+from tests import ref_unet as RU
 from tests import tome_ref as R
 from tests import util as U
 
@@ -345,10 +347,10 @@ def _adapter(tiny):
 def _device_plans(unet, tcfg, hw, n):
     """the plans of the last forward, read back: dict prefix -> a plan per sample (blocks that merged nothing are left out)"""
     forced = {}
-    pre = R.merged_prefixes(tcfg, unet.cfg["layers_per_block"])
-    assert [R.block_prefixes()[b] for b in unet.token_merging_blocks()] == pre
+    pre = RU.merged_prefixes(tcfg, unet.cfg["layers_per_block"])
+    assert [RU.block_prefixes()[b] for b in unet.token_merging_blocks()] == pre
     for k, p in enumerate(pre):
-        lv = R.level_of(p)
+        lv = RU.level_of(p)
         h, w = hw
         for _ in range(lv):
             h, w = (h + 1) // 2, (w + 1) // 2
@@ -411,7 +413,7 @@ FWD_CASES = {
 @pytest.mark.parametrize("hw", [(8, 6), (5, 3)])
 @pytest.mark.parametrize("case", list(FWD_CASES) + ["attn+ip", "all+ip"])
 def test_forward_with_forced_plans(tiny, case, hw):
-    """NativeUNet tiny, B = 2, t = 481: every merged block's plan is read back and forced into tome_ref's forward; thresholds of
+    """NativeUNet tiny, B = 2, t = 481: every merged block's plan is read back and forced into ref_unet's forward; thresholds of
     tests/test_gpu_pag.py's forward comparison (rel-L2 <= 5e-3, PSNR >= 55 dB).  +ip: with an IP-Adapter image context set (one block at
     scale 0), the image term from the merged rows where the cross-attention merges; "plain" is then the unmerged forward with that context"""
     from ladi_vton_amd import tome
@@ -427,7 +429,7 @@ def test_forward_with_forced_plans(tiny, case, hw):
     got = unet(xd, T0, encoder_hidden_states=ed, **kw).sample.float().cpu()
     forced = _device_plans(unet, tcfg, hw, 2)
     assert forced, "nothing merged"
-    ref = R.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, tcfg, forced, ip=ip)
+    ref = RU.unet_forward(tiny["sd"]["unet"], tiny["ucfg"], x, T0, ehs, tome=(tcfg, forced, None, "proj_in"), ip=ip)
     ps, rl = U.psnr(got, ref), U.rel_l2(got, ref)
     print("ToMe forward %s %dx%d: PSNR %.2f dB, rel-L2 %.3g; against plain %.2f dB" % ((case,) + hw + (ps, rl, U.psnr(got, plain))))
     U.record_parity("tome_forward_tiny_%s_%dx%d" % ((case,) + hw), dict(psnr_db=round(ps, 2), rel_l2=rl))
@@ -439,12 +441,12 @@ def test_forward_with_forced_plans(tiny, case, hw):
 def wiring_shares(sd, ucfg, x, ehs, tcfg):
     """CPU side of the wiring test -> (reference plans of the first merged block, d0, share with the metric after norm1, share with the
     metric before proj_in)"""
-    first = R.merged_prefixes(tcfg)[0]
+    first = RU.merged_prefixes(tcfg)[0]
     rec = {}
 
     def grab(metric):
         out = {}
-        R.unet_forward(sd, ucfg, x, T0, ehs, tcfg, None, lambda p, t, plans: out.setdefault(p, (t, plans)), metric)
+        RU.unet_forward(sd, ucfg, x, T0, ehs, tome=(tcfg, None, lambda p, t, plans: out.setdefault(p, (t, plans)), metric))
         return out[first]
     t0, ref = grab("proj_in")
     h, w = x.shape[2:]
@@ -471,7 +473,7 @@ def test_plan_wiring(tiny):
     bound = max(4 * d0, 2.0 / Ns)
     unet.set_token_merging(0.5)
     unet(xd, T0, encoder_hidden_states=ed)
-    dev = _device_plans(unet, tcfg, (8, 6), 2)[R.merged_prefixes(tcfg)[0]]
+    dev = _device_plans(unet, tcfg, (8, 6), 2)[RU.merged_prefixes(tcfg)[0]]
     d_dev = sum(R.plan_diff(dev[s], ref[s]) for s in range(2)) / 2
     print("ToMe plan wiring: device share %.4f, bound %.4f (d0 %.4f), after norm1 %.4f, before proj_in %.4f" % (d_dev, bound, d0, d_norm1, d_input))
     U.record_parity("tome_plan_wiring", dict(device=d_dev, d0=d0, bound=bound, norm1=d_norm1, before_proj_in=d_input))
@@ -530,7 +532,7 @@ def _merged(tiny, arm):
 
 @pytest.mark.parametrize("arm", ["graph", "eager", "modular", "lanes"])
 def test_loop_vs_reference(tiny, arm):
-    """4 DDIM steps, all three sub-layers merged: a step callback reads the plans of every evaluation back, tome_ref.tryon_reference runs
+    """4 DDIM steps, all three sub-layers merged: a step callback reads the plans of every evaluation back, ref_tryon.tryon_reference runs
     with them forced; thresholds of tests/test_gpu_pag.py's end-to-end test (latents >= 40 dB, image >= 35 dB).  The callback changes
     nothing: the run equals the run without one bit for bit.  lanes: the graph run on two sample-group lanes (a merge that flips between one
     lane and two moves the result by more than rounding, so the lanes are held to the reference with their own plans, not to the one-lane run)"""
@@ -547,8 +549,8 @@ def test_loop_vs_reference(tiny, arm):
     img, lat = _call(tiny, pipe, fused=arm != "modular", graph=arm != "eager",
                      callback=lambda i, t, latents: per_eval.append(_device_plans(unet, tcfg, (8, 6), 4)))
     assert len(per_eval) == STEPS
-    ref_img, ref_lat = R.tryon_reference(tiny["sd"]["unet"], tiny["ucfg"], tiny["sd"]["vae"], tiny["vcfg"], tiny["sd"]["emasc"], _inputs(tiny), STEPS,
-                                         "ddim", tcfg, per_eval)
+    ref_img, ref_lat = RT.tryon_reference(tiny["sd"]["unet"], tiny["ucfg"], tiny["sd"]["vae"], tiny["vcfg"], tiny["sd"]["emasc"], _inputs(tiny), STEPS,
+                                          "ddim", tome=(tcfg, per_eval))
     p_img, p_lat = U.psnr(img, ref_img, peak=1.0), U.psnr(lat, ref_lat)
     p_plain = U.psnr(lat, plain_lat)
     print("tiny ToMe %s: image %.2f dB, latents %.2f dB; against the plain run %.2f dB" % (arm, p_img, p_lat, p_plain))
