@@ -594,7 +594,7 @@ const char* ladi_igemm_cfg_symbol_name(int cfg);
 /* Host-only introspection of the tile selection a launch with tile_cfg = 0 makes (ladi_igemm_desc is declared below).  None of these launches
  * anything or dereferences an operand pointer; only null / non-null is looked at.
  *   tune_key:       the key the launch would look up, key = {P, Q, K, C0, C1, Wo, flags, batch}; returns 0, or the launch's own argument refusal
- *                   (-1 .. -6, -18, -19) and leaves key alone.  The launch computes its key with the same function.
+ *                   (-1 .. -6, -18, -19, -20) and leaves key alone.  The launch computes its key with the same function.
  *   tune_lookup:    the configuration the selection table holds for key (the shipped tune_gfx950.txt, LADI_TUNE_CACHE and this process's
  *                   measurements, loaded exactly as a launch loads them), 0 = none
  *   tune_put:       process-local: set the table's entry for key (cfg = 0 erases it); returns the previous value (0 = none), -1 for a bad cfg
@@ -602,7 +602,7 @@ const char* ladi_igemm_cfg_symbol_name(int cfg);
  *                   are judged; strict = 0: as the cost model's candidates are), else 0
  *   last_selection: out = {configuration launched, source} of the last launch made from outside the library: source 0 = tile_cfg given,
  *                   1 = table, 2 = measured by this launch, 3 = cost model (also after an inadmissible table hit), 4 = the fixed list of
- *                   X-stationary forms a gn_ss launch falls back to.  The tuner's own timing launches do not overwrite it.
+ *                   X-stationary forms a gn_ss launch (or one whose pixel operand is beyond every tile's reach, rc -20) falls back to.  The tuner's own timing launches do not overwrite it.
  *   launch_log:     on = 1 clears the log and starts recording, on = 0 stops (the log stays readable).  While on, every launch made from
  *                   outside the library (product call sites and ladi_op_igemm alike; not the tuner's timing launches) adds one text line per
  *                   DISTINCT launch: "name=value" pairs for every integer field of the descriptor, the four batch strides, batch,
@@ -610,7 +610,7 @@ const char* ladi_igemm_cfg_symbol_name(int cfg);
  *                   256 ln_gamma, 512 ln_scratch, 1024 gn_ss, 2048 bias_mul not in {0, 1}, 4096 out_scale != 1), key = the eight key integers,
  *                   cfg, src (as last_selection), rc, last = the four ladi_igemm_last_launch values, px = stats_row_px, n = repeat count.
  *                   No pointer and no value is recorded.  launch_log_read has the calling convention of ladi_profile_igemm_symbols.
- *   A launch that is refused AFTER its configuration was chosen (rc -2, -7 .. -9, -12 .. -15, -17) counts: last_selection reports its choice,
+ *   A launch that is refused AFTER its configuration was chosen (rc -2, -7 .. -9, -12 .. -17, -20 for its configuration) counts: last_selection reports its choice,
  *   the log holds its line with that rc, and ladi_igemm_last_launch reports family 0.  A launch refused for its arguments (the codes tune_key
  *   returns) has no key and no selection: it is not logged and leaves last_selection alone. */
 int ladi_igemm_tune_lookup(const int key[8]);
@@ -642,7 +642,19 @@ typedef struct {
        output channel, or by pixel when bias_per_pixel.  batch > 1 runs `batch` problems whose src0 / W / out / res0 and res1 lie bs_src0 / bs_w /
        bs_out / bs_res elements apart (0 = shared).  Two combinations are refused, for every tile_cfg (0 included):
          rc -18: batch > 1 with a second source (src1 / C1): there is no batch stride for it;
-         rc -19: out_f32 with an activation, rowadd, res0, res1 or mask: the fp32 store is (acc + bias * bias_mul) * out_scale only. */
+         rc -19: out_f32 with an activation, rowadd, res0, res1 or mask: the fp32 store is (acc + bias * bias_mul) * out_scale only.
+       The size limit of the pixel operands and the weight (rc -20).  The tiled kernels (ring, igemm8, loader / consumer) gather src0 / src1
+       through 32-bit byte offsets from the first sample a workgroup's pixel tile touches, so what a tile of bp pixels can reach,
+           span = 2 ((ns Hs Ws + Hs Ws - 1 + back_px) ld + C) bytes,   back_px = ups ? 0 : pad Ws + pad,
+           ns = min((Ho Wo - gcd(bp, Ho Wo) + bp - 1) / (Ho Wo), samples - 1)   (0 when bp divides Ho Wo),
+       has to stay below 0x7FFFFFFF for each source (ld = ld0 / ld1, C = C0 / C1), and so has the weight's 2 ((Q - 1) ldw + K).  The tensor as
+       a whole may be of any size: only a sample (Hs Ws ld) counts, twice that where a tile straddles two samples.  A configuration whose span
+       reaches the limit is not admissible (ladi_igemm_cfg_admissible returns 0, tile_cfg = 0 never selects it and prefers one whose tiles lie
+       inside single samples); an explicit tile_cfg of that kind, and tile_cfg = 0 when no configuration is left, return rc -20 and launch
+       nothing; ladi_last_error then names P, Hs Ws, ld and the span.  When already a single sample (or the weight) is out of reach and the
+       launch is not one the X-stationary kernel takes (which addresses its pixel operand with 64 bits), -20 is an argument refusal like -18
+       and -19: ladi_igemm_tune_key returns it too.  The halo forms keep their stricter rule (the whole tensor below 0x7FFFFFFF bytes, rc -16
+       for an explicit tile_cfg).  out, res0, res1, mask, the statistics rows and every batch stride are addressed with 64 bits: no limit. */
 } ladi_igemm_desc;
 int ladi_op_igemm(const ladi_igemm_desc* d, int batch, int tile_cfg, void* stream);
 int ladi_igemm_tune_key(const ladi_igemm_desc* d, int batch, int key[8]);
@@ -672,6 +684,10 @@ int ladi_op_xattn_block(const void* x, const void* ln_gamma, const void* ln_beta
                         const void* bo, int n, int T, void* out, void* stream);
 int ladi_op_ff_block(const void* x, const void* ln_gamma, const void* ln_beta, float eps, const void* w1_geglu, const void* b1_geglu, const void* w2,
                      const void* bo, int P, void* out, void* stream);
+/* flash attention on heads of 64 (ladi_op_attention, ladi_op_attention_causal).  Size limit: the keys of ONE sample are streamed through 32-bit
+ * byte offsets from that sample's base, so 2 ((Nk - 1) max(ldk, ldv) + 64) has to stay below 0x7FFFFFFF; a launch beyond that returns -3 with a
+ * ladi_last_error text and launches nothing.  q / o rows and the four sample strides are addressed with 64 bits: any size.  The generic and the
+ * wide kernel address everything with 64 bits. */
 int ladi_op_attention(const void* q, const void* k, const void* v, void* o, int ldq, int ldk, int ldv, int ldo, long long sq,
                       long long sk, long long sv, long long so, int n, int heads, int Nq, int Nk, float scale, void* stream);
 /* same with causal = 1: query i attends to keys <= i (the CLIP text encoder's mask; Nq == Nk) */

@@ -15,6 +15,7 @@
 //   until the tile maximum exceeds the reference by more than 2^8 (wave-uniform decision; P <= 256 fits fp16).
 #include "common.h"
 #include "kernels.h"
+#include <algorithm>
 #pragma clang diagnostic ignored "-Winline-asm"   // the "m0" clobber of FA_DMA (see there)
 #include <cstdlib>
 
@@ -605,6 +606,11 @@ __global__ __launch_bounds__(64) void attn_single_query_kernel(const h16* __rest
 
 int ladi_launch_flash_attn64(const AttnArgs& a, hipStream_t st) {
     if ((a.ldq & 7) || (a.ldk & 7) || (a.ldv & 7) || (a.ldo & 3) || a.Nk <= 0 || a.Nq <= 0) return -1;
+    // the K / V stream (FA_DMA above) addresses the keys of ONE (sample, head) by 32-bit byte offsets 2 (key ld + 8 chunk), key <= Nk - 1,
+    // chunk <= 7, from a descriptor of 0x7FFFFFFF bytes that starts at the sample's base: the last byte asked for is below
+    // 2 ((Nk - 1) ld + 64), which has to stay inside the descriptor -- past it the load returns zeros (a silently wrong softmax), and the
+    // `int` product overflows from 2^31 on.  q and o rows, and every sample stride, are addressed with 64 bits: no limit there.
+    if (2 * ((long long)(a.Nk - 1) * std::max(a.ldk, a.ldv) + 64) >= 0x7FFFFFFFLL) return -3;
     static const int force_qb = getenv("LADI_ATTN_QB") ? atoi(getenv("LADI_ATTN_QB")) : 0;
     // two query blocks per wave once the 256-query tiles alone oversubscribe the 256 CUs and the K/V stream is long
     // (measured on the UNet shapes, n = 16: self L0 594 -> 623 TFLOP/s, self L1 452 -> 494; short K/V or few tiles: no gain)

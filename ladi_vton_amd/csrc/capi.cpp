@@ -6,6 +6,7 @@
 #include <vector>
 #include <cstring>
 #include <cmath>
+#include <algorithm>
 
 using namespace ladi;
 
@@ -1204,7 +1205,7 @@ int ladi_op_igemm(const ladi_igemm_desc* d, int batch, int tile_cfg, void* strea
         IGemmArgs a;
         std::memcpy(&a, d, sizeof(a));
         int rc = ladi_launch_igemm(a, batch, tile_cfg, S(stream));
-        if (rc) set_error("igemm launch rc=" + std::to_string(rc));
+        if (rc) set_error("igemm launch rc=" + std::to_string(rc) + (rc == -20 ? std::string(": ") + ladi_igemm_span_refusal() : std::string()));
         return rc;
     });
 }
@@ -1227,7 +1228,7 @@ int ladi_op_igemm_stats(const ladi_igemm_desc* d, int batch, int tile_cfg, int* 
         IGemmArgs a;
         std::memcpy(&a, d, sizeof(a));
         int rc = ladi_launch_igemm(a, batch, tile_cfg, S(stream), stats_row_px);
-        if (rc) set_error("igemm launch rc=" + std::to_string(rc));
+        if (rc) set_error("igemm launch rc=" + std::to_string(rc) + (rc == -20 ? std::string(": ") + ladi_igemm_span_refusal() : std::string()));
         return rc;
     });
 }
@@ -1295,13 +1296,21 @@ int ladi_op_layer_norm(const void* x, const void* gamma, const void* beta, float
 int ladi_op_layer_norm_ld(const void* x, int ldx, const void* gamma, const void* beta, float eps, int rows, int C, void* out, int ldo, void* stream) {
     return ladi_launch_layernorm((const h16*)x, ldx, (const h16*)gamma, (const h16*)beta, eps, rows, C, (h16*)out, ldo, S(stream));
 }
+// rc -3 of the flash kernel: the keys of one sample span more than its 32-bit K / V offsets reach (attention.hip ladi_launch_flash_attn64)
+static int flash_attn_rc(const char* what, const AttnArgs& a, int rc) {
+    if (rc == -3)
+        set_error(std::string(what) + ": refused: Nk = " + std::to_string(a.Nk) + " keys at row strides ldk = " + std::to_string(a.ldk) + ", ldv = " +
+                  std::to_string(a.ldv) + " span " + std::to_string(2 * ((long long)(a.Nk - 1) * std::max(a.ldk, a.ldv) + 64)) +
+                  " bytes per sample; the K / V stream reaches less than 2147483647");
+    return rc;
+}
 int ladi_op_attention(const void* q, const void* k, const void* v, void* o, int ldq, int ldk, int ldv, int ldo, long long sq, long long sk,
                       long long sv, long long so, int n, int heads, int Nq, int Nk, float scale, void* stream) {
     AttnArgs a;
     a.q = (const h16*)q; a.k = (const h16*)k; a.v = (const h16*)v; a.o = (h16*)o;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.sq = sq; a.sk = sk; a.sv = sv; a.so = so;
     a.n = n; a.heads = heads; a.Nq = Nq; a.Nk = Nk; a.scale = scale;
-    return ladi_launch_flash_attn64(a, S(stream));
+    return flash_attn_rc("ladi_op_attention", a, ladi_launch_flash_attn64(a, S(stream)));
 }
 int ladi_op_attention_causal(const void* q, const void* k, const void* v, void* o, int ldq, int ldk, int ldv, int ldo, long long sq,
                              long long sk, long long sv, long long so, int n, int heads, int Nq, int Nk, float scale, int causal,
@@ -1311,7 +1320,7 @@ int ladi_op_attention_causal(const void* q, const void* k, const void* v, void* 
     a.q = (const h16*)q; a.k = (const h16*)k; a.v = (const h16*)v; a.o = (h16*)o;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.sq = sq; a.sk = sk; a.sv = sv; a.so = so;
     a.n = n; a.heads = heads; a.Nq = Nq; a.Nk = Nk; a.scale = scale; a.causal = causal ? 1 : 0;
-    return ladi_launch_flash_attn64(a, S(stream));
+    return flash_attn_rc("ladi_op_attention_causal", a, ladi_launch_flash_attn64(a, S(stream)));
 }
 int ladi_op_attention_generic(const void* q, const void* k, const void* v, void* o, int ldq, int ldk, int ldv, int ldo, long long sq,
                               long long sk, long long sv, long long so, int n, int heads, int head_dim, int Nq, int Nk, float scale,

@@ -34,6 +34,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <utility>
+#include <numeric>
 #include <dlfcn.h>
 
 int ladi_igemm_num_cfgs();
@@ -443,6 +444,60 @@ static bool splitk_admissible(const IGemmArgs& a, int c) {
     return !(tiles * kCfg[c].split > 1024 || tiles > 256 || (a.K / 64) / kCfg[c].split < 8);
 }
 
+// ---- the span guard of the tiled gather (ring, igemm8 and loader / consumer kernels: igemm_kernel.h "buffer descriptors", igemm8.hip,
+// igemm_lc.hip; the three address their activations in the same way).  A workgroup's activation descriptor starts at
+//     base = src + n_first HsWs ld - back_px ld,       n_first = the sample of the tile's first pixel, back_px = pad Ws + pad (0 when ups),
+// holds num_records = 0x7FFFFFFF bytes, and every 16-byte gather of the tile is addressed from it by a 32-bit byte offset
+//     2 (pix ld + c),   pix = (n - n_first) HsWs + iy Ws + ix + back_px,   c = channel chunk base + 8 * chunk in [0, C - 8],
+// formed in `int` as a per-lane part (the top-left tap, chunk) plus a wave-uniform part (tap and channel-chunk displacement); the folded-
+// upsample path forms the same sum in one piece with back_px = 0.  Only taps inside the image are dereferenced, so iy Ws + ix <= HsWs - 1,
+// and a tile of bp pixels that starts r pixels into a sample ends in sample floor((r + bp - 1) / HoWo) behind it.  Tiles start at multiples
+// of bp, so r is a multiple of g = gcd(bp, HoWo) and at most HoWo - g: a tile reaches at most
+//     ns = min(floor((HoWo - g + bp - 1) / HoWo), samples - 1)     samples behind its first one -- 0 when bp divides HoWo (every tile ends
+// inside the sample it starts in), bp / HoWo - 1 when HoWo divides bp.  The last byte a tile can ask for is therefore below
+//     span = 2 ((ns HsWs + HsWs - 1 + back_px) ld + C)
+// for each source.  An offset at or past num_records is outside the descriptor: the hardware returns zeros for it, without an error, and
+// from 2^31 on the `int` product has overflowed before that.  So a configuration is admitted only while span < 0x7FFFFFFF for both sources
+// (the bound is exact when every residue r occurs among the launch's tiles and conservative otherwise).  The weight descriptor starts at W with the same
+// num_records, offsets 2 (q ldw + k): span_w = 2 ((Q - 1) ldw + K).  bp = 0 asks for a tile inside one sample, the least any tile spans.
+// The halo forms and the X-stationary kernel have their own rules (igemm_halo.hip, linear_xs.hip: the whole tensor below 0x7FFFFFFF bytes
+// for the former, 64-bit activation addresses in the latter).
+constexpr long long SPAN_LIMIT = 0x7FFFFFFFLL;
+struct SpanInfo { long long span, span_w; int ns, ld; };
+static SpanInfo igemm_tile_span(const IGemmArgs& a, int bp) {
+    const long long HoWo = (long long)a.Ho * a.Wo, HsWs = (long long)a.Hs * a.Ws;
+    SpanInfo s{0, 0, 0, a.ld0};
+    if (HoWo > 0 && bp > 0) {
+        const long long samples = (a.P + HoWo - 1) / HoWo, g = std::gcd(HoWo, (long long)bp);
+        s.ns = (int)std::max(0LL, std::min((HoWo - g + bp - 1) / HoWo, samples - 1));
+    }
+    const long long back_px = a.ups ? 0 : (long long)a.pad * a.Ws + a.pad;
+    const long long last_px = (long long)s.ns * HsWs + HsWs - 1 + back_px;
+    // a LayerNorm of the operand that runs as its own kernel leaves the tiled kernel the dense scratch (ld = C0) to gather from
+    if (a.ln_gamma && a.ln_scratch) s.ld = a.C0;
+    const long long s0 = 2 * (last_px * s.ld + a.C0), s1 = a.C1 ? 2 * (last_px * a.ld1 + a.C1) : 0;
+    s.span = std::max(s0, s1);
+    if (s1 > s0) s.ld = a.ld1;
+    s.span_w = 2 * ((long long)(a.Q - 1) * (a.ldw ? a.ldw : a.K) + a.K);
+    return s;
+}
+static bool span_ok(const IGemmArgs& a, int bp) {
+    const SpanInfo s = igemm_tile_span(a, bp);
+    return s.span < SPAN_LIMIT && s.span_w < SPAN_LIMIT;
+}
+// the shapes the X-stationary kernel can take: the one family that is not bound by the span of its pixel operand
+static bool xs_shape(const IGemmArgs& a, int batch) {
+    return batch == 1 && a.ksize == 1 && a.stride == 1 && !a.ups && !a.C1 && !a.src1 && a.K == a.C0 && (a.K == 320 || a.K == 640);
+}
+static std::string g_span_text;
+static void note_span_refusal(const IGemmArgs& a, int bp) {
+    const SpanInfo s = igemm_tile_span(a, bp);
+    char b[320];
+    snprintf(b, sizeof(b), "a tile of %d pixels spans %d sample(s) beyond its first: P=%d HsWs=%lld ld=%d span=%lld bytes, weight span=%lld bytes; "
+             "32-bit gather offsets allow less than %lld", bp, s.ns, a.P, (long long)a.Hs * a.Ws, s.ld, s.span, s.span_w, SPAN_LIMIT);
+    g_span_text = b;
+}
+
 // Everything that makes configuration c illegal (or, with `strict`, pointless) for this launch.  The tuner, a selection read from the
 // tune table and an explicitly requested configuration all pass through it: the tune key folds several epilogue features into one bit,
 // so a cached choice is re-validated against the launch it is applied to (a split-K selection must never reach a launch with a
@@ -458,6 +513,7 @@ static bool cfg_admissible(const IGemmArgs& a, int batch, int c, bool strict) {
     if (a.gn_ss) return false;                                        // GroupNorm affine of the operand: X-stationary kernel only
     if (a.ln_gamma && !a.ln_scratch) return false;                    // no scratch: only the fused (X-stationary) form
     if (t.family == FAM_LC && (a.ups || batch != 1)) return false;    // loader / consumer kernel: no folded upsample, no batched launches
+    if (t.family == FAM_HALO ? igemm_tile_span(a, 0).span_w >= SPAN_LIMIT : !span_ok(a, t.bp)) return false;   // the span guard (above)
     if (t.family == FAM_HALO) {
         // folded-upsample form: single source, whole tiles inside a sample; 2-D blocked form: W % 32 == 0, whole blocks; else the ring-halo form:
         // 3x3 stride-1 convolutions on images no wider than the form's halo buffer was sized for
@@ -504,6 +560,9 @@ static int igemm_tune_key(const IGemmArgs& a, int batch, TuneKey* key) {
     // read element 0's), and the fp32 store (igemm_epilogue_generic) applies bias and out_scale only
     if (batch > 1 && (a.src1 || a.C1)) return -18;
     if (a.out_f32 && (a.act != LADI_ACT_NONE || a.rowadd || a.res0 || a.res1 || a.mask)) return -19;
+    // a single sample (or the weight) already out of reach of a tile's 32-bit gather offsets, and not a shape the X-stationary kernel takes: no
+    // configuration can run it (the span guard above; the per-configuration part of the guard is in cfg_admissible)
+    if (!xs_shape(a, batch) && !span_ok(a, 0)) return -20;
     // flags also carry the epilogue features that decide which kernels are admissible (residuals, fused statistics, other)
     // (bits 12 / 13 sit ABOVE the ksize field at bits 8..10: at 256 / 512 they were absorbed by ksize = 1 / 3 and a fused-GroupNorm
     // projection shared its entry with the plain 1x1 of the same shape -- ADVICE r04)
@@ -548,7 +607,10 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
     int sel = cfg ? SEL_EXPLICIT : SEL_COST_MODEL, row_px = 0;
     if (stats_row_px) *stats_row_px = 0;
     TuneKey key;
-    if (const int krc = igemm_tune_key(a, batch, &key)) return krc;
+    if (const int krc = igemm_tune_key(a, batch, &key)) {
+        if (krc == -20) note_span_refusal(a, 0);
+        return krc;
+    }
     const bool geglu = a.act == LADI_ACT_GEGLU;
     // ---- measured tile-shape selection ("measure, don't guess"): the first time a problem shape is seen outside a stream
     //      capture, every admissible configuration is timed with HIP events on the launch stream and the fastest is cached.
@@ -627,7 +689,9 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
             if (cost < best) { best = cost; cfg = c; }
         }
     }
-    if (cfg == 0 && a.gn_ss) {      // no measured selection and the cost model does not rank the X-stationary kernel: first eligible form
+    // no measured selection and the cost model does not rank the X-stationary kernel: first eligible form, for a GroupNorm affine of the operand
+    // and for a pixel operand beyond the reach of every tile (the span guard; the X-stationary kernel addresses it with 64 bits)
+    if (cfg == 0 && (a.gn_ss || (xs_shape(a, batch) && !span_ok(a, 64)))) {
         for (int c : {25, 26, 27, 23, 24, 93, 94, 95}) if (cfg_admissible(a, batch, c, true)) { cfg = c; sel = SEL_GN_LIST; break; }
     }
     // a launch refused after the selection was made launched nothing: it is still the last top-level launch (selection, log line with its rc),
@@ -640,8 +704,13 @@ int ladi_launch_igemm(const IGemmArgs& a_in, int batch, int cfg, hipStream_t st,
         }
         return rc;
     };
+    if (cfg == 0 && !span_ok(a, 64)) { note_span_refusal(a, 64); return refused(-20); }   // not even the smallest tile (64 pixels) passes the span guard
     if (cfg < 1 || cfg > NCFG) return refused(-7);
     const BaseTrait t = cfg_trait(cfg);
+    if (t.family != FAM_XS && (t.family == FAM_HALO ? igemm_tile_span(a, 0).span_w >= SPAN_LIMIT : !span_ok(a, t.bp))) {
+        note_span_refusal(a, t.family == FAM_HALO ? 0 : t.bp);
+        return refused(-20);
+    }
     if (a.gn_ss && t.family != FAM_XS) return refused(-17);
     if (a.ln_gamma && t.family != FAM_XS) {   // LayerNorm as its own kernel into the caller's scratch (timed by the tuner as part of cfg)
         if (!a.ln_scratch || a.C1 || a.src1 || a.ksize != 1 || batch != 1) return refused(-15);
@@ -740,6 +809,7 @@ int ladi_igemm_admissible(const IGemmArgs& a, int batch, int cfg, int strict) {
     if (cfg < 1 || cfg > NCFG) return 0;
     return cfg_admissible(a, batch, cfg, strict != 0) ? 1 : 0;
 }
+const char* ladi_igemm_span_refusal() { return g_span_text.c_str(); }
 void ladi_igemm_selection(int out[2]) { out[0] = g_last_sel[0]; out[1] = g_last_sel[1]; }
 void ladi_igemm_log_enable(int on) {
     g_log = on != 0;

@@ -13,6 +13,8 @@
 // zeroed) -- one buffer per stream that may run split-K launches concurrently; null -> a process-wide buffer (single-stream callers)
 int ladi_launch_igemm(const IGemmArgs& a, int batch, int cfg, hipStream_t st, int* stats_row_px = nullptr, float* ws = nullptr,
                       size_t ws_bytes = 0, int* sk_cnt = nullptr);
+// text of the last rc -20 refusal (the span guard of igemm.hip): P, HsWs, ld and the span that reached the limit
+const char* ladi_igemm_span_refusal();
 // worst-case split-K slab for this problem over every admissible split configuration (0: split-K can never be chosen); depends on
 // the problem shape only, so a planning pass and the real pass allocate identically
 size_t ladi_igemm_splitk_ws_bytes(const IGemmArgs& a, int batch);

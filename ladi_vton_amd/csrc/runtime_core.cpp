@@ -101,7 +101,7 @@ Act Ctx::new_act(int n, int h, int w, int cc, int ld) {
     return a;
 }
 void Ctx::check(int rc, const char* what) {
-    if (rc != 0) throw std::runtime_error(std::string(what) + " failed rc=" + std::to_string(rc));
+    if (rc != 0) throw std::runtime_error(std::string(what) + " failed rc=" + std::to_string(rc) + (rc == -20 ? std::string(": ") + ladi_igemm_span_refusal() : std::string()));
 }
 
 // ------------------------------------------------------------------------------------------------

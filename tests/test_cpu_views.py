@@ -134,3 +134,55 @@ def test_guarded_layout_and_assert_untouched(dtype):
     assert g3.rows == 24 and g3.ld == 8 and int(g3.poison_mask().sum()) == 4 * 8
     out = U.guarded_out(6, 8, ld=16, device="cpu", dtype=dtype)
     assert bool(torch.isnan(out.buf).all())
+
+
+# ---------------------------------------------------------------------------------------------------------------------- far views
+@pytest.mark.parametrize("dtype", [torch.float16, torch.float32])
+@pytest.mark.parametrize("samples,sstride", [(1, None), (3, None), (3, 5 * 1000 + 7 * 8)])
+def test_far_view_harness_places_detects_strays_and_unwritten_elements(dtype, samples, sstride, monkeypatch):
+    """guarded_far() / assert_untouched_far() at a small span on the CPU, with the chunk size cut down so that the allocation takes several
+    chunks: (1) every operand element sits where the documented formula says and everything else is poison, (2) ONE planted stray write is
+    found wherever it lies -- the first and last element of the allocation, the column behind a row, the gap between two samples, a chunk
+    boundary --, (3) an output element that was never written fails check_elem, a fully written output passes and leaves the count at zero."""
+    monkeypatch.setattr(U, "FAR_CHUNK", 1000)
+    srows, C, ld = 4, 24, 1000
+    t = (_rand((samples * srows, C), 5) if dtype == torch.float16 else _rand((samples * srows, C), 5)).to(dtype)
+    g = U.guarded_far(t, ld, samples=samples, sstride=sstride, device="cpu")
+    ss = srows * ld if sstride is None else sstride
+    it, word = U._poison_word(dtype)
+    bits = g.buf.view(it)
+    assert g.buf.numel() == 2 * U.FAR_PAD + (samples - 1) * ss + (srows - 1) * ld + C and g.buf.numel() > 3 * U.FAR_CHUNK
+    expect = torch.full_like(bits, word)
+    for s in range(samples):
+        for r in range(srows):
+            e0 = U.FAR_PAD + s * ss + r * ld
+            assert torch.equal(g.buf[e0:e0 + C], t[s * srows + r])
+            expect[e0:e0 + C] = t[s * srows + r].view(it)
+    assert torch.equal(bits, expect)
+    assert torch.equal(g.cpu(), t) and g.ptr == g.buf.data_ptr() + U.FAR_PAD * g.buf.element_size()
+    assert g.last_byte == ((samples - 1) * ss + (srows - 1) * ld + C) * g.buf.element_size() - 1
+    U.assert_untouched_far(g, "clean")
+    spots = [0, g.buf.numel() - 1, U.FAR_PAD - 1, U.FAR_PAD + C, U.FAR_PAD + ld - 1, U.FAR_PAD + (srows - 1) * ld + C, 2 * U.FAR_CHUNK - 1, 2 * U.FAR_CHUNK]
+    if samples > 1:
+        spots += [U.FAR_PAD + ss - 1, U.FAR_PAD + (samples - 1) * ss + C]
+    inside = g.inside(torch.tensor(spots))
+    assert not bool(inside.any()), (spots, inside)
+    assert bool(g.inside(torch.tensor([U.FAR_PAD, U.FAR_PAD + C - 1, U.FAR_PAD + (samples - 1) * ss + (srows - 1) * ld + C - 1])).all())
+    for e in spots:
+        keep = bits[e].clone()
+        g.buf[e] = 0.0
+        assert U.far_stray_count(g) == 1, e
+        with pytest.raises(AssertionError, match="allocation elements %d " % e):
+            U.assert_untouched_far(g, "stray at %d" % e)
+        bits[e] = keep
+    U.assert_untouched_far(g, "restored")
+    # an operand element that changes is no stray (a kernel may write its output), whatever it holds
+    g.views[-1][srows - 1, C - 1] = 3.0
+    U.assert_untouched_far(g, "operand write")
+    out = U.guarded_far_out(samples * srows, C, ld, samples=samples, sstride=sstride, dtype=dtype, device="cpu")
+    for s, v in enumerate(out.views):
+        v.copy_(t[s * srows:(s + 1) * srows])
+    assert U.check_elem(out.cpu().float(), t.double(), 0.0, "written") == 0.0
+    U.assert_untouched_far(out, "written output")
+    out.views[samples - 1][srows - 1, C - 1] = float("nan")          # as an element the launch never reached
+    _rejects(out.cpu().float(), t.double(), 0.0, "unwritten")

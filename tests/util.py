@@ -275,6 +275,110 @@ def assert_untouched(g, what=""):
                              "bits 0x%X" % (what, int(bad.sum()), r, r - g.pre, g.rows, c, g.C, g.ld, int(bits[r, c]) & (0xFFFF if g.buf.dtype == torch.float16 else 0xFFFFFFFF)))
 
 
+# ----------------------------------------------------------------------------------------------------------------------------------------
+# Far views (tests/far_cases.py, tests/test_gpu_far.py, tests/test_cpu_far.py): the same placement at row strides of megabytes, so that a
+# problem of a few hundred rows spans more than 2^31 or 2^32 bytes.  Only the allocation is large: the operand stays [rows, C].  Nothing
+# here copies the allocation to the host or builds a host tensor that grows with the span -- the poison is counted on the device, in chunks.
+# ----------------------------------------------------------------------------------------------------------------------------------------
+FAR_PAD = 4096                      # poison elements in front of the first and behind the last operand element (a multiple of 8)
+FAR_CHUNK = 1 << 26                 # elements compared per step of the poison count: a 64 MiB bool temporary at most
+
+
+class FarGuarded:
+    """one operand of n samples x srows rows x C columns inside ONE poisoned 1-D allocation .buf: row r of sample s starts at element
+    .pad + s * sstride + r * ld.  .views[s] is the [srows, C] strided device view of sample s (.view = .views[0] when n == 1), .ptr the address
+    of the first element, .bytes the allocation's size, .last_byte the byte offset (from .ptr) of the operand's last element."""
+
+    def __init__(self, buf, n, srows, C, ld, sstride, pad):
+        self.buf, self.n, self.srows, self.C, self.ld, self.sstride, self.pad = buf, n, srows, C, ld, sstride, pad
+        self.rows = n * srows
+        self.views = [buf.as_strided((srows, C), (ld, 1), pad + s * sstride) for s in range(n)]
+        self.view = self.views[0] if n == 1 else None
+        self.ptr = self.views[0].data_ptr()
+        self.bytes = buf.numel() * buf.element_size()
+        self.last_byte = ((n - 1) * sstride + (srows - 1) * ld + C) * buf.element_size() - 1
+
+    def col(self, c0):
+        return self.ptr + c0 * self.buf.element_size()
+
+    def cpu(self):
+        """the operand's values, [n * srows, C], on the host (the views only: rows x C elements)"""
+        return torch.cat([v.cpu() for v in self.views])
+
+    def inside(self, idx):
+        """bool tensor: which of the flat allocation indices idx (int64 tensor) belong to the operand"""
+        rel = idx - self.pad
+        s = torch.div(rel, self.sstride, rounding_mode="floor") if self.n > 1 else torch.zeros_like(rel)
+        s = s.clamp(0, self.n - 1)
+        within = rel - s * self.sstride
+        r, c = torch.div(within, self.ld, rounding_mode="floor"), within % self.ld
+        return (rel >= 0) & (r >= 0) & (r < self.srows) & (c < self.C)
+
+
+def guarded_far(t, ld, samples=1, sstride=None, device=None):
+    """guarded() for wide strides: the fp16 / fp32 operand t ([rows, C], or NHWC flattened to pixel rows; CPU or GPU) placed at row stride ld
+    elements, its rows split into `samples` equal groups that lie sstride elements apart (default: srows * ld, i.e. one uniform row stride;
+    a per-sample or batch stride otherwise -- at least (srows - 1) * ld + C so that samples do not overlap).  Everything else of the
+    allocation -- FAR_PAD elements before and after, the columns [C, ld) of every row, the gaps between samples -- holds POISON16 / POISON32.
+    ld and sstride are multiples of 8 (16-byte aligned rows of fp16, as every launcher requires).  Returns a FarGuarded."""
+    assert t.dtype in (torch.float16, torch.float32)
+    t2 = t.reshape(-1, t.shape[-1])
+    rows, C = t2.shape
+    assert rows % samples == 0, (rows, samples)
+    srows = rows // samples
+    sstride = srows * ld if sstride is None else sstride
+    assert ld >= C and ld % 8 == 0 and sstride % 8 == 0 and (samples == 1 or sstride >= (srows - 1) * ld + C), (C, ld, sstride)
+    it, word = _poison_word(t.dtype)
+    device = dev() if device is None else torch.device(device)
+    total = FAR_PAD + (samples - 1) * sstride + (srows - 1) * ld + C + FAR_PAD
+    buf = torch.full((total,), word, dtype=it, device=device).view(t.dtype)
+    g = FarGuarded(buf, samples, srows, C, ld, sstride, FAR_PAD)
+    for s, v in enumerate(g.views):
+        v.copy_(t2[s * srows:(s + 1) * srows].to(device))
+    assert g.ptr % 16 == 0
+    return g
+
+
+def guarded_far_out(rows, C, ld, samples=1, sstride=None, dtype=torch.float16, device=None):
+    """an OUTPUT placed like guarded_far(): the operand itself starts as NaN (not the poison pattern), so an element the kernel never wrote
+    fails check_elem"""
+    return guarded_far(torch.full((rows, C), float("nan"), dtype=dtype), ld, samples, sstride, device)
+
+
+def far_stray_count(g):
+    """number of elements of g's allocation OUTSIDE the operand that no longer hold the poison pattern, counted where the allocation lives:
+    the raw words that differ from the poison are counted chunk by chunk over the whole allocation, and those inside the operand (rows x C
+    elements, gathered through the views) are subtracted.  One scalar reaches the host."""
+    it, word = _poison_word(g.buf.dtype)
+    bits = g.buf.view(it)
+    total = torch.zeros((), dtype=torch.int64, device=bits.device)
+    for c0 in range(0, bits.numel(), FAR_CHUNK):
+        total += (bits[c0:c0 + FAR_CHUNK] != word).sum()
+    for v in g.views:
+        total -= (v.view(it) != word).sum()
+    return int(total)
+
+
+def assert_untouched_far(g, what=""):
+    """assert_untouched() for a FarGuarded: every poison element of the allocation is still bit-identical.  The count runs on the device
+    (far_stray_count); only after a failure are the first strays located, chunk by chunk, for the message."""
+    n = far_stray_count(g)
+    if n == 0:
+        return
+    it, word = _poison_word(g.buf.dtype)
+    bits = g.buf.view(it)
+    found = []
+    for c0 in range(0, bits.numel(), FAR_CHUNK):
+        idx = (bits[c0:c0 + FAR_CHUNK] != word).nonzero().reshape(-1) + c0
+        idx = idx[~g.inside(idx)][:4]
+        found += [(int(i), int(bits[int(i)]) & (0xFFFF if g.buf.dtype == torch.float16 else 0xFFFFFFFF)) for i in idx]
+        if len(found) >= 4:
+            break
+    raise AssertionError("%s: %d poison elements were overwritten; first at allocation elements %s (operand: %d samples x %d rows x %d columns at "
+                         "element %d, ld = %d, sample stride = %d)" % (what, n, ", ".join("%d (bits 0x%X)" % f for f in found), g.n, g.srows, g.C,
+                                                                       g.pad, g.ld, g.sstride))
+
+
 U16 = 2.0 ** -11       # unit roundoff of fp16 (round to nearest): |fp16(x) - x| <= U16 |x| for normal x
 U32 = 2.0 ** -24       # unit roundoff of fp32
 
