@@ -565,6 +565,49 @@ int ladi_tryon_set_ip_adapter(ladi_tryon* t, const void* embeds_dev, const void*
  * loop replays up to two more graphs (PAG evaluation over all groups, and over cond + perturbed); works with any lane count. */
 #define LADI_TRYON_PAG_WITH_FEATURE_CACHE (-12)
 int ladi_tryon_set_pag(ladi_tryon* t, const float* scales_host, int count);
+/* ---- Self-attention guidance (diffusers StableDiffusionSAGPipeline, sag_scale; DESIGN.md "Self-attention guidance").
+ * The SAG map: for the self-attention (attn1) of mid_block.attentions.0's transformer block, per sample,
+ *   s[j] = sum_i mean_h softmax_j(q_i k_j / 8)     (fp32, the column sums of the attention map)     m[j] = s[j] > 1
+ * over the T = hm * wm tokens of the mid block (ladi_unet_sag_tokens: three times ceil(x / 2) of the latent sides).
+ * ladi_unet_set_sag_capture: sticky, off at creation.  On: every forward of this UNet (forward, forward_pag, forward_cached whole, the fused
+ * loop) runs csrc/sag.hip's sag_map right after that block's Q / K projection, for all its samples, into buffers of the UNet's at the rows
+ * of the samples' indices in the context batch.  Two small launches; the forward's output does not change by a bit.  Off: nothing is
+ * allocated or launched.  Captured graphs are keyed on it.
+ * ladi_unet_sag_map: what the last capturing forward left, rows [0, n) of the context batch: s_out_dev fp32 [n][T], m_out_dev bytes [n][T]
+ * (either may be NULL).  T has to be the last capture's.  Waits for the device.
+ * ladi_tryon_set_sag: the scale of the following runs (sticky per handle; 0 = off, the state of a new handle: the run is the plain run bit
+ * for bit).  With a scale > 0 EVERY evaluation is
+ *   first forward (as today, capturing the map) -> sag_degrade -> second forward over B samples -> combine + scheduler step
+ * where, with a = alphas_cumprod[t], b the base prediction (the unconditional one in a CFG evaluation, else the conditional one) and m the
+ * base group's mask,   x0 = (x - sqrt(1 - a) b) / sqrt(a),  x0d = blur9(x0) where nearest-upsample(m) is 1 else x0,
+ * xd = sqrt(a) x0d + sqrt(1 - a) b;  the second forward sees xd in channels 0..3 and the base group's other channels, context rows and image
+ * tokens, and gives d;  e = [u + g (c - u) | c] + sag_scale (b - d), guidance rescale acting on the whole sum.  blur9: depthwise 9 x 9
+ * Gaussian, sigma 1, reflect padding 4.  All of it inside the same captured graph; the scale is read from device memory, so another value
+ * replays the same graphs, while switching between 0 and > 0 drops them.  Works at any lane count (the second forward runs on the lanes
+ * that divide B).  Composes with guidance schedules, rescale, strength, preserve-unmasked, callbacks, FreeU, LoRA, IP-Adapter and token merging
+ * on the outer levels.  Refused before anything is launched, with a message:
+ *   LADI_TRYON_SAG_WITH_FEATURE_CACHE  a feature-cache plan is set (shallow evaluations do not run the mid block)
+ *   LADI_TRYON_SAG_WITH_PAG            a positive PAG scale is set
+ *   LADI_TRYON_SAG_TOME_MID            token merging is configured so that the mid block merges
+ *   LADI_TRYON_SAG_SCHEDULER           Euler, Euler-ancestral or LMS (sigma space: pred_x0 / add_noise do not describe them)
+ *   LADI_TRYON_SAG_SMALL_LATENTS       latents under 5 x 5
+ * ladi_tryon_plan_forms_sag: ladi_tryon_plan_forms with the SAG state -- the scale, the scheduler code, the latent size and whether token
+ * merging merges in the mid block -- so the refusals above are reported without a GPU.  A SAG run's evaluation count and forms are the
+ * plain run's. */
+#define LADI_TRYON_SAG_WITH_FEATURE_CACHE (-14)
+#define LADI_TRYON_SAG_WITH_PAG (-15)
+#define LADI_TRYON_SAG_TOME_MID (-16)
+#define LADI_TRYON_SAG_SCHEDULER (-17)
+#define LADI_TRYON_SAG_SMALL_LATENTS (-18)
+int ladi_unet_set_sag_capture(ladi_unet* u, int on);
+int ladi_unet_sag_tokens(const ladi_unet* u, int h, int w, int* hm, int* wm);
+int ladi_unet_sag_map(ladi_unet* u, float* s_out_dev, unsigned char* m_out_dev, int n, int T);
+int ladi_tryon_set_sag(ladi_tryon* t, float sag_scale);
+/* how many hipGraph captures this handle has made over its life (-1 for a null handle): a run that replays the graphs it has adds none */
+long long ladi_tryon_graph_captures(ladi_tryon* t);
+int ladi_tryon_plan_forms_sag(int evals, int first_step, int steps, float guidance_scale, const float* guidance_tab_host, int guidance_count,
+                              float phi, const float* pag_tab_host, int pag_count, const unsigned char* full_flags_host, int flag_count,
+                              float sag_scale, int scheduler, int lat_h, int lat_w, int tome_mid_merges, unsigned char* forms_out);
 
 /* per-launch HIP-event timing of the implicit-GEMM kernel family (the dominant kernel): enable, run any entry point,
  * then collect: out[cfg*3 + {0,1,2}] = {total ms, algorithmic FLOP = 2*P*Q*K, launches} for tile configuration cfg = 1..ladi_igemm_cfg_count()
@@ -771,6 +814,29 @@ int ladi_op_cfg_stats_pag(const void* eps_dev, int ld_eps, int B, int hw, float 
  * third of a fused QKV buffer), 16-byte vectors.  C and both strides multiples of 8, strides >= C, both bases 16-byte aligned, else an
  * error with a message and nothing is launched.  Columns [C, ld) are never touched. */
 int ladi_op_pag_identity(const void* v_dev, int ldv, void* o_dev, int ldo, long long rows, int C, void* stream);
+/* the kernels of self-attention guidance on their own (csrc/sag.hip).
+ * ladi_op_sag_map: q, k fp16 with sample s, token t, head h at base + s * sq + t * ld + h * 64 (strides in halves, multiples of 8, row strides
+ *   >= 64 * heads, bases 16-byte aligned), any T >= 1 and heads >= 1 -> s_out_dev fp32 [n][T], m_out_dev bytes [n][T] as above.  Allocates
+ *   its scratch and synchronises `stream`.  Two calls give the same bits.
+ * ladi_op_sag_degrade: latents_dev fp32 [B][h * w][4], eps_dev fp16 [B][h * w][ld_eps] (the base prediction, channels 0..3), mask_dev bytes
+ *   [B][hm][wm] -> channels 0..3 of dst_rows_dev fp16 [B][h * w][ld_in] = fp16(in_scale * xd) as under ladi_tryon_set_sag, with the
+ *   coefficients given.  src_rows_dev non-NULL and another pointer than dst_rows_dev: its channels [4, copy_end) are copied too (copy_end a
+ *   multiple of 4, <= ld_in); else no other channel is touched.  Latents under 5 x 5 are an error.  Synchronises `stream`.
+ * ladi_op_cfg_stats_sag: ladi_op_cfg_stats with eps_dev [3B][hw], rows [2B, 3B) the degraded input's prediction d: the guided prediction is
+ *   u + guidance (c - u) + sag_scale (u - d).  sag_scale == 0 reads the first 2B rows alone and is ladi_op_cfg_stats bit for bit.
+ * ladi_op_sched_run_sag: ladi_op_sched_run_pag's layout with d in the third group of every evaluation and ONE scale: e = u + g (c - u) +
+ *   s (u - d) with cfg, c + s (c - d) without and in a cond-only evaluation; phi acts on the whole sum of a CFG evaluation.  s == 0 never
+ *   reads the third group and gives ladi_op_sched_run_guided's latents bit for bit. */
+int ladi_op_sag_map(const void* q_dev, int ldq, long long sq, const void* k_dev, int ldk, long long sk, int n, int T, int heads, float* s_out_dev,
+                    unsigned char* m_out_dev, void* stream);
+int ladi_op_sag_degrade(const float* latents_dev, const void* eps_dev, int ld_eps, const unsigned char* mask_dev, int B, int h, int w, int hm,
+                        int wm, float sqrt_a, float sqrt_1ma, float in_scale, const void* src_rows_dev, void* dst_rows_dev, int ld_in,
+                        int copy_end, void* stream);
+int ladi_op_cfg_stats_sag(const void* eps_dev, int ld_eps, int B, int hw, float guidance, float sag_scale, float phi, float* factor_dev,
+                          void* stream);
+int ladi_op_sched_run_sag(int kind, int steps, const float* alphas_cumprod_host, float eta, const void* eps_seq_dev, int ld_eps, int evals, int B,
+                          int hw, int cfg, const float* guidance_tab_host, float sag_scale, float phi, float* latents_dev,
+                          const float* step_noise_dev, int noise_steps, void* stream);
 /* pipeline pre-processing kernels, one entry point per kernel so each can be checked on its own:
  * prepare_mask_and_masked_image (diffusers tensor branch; tryon_pipe.py:630): mask binarised at 0.5 -> mask_bin_dev fp16 [B,H,W];
  *   masked_image_dev NHWC fp16 [B,H,W,ld] (3 valid channels, the rest zero) = image * (mask < 0.5) */

@@ -270,6 +270,18 @@ SIGNATURES = {
                                       _P, _P, c_int, _P]),
     "ladi_op_cfg_stats_pag": (c_int, [_P, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P]),
     "ladi_op_pag_identity": (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_int, _P]),
+    "ladi_unet_set_sag_capture": (c_int, [_P, c_int]),
+    "ladi_unet_sag_tokens": (c_int, [_P, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "ladi_unet_sag_map": (c_int, [_P, _P, _P, c_int, c_int]),
+    "ladi_tryon_set_sag": (c_int, [_P, c_float]),
+    "ladi_tryon_graph_captures": (c_longlong, [_P]),
+    "ladi_tryon_plan_forms_sag": (c_int, [c_int, c_int, c_int, c_float, POINTER(c_float), c_int, c_float, POINTER(c_float), c_int,
+                                          POINTER(ctypes.c_ubyte), c_int, c_float, c_int, c_int, c_int, c_int, POINTER(ctypes.c_ubyte)]),
+    "ladi_op_sag_map": (c_int, [_P, c_int, c_longlong, _P, c_int, c_longlong, c_int, c_int, c_int, _P, _P, _P]),
+    "ladi_op_sag_degrade": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P, c_int, c_int, _P]),
+    "ladi_op_cfg_stats_sag": (c_int, [_P, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P]),
+    "ladi_op_sched_run_sag": (c_int, [c_int, c_int, _P, c_float, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_float, c_float,
+                                      _P, _P, c_int, _P]),
     "ladi_op_prepare_mask": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
     "ladi_op_mask_down": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "ladi_op_pose_down8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),

@@ -177,6 +177,30 @@ int ladi_unet_set_pag_layers(ladi_unet* u, unsigned layer_mask) {
     return 0;
 }
 unsigned ladi_unet_pag_layers(const ladi_unet* u) { return u ? u->u.pag_mask : 0u; }
+int ladi_unet_set_sag_capture(ladi_unet* u, int on) {
+    if (!u) { set_error("ladi_unet_set_sag_capture: null handle"); return -1; }
+    u->u.sag_capture = on != 0;
+    return 0;
+}
+int ladi_unet_sag_tokens(const ladi_unet* u, int h, int w, int* hm, int* wm) {
+    if (!u || !hm || !wm || h < 1 || w < 1) { set_error("ladi_unet_sag_tokens: null argument or an empty latent size"); return -1; }
+    UNet::sag_tokens(h, w, hm, wm);
+    return 0;
+}
+int ladi_unet_sag_map(ladi_unet* u, float* s_out, unsigned char* m_out, int n, int T) {
+    return guarded("ladi_unet_sag_map", [&]() {
+        if (!u || (!s_out && !m_out)) throw std::runtime_error("null handle or no output");
+        const UNet& U = u->u;
+        if (!U.sag_mem || U.sag_T < 1) throw std::runtime_error("no forward has captured a SAG map (ladi_unet_set_sag_capture, or a SAG run)");
+        if (T != U.sag_T || n < 1 || n > U.sag_cap_n)
+            throw std::runtime_error("asked for " + std::to_string(n) + " samples of " + std::to_string(T) + " tokens, the last capture has " +
+                                     std::to_string(U.sag_T) + " tokens and room for " + std::to_string(U.sag_cap_n) + " samples");
+        HIP_OK(hipDeviceSynchronize());
+        if (s_out) HIP_OK(hipMemcpy(s_out, U.sag_s, (size_t)n * T * sizeof(float), hipMemcpyDeviceToDevice));
+        if (m_out) HIP_OK(hipMemcpy(m_out, U.sag_m, (size_t)n * T, hipMemcpyDeviceToDevice));
+        return 0;
+    });
+}
 
 // ------------------------------------------------------------------------------------------------ token merging (runtime.h ToMe, tome.hip)
 static ToMeCfg tome_from(const ladi_tome_config& c) {
@@ -1065,6 +1089,30 @@ int ladi_tryon_plan_forms(int evals, int first_step, int steps, float guidance, 
         return evals;
     });
 }
+long long ladi_tryon_graph_captures(ladi_tryon* t) { return t ? t->t.graphs.captures : -1; }
+int ladi_tryon_set_sag(ladi_tryon* t, float sag_scale) {
+    if (!t || !std::isfinite(sag_scale) || sag_scale < 0.f) { set_error("ladi_tryon_set_sag: null handle, or a negative or non-finite scale"); return -1; }
+    t->t.sag_scale = sag_scale;
+    return 0;
+}
+int ladi_tryon_plan_forms_sag(int evals, int first_step, int steps, float guidance, const float* guidance_tab_host, int guidance_count, float phi,
+                              const float* pag_tab_host, int pag_count, const unsigned char* full_flags_host, int flag_count, float sag_scale,
+                              int scheduler, int lat_h, int lat_w, int tome_mid_merges, unsigned char* forms_out) {
+    if (evals < 1 || guidance_count < 0 || pag_count < 0 || flag_count < 0 || !forms_out || !std::isfinite(sag_scale) || sag_scale < 0.f) {
+        set_error("ladi_tryon_plan_forms_sag: evals < 1, a negative count, no output, or a negative or non-finite SAG scale");
+        return -1;
+    }
+    return guarded("ladi_tryon_plan_forms_sag", [&]() {
+        EvalPlan p;
+        const std::vector<float> g(guidance_tab_host, guidance_tab_host + (guidance_tab_host ? guidance_count : 0));
+        const std::vector<float> pag(pag_tab_host, pag_tab_host + (pag_tab_host ? pag_count : 0));
+        const std::vector<unsigned char> fc(full_flags_host, full_flags_host + (full_flags_host ? flag_count : 0));
+        SagPlan sp; sp.scale = sag_scale; sp.scheduler = scheduler; sp.h = lat_h; sp.w = lat_w; sp.mid_merges = tome_mid_merges != 0;
+        if (plan_evals(p, evals, first_step, steps, guidance, g, phi, pag, fc, &sp)) { set_error(p.error); return p.rc; }
+        std::memcpy(forms_out, p.form.data(), (size_t)evals);
+        return evals;
+    });
+}
 int ladi_tryon_set_feature_cache(ladi_tryon* t, const unsigned char* full_flags_host, int count, int branch) {
     if (!t || count < 0) { set_error("ladi_tryon_set_feature_cache: null handle or negative count"); return -1; }
     if (!full_flags_host || count == 0) { t->t.fc_plan.clear(); t->t.fc_branch = 0; return 0; }
@@ -1572,9 +1620,11 @@ int ladi_op_cfg_stats(const void* eps, int ld_eps, int B, int hw, float guidance
 static int sched_run_guided_any(const char* name, int kind, int steps, const float* ac_host, float eta, const void* eps_seq, int ld_eps, int evals,
                                 int B, int hw, const float* guidance_tab_host, float phi, float* latents, const float* step_noise, int noise_steps,
                                 const float* keep_x0, const float* keep_noise, const float* keep_mask, void* stream, int cfg = 1,
-                                const float* pag_tab_host = nullptr) {
+                                const float* pag_tab_host = nullptr, const float* sag_scale_host = nullptr) {
     return guarded(name, [&]() {
         hipStream_t st = S(stream);
+        if (sag_scale_host && pag_tab_host) throw std::runtime_error("a PAG table together with a SAG scale");
+        if (sag_scale_host && (!std::isfinite(*sag_scale_host) || *sag_scale_host < 0.f)) throw std::runtime_error("SAG scale negative or not finite");
         std::vector<float> ones;
         if (!cfg && !guidance_tab_host && evals > 0) { ones.assign((size_t)evals, 1.f); guidance_tab_host = ones.data(); }
         if (!eps_seq || !latents || !guidance_tab_host || evals <= 0 || B <= 0 || hw <= 0) throw std::runtime_error("null argument or empty shape");
@@ -1600,7 +1650,7 @@ static int sched_run_guided_any(const char* name, int kind, int steps, const flo
         std::vector<float> kt;
         if (keep_mask) build_keep_coeffs(kind, steps, ac.data(), 0, kt);
         const size_t kt_bytes = (kt.size() * sizeof(float) + 255) & ~(size_t)255;
-        const size_t pt_bytes = pag_tab_host ? gt_bytes : 0;
+        const size_t pt_bytes = pag_tab_host ? gt_bytes : sag_scale_host ? 256 : 0;
         HIP_OK(hipMalloc(reinterpret_cast<void**>(&buf), tb_bytes + 256 + gt_bytes + fc_bytes + kt_bytes + 5 * plane + pt_bytes));
         StepTable* dt = reinterpret_cast<StepTable*>(buf);
         int* dstep = reinterpret_cast<int*>(buf + tb_bytes);
@@ -1610,23 +1660,26 @@ static int sched_run_guided_any(const char* name, int kind, int steps, const flo
         float* cur = reinterpret_cast<float*>(buf + tb_bytes + 256 + gt_bytes + fc_bytes + kt_bytes);
         float* ets = cur + (size_t)B * hw * 4;
         float* dpt = pag_tab_host ? ets + (size_t)4 * B * hw * 4 : nullptr;
+        float* dsg = sag_scale_host ? ets + (size_t)4 * B * hw * 4 : nullptr;     // the SAG scale's device word, where a PAG table would stand
         int rc = 0;
         try {
             if (dpt) HIP_OK(hipMemcpyAsync(dpt, pag_tab_host, (size_t)evals * sizeof(float), hipMemcpyHostToDevice, st));
+            if (dsg) HIP_OK(hipMemcpyAsync(dsg, sag_scale_host, sizeof(float), hipMemcpyHostToDevice, st));
             if (keep_mask) HIP_OK(hipMemcpyAsync(dkt, kt.data(), kt.size() * sizeof(float), hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(dt, tb.data(), tb.size() * sizeof(StepTable), hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(dgt, guidance_tab_host, (size_t)evals * sizeof(float), hipMemcpyHostToDevice, st));
             HIP_OK(hipMemsetAsync(dstep, 0, 8, st));       // evaluation index + the step kernel's arrival ticket
-            const size_t per_eval = (size_t)((cfg ? 2 : 1) + (dpt ? 1 : 0)) * B * hw * ld_eps;
+            const size_t per_eval = (size_t)((cfg ? 2 : 1) + (dpt || dsg ? 1 : 0)) * B * hw * ld_eps;
             for (int i = 0; i < evals && !rc; ++i) {
                 StepArgs sa; std::memset(&sa, 0, sizeof(sa));
                 sa.eps = reinterpret_cast<const h16*>(eps_seq) + (size_t)i * per_eval; sa.ld_eps = ld_eps;
                 sa.B = B; sa.hw = hw; sa.cfg = cfg ? 1 : 0; sa.latents = latents; sa.cur_sample = cur; sa.ets = ets;
                 sa.table = dt; sa.step_idx = dstep; sa.unet_in = nullptr; sa.step_noise = step_noise;
-                sa.guidance_tab = dgt; sa.factor = (cfg && phi > 0.f) ? dfc : nullptr; sa.pag_tab = dpt;
+                sa.guidance_tab = dgt; sa.factor = (cfg && phi > 0.f) ? dfc : nullptr; sa.pag_tab = dpt; sa.sag_scale = dsg;
                 if (keep_mask) { sa.keep_x0 = keep_x0; sa.keep_noise = keep_noise; sa.keep_mask = keep_mask; sa.keep_tab = dkt; }
                 if (cfg && phi > 0.f && guidance_tab_host[i] > 1.0f)
-                    rc = dpt ? ladi_launch_cfg_stats_pag(sa.eps, ld_eps, B, hw, dgt, dstep, 0.f, dpt, 0.f, phi, dfc, st)
+                    rc = dsg ? ladi_launch_cfg_stats_sag(sa.eps, ld_eps, B, hw, dgt, dstep, 0.f, dsg, 0.f, phi, dfc, st)
+                       : dpt ? ladi_launch_cfg_stats_pag(sa.eps, ld_eps, B, hw, dgt, dstep, 0.f, dpt, 0.f, phi, dfc, st)
                              : ladi_launch_cfg_stats(sa.eps, ld_eps, B, hw, dgt, dstep, 0.f, phi, dfc, st);
                 if (!rc) rc = ladi_launch_sched_step(sa, st);
             }
@@ -1656,6 +1709,62 @@ int ladi_op_cfg_stats_pag(const void* eps, int ld_eps, int B, int hw, float guid
         if (!std::isfinite(pag_scale) || pag_scale < 0.f) throw std::runtime_error("PAG scale negative or not finite");
         return ladi_launch_cfg_stats_pag(reinterpret_cast<const h16*>(eps), ld_eps, B, hw, nullptr, nullptr, guidance, nullptr, pag_scale, phi, factor,
                                          S(stream));
+    });
+}
+int ladi_op_sched_run_sag(int kind, int steps, const float* ac_host, float eta, const void* eps_seq, int ld_eps, int evals, int B, int hw, int cfg,
+                          const float* guidance_tab_host, float sag_scale, float phi, float* latents, const float* step_noise, int noise_steps,
+                          void* stream) {
+    return sched_run_guided_any("ladi_op_sched_run_sag", kind, steps, ac_host, eta, eps_seq, ld_eps, evals, B, hw, guidance_tab_host, phi, latents,
+                                step_noise, noise_steps, nullptr, nullptr, nullptr, stream, cfg ? 1 : 0, nullptr, &sag_scale);
+}
+int ladi_op_cfg_stats_sag(const void* eps, int ld_eps, int B, int hw, float guidance, float sag_scale, float phi, float* factor, void* stream) {
+    return guarded("ladi_op_cfg_stats_sag", [&]() {
+        if (!eps || !factor || B <= 0 || hw <= 0) throw std::runtime_error("null argument or empty shape");
+        if (ld_eps < 4 || (ld_eps & 3) || ((uintptr_t)eps & 7)) throw std::runtime_error("ld_eps must be a multiple of 4 (>= 4) and eps 8-byte aligned");
+        if (!(phi >= 0.f && phi <= 1.f)) throw std::runtime_error("phi outside [0, 1]");
+        if (!std::isfinite(sag_scale) || sag_scale < 0.f) throw std::runtime_error("SAG scale negative or not finite");
+        return ladi_launch_cfg_stats_sag(reinterpret_cast<const h16*>(eps), ld_eps, B, hw, nullptr, nullptr, guidance, nullptr, sag_scale, phi, factor,
+                                         S(stream));
+    });
+}
+int ladi_op_sag_map(const void* q, int ldq, long long sq, const void* k, int ldk, long long sk, int n, int T, int heads, float* s_out,
+                    unsigned char* m_out, void* stream) {
+    return guarded("ladi_op_sag_map", [&]() {
+        if (!q || !k || !s_out || !m_out) throw std::runtime_error("null argument");
+        if (n < 1 || T < 1 || heads < 1) throw std::runtime_error("n, T and heads have to be >= 1");
+        if (ldq < heads * 64 || ldk < heads * 64 || (ldq & 7) || (ldk & 7) || (sq & 7) || (sk & 7) || ((uintptr_t)q & 15) || ((uintptr_t)k & 15))
+            throw std::runtime_error("every stride has to be a multiple of 8, the row strides >= 64 * heads, both bases 16-byte aligned");
+        hipStream_t st = S(stream);
+        float* part = nullptr;
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&part), (size_t)ladi_sag_partial_floats(n, T, heads) * sizeof(float)));
+        const int rc = ladi_launch_sag_map(reinterpret_cast<const h16*>(q), ldq, sq, reinterpret_cast<const h16*>(k), ldk, sk, n, T, heads, part, s_out,
+                                           m_out, st);
+        const hipError_t e = hipStreamSynchronize(st);
+        (void)hipFree(part);
+        if (rc) throw std::runtime_error("launch refused or failed (rc = " + std::to_string(rc) + ")");
+        HIP_OK(e);
+        return 0;
+    });
+}
+int ladi_op_sag_degrade(const float* latents, const void* eps, int ld_eps, const unsigned char* mask, int B, int h, int w, int hm, int wm,
+                        float sqrt_a, float sqrt_1ma, float in_scale, const void* src_rows, void* dst_rows, int ld_in, int copy_end, void* stream) {
+    return guarded("ladi_op_sag_degrade", [&]() {
+        if (!latents || !eps || !mask || !dst_rows) throw std::runtime_error("null argument");
+        if (B < 1 || hm < 1 || wm < 1) throw std::runtime_error("B, hm and wm have to be >= 1");
+        if (h < 5 || w < 5) throw std::runtime_error("latents of " + std::to_string(h) + " x " + std::to_string(w) + " are under 5 x 5 (the blur's reflect padding)");
+        if (!(sqrt_a > 0.f) || !std::isfinite(sqrt_a) || !std::isfinite(sqrt_1ma) || !std::isfinite(in_scale)) throw std::runtime_error("sqrt(a) has to be positive and every coefficient finite");
+        hipStream_t st = S(stream);
+        float* tab = nullptr;
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&tab), 256));
+        const float row[4] = {sqrt_a, sqrt_1ma, in_scale, 0.f};
+        int rc = hipMemcpyAsync(tab, row, sizeof(row), hipMemcpyHostToDevice, st) == hipSuccess ? 0 : -100;
+        if (!rc) rc = ladi_launch_sag_degrade(latents, reinterpret_cast<const h16*>(eps), ld_eps, mask, B, h, w, hm, wm, tab, nullptr,
+                                              reinterpret_cast<const h16*>(src_rows), reinterpret_cast<h16*>(dst_rows), ld_in, copy_end, st);
+        const hipError_t e = hipStreamSynchronize(st);
+        (void)hipFree(tab);
+        if (rc) throw std::runtime_error("launch refused or failed (rc = " + std::to_string(rc) + ")");
+        HIP_OK(e);
+        return 0;
     });
 }
 int ladi_op_sched_run_keep(int kind, int steps, const float* ac_host, float eta, const void* eps_seq, int ld_eps, int evals, int B, int hw,

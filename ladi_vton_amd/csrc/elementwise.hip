@@ -137,6 +137,8 @@ __device__ __forceinline__ void sched_step_body(const StepArgs& a, const int idx
     // perturbed-attention guidance: this evaluation's scale (0 = none) and the perturbed group's row, behind the cond group's
     const float ps = a.pag_tab ? a.pag_tab[step] : 0.f;
     const size_t row_p = (size_t)idx + (size_t)(a.cfg ? 2 : 1) * (size_t)total;
+    // self-attention guidance: the scale (0 = none) and, in the same rows behind the last group, the prediction of the degraded input
+    const float ss = a.sag_scale ? a.sag_scale[0] : 0.f;
     if (a.cfg && a.guidance_tab && !(g > 1.0f)) {
         const h16x4 ec = *reinterpret_cast<const h16x4*>(a.eps + row_c * a.ld_eps);
 #pragma unroll
@@ -145,6 +147,11 @@ __device__ __forceinline__ void sched_step_body(const StepArgs& a, const int idx
             const h16x4 ep = *reinterpret_cast<const h16x4*>(a.eps + row_p * a.ld_eps);
 #pragma unroll
             for (int c = 0; c < 4; ++c) e[c] += ps * ((float)ec[c] - (float)ep[c]);
+        }
+        if (ss != 0.f) {         // c + s (c - d)
+            const h16x4 ed = *reinterpret_cast<const h16x4*>(a.eps + row_p * a.ld_eps);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) e[c] += ss * ((float)ec[c] - (float)ed[c]);
         }
     } else {
         const h16x4 eu = *reinterpret_cast<const h16x4*>(a.eps + row_u * a.ld_eps);
@@ -156,6 +163,11 @@ __device__ __forceinline__ void sched_step_body(const StepArgs& a, const int idx
                 const h16x4 ep = *reinterpret_cast<const h16x4*>(a.eps + row_p * a.ld_eps);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) e[c] += ps * ((float)ec[c] - (float)ep[c]);
+            }
+            if (ss != 0.f) {     // u + g (c - u) + s (u - d): the base is the uncond prediction
+                const h16x4 ed = *reinterpret_cast<const h16x4*>(a.eps + row_p * a.ld_eps);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) e[c] += ss * ((float)eu[c] - (float)ed[c]);
             }
             if (a.factor) {      // guidance rescale: the per-sample factor cfg_stats_kernel wrote for this evaluation
                 const float f = a.factor[b];
@@ -169,6 +181,11 @@ __device__ __forceinline__ void sched_step_body(const StepArgs& a, const int idx
                 const h16x4 ep = *reinterpret_cast<const h16x4*>(a.eps + row_p * a.ld_eps);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) e[c] += ps * ((float)eu[c] - (float)ep[c]);
+            }
+            if (ss != 0.f) {     // no CFG: c + s (c - d)
+                const h16x4 ed = *reinterpret_cast<const h16x4*>(a.eps + row_p * a.ld_eps);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) e[c] += ss * ((float)eu[c] - (float)ed[c]);
             }
         }
     }
@@ -273,7 +290,9 @@ __device__ __forceinline__ void block_sum2(float& x, float& y, float (*red)[4]) 
 }
 // PAG: the instantiation with the perturbed rows [2B, 3B) and a scale s (table entry or scalar); where s > 0 the guided prediction gains
 // s (c - p), where it is 0 those rows are not read.  The instantiation without is the kernel as it was
-template <bool PAG>
+// SAG (MODE 2): the rows [2B, 3B) hold the prediction d of the degraded input, s is one device float (or the scalar) and the term is
+// s (u - d); s = 0 reads nothing more
+template <int MODE>
 __global__ __launch_bounds__(256) void cfg_stats_kernel(const h16* __restrict__ eps, int ld_eps, int B, int hw,
                                                         const float* __restrict__ guidance_tab, const int* __restrict__ step_idx,
                                                         float guidance, const float* __restrict__ pag_tab, float pag_scale, float phi,
@@ -284,8 +303,8 @@ __global__ __launch_bounds__(256) void cfg_stats_kernel(const h16* __restrict__ 
     const h16* pu = eps + (size_t)b * hw * ld_eps;               // uncond rows of sample b
     const h16* pc = eps + ((size_t)B + b) * hw * ld_eps;         // cond rows
     const h16* pp = eps + ((size_t)2 * B + b) * hw * ld_eps;     // perturbed rows (PAG)
-    const float s = PAG ? (pag_tab ? pag_tab[*step_idx] : pag_scale) : 0.f;
-    const bool has_p = PAG && s > 0.f;
+    const float s = MODE == 1 ? (pag_tab ? pag_tab[*step_idx] : pag_scale) : MODE == 2 ? (pag_tab ? pag_tab[0] : pag_scale) : 0.f;
+    const bool has_p = MODE == 1 ? s > 0.f : MODE == 2 ? s != 0.f : false;
     float sc = 0.f, sg = 0.f;
     for (int p = threadIdx.x; p < hw; p += 256) {
         const h16x4 eu = *reinterpret_cast<const h16x4*>(pu + (size_t)p * ld_eps);
@@ -295,7 +314,7 @@ __global__ __launch_bounds__(256) void cfg_stats_kernel(const h16* __restrict__ 
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const float u = (float)eu[c], cv = (float)ec[c];
-                float gv = u + g * (cv - u); gv += s * (cv - (float)ep[c]);
+                float gv = u + g * (cv - u); gv += s * ((MODE == 2 ? u : cv) - (float)ep[c]);
                 sc += cv; sg += gv;
             }
         } else {
@@ -315,7 +334,7 @@ __global__ __launch_bounds__(256) void cfg_stats_kernel(const h16* __restrict__ 
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const float u = (float)eu[c], cv = (float)ec[c];
-                float gv = u + g * (cv - u); gv += s * (cv - (float)ep[c]);
+                float gv = u + g * (cv - u); gv += s * ((MODE == 2 ? u : cv) - (float)ep[c]);
                 const float dc = cv - mc, dg = gv - mg;
                 qc += dc * dc; qg += dg * dg;
             }
@@ -591,7 +610,7 @@ int ladi_launch_sched_step(const StepArgs& a, hipStream_t st) {
 int ladi_launch_cfg_stats(const h16* eps, int ld_eps, int B, int hw, const float* guidance_tab, const int* step_idx, float guidance,
                           float phi, float* factor, hipStream_t st) {
     if (B <= 0 || hw <= 0 || ld_eps < 4 || (ld_eps & 3) || ((uintptr_t)eps & 7) || (guidance_tab && !step_idx)) return -1;
-    hipLaunchKernelGGL(cfg_stats_kernel<false>, dim3(B), dim3(256), 0, st, eps, ld_eps, B, hw, guidance_tab, step_idx, guidance, nullptr, 0.f, phi,
+    hipLaunchKernelGGL(cfg_stats_kernel<0>, dim3(B), dim3(256), 0, st, eps, ld_eps, B, hw, guidance_tab, step_idx, guidance, nullptr, 0.f, phi,
                        factor);
     return ok();
 }
@@ -601,8 +620,17 @@ int ladi_launch_cfg_stats_pag(const h16* eps, int ld_eps, int B, int hw, const f
     if (!pag_tab && pag_scale == 0.f) return ladi_launch_cfg_stats(eps, ld_eps, B, hw, guidance_tab, step_idx, guidance, phi, factor, st);
     if (B <= 0 || hw <= 0 || ld_eps < 4 || (ld_eps & 3) || ((uintptr_t)eps & 7) || ((guidance_tab || pag_tab) && !step_idx) ||
         !(pag_scale >= 0.f)) return -1;
-    hipLaunchKernelGGL(cfg_stats_kernel<true>, dim3(B), dim3(256), 0, st, eps, ld_eps, B, hw, guidance_tab, step_idx, guidance, pag_tab,
+    hipLaunchKernelGGL(cfg_stats_kernel<1>, dim3(B), dim3(256), 0, st, eps, ld_eps, B, hw, guidance_tab, step_idx, guidance, pag_tab,
                        pag_scale, phi, factor);
+    return ok();
+}
+
+int ladi_launch_cfg_stats_sag(const h16* eps, int ld_eps, int B, int hw, const float* guidance_tab, const int* step_idx, float guidance,
+                              const float* sag_dev, float sag_scale, float phi, float* factor, hipStream_t st) {
+    if (!sag_dev && sag_scale == 0.f) return ladi_launch_cfg_stats(eps, ld_eps, B, hw, guidance_tab, step_idx, guidance, phi, factor, st);
+    if (B <= 0 || hw <= 0 || ld_eps < 4 || (ld_eps & 3) || ((uintptr_t)eps & 7) || (guidance_tab && !step_idx) || sag_scale != sag_scale) return -1;
+    hipLaunchKernelGGL(cfg_stats_kernel<2>, dim3(B), dim3(256), 0, st, eps, ld_eps, B, hw, guidance_tab, step_idx, guidance, sag_dev,
+                       sag_scale, phi, factor);
     return ok();
 }
 

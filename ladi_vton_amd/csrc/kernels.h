@@ -171,6 +171,11 @@ struct StepArgs {
     // and p only).  `factor` multiplies the three-term sum.  With a table, eps and unet_in have the third group's rows whatever s is: the
     // refresh of unet_in (and the cloth zeroing) writes them too; an evaluation with s = 0 never reads the third group of eps
     const float* pag_tab;
+    // self-attention guidance (null = the code path above, bit for bit; never together with pag_tab).  sag_scale: ONE device fp32, read by
+    // every evaluation.  With s = *sag_scale != 0 the prediction d of the degraded input stands in the rows behind the last group,
+    // [(cfg ? 2 : 1) * B, ..+B) of eps, and the combine gains s (b - d) with b the base prediction: u in a CFG evaluation, c without CFG or
+    // in a cond-only evaluation.  `factor` multiplies the whole sum.  s = 0 never reads those rows
+    const float* sag_scale;
 };
 int ladi_launch_sched_step(const StepArgs& a, hipStream_t st);
 // guidance rescale statistics of one evaluation: eps as in StepArgs with cfg = 1 (rows [0,B) uncond, [B,2B) cond, row stride ld_eps halves, a
@@ -184,6 +189,10 @@ int ladi_launch_cfg_stats(const h16* eps, int ld_eps, int B, int hw, const float
 // ladi_launch_cfg_stats' bit for bit.  Same two passes, same fixed-order sums
 int ladi_launch_cfg_stats_pag(const h16* eps, int ld_eps, int B, int hw, const float* guidance_tab, const int* step_idx, float guidance,
                               const float* pag_tab, float pag_scale, float phi, float* factor, hipStream_t st);
+// the same with self-attention guidance: s = *sag_dev (device) or, with a null pointer, sag_scale; with s != 0 the guided prediction is
+// u + g (c - u) + s (u - d), d the rows [2B, 3B) of eps; with s = 0 those rows are not read and the result is ladi_launch_cfg_stats' bit for bit
+int ladi_launch_cfg_stats_sag(const h16* eps, int ld_eps, int B, int hw, const float* guidance_tab, const int* step_idx, float guidance,
+                              const float* sag_dev, float sag_scale, float phi, float* factor, hipStream_t st);
 
 // static part of the 31-channel UNet input: mask, masked-image latents, pose, cloth; uncond half zero pose/cloth
 int ladi_launch_assemble_static(h16* unet_in, int ld_in, int B, int hw, int cfg, const float* latents, const h16* mask_lat,
@@ -274,6 +283,23 @@ int ladi_launch_freeu(h16* hidden, int ld_h, int C_h, float b, const h16* skip, 
 // rows < 1; -2: C < 8 or C % 8; -3: a row stride below C or not a multiple of 8, or a base that is not 16-byte aligned.  Nothing is launched
 // on a refusal
 int ladi_launch_pag_identity(const h16* v, int ldv, h16* o, int ldo, long long rows, int C, hipStream_t st);
+
+// ---- sag.hip: self-attention guidance (StableDiffusionSAGPipeline).
+// sag_map: q, k fp16 in the layout flash_attn64 reads (sample s, token t, head h at base + s * sq + t * ldq + h * 64; strides in halves,
+// multiples of 8, bases 16-byte aligned), head dimension 64, any T >= 1 and any head count.  Writes s_out fp32 [n][T],
+// s[j] = (sum_h sum_i softmax_j(q_i . k_j / 8)) / heads, and m_out [n][T] bytes, m = s > 1.  partial: scratch of ladi_sag_partial_floats(n, T,
+// heads) floats.  fp32 accumulation, two launches, fixed-order sums: bit-reproducible.  -1: null / empty; -3: strides or alignment
+long long ladi_sag_partial_floats(int n, int T, int heads);
+int ladi_launch_sag_map(const h16* q, int ldq, long long sq, const h16* k, int ldk, long long sk, int n, int T, int heads, float* partial,
+                        float* s_out, unsigned char* m_out, hipStream_t st);
+// sag_degrade: latents fp32 [B][h * w][4] (the loop's), eps the base prediction's rows fp16 [B][h * w][ld_eps] (channels 0..3), mask bytes
+// [B][hm][wm] (sag_map's m of the same samples), tab device fp32 [evals][4] = {sqrt(a), sqrt(1 - a), model-input scale, 0} read at row
+// *step_idx (null: row 0).  Writes fp16(in_scale * xd) to channels 0..3 of dst_rows [B][h * w][ld_in], xd = sqrt(a) x0d + sqrt(1 - a) b,
+// x0 = (x - sqrt(1 - a) b) / sqrt(a), x0d = blur9(x0) where the nearest-upsampled mask is 1 (9 x 9, sigma 1, reflect padding 4) and x0
+// elsewhere.  src_rows non-null and != dst_rows: channels [4, copy_end) of src_rows are copied to dst_rows too (copy_end a multiple of 4,
+// <= ld_in); otherwise nothing but channels 0..3 is written.  -2: a latent side under 5; -3: strides or alignment
+int ladi_launch_sag_degrade(const float* latents, const h16* eps, int ld_eps, const unsigned char* mask, int B, int h, int w, int hm, int wm,
+                            const float* tab, const int* step_idx, const h16* src_rows, h16* dst_rows, int ld_in, int copy_end, hipStream_t st);
 
 // ---- ip_adapter.hip: the image-prompt term of a cross-attention (IP-Adapter), accumulated in place into the attention output:
 //   o[s][t][h*64 + d] = fp16(float(o[..]) + scale * sum_j softmax_j(0.125 <q[s][t][h*64 ..], k[s][j][h*64 ..]>) v[s][j][h*64 + d]),  j < N

@@ -241,8 +241,9 @@ enum { PAG_NONE = 0x7fffffff };
 // fc: deep-feature cache mode of this forward (FeatCache); null or mode NONE launches exactly the plain forward
 // pag_first: samples whose index in the context batch (the numbering of sample0) is >= pag_first are perturbed; a forward's own count of
 // leading unperturbed samples is clamp(pag_first - sample0, 0, n), every lane clamps it to its own samples.  Arena use does not depend on it
+// sag: capture the SAG map in this forward (UNet::sag_capture): -1 = the UNet's sticky flag, 0 = no, 1 = yes
 struct FwdOpt {
-    const Act* eps_out = nullptr; int sample0 = 0; const FeatCache* fc = nullptr; int pag_first = PAG_NONE;
+    const Act* eps_out = nullptr; int sample0 = 0; const FeatCache* fc = nullptr; int pag_first = PAG_NONE; int sag = -1;
 };
 
 // Token merging (tomesd.apply_patch; ladi_unet_set_token_merging, sticky, off by default; tome.hip, DESIGN.md "Token merging").  In the
@@ -337,6 +338,20 @@ struct UNet {
     void tome_set(const ToMeCfg* c);                          // throws on a refused configuration, nothing changed; null / ratio 0: off
     std::vector<int> tome_blocks() const;
     const ToMeLevel* tome_prepare(int level, int h, int w, int need_n, bool dry);
+    // self-attention guidance map (sag.hip; ladi_unet_set_sag_capture, sticky, off by default; DESIGN.md "Self-attention guidance").  A
+    // capturing forward runs sag_map in mid_block.attentions.0's transformer block right after its attn1 Q / K projection and leaves
+    // s fp32 [sample][T] and m bytes [sample][T] in sag_s / sag_m, at the rows of the forward's own samples in the context batch (sample0),
+    // so lanes and sub-batch forwards share the buffers.  The buffers are grown by a planning pass only (sag_prepare, as tome_prepare) and
+    // sag_gen counts the regrowths; with capture off nothing is allocated or launched.  sag_T: the token count of the last capture
+    bool sag_capture = false;
+    float* sag_s = nullptr; unsigned char* sag_m = nullptr; void* sag_mem = nullptr; int sag_T = 0, sag_cap_n = 0, sag_cap_T = 0;
+    void sag_prepare(int T, int need_n, bool dry);
+    // the mid block's map size for h x w latents: three stride-2 convolutions with padding 1, each ceil(x / 2)
+    static void sag_tokens(int h, int w, int* hm, int* wm) {
+        for (int i = 0; i < 3; ++i) { h = (h + 1) / 2; w = (w + 1) / 2; }
+        *hm = h; *wm = w;
+    }
+    int mid_bit = 0;                                          // xf index of mid_block.attentions.0
     DevPool pool;
     DConv conv_in, conv_out, time_l1, time_l2, temb_all;
     DNorm norm_out;
@@ -372,8 +387,10 @@ struct UNet {
         unsigned pag_mask;
         int ip_on, ip_N; const void* ip_kv; unsigned ip_scale[32];     // tokens per sample, the image K/V, every block's scale by its bits
         int tome_on; int tome_opts[8]; unsigned long long tome_ratio, tome_gen;   // every configuration field and the generation of the level state
+        int sag_on; const void* sag_buf;            // a forward of the graph captures the SAG map, into this buffer
     };
-    void key(Key& k, bool perturbed) const;
+    // sag: -1 = the sticky flag decides (stand-alone forwards), else whether the owner's forwards capture the map (FwdOpt::sag)
+    void key(Key& k, bool perturbed, int sag = -1) const;
     int fc_channels(int branch) const { return cfg.boc[branch >= cfg.layers_per_block ? 1 : 0]; }   // channels of the cached tensor
     // cache of the stand-alone entry ladi_unet_forward_cached: grow-only buffer over the context batch, the geometry it was captured at and
     // which sample rows hold a capture made since the last set_context
@@ -600,6 +617,14 @@ struct TryOnInputs {
 };
 enum { TRYON_PAG_WITH_CACHE = -12 };  // TryOn::run: a PAG table with a positive entry together with a feature-cache plan (LADI_TRYON_PAG_WITH_FEATURE_CACHE)
 enum { TRYON_IP_NO_ADAPTER = -13 };   // TryOn::run: image embeddings are set but the UNet has no IP-Adapter loaded (LADI_TRYON_IP_NO_ADAPTER)
+// TryOn::run with self-attention guidance on (ladi_tryon_set_sag), refused before anything is launched (LADI_TRYON_SAG_*):
+enum {
+    TRYON_SAG_WITH_CACHE = -14,    // together with a feature-cache plan: shallow evaluations do not run the mid block
+    TRYON_SAG_WITH_PAG = -15,      // together with a positive PAG scale
+    TRYON_SAG_TOME_MID = -16,      // token merging configured so that the mid block merges
+    TRYON_SAG_SCHEDULER = -17,     // a sigma-space scheduler (Euler, Euler-ancestral, LMS)
+    TRYON_SAG_SMALL = -18          // latents under 5 x 5 (the blur's reflect padding)
+};
 enum { TRYON_CALLBACK_ABORT = -8 };   // TryOn::run: the step callback returned non-zero (LADI_TRYON_CALLBACK_ABORTED, include/ladi_native.h)
 // The forms of one evaluation of the fused loop: bit 0 cond-only, bit 1 shallow (feature cache), bit 2 PAG (never together with bit 1), so
 // 0 .. 5.  The form is the index of GraphTable and of EvalPlan::has_form.
@@ -608,6 +633,7 @@ enum { TRYON_CALLBACK_ABORT = -8 };   // TryOn::run: the step callback returned 
 struct GraphTable {
     static constexpr int N = 6;
     hipGraph_t g[N] = {}; hipGraphExec_t e[N] = {};
+    long long captures = 0;  // captures made over the owner's life (ladi_tryon_graph_captures): a run that replays what it has adds none
     void clear();            // destroy every graph and executable (the owner's destructor; a changed GraphKey)
     // capture fn's launches on st into slot f and instantiate them; a throw of fn ends the capture and is passed on.  A graph left in the slot
     // by a capture whose instantiation failed is destroyed first
@@ -637,6 +663,9 @@ struct GraphKey {
     // ... and with PAG: whether the run has the third group and its scale table; a graph captured with PAG is never replayed without it,
     // nor the reverse
     int pag_on; const void* pag_tab;
+    // ... and with SAG: whether every evaluation has the degrade launch and the second forward, the device scale and the alpha table.  The
+    // scale's VALUE is not part of the key: the graphs read it from device memory
+    int sag_on; const void *sag_scale, *sag_tab;
 };
 // The per-evaluation plan of one run: host arithmetic only (plan_evals; ladi_tryon_plan_forms runs it without a GPU)
 struct EvalPlan {
@@ -649,11 +678,15 @@ struct EvalPlan {
     std::vector<float> gtab;   // scale of every evaluation
     std::vector<unsigned char> form;   // form of every evaluation, after the feature cache's one promotion
     bool has_form[GraphTable::N] = {};
-    int rc = 0; std::string error;     // a refusal: -9 (guidance / PAG table length), -10 (feature-cache plan), TRYON_PAG_WITH_CACHE
+    bool sag_on = false;       // SAG run: EVERY evaluation degrades and runs a second forward over B samples; the forms are the plain run's
+    int rc = 0; std::string error;     // a refusal: -9 (guidance / PAG table length), -10 (feature-cache plan), TRYON_PAG_WITH_CACHE, TRYON_SAG_*
 };
+// What plan_evals needs to know of a run with self-attention guidance (scale != 0 = on): the scheduler code, the latent size and whether the
+// UNet's token merging merges in the mid block
+struct SagPlan { float scale = 0.f; int scheduler = 0, h = 0, w = 0; bool mid_merges = false; };
 // first_step / steps: for the message of a length refusal only.  Returns p.rc
 int plan_evals(EvalPlan& p, int evals, int first_step, int steps, float guidance, const std::vector<float>& g_sched, float phi,
-               const std::vector<float>& pag_sched, const std::vector<unsigned char>& fc_plan);
+               const std::vector<float>& pag_sched, const std::vector<unsigned char>& fc_plan, const SagPlan* sag = nullptr);
 
 struct TryOn {
     UNet* unet = nullptr; VAE* vae = nullptr; EMASC* emasc = nullptr;
@@ -695,6 +728,12 @@ struct TryOn {
     // with a scale > 0 runs the forward over the perturbed group too (form bit 2; never together with the feature cache, which run() refuses)
     std::vector<float> pag_sched;
     float* d_pag = nullptr; int pag_cap = 0;
+    // self-attention guidance (ladi_tryon_set_sag, sticky; 0 = off: nothing below is allocated or launched).  On: unet_in and eps grow by
+    // one group of B rows behind the last (the context does not), and every evaluation is first forward (capturing the SAG map) ->
+    // sag_degrade into those rows -> second forward over them with the base group's context rows -> combine + step.  The scale lives in the
+    // device word d_sag (uploaded per run: another value replays the same graphs); d_sag_tab holds {sqrt(a), sqrt(1 - a), 1, 0} per evaluation
+    float sag_scale = 0.f;
+    float* d_sag = nullptr; float* d_sag_tab = nullptr; int sag_tab_cap = 0;
     // image prompt (ladi_tryon_set_ip_adapter, sticky; ip_pos null = off: the run clears the UNet's image context and launches the plain
     // run).  The caller's fp16 [B][E] embeddings (ip_neg null: zeros, diffusers' zeros_like) are assembled per run into the runtime-owned
     // ip_buf [groups * B][E] -- [neg ; pos], [neg ; pos ; pos] with PAG, [pos] without CFG -- on the run's stream, next to the prompt

@@ -24,6 +24,7 @@ void GraphTable::capture(int f, hipStream_t st, const std::function<void()>& fn)
     try { fn(); } catch (...) { hipGraph_t x = nullptr; (void)hipStreamEndCapture(st, &x); if (x) (void)hipGraphDestroy(x); throw; }
     HIP_OK(hipStreamEndCapture(st, &gr));
     HIP_OK(hipGraphInstantiate(&ge, gr, nullptr, nullptr, 0));
+    ++captures;
 }
 
 TryOn::~TryOn() {
@@ -64,8 +65,9 @@ static int wrong_length(EvalPlan& p, int rc, const char* what, size_t have, int 
 }
 
 int plan_evals(EvalPlan& p, int evals, int first_step, int steps, float guidance, const std::vector<float>& g_sched, float phi,
-               const std::vector<float>& pag_sched, const std::vector<unsigned char>& fc_plan) {
+               const std::vector<float>& pag_sched, const std::vector<unsigned char>& fc_plan, const SagPlan* sag) {
     p = EvalPlan();
+    p.sag_on = sag && sag->scale != 0.f;
     const bool has_sched = !g_sched.empty();
     p.cfg = cfg_shaped(guidance, g_sched);
     p.guided = p.cfg && (has_sched || phi > 0.f);
@@ -78,6 +80,27 @@ int plan_evals(EvalPlan& p, int evals, int first_step, int steps, float guidance
     if (p.pag_on && !fc_plan.empty())
         return refuse(p, TRYON_PAG_WITH_CACHE, "tryon: perturbed-attention guidance together with a feature-cache plan is not supported (the cache's "
                       "group promotion has no third group): clear one of ladi_tryon_set_pag / ladi_tryon_set_feature_cache");
+    // self-attention guidance: what it cannot run with.  A feature-cache plan counts whatever its flags say (as for PAG)
+    if (p.sag_on) {
+        const char* off = ": set ladi_tryon_set_sag(t, 0) or ";
+        if (!fc_plan.empty())
+            return refuse(p, TRYON_SAG_WITH_CACHE, std::string("tryon: self-attention guidance together with a feature-cache plan is not supported (a shallow "
+                          "evaluation does not run the mid block, whose attention map SAG reads)") + off + "clear ladi_tryon_set_feature_cache");
+        if (p.pag_on)
+            return refuse(p, TRYON_SAG_WITH_PAG, std::string("tryon: self-attention guidance together with a positive PAG scale is not supported (both "
+                          "claim the sample group behind the conditional one)") + off + "clear ladi_tryon_set_pag");
+        if (sag->mid_merges)
+            return refuse(p, TRYON_SAG_TOME_MID, std::string("tryon: self-attention guidance with token merging in the mid block is not supported (the "
+                          "map would have merged tokens)") + off + "merge on the outer levels only");
+        const int kind = decode_sched_code(sag->scheduler).kind;
+        if (kind == SCHED_LMS || kind == SCHED_EULER || kind == SCHED_EULER_A)
+            return refuse(p, TRYON_SAG_SCHEDULER, std::string("tryon: self-attention guidance does not run with the sigma-space schedulers (Euler, "
+                          "Euler-ancestral, LMS: their model input is rescaled, and pred_x0 / add_noise do not describe them)") + off +
+                          "use DDIM, PNDM, DPM-Solver++, LCM or TCD");
+        if (sag->h < 5 || sag->w < 5)
+            return refuse(p, TRYON_SAG_SMALL, "tryon: self-attention guidance needs latents of at least 5 x 5 (the blur's 4-pixel reflect padding), got " +
+                          std::to_string(sag->h) + " x " + std::to_string(sag->w) + off + "run a larger image");
+    }
     if (!fc_plan.empty()) {
         if ((int)fc_plan.size() != evals) return wrong_length(p, -10, "feature-cache plan", fc_plan.size(), evals, first_step, steps);
         if (!fc_plan[0]) return refuse(p, -10, "tryon: the feature-cache plan must start with a whole evaluation (flag 0 = 1)");
@@ -106,10 +129,10 @@ int plan_evals(EvalPlan& p, int evals, int first_step, int steps, float guidance
 // what the stages of one run() share: the arguments, the host plan, and the buffers of the current pass (dry, then real)
 struct TryOn::Run {
     const TryOnInputs& in; void* images_out; int images_u8; float* latents_out; hipStream_t user_st, st;
-    int B = 0, H = 0, W = 0, h = 0, w = 0, hw = 0, pose_ch = 0, L = 0, D = 0, first_step = 0, evals = 0, n = 0;
+    int B = 0, H = 0, W = 0, h = 0, w = 0, hw = 0, pose_ch = 0, L = 0, D = 0, first_step = 0, evals = 0, n = 0, rows = 0;
     bool has_cloth = false, keep_lat = false, keep_pix = false, use_step_noise = false; size_t step_noise_bytes = 0;
     EvalPlan plan;
-    std::vector<float> ac, keep_tab; std::vector<double> timesteps; std::vector<StepTable> table; SchedInfo sinfo;
+    std::vector<float> ac, keep_tab, sag_tab; std::vector<double> timesteps; std::vector<StepTable> table; SchedInfo sinfo;
     Ctx c;
     h16 *ehs, *mask_bin, *mask2, *mask4, *mask8, *pose_lat;
     float *cloth_lat, *masked_lat, *latents, *cur_sample, *ets, *keep_x0, *keep_noise, *keep_mask;
@@ -203,11 +226,25 @@ int TryOn::plan(Run& r) {
     r.first_step = (init_src && init_first > 0) ? init_first : 0;
     build_step_table(in.scheduler, in.steps, r.ac.data(), in.cloth_zero_from, r.timesteps, r.table, &r.sinfo, eta, r.first_step);
     r.evals = (int)r.timesteps.size();
-    if (plan_evals(r.plan, r.evals, r.first_step, in.steps, in.guidance, g_sched, phi, pag_sched, fc_plan)) { set_error(r.plan.error); return r.plan.rc; }
+    SagPlan sp; sp.scale = sag_scale; sp.scheduler = in.scheduler; sp.h = r.h; sp.w = r.w;
+    for (int b : unet->tome_blocks()) sp.mid_merges = sp.mid_merges || b == unet->mid_bit;
+    if (plan_evals(r.plan, r.evals, r.first_step, in.steps, in.guidance, g_sched, phi, pag_sched, fc_plan, &sp)) { set_error(r.plan.error); return r.plan.rc; }
     r.n = r.plan.groups * r.B;
+    r.rows = r.n + (r.plan.sag_on ? r.B : 0);     // SAG: the degraded input's rows of unet_in and eps; the context stays r.n samples
     // preserve-unmasked: the blend's coefficients per evaluation, float64 on the host like the step table
     r.keep_lat = (preserve_mode & 1) != 0; r.keep_pix = (preserve_mode & 2) != 0;
     if (r.keep_lat) keep_coeffs_of(in.scheduler, r.timesteps, r.sinfo, r.ac.data(), r.first_step, r.keep_tab);
+    // self-attention guidance: sqrt(a), sqrt(1 - a) at every evaluation's (integer) timestep and the model-input scale, which is 1 for every
+    // scheduler SAG runs with; float64 on the host like the step table
+    if (r.plan.sag_on) {
+        r.sag_tab.assign((size_t)r.evals * 4, 0.f);
+        for (int i = 0; i < r.evals; ++i) {
+            long t = std::lround(r.timesteps[i]);
+            t = t < 0 ? 0 : t > 999 ? 999 : t;
+            const double a = (double)r.ac[(size_t)t];
+            r.sag_tab[4 * i] = (float)std::sqrt(a); r.sag_tab[4 * i + 1] = (float)std::sqrt(1.0 - a); r.sag_tab[4 * i + 2] = 1.f;
+        }
+    }
     last_shallow = 0;
     last_evals = r.evals;
     last_cond_only = 0;      // counted in denoise(), where an evaluation over B samples is actually launched
@@ -222,6 +259,8 @@ int TryOn::grow_tables(Run& r) {
     if (evals > table_cap) { d_table = reinterpret_cast<StepTable*>(pool.alloc((size_t)evals * sizeof(StepTable))); table_cap = evals; }
     if (p.guided && evals > gtab_cap) { d_gtab = reinterpret_cast<float*>(pool.alloc((size_t)evals * sizeof(float))); gtab_cap = evals; }
     if (p.pag_on && evals > pag_cap) { d_pag = reinterpret_cast<float*>(pool.alloc((size_t)evals * sizeof(float))); pag_cap = evals; }
+    if (p.sag_on && !d_sag) d_sag = reinterpret_cast<float*>(pool.alloc(256));
+    if (p.sag_on && evals > sag_tab_cap) { d_sag_tab = reinterpret_cast<float*>(pool.alloc((size_t)evals * 4 * sizeof(float))); sag_tab_cap = evals; }
     if (p.use_factor && B > factor_cap) { d_factor = reinterpret_cast<float*>(pool.alloc((size_t)B * sizeof(float))); factor_cap = B; }
     if (r.keep_lat && evals > keep_tab_cap) { d_keep_tab = reinterpret_cast<float*>(pool.alloc((size_t)evals * 2 * sizeof(float))); keep_tab_cap = evals; }
     if (!ev[0]) for (auto& e : ev) HIP_OK(hipEventCreate(&e));
@@ -283,6 +322,10 @@ void TryOn::upload_tables(Run& r) {
     if (p.guided) HIP_OK(hipMemcpyAsync(d_gtab, p.gtab.data(), (size_t)evals * sizeof(float), hipMemcpyHostToDevice, st));
     if (p.pag_on) HIP_OK(hipMemcpyAsync(d_pag, pag_sched.data(), (size_t)evals * sizeof(float), hipMemcpyHostToDevice, st));
     if (r.keep_lat) HIP_OK(hipMemcpyAsync(d_keep_tab, r.keep_tab.data(), (size_t)evals * 2 * sizeof(float), hipMemcpyHostToDevice, st));
+    if (p.sag_on) {
+        HIP_OK(hipMemcpyAsync(d_sag_tab, r.sag_tab.data(), (size_t)evals * 4 * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_sag, &sag_scale, sizeof(float), hipMemcpyHostToDevice, st));
+    }
     if (r.use_step_noise) HIP_OK(hipMemcpyAsync(step_noise_buf, step_noise_src, r.step_noise_bytes, hipMemcpyDeviceToDevice, st));
     std::vector<float> tsf(r.timesteps.begin(), r.timesteps.end());
     if (unet->compute_temb(tsf.data(), evals, st)) { r.rc = -5; return; }
@@ -308,7 +351,7 @@ void TryOn::encode(Run& r) {
     float* latents = r.latents = c.alloc_f32((size_t)B * hw * 4);
     r.cur_sample = c.alloc_f32((size_t)B * hw * 4);
     r.ets = c.alloc_f32((size_t)4 * B * hw * 4);
-    Act& unet_in = r.unet_in = c.new_act(n, h, w, 64);
+    Act& unet_in = r.unet_in = c.new_act(r.rows, h, w, 64);
     if (emasc) {
         const int sh[5] = {H, H, H / 2, H / 4, H / 8}, sw[5] = {W, W, W / 2, W / 4, W / 8};
         for (int i = 0; i < 5; ++i) r.skips[i] = c.new_act(B, sh[i], sw[i], emasc->cfg.out_ch[i]);
@@ -431,11 +474,14 @@ void TryOn::denoise(Run& r) {
     sa.guidance_tab = p.guided ? d_gtab : nullptr;
     sa.factor = p.use_factor ? d_factor : nullptr;
     sa.pag_tab = p.pag_on ? d_pag : nullptr;
+    sa.sag_scale = p.sag_on ? d_sag : nullptr;
+    int sag_hm = 0, sag_wm = 0;
+    UNet::sag_tokens(r.h, r.w, &sag_hm, &sag_wm);
     if (r.keep_lat) { sa.keep_x0 = r.keep_x0; sa.keep_noise = r.keep_noise; sa.keep_mask = r.keep_mask; sa.keep_tab = d_keep_tab; }
     // the UNet forward runs as lanes.G independent sample groups on as many streams (runtime.h UNetLanes); the lanes own their
     // arenas, the shared noise prediction lives in this one
     const int eps_ld = (unet->cfg.out_channels + 3) / 4 * 4;
-    Act eps = c.new_act(r.n, r.h, r.w, unet->cfg.out_channels, eps_ld);
+    Act eps = c.new_act(r.rows, r.h, r.w, unet->cfg.out_channels, eps_ld);
     const size_t mk_loop = arena.mark();
     // one evaluation of form f (runtime.h GraphTable).  Bit 0, cond-only evaluation of a guided run: the UNet runs over the conditional
     // samples [B, 2B) (their rows of unet_in and eps, their part of the K/V cache) and the step kernel, told by the table, reads only those
@@ -451,12 +497,27 @@ void TryOn::denoise(Run& r) {
         xs.n = ns; xs.p = unet_in.p + (size_t)s0 * hw * unet_in.ld;
         es.n = ns; es.p = eps.p + (size_t)s0 * hw * eps.ld;
         FwdOpt fo; fo.sample0 = s0; fo.fc = p.fc_on ? &fcs : nullptr; fo.pag_first = pg ? p.ng * B : (int)PAG_NONE;
+        if (p.sag_on) fo.sag = 1;
         lanes.forward(*unet, st, c.dry(), concurrent, xs, es, unet->temb_table, d_step, fo);
+        // SAG: degrade the latents where the base group (the first group of this evaluation: uncond under CFG, else cond) attends most, into
+        // the rows behind the last group, and run those B samples with the base group's context rows; the map stays the first forward's
+        if (p.sag_on) {
+            const size_t d0 = (size_t)p.ng * B;
+            Act xd = unet_in, ed = eps;
+            xd.n = B; xd.p = unet_in.p + d0 * hw * unet_in.ld;
+            ed.n = B; ed.p = eps.p + d0 * hw * eps.ld;
+            if (!c.dry())
+                c.check(ladi_launch_sag_degrade(latents, es.p, eps.ld, unet->sag_m + (size_t)s0 * unet->sag_T, B, r.h, r.w, sag_hm, sag_wm, d_sag_tab,
+                                                d_step, xs.p, xd.p, unet_in.ld, unet_in.ld, st), "sag_degrade");
+            FwdOpt f2; f2.sample0 = s0; f2.sag = 0;
+            lanes.forward(*unet, st, c.dry(), concurrent, xd, ed, unet->temb_table, d_step, f2);
+        }
         if (c.dry()) return;
         sa.eps = eps.p; sa.ld_eps = eps.ld;
         if (p.use_factor && !cond)
-            c.check(p.pag_on ? ladi_launch_cfg_stats_pag(eps.p, eps.ld, B, hw, d_gtab, d_step, 0.f, d_pag, 0.f, phi, d_factor, st)
-                             : ladi_launch_cfg_stats(eps.p, eps.ld, B, hw, d_gtab, d_step, 0.f, phi, d_factor, st), "cfg_stats");
+            c.check(p.sag_on ? ladi_launch_cfg_stats_sag(eps.p, eps.ld, B, hw, d_gtab, d_step, 0.f, d_sag, 0.f, phi, d_factor, st)
+                    : p.pag_on ? ladi_launch_cfg_stats_pag(eps.p, eps.ld, B, hw, d_gtab, d_step, 0.f, d_pag, 0.f, phi, d_factor, st)
+                               : ladi_launch_cfg_stats(eps.p, eps.ld, B, hw, d_gtab, d_step, 0.f, phi, d_factor, st), "cfg_stats");
         c.check(ladi_launch_sched_step(sa, st), "sched_step");
     };
     // step callback after evaluation i (between launches, never inside a capture): latents out to the caller's NCHW buffer, the host
@@ -498,7 +559,8 @@ void TryOn::denoise(Run& r) {
         key.trace_eps = trace_eps; key.trace_lat = trace_lat; key.trace_cap = trace_cap;
         key.step_noise = sa.step_noise;
         lanes.key(key.lanes);
-        unet->key(key.unet, p.pag_on);
+        unet->key(key.unet, p.pag_on, p.sag_on ? 1 : -1);
+        if (p.sag_on) { key.sag_on = 1; key.sag_scale = d_sag; key.sag_tab = d_sag_tab; }
         key.guidance_tab = sa.guidance_tab; key.factor = sa.factor; key.guided = p.guided;
         if (p.guided) std::memcpy(&key.phi, &phi, 4);
         if (p.fc_on) { key.fcache = fcache; key.fc_on = 1; key.fc_branch = fc_branch; }

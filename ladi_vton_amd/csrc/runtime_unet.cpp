@@ -93,6 +93,7 @@ void UNet::load(const UNetCfg& c, const WeightStore& ws) {
     add_res(nullptr, &mid_res[0], "mid_block.resnets.0");
     add_xf("mid_block.attentions.0", 3);
     pag_mask = 1u << xf.back().bit;         // pag_applied_layers defaults to the mid block
+    mid_bit = xf.back().bit;
     add_res(nullptr, &mid_res[1], "mid_block.resnets.1");
     for (int i = 0; i < 4; ++i) {
         for (int j = 0; j < L + 1; ++j) {
@@ -114,6 +115,23 @@ UNet::~UNet() {
     if (in_buf) (void)hipFree(in_buf);
     if (fc_buf) (void)hipFree(fc_buf);
     for (auto& l : tome.lv) if (l.mem) (void)hipFree(l.mem);
+    if (sag_mem) (void)hipFree(sag_mem);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Self-attention guidance map (runtime.h UNet::sag_capture; sag.hip)
+// ------------------------------------------------------------------------------------------------
+void UNet::sag_prepare(int T, int need_n, bool dry) {
+    if (sag_cap_n >= need_n && sag_cap_T >= T) { if (dry) sag_T = T; return; }
+    if (!dry) throw std::runtime_error("SAG map: no planning pass has seen " + std::to_string(need_n) + " samples of " + std::to_string(T) + " tokens");
+    const int cn = need_n > sag_cap_n ? need_n : sag_cap_n, cT = T > sag_cap_T ? T : sag_cap_T;
+    if (sag_mem) { HIP_OK(hipDeviceSynchronize()); (void)hipFree(sag_mem); }
+    sag_mem = nullptr; sag_s = nullptr; sag_m = nullptr; sag_cap_n = sag_cap_T = 0;
+    const size_t fl = ((size_t)cn * cT * sizeof(float) + 255) & ~(size_t)255, by = ((size_t)cn * cT + 255) & ~(size_t)255;
+    HIP_OK(hipMalloc(&sag_mem, fl + by));
+    HIP_OK(hipMemset(sag_mem, 0, fl + by));
+    sag_s = reinterpret_cast<float*>(sag_mem); sag_m = reinterpret_cast<unsigned char*>(sag_mem) + fl;
+    sag_cap_n = cn; sag_cap_T = cT; sag_T = T;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -381,6 +399,7 @@ namespace {
 struct Fwd {
     Ctx& c; UNet& u; const float* temb; const int* tidx; int sample0;
     int pag_first = PAG_NONE;   // context index of the first perturbed sample (PAG)
+    bool sag = false;           // this forward captures the SAG map (runtime.h UNet::sag_capture)
     Act res(const ResBlock& r, const Act& x, const Act* x2) {
         Act out;
         // block output is allocated first so temporaries can be released (stack discipline)
@@ -508,7 +527,21 @@ struct Fwd {
         // residual, which the unmerge kernel adds
         Merge mg;
         if (tl) mg = tome_plan(tl, t0, bit);
+        // SAG map of the mid block: the column sums of attn1's softmax, from the Q and K the attention is about to read, into the rows of
+        // this forward's samples; the scratch of the two-stage sum lives in the arena until the block releases its mark
+        const bool sag_here = sag && bit == u.mid_bit;
+        if (sag_here) {
+            if (m1) throw std::runtime_error("UNet::forward: the SAG map in a transformer block that merges tokens");
+            const int need = c.dry() && u.ctx_n > sample0 + n ? u.ctx_n : sample0 + n;
+            u.sag_prepare(T, need, c.dry());
+        }
         Act t1 = sublayer(m1 ? &mg : nullptr, b.ln1, b.qkv, ConvOpt(), b.o1, t0, T, [&](const Act& qkv, int T1) {
+            if (sag_here) {
+                float* part = c.alloc_f32((size_t)ladi_sag_partial_floats(n, T1, b.heads));
+                if (!c.dry())
+                    c.check(ladi_launch_sag_map(qkv.p, 3 * C, (long long)T1 * 3 * C, qkv.p + C, 3 * C, (long long)T1 * 3 * C, n, T1, b.heads, part,
+                                                u.sag_s + (size_t)sample0 * T1, u.sag_m + (size_t)sample0 * T1, c.st), "sag_map");
+            }
             return attn(qkv.p, 3 * C, (long long)T1 * 3 * C, qkv.p + C, qkv.p + 2 * C, 3 * C, (long long)T1 * 3 * C, n, T1, T1, b.heads, np);
         });
         // attn2 and the feed-forward as ONE kernel each on the C = 320 level (xf_fused.hip; LADI_XF_FUSE=0 / =1 / =2: none / attn2 only / both,
@@ -596,7 +629,7 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
     if (ip_ctx_n > 0 && ip_ctx_n != ctx_n && !c.dry())
         throw std::runtime_error("UNet::forward: image context batch mismatch: " + std::to_string(ip_ctx_n) + " samples, set_context has " + std::to_string(ctx_n));
     if (pag_first != PAG_NONE && fmode != FeatCache::NONE) throw std::runtime_error("UNet::forward: perturbed samples together with a feature cache");
-    Fwd f{c, *this, temb_row, temb_idx, sample0, pag_first};
+    Fwd f{c, *this, temb_row, temb_idx, sample0, pag_first, opt.sag < 0 ? sag_capture : opt.sag != 0};
     ProbeScope probe_scope(c, probe);
     // range probe points, named by the diffusers key prefix of the module that produced the tensor (off: one pointer test each)
     auto pp = [&](const Act& a, const char* fmt, int i = 0, int j = 0) {
@@ -687,7 +720,7 @@ Act UNet::forward(Ctx& c, const Act& x, const float* temb_row, const int* temb_i
     return out;
 }
 
-void UNet::key(Key& k, bool perturbed) const {
+void UNet::key(Key& k, bool perturbed, int sag) const {
     if (xf.empty()) throw std::runtime_error("UNet::key: the UNet is not loaded");
     k.temb_table = temb_table; k.kv_cache = xf.front().kv_cache;
     k.probe = probe ? probe->id : 0ULL;
@@ -706,6 +739,7 @@ void UNet::key(Key& k, bool perturbed) const {
         k.tome_on = 1; std::memcpy(k.tome_opts, opts, sizeof(opts));
         std::memcpy(&k.tome_ratio, &tc.ratio, sizeof(double)); k.tome_gen = tome.gen;
     }
+    if (sag < 0 ? sag_capture : sag != 0) { k.sag_on = 1; k.sag_buf = sag_mem; }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -126,6 +126,7 @@ class NativeUNet(_Base):
         self._lora_disabled = None    # the active set disable_lora() put aside for enable_lora()
         self._ip_key = None           # the image context the library holds (the tensor is kept alive, as for _ctx_key)
         self._ip_keepalive = None
+        self._sag_last = None         # (samples of the context batch, h, w) of the last forward, for sag_map()'s defaults
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -159,6 +160,34 @@ class NativeUNet(_Base):
     def pag_applied_layers(self):
         """the mask of selected transformer blocks, bit i = block i in execution order"""
         return int(self.lib.ladi_unet_pag_layers(self.h))
+
+    # ---- self-attention guidance (include/ladi_native.h "Self-attention guidance"): the mid block's attention column sums
+    def set_sag_capture(self, on):
+        """Sticky, off by default.  On: every forward of this UNet also leaves the SAG map of mid_block.attentions.0's self-attention
+        (sag_map()); the forward's output does not change.  A fused run with sag_scale > 0 captures whatever this says."""
+        check(self.lib.ladi_unet_set_sag_capture(self.h, 1 if on else 0), "ladi_unet_set_sag_capture")
+
+    def sag_tokens(self, h, w):
+        """-> (hm, wm), the mid block's map size for h x w latents"""
+        hm, wm = c_int(0), c_int(0)
+        check(self.lib.ladi_unet_sag_tokens(self.h, int(h), int(w), ctypes.byref(hm), ctypes.byref(wm)), "ladi_unet_sag_tokens")
+        return hm.value, wm.value
+
+    def sag_map(self, n=None, latent_size=None):
+        """-> (s, m) of the last capturing forward: s fp32 [n, hm, wm], the column sums sum_i mean_h softmax(q k^T / 8)[i, j] of the mid block's
+        self-attention, and m uint8 [n, hm, wm] = s > 1, for the first n samples of the encoder_hidden_states batch.  n and latent_size
+        (h, w) default to the last forward's through this object."""
+        if n is None or latent_size is None:
+            if self._sag_last is None:
+                raise ValueError("sag_map() needs n and latent_size=(h, w): no forward has run through this object")
+            n = self._sag_last[0] if n is None else n
+            latent_size = self._sag_last[1:] if latent_size is None else latent_size
+        hm, wm = self.sag_tokens(*latent_size)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        s = torch.empty((int(n), hm, wm), dtype=torch.float32, device=dev)
+        m = torch.empty((int(n), hm, wm), dtype=torch.uint8, device=dev)
+        check(self.lib.ladi_unet_sag_map(self.h, ptr(s), ptr(m), int(n), hm * wm), "ladi_unet_sag_map")
+        return s, m
 
     # ---- LoRA (lora.py, include/ladi_native.h "LoRA adapters"): merged onto the device weights, which keep their addresses
     def lora_target_modules(self):
@@ -405,6 +434,7 @@ class NativeUNet(_Base):
         if C != self.cfg["in_channels"]:
             raise ValueError("expected %d input channels, got %d" % (self.cfg["in_channels"], C))
         out = torch.empty((n, self.cfg["out_channels"], h, w), dtype=x.dtype, device=x.device)
+        self._sag_last = (int(sample0) + n, h, w)
         if pag_first is not None:
             if feature_cache is not None:
                 raise ValueError("`pag_first` and `feature_cache` cannot be combined.")

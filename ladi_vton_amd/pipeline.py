@@ -179,6 +179,36 @@ def pag_plan(pag_scale, pag_adaptive_scale, timesteps):
     return [max(s - a * (1000.0 - float(t)), 0.0) for t in timesteps]
 
 
+def sag_check(sag_scale, scheduler=None, latent_size=None, feature_cache=None, pag_table=None, tome_cfg=None, layers_per_block=2):
+    """-> float(sag_scale), after the refusals of a run with self-attention guidance (the ones ladi_tryon_run makes, as ValueError).  0 checks
+    nothing but the number.  scheduler: the scheduler object; latent_size: (h, w); pag_table: the PAG scales of the run or None; tome_cfg:
+    the UNet's token-merging configuration or None."""
+    try:
+        s = float(sag_scale)
+    except (TypeError, ValueError):
+        raise ValueError("`sag_scale` has to be a number but is %r." % (sag_scale,))
+    if not math.isfinite(s) or s < 0.0:
+        raise ValueError("`sag_scale` has to be finite and >= 0 but is %r." % (sag_scale,))
+    if s == 0.0:
+        return s
+    if feature_cache is not None:
+        raise ValueError("`sag_scale` > 0 and `feature_cache` cannot be combined (a shallow evaluation does not run the mid block, whose "
+                         "attention map SAG reads).")
+    if pag_table is not None and any(p > 0.0 for p in pag_table):
+        raise ValueError("`sag_scale` > 0 and `pag_scale` > 0 cannot be combined (both claim the sample group behind the conditional one).")
+    if tome_cfg:
+        from . import tome
+        if tome.merged_mask(tome_cfg, layers_per_block) >> (3 * layers_per_block) & 1:
+            raise ValueError("`sag_scale` > 0 with token merging in the mid block: the map would have merged tokens.")
+    if isinstance(scheduler, (EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, LMSDiscreteScheduler)):
+        raise ValueError("`sag_scale` > 0 does not run with %s: the sigma-space schedulers rescale the model input, and pred_x0 / add_noise "
+                         "do not describe them; use DDIM, PNDM, DPM-Solver++, LCM or TCD." % type(scheduler).__name__)
+    if latent_size is not None and min(latent_size) < 5:
+        raise ValueError("`sag_scale` > 0 needs latents of at least 5 x 5 (the blur's 4-pixel reflect padding) but they are %d x %d."
+                         % tuple(latent_size))
+    return s
+
+
 def strength_first_step(strength, num_inference_steps):
     """-> first_step: the step of the schedule a run with `strength` starts at.  diffusers' get_timesteps arithmetic in Python float64:
     init_timestep = min(int(N * strength), N), first_step = N - init_timestep.  Raises ValueError for a strength outside [0, 1] or not finite,
@@ -503,7 +533,7 @@ class StableDiffusionTryOnePipeline:
                  callback_steps=1, cloth_cond_rate=1.0, no_pose=False, cloth_input_type="warped", fused=True, noise=None,
                  use_graph=True, guidance_rescale=0.0, strength=1.0, init_image=None, init_latents=None, init_is_noisy=False,
                  feature_cache=None, preserve_unmasked=None, mask_feather=0.0, pag_scale=0.0, pag_adaptive_scale=0.0,
-                 ip_adapter_image_embeds=None, negative_ip_adapter_image_embeds=None):
+                 ip_adapter_image_embeds=None, negative_ip_adapter_image_embeds=None, sag_scale=0.0):
         """tryon_pipe.py's __call__.  `guidance_scale`: a float, a sequence with one scale per evaluation (len(scheduler.timesteps); PNDM: steps
         + 1) or a callable f(i, n_evals) -- see guidance_interval.  Classifier-free guidance is on if any scale is > 1; an evaluation whose scale
         is <= 1 then runs the UNet over the conditional samples only.  `guidance_rescale` (rescale_noise_cfg's phi, [0, 1]) acts on the CFG
@@ -553,7 +583,15 @@ class StableDiffusionTryOnePipeline:
         `ip_adapter_image_embeds` is the image prompt of a loaded IP-Adapter (load_ip_adapter): [B, E] or [B, 1, E] image embeddings, or
         diffusers' one-element list holding [2B, 1, E] with the negatives first.  `negative_ip_adapter_image_embeds` defaults to zeros.  Every
         cross-attention then adds scale * softmax(q k_ip^T / 8) v_ip over the projected image tokens (set_ip_adapter_scale; fused and modular
-        path alike).  None is the plain run; a raw `ip_adapter_image` is not taken (this package's vision encoder has no visual_projection)."""
+        path alike).  None is the plain run; a raw `ip_adapter_image` is not taken (this package's vision encoder has no visual_projection).
+
+        `sag_scale` > 0 is self-attention guidance (diffusers StableDiffusionSAGPipeline, whose default is 0.75): every evaluation reads the
+        self-attention map of the mid block, blurs the regions of its own x0 estimate that receive more than average attention (9 x 9
+        Gaussian, sigma 1), re-noises them with the predicted noise and steers away from the prediction d for that degraded input:
+        e + sag_scale * (b - d), b the unconditional prediction under classifier-free guidance, else the conditional one;
+        `guidance_rescale` acts on the whole sum.  One more forward over B samples per evaluation.  Needs the native UNet, DDIM / PNDM /
+        DPM-Solver++ / LCM / TCD and latents of at least 5 x 5; not together with `feature_cache`, `pag_scale` > 0 or token merging in the mid
+        block (sag_check).  0 is the plain run bit for bit."""
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
@@ -602,6 +640,10 @@ class StableDiffusionTryOnePipeline:
             pag_table = pag_plan(pag_scale, pag_adaptive_scale, self.scheduler.timesteps)
             if not any(s > 0.0 for s in pag_table):
                 pag_table = None
+        sag_scale = sag_check(sag_scale, self.scheduler, (height // self.vae_scale_factor, width // self.vae_scale_factor), feature_cache,
+                              pag_table, getattr(self.unet, "token_merging", None), getattr(self.unet, "cfg", {}).get("layers_per_block", 2))
+        if sag_scale > 0.0 and not isinstance(self.unet, NativeUNet):
+            raise ValueError("`sag_scale` needs the native UNet (NativeUNet), the pipeline holds %s." % type(self.unet).__name__)
         fc_flags, fc_branch = feature_cache_spec(feature_cache, n_evals)
         if feature_cache is not None and not isinstance(self.unet, NativeUNet):
             raise ValueError("`feature_cache` needs the native UNet (NativeUNet), the pipeline holds %s." % type(self.unet).__name__)
@@ -664,7 +706,7 @@ class StableDiffusionTryOnePipeline:
                                      no_pose, use_graph, step_noise=step_noise, eta=ddim_eta, callback=callback,
                                      callback_steps=callback_steps, guidance_table=g_table, guidance_rescale=guidance_rescale,
                                      init_latents=init, first_step=first_step, init_is_noisy=init_is_noisy,
-                                     feature_cache=(fc_flags, fc_branch), preserve=preserve, pag_table=pag_table, ip=ip)
+                                     feature_cache=(fc_flags, fc_branch), preserve=preserve, pag_table=pag_table, ip=ip, sag_scale=sag_scale)
             # prepare_mask_and_masked_image binarises the caller's mask in place; keep that side effect
             mask_image[mask_image < 0.5] = 0
             mask_image[mask_image >= 0.5] = 1
@@ -674,7 +716,7 @@ class StableDiffusionTryOnePipeline:
                                        no_pose, eta, generator, callback, callback_steps, guidance_table=g_table,
                                        guidance_rescale=guidance_rescale, init_latents=init, first_step=first_step,
                                        init_is_noisy=init_is_noisy, feature_cache=(fc_flags, fc_branch), preserve=preserve,
-                                       pag_table=pag_table, ip=ip)
+                                       pag_table=pag_table, ip=ip, sag_scale=sag_scale)
         if output_type == "pil":
             images = numpy_to_pil(images)
         if not return_dict:
@@ -703,7 +745,7 @@ class StableDiffusionTryOnePipeline:
     def _run_fused(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose,
                    use_graph, return_device=False, out_uint8=False, lanes=None, step_noise=None, eta=0.0, callback=None, callback_steps=1,
                    guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0, init_is_noisy=False, feature_cache=None,
-                   preserve=None, pag_table=None, ip=None):
+                   preserve=None, pag_table=None, ip=None, sag_scale=0.0):
         """ip: (embeds, negative embeds), fp16 [B, E] device tensors each (ladi_tryon_set_ip_adapter); None = no image prompt.
         return_device: hand back the device tensor (no host copy); out_uint8: the batch as uint8 [B,H,W,3] = numpy_to_pil's
         (images * 255).round() computed by the decode epilogue (ladi_tryon_run_u8); lanes: sample-group lanes of the UNet forward;
@@ -720,7 +762,8 @@ class StableDiffusionTryOnePipeline:
         feature_cache: (flags, branch) of feature_cache_spec, one flag per evaluation before promotion (ladi_tryon_set_feature_cache does the
         promotion); None or flags None = off.
         preserve: (mode_bits, feather sigma) of preserve_spec (ladi_tryon_set_preserve); None = off.
-        pag_table: one PAG scale per evaluation (pag_plan; ladi_tryon_set_pag); None = off."""
+        pag_table: one PAG scale per evaluation (pag_plan; ladi_tryon_set_pag); None = off.
+        sag_scale: the self-attention guidance scale (ladi_tryon_set_sag); 0 = off."""
         lib = _lib.load()
         if self._tryon is None:
             self._tryon = lib.ladi_tryon_create(self.unet.h, self.vae.h, self.emasc.h if self.emasc else None)
@@ -808,6 +851,9 @@ class StableDiffusionTryOnePipeline:
             check(lib.ladi_tryon_set_pag(self._tryon, pt, len(pag_table)), "ladi_tryon_set_pag")
         else:
             check(lib.ladi_tryon_set_pag(self._tryon, None, 0), "ladi_tryon_set_pag")
+        check(lib.ladi_tryon_set_sag(self._tryon, float(sag_scale)), "ladi_tryon_set_sag")
+        if float(sag_scale) > 0.0:
+            self.unet._sag_last = ((2 if neg16 is not None else 1) * B, h8, w8)      # sag_map()'s defaults: the run's context batch
         p_bits, p_sigma = preserve if preserve is not None else (0, 0.0)
         check(lib.ladi_tryon_set_preserve(self._tryon, int(p_bits), float(p_sigma)), "ladi_tryon_set_preserve")
         if ip is not None:
@@ -883,6 +929,19 @@ class StableDiffusionTryOnePipeline:
             self.last_stage_ms = list(ms)
         return out
 
+    def _sag_degrade(self, latents, e_b, m, sqrt_a, sqrt_1ma):
+        """steps 2-3 of self-attention guidance through the kernel the fused loop runs (ladi_op_sag_degrade): latents fp32 [B, 4, h, w], the
+        base prediction e_b (fp16 values), the SAG mask m uint8 [B, hm, wm] -> the degraded latents fp32 [B, 4, h, w] (fp16 values, as the
+        UNet input holds them)"""
+        B, _, h, w = latents.shape
+        lat = latents.float().permute(0, 2, 3, 1).contiguous()
+        eb = e_b.permute(0, 2, 3, 1).to(torch.float16).contiguous()
+        out = torch.empty((B, h, w, 4), dtype=torch.float16, device=latents.device)
+        m = m.contiguous()
+        check(_lib.load().ladi_op_sag_degrade(ptr(lat), ptr(eb), 4, ptr(m), B, h, w, m.shape[1], m.shape[2], sqrt_a, sqrt_1ma, 1.0, None, ptr(out),
+                                              4, 4, stream_ptr()), "ladi_op_sag_degrade")
+        return out.permute(0, 3, 1, 2).float().contiguous()
+
     def check_overflow(self):
         """True if the last fused run's decode left the fp16 range (its images are invalid; the automatic range shift has been raised, so running
         the batch again gives the result).  For callers that keep results on the device (return_device=True): waits for the run to finish."""
@@ -909,7 +968,7 @@ class StableDiffusionTryOnePipeline:
     # -------------------------------------------------------------------------------------------------------
     def _run_modular(self, image, mask_image, pose_map, cloth, pe, neg, n_cloth, n_lat, n_mask, H, W, steps, guidance, ccr, no_pose, eta,
                      generator, callback, callback_steps, guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0,
-                     init_is_noisy=False, feature_cache=None, preserve=None, pag_table=None, ip=None):
+                     init_is_noisy=False, feature_cache=None, preserve=None, pag_table=None, ip=None, sag_scale=0.0):
         F = torch.nn.functional
         dev = self._execution_device
         do_cfg = neg is not None
@@ -1012,6 +1071,22 @@ class StableDiffusionTryOnePipeline:
             elif fc_flags is not None:
                 eps = self.unet(x, t, encoder_hidden_states=ehs, feature_cache="capture" if fc_flags[i] else "reuse", cache_branch=fc_branch,
                                 sample0=B if do_cfg and not cfg_i else 0, **ipkw(ip_all)).sample.float()
+            elif sag_scale > 0.0:
+                # self-attention guidance, steps 1-4: the first forward leaves the SAG map; the base group is the first B rows of this
+                # evaluation (uncond under CFG, else cond); sag_degrade gives the degraded latents; the second forward runs them with the
+                # base group's other channels, context rows and image tokens, and leaves the map alone
+                whole = cfg_i or not do_cfg
+                ctx, ipx = (ehs if whole else pe), (ip_all if whole else ip_c)
+                self.unet.set_sag_capture(True)
+                try:
+                    eps = self.unet(x, t, encoder_hidden_states=ctx, **ipkw(ipx)).sample.float()
+                finally:
+                    self.unet.set_sag_capture(False)
+                e_b = eps[:B]
+                a_t = float(self.scheduler.alphas_cumprod[int(round(float(t)))].float())
+                xd = self._sag_degrade(latents, e_b, self.unet.sag_map(n=B, latent_size=(H // 8, W // 8))[1], math.sqrt(a_t), math.sqrt(1.0 - a_t))
+                x2 = torch.cat([xd] + [p[:B].float() for p in parts[1:]], dim=1)
+                e_d = self.unet(x2, t, encoder_hidden_states=ctx[:B], **ipkw(ipx[:B] if ipx is not None else None)).sample.float()
             else:
                 whole = cfg_i or not do_cfg
                 eps = self.unet(x, t, encoder_hidden_states=ehs if whole else pe, **ipkw(ip_all if whole else ip_c)).sample.float()
@@ -1020,10 +1095,14 @@ class StableDiffusionTryOnePipeline:
                 eps = eu + g_i * (et - eu)
                 if s_i > 0.0:
                     eps = eps + s_i * (et - ep)
+                if sag_scale > 0.0:
+                    eps = eps + sag_scale * (eu - e_d)
                 if guidance_rescale > 0.0:
                     eps = rescale_noise_cfg(eps, et, guidance_rescale)
             elif s_i > 0.0:
                 eps = eps + s_i * (eps - ep)
+            elif sag_scale > 0.0:
+                eps = eps + sag_scale * (eps - e_d)
             latents = self.scheduler.step(eps, t, latents, **extra).prev_sample
             if p_bits & 1:
                 known = self.scheduler.add_noise(z0, keep_noise, timesteps[i + 1]) if i + 1 < len(timesteps) else z0
