@@ -173,7 +173,9 @@ int ladi_text_encoder_forward_dev(ladi_text_encoder* t, const int* input_ids_dev
 typedef struct { int hidden, heads, mlp_dim, layers, image_size, patch_size; float layer_norm_eps; } ladi_vision_config;
 typedef struct ladi_vision_encoder ladi_vision_encoder;
 /* weights: transformers-4.27 key layout (vision_model.embeddings.*, vision_model.pre_layrnorm.*, vision_model.encoder.layers.N.*,
- * vision_model.post_layernorm.*); the flattened layout without the vision_model. prefix is accepted too; visual_projection unused */
+ * vision_model.post_layernorm.*); the flattened layout without the vision_model. prefix is accepted too.  visual_projection.weight
+ * ([projection_dim, hidden], no bias: CLIPVisionModelWithProjection) is loaded when the weights hold it -- it only feeds
+ * ladi_vision_encoder_forward_ex's image_embeds; without the key the encoder is the same in every respect */
 ladi_vision_encoder* ladi_vision_encoder_create(const ladi_vision_config* cfg, const ladi_weights* ws);
 void ladi_vision_encoder_destroy(ladi_vision_encoder* v);
 /* pixel_values_dev: [B,3,S,S] (dtype: 0 fp32, 1 fp16), already CLIP-normalised (the CLIPProcessor stays on the caller's side);
@@ -181,6 +183,36 @@ void ladi_vision_encoder_destroy(ladi_vision_encoder* v);
  * out_pooled_dev: fp16 [B][hidden] = post_layernorm(last_hidden_state[:, 0]) (pooler_output) or NULL */
 int ladi_vision_encoder_forward(ladi_vision_encoder* v, const void* pixel_values_dev, int dtype, int B, void* out_hidden_dev,
                                 void* out_pooled_dev, void* stream);
+/* projection_dim of the loaded visual_projection.weight, 0 when the weights held none (-1: null handle) */
+int ladi_vision_encoder_projection_dim(const ladi_vision_encoder* v);
+/* ladi_vision_encoder_forward with every output optional (NULL: not produced; with all four NULL nothing is launched) and two more:
+ * out_penultimate_dev: fp16 [B][tokens][hidden] = the INPUT of the last encoder layer, i.e. transformers' hidden_states[-2], no
+ *   post_layernorm (what the IP-Adapter Plus Resampler reads); with layers == 1 it is the pre_layrnorm output.  Its producer writes it
+ *   directly, as the last layer writes out_hidden_dev.
+ * out_image_embeds_dev: fp16 [B][projection_dim] = visual_projection(pooler_output).  Asking for it without a loaded projection is an
+ *   error with a message, and nothing is launched or written.
+ * out_hidden_dev and out_pooled_dev hold the bits ladi_vision_encoder_forward gives. */
+int ladi_vision_encoder_forward_ex(ladi_vision_encoder* v, const void* pixel_values_dev, int dtype, int B, void* out_hidden_dev,
+                                   void* out_pooled_dev, void* out_penultimate_dev, void* out_image_embeds_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Resampler — the image projection of IP-Adapter Plus (tencent-ailab/IP-Adapter `Resampler`, a Perceiver resampler): hidden states of
+ * the image encoder [n][T][E] -> N image tokens [n][N][out_dim].  The arithmetic (csrc/runtime_resampler.cpp) is restated from memory of
+ * that package, which is not a dependency, and was not checked against it.  Runs once per call, from the kernels of the hot path.
+ * weights: the original key layout -- latents [1, N, dim], proj_in.{weight,bias}, proj_out.{weight,bias}, norm_out.{weight,bias} and per
+ * layer i: layers.i.0.norm1.*, layers.i.0.norm2.*, layers.i.0.to_q.weight [inner, dim], layers.i.0.to_kv.weight [2 inner, dim],
+ * layers.i.0.to_out.weight [dim, inner], layers.i.1.0.{weight,bias} (LayerNorm), layers.i.1.1.weight, layers.i.1.3.weight (bias-free).
+ * The geometry comes from the weights; heads = inner / dim_head.  Refused at create, with a message and before the device is touched:
+ * N outside 1..64, dim_head not one of 64 / 80 / 96 / 128, inner % dim_head != 0, E, dim or out_dim not a multiple of 8 (dim and
+ * out_dim at most 4096), no layer, a missing, mis-shaped or unexpected key.  T is free (>= 1).
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct ladi_resampler ladi_resampler;
+ladi_resampler* ladi_resampler_create(const ladi_weights* ws, int dim_head);
+void ladi_resampler_destroy(ladi_resampler* r);
+/* any output pointer may be NULL */
+int ladi_resampler_info(const ladi_resampler* r, int* N, int* E, int* dim, int* depth, int* heads, int* out_dim);
+/* x_dev fp16 [n][T][E] dense -> tokens_out_dev fp16 [n][N][out_dim] dense, asynchronous on `stream` */
+int ladi_resampler_forward(ladi_resampler* r, const void* x_dev, int n, int T, void* tokens_out_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Refinement UNet of the warping module — replaces src/models/UNet.py UNetVanilla.forward (:23-34; parts in src/models/unet_parts.py)
@@ -533,8 +565,18 @@ long long ladi_unet_export_weight(ladi_unet* u, const char* key, float* host_out
  * A forward reads the image K/V rows of its own samples (sample0), as it reads the text K/V; an image context whose n is not the text
  * context's fails with a "batch mismatch" error.  Under LADI_XF_FUSE a block with an image term takes the un-fused chain.  Shallow forwards
  * of the feature cache skip the blocks they skip; PAG perturbs attn1 only.  ladi_unet_set_adapters (LoRA) leaves the image K/V alone: LoRA
- * has no to_k_ip / to_v_ip target. */
+ * has no to_k_ip / to_v_ip target.
+ * Plus adapters: when `ws` holds image_proj.latents, image_proj.* is a Resampler in its original key layout (ladi_resampler_create above,
+ * every key prefixed with image_proj.) instead of the Linear + LayerNorm; its out_dim has to be cross_dim, and its limits are checked like
+ * everything else, before anything changes.  ladi_unet_ip_adapter_load builds it with dim_head 64, ladi_unet_ip_adapter_load_ex with the
+ * given one (ignored for a plain adapter).  ladi_unet_ip_adapter_info then reports the Resampler's N and E, ladi_unet_ip_adapter_is_plus
+ * returns 1 (0: plain or none).  ladi_unet_set_ip_context_seq: hidden_dev fp16 [n][T][E] (the encoder's penultimate hidden states)
+ * -> the Resampler -> the per-block K/V GEMMs, asynchronous on `stream`; on a plain adapter it is refused with a message, as
+ * ladi_unet_set_ip_context is on a Plus adapter.  ladi_unet_set_ip_tokens works with both. */
 int ladi_unet_ip_adapter_load(ladi_unet* u, const ladi_weights* ws);
+int ladi_unet_ip_adapter_load_ex(ladi_unet* u, const ladi_weights* ws, int image_proj_dim_head);
+int ladi_unet_ip_adapter_is_plus(const ladi_unet* u);
+int ladi_unet_set_ip_context_seq(ladi_unet* u, const void* hidden_dev, int n, int T, void* stream);
 int ladi_unet_ip_adapter_unload(ladi_unet* u);
 int ladi_unet_ip_adapter_info(const ladi_unet* u, int* tokens, int* embed_dim);
 int ladi_unet_set_ip_scale(ladi_unet* u, const float* scales, int count);
@@ -554,6 +596,14 @@ int ladi_unet_set_ip_route(ladi_unet* u, int route);
  * scale 0 is the plain run bit for bit.  The captured graphs are keyed on the image term: on / off, N, the image K/V and every scale. */
 #define LADI_TRYON_IP_NO_ADAPTER (-13)
 int ladi_tryon_set_ip_adapter(ladi_tryon* t, const void* embeds_dev, const void* negative_embeds_dev);
+/* The same for a Plus adapter: hidden states of the image encoder, fp16 [B][T][E] each (hidden_states[-2]; negative_hidden_dev NULL means
+ * zeros).  Sticky; this setter and ladi_tryon_set_ip_adapter replace each other, and hidden_dev NULL switches the image prompt off.  A run
+ * assembles the same groups with rows of T * E halves and hands them to ladi_unet_set_ip_context_seq, i.e. the Resampler runs once per
+ * run, outside the captured graphs; graph key, lanes, feature cache, PAG and SAG behave as with the plain adapter.  A run whose kind of
+ * input does not fit the loaded adapter -- hidden states with a plain adapter, embeddings with a Plus adapter -- fails with
+ * LADI_TRYON_IP_ADAPTER_KIND before anything is launched. */
+#define LADI_TRYON_IP_ADAPTER_KIND (-19)
+int ladi_tryon_set_ip_adapter_seq(ladi_tryon* t, const void* hidden_dev, const void* negative_hidden_dev, int T);
 /* PAG scales of the following runs (sticky per handle; copied): scales_host[i] = s_i of evaluation i.  NULL or count 0 switches it off; a
  * table of zeros is the plain run bit for bit (nothing is allocated or launched for it).  With any s_i > 0 the run has the third sample group
  * ([uncond ; cond ; perturbed], or [cond ; perturbed] without CFG; context [neg ; pe ; pe]) and the guided prediction of an evaluation with

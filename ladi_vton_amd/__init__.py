@@ -14,6 +14,7 @@ from .schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncest
                          LCMScheduler, LMSDiscreteScheduler, PNDMScheduler, TCDScheduler)
 from .text import NativeCLIPTextEncoder, encode_text_word_embedding  # noqa: F401
 from .vision import NativeCLIPVisionEncoder  # noqa: F401
+from .resampler import NativeResampler  # noqa: F401
 from .warp import NativeRefinementUNet, NativeTPS, clip_preprocess, grid_sample_border, resize_antialias, warp_cloth  # noqa: F401
 
 

@@ -136,9 +136,13 @@ SIGNATURES = {
     "ladi_unet_ip_scale": (c_int, [_P, POINTER(c_float), c_int]),
     "ladi_unet_set_ip_context": (c_int, [_P, _P, c_int, _P]),
     "ladi_unet_set_ip_tokens": (c_int, [_P, _P, c_int, c_int, _P]),
+    "ladi_unet_ip_adapter_load_ex": (c_int, [_P, _P, c_int]),
+    "ladi_unet_ip_adapter_is_plus": (c_int, [_P]),
+    "ladi_unet_set_ip_context_seq": (c_int, [_P, _P, c_int, c_int, _P]),
     "ladi_unet_clear_ip_context": (c_int, [_P]),
     "ladi_unet_set_ip_route": (c_int, [_P, c_int]),
     "ladi_tryon_set_ip_adapter": (c_int, [_P, _P, _P]),
+    "ladi_tryon_set_ip_adapter_seq": (c_int, [_P, _P, _P, c_int]),
     "ladi_op_ip_attn_add": (c_int, [_P, c_int, c_longlong, _P, c_int, c_longlong, _P, c_int, c_longlong, _P, c_int, c_longlong, c_int, c_int,
                                     c_int, c_int, c_float, _P]),
     "ladi_tome_config_check": (c_int, [POINTER(ToMeConfig)]),
@@ -168,6 +172,12 @@ SIGNATURES = {
     "ladi_vision_encoder_create": (_P, [POINTER(VisionConfig), _P]),
     "ladi_vision_encoder_destroy": (None, [_P]),
     "ladi_vision_encoder_forward": (c_int, [_P, _P, c_int, c_int, _P, _P, _P]),
+    "ladi_vision_encoder_projection_dim": (c_int, [_P]),
+    "ladi_vision_encoder_forward_ex": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
+    "ladi_resampler_create": (_P, [_P, c_int]),
+    "ladi_resampler_destroy": (None, [_P]),
+    "ladi_resampler_info": (c_int, [_P] + [POINTER(c_int)] * 6),
+    "ladi_resampler_forward": (c_int, [_P, _P, c_int, c_int, _P, _P]),
     "ladi_tps_create": (_P, [POINTER(TpsConfig), _P]),
     "ladi_tps_destroy": (None, [_P]),
     "ladi_tps_forward": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P]),

@@ -252,6 +252,14 @@ def vision_shapes(cfg):
     return sd
 
 
+def vision_projection_shapes(cfg, projection_dim):
+    """the key CLIPVisionModelWithProjection adds to vision_shapes: visual_projection (Linear hidden -> projection_dim, no bias), the
+    source of `image_embeds` (1024 for the released ViT-H/14)"""
+    sd = OrderedDict()
+    sd["visual_projection.weight"] = (int(projection_dim), cfg["hidden"])
+    return sd
+
+
 def text_shapes(cfg):
     """transformers 4.27 CLIPTextModel key layout (the layout of the released text_encoder checkpoint): text_model.*"""
     sd = OrderedDict()

@@ -19,6 +19,7 @@ struct ladi_emasc { EMASC e; };
 struct ladi_adapter { Adapter a; };
 struct ladi_text_encoder { TextEncoder t; };
 struct ladi_vision_encoder { VisionEncoder v; };
+struct ladi_resampler { Resampler r; };
 struct ladi_refine { Refine r; };
 struct ladi_tps { Tps t; };
 struct ladi_tryon { TryOn t; };
@@ -35,6 +36,7 @@ static void set_module_probe(Probe*& slot, ladi_probe* p) {
 }
 static_assert(TRYON_CALLBACK_ABORT == LADI_TRYON_CALLBACK_ABORTED, "callback abort code");
 static_assert(TRYON_IP_NO_ADAPTER == LADI_TRYON_IP_NO_ADAPTER, "IP-Adapter refusal code");
+static_assert(TRYON_IP_ADAPTER_KIND == LADI_TRYON_IP_ADAPTER_KIND, "IP-Adapter kind refusal code");
 
 static_assert(sizeof(ladi_igemm_desc) == sizeof(IGemmArgs), "public igemm descriptor must mirror IGemmArgs");
 static_assert(sizeof(ladi_conv_f32_desc) == sizeof(ConvF32Args), "public fp32 convolution descriptor must mirror ConvF32Args");
@@ -387,6 +389,23 @@ int ladi_unet_ip_adapter_load(ladi_unet* u, const ladi_weights* ws) {
         if (!u || !ws) throw std::runtime_error("null handle or weights");
         u->u.ip_load(ws->ws);
         return 0;
+    });
+}
+int ladi_unet_ip_adapter_load_ex(ladi_unet* u, const ladi_weights* ws, int image_proj_dim_head) {
+    return guarded("ladi_unet_ip_adapter_load_ex", [&]() {
+        if (!u || !ws) throw std::runtime_error("null handle or weights");
+        u->u.ip_load(ws->ws, image_proj_dim_head);
+        return 0;
+    });
+}
+int ladi_unet_ip_adapter_is_plus(const ladi_unet* u) {
+    if (!u) { set_error("ladi_unet_ip_adapter_is_plus: null handle"); return -1; }
+    return u->u.ip_resampler ? 1 : 0;
+}
+int ladi_unet_set_ip_context_seq(ladi_unet* u, const void* hidden, int n, int T, void* stream) {
+    return guarded("ladi_unet_set_ip_context_seq", [&]() {
+        if (!u) throw std::runtime_error("null handle");
+        return u->u.set_ip_context_seq(reinterpret_cast<const h16*>(hidden), n, T, S(stream));
     });
 }
 int ladi_unet_ip_adapter_unload(ladi_unet* u) {
@@ -846,6 +865,55 @@ int ladi_vision_encoder_forward(ladi_vision_encoder* v, const void* px, int dtyp
     });
 }
 
+int ladi_vision_encoder_projection_dim(const ladi_vision_encoder* v) {
+    if (!v) { set_error("ladi_vision_encoder_projection_dim: null handle"); return -1; }
+    return v->v.proj_dim;
+}
+int ladi_vision_encoder_forward_ex(ladi_vision_encoder* v, const void* px, int dtype, int B, void* out_hidden, void* out_pooled,
+                                   void* out_penultimate, void* out_image_embeds, void* stream) {
+    return guarded("ladi_vision_encoder_forward_ex", [&]() {
+        if (!v || !px) throw std::runtime_error("null argument");
+        if (dtype != 0 && dtype != 1) throw std::runtime_error("pixel_values dtype must be fp32 (0) or fp16 (1)");
+        return v->v.forward_ex(px, dtype == 0, B, reinterpret_cast<h16*>(out_hidden), reinterpret_cast<h16*>(out_pooled),
+                               reinterpret_cast<h16*>(out_penultimate), reinterpret_cast<h16*>(out_image_embeds), S(stream));
+    });
+}
+
+// ------------------------------------------------------------------------------------------------ Resampler (IP-Adapter Plus image projection)
+ladi_resampler* ladi_resampler_create(const ladi_weights* ws, int dim_head) {
+    ladi_resampler* h = nullptr;
+    int rc = guarded("ladi_resampler_create", [&]() {
+        if (!ws) throw std::runtime_error("null weights");
+        // the geometry and every limit are checked on the host first (Resampler::load), so a refusal needs no device
+        std::unique_ptr<ladi_resampler> r(new ladi_resampler());
+        r->r.check(ws->ws, "", dim_head);
+        require_gpu();
+        r->r.upload(ws->ws, "");
+        h = r.release();
+        return 0;
+    });
+    if (rc) return nullptr;
+    return h;
+}
+void ladi_resampler_destroy(ladi_resampler* r) { delete r; }
+int ladi_resampler_info(const ladi_resampler* r, int* N, int* E, int* dim, int* depth, int* heads, int* out_dim) {
+    if (!r) { set_error("ladi_resampler_info: null handle"); return -1; }
+    if (N) *N = r->r.N;
+    if (E) *E = r->r.E;
+    if (dim) *dim = r->r.dim;
+    if (depth) *depth = r->r.depth;
+    if (heads) *heads = r->r.heads;
+    if (out_dim) *out_dim = r->r.out_dim;
+    return 0;
+}
+int ladi_resampler_forward(ladi_resampler* r, const void* x, int n, int T, void* tokens_out, void* stream) {
+    return guarded("ladi_resampler_forward", [&]() {
+        if (!r) throw std::runtime_error("null handle");
+        r->r.forward(reinterpret_cast<const h16*>(x), n, T, reinterpret_cast<h16*>(tokens_out), S(stream));
+        return 0;
+    });
+}
+
 // ------------------------------------------------------------------------------------------------ refinement UNet
 ladi_refine* ladi_refine_create(const ladi_refine_config* cfg, const ladi_weights* ws) {
     ladi_refine* h = nullptr;
@@ -1055,6 +1123,15 @@ int ladi_tryon_set_ip_adapter(ladi_tryon* t, const void* embeds, const void* neg
     if (!t) { set_error("ladi_tryon_set_ip_adapter: null handle"); return -1; }
     t->t.ip_pos = reinterpret_cast<const h16*>(embeds);
     t->t.ip_neg = embeds ? reinterpret_cast<const h16*>(negative_embeds) : nullptr;
+    t->t.ip_T = 0;
+    return 0;
+}
+int ladi_tryon_set_ip_adapter_seq(ladi_tryon* t, const void* hidden, const void* negative_hidden, int T) {
+    if (!t) { set_error("ladi_tryon_set_ip_adapter_seq: null handle"); return -1; }
+    if (hidden && T < 1) { set_error("ladi_tryon_set_ip_adapter_seq: T = " + std::to_string(T) + ", hidden states have at least one token"); return -1; }
+    t->t.ip_pos = reinterpret_cast<const h16*>(hidden);
+    t->t.ip_neg = hidden ? reinterpret_cast<const h16*>(negative_hidden) : nullptr;
+    t->t.ip_T = hidden ? T : 0;
     return 0;
 }
 int ladi_tryon_set_pag(ladi_tryon* t, const float* scales_host, int count) {

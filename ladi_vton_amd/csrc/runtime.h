@@ -291,6 +291,24 @@ struct LoraAdapter {
     ~LoraAdapter();
 };
 
+// IP-Adapter Plus image projection: the tencent-ailab `Resampler` (Perceiver resampler), restated from memory of that package, not checked
+// against it (runtime_resampler.cpp has the arithmetic).  Geometry comes from the weights: N latents of width dim, input width E, `depth`
+// layers of heads = inner / dim_head attention heads over T + N keys and a bias-free 4x GELU feed-forward, output width out_dim
+struct ResamplerLayer { DNorm n1, n2, ffn; DConv q, kv, o, w1, w2; };
+struct Resampler {
+    DevPool pool;
+    int N = 0, E = 0, dim = 0, depth = 0, heads = 0, dim_head = 0, out_dim = 0;
+    h16* latents = nullptr;                  // [N][dim]
+    DConv proj_in, proj_out; DNorm norm_out; std::vector<ResamplerLayer> layers;
+    Arena arena;
+    // prefix: what stands before the original keys ("" or "image_proj.").  check: host only -- every key, shape and limit
+    // (include/ladi_native.h), throws with a message, else fills the geometry; upload: the weights of a checked store to the device
+    void check(const WeightStore& ws, const std::string& prefix, int dim_head);
+    void upload(const WeightStore& ws, const std::string& prefix);
+    // x fp16 [n][T][E] dense -> tokens_out fp16 [n][N][out_dim] dense.  Throws on a launch failure
+    void forward(const h16* x, int n, int T, h16* tokens_out, hipStream_t st);
+};
+
 struct UNet {
     UNetCfg cfg;
     std::vector<LoraTarget> lora_targets; std::unordered_map<std::string, int> lora_index;
@@ -316,12 +334,17 @@ struct UNet {
     h16* ip_proj_w = nullptr; h16* ip_proj_b = nullptr; DNorm ip_norm;
     int ip_ctx_n = 0, ip_ctx_N = 0; size_t ip_ctx_cap = 0;    // image context: samples (0 = none), tokens per sample; capacity in rows (n * N)
     std::unique_ptr<DevPool> ip_ctx_pool; h16* ip_lin = nullptr; h16* ip_tok = nullptr;   // projection output / tokens [rows][cross_dim]
-    void ip_load(const WeightStore& ws);                      // throws; everything is checked before anything changes
+    void ip_load(const WeightStore& ws, int dim_head = 64);   // throws; everything is checked before anything changes
     void ip_unload();
     void ip_set_scale(const float* scales, int count);        // throws on a wrong count or a non-finite value, nothing changed
     void ip_reserve(int n, int N);                            // host only: buffers for n samples of N tokens, and the context's shape (planning passes)
     int set_ip_context(const h16* embeds, int n, hipStream_t st);          // fp16 [n][ip_E] -> projection, LayerNorm, one igemm per block
     int set_ip_tokens(const h16* tokens, int n, int N, hipStream_t st);    // finished tokens fp16 [n][N][cross_dim]
+    // Plus adapter: image_proj.* of the loaded weights is a Resampler (out_dim = cross_dim) instead of the Linear + LayerNorm; ip_N / ip_E are
+    // its N and E.  set_ip_context is refused then, and set_ip_context_seq -- hidden states fp16 [n][T][ip_E] -> Resampler into ip_tok -> the
+    // per-block K/V GEMMs -- is refused on a plain adapter.  ip_dim_head: the head width ip_load builds the Resampler with
+    std::unique_ptr<Resampler> ip_resampler; int ip_dim_head = 64;
+    int set_ip_context_seq(const h16* hidden, int n, int T, hipStream_t st);
     void clear_ip_context() { ip_ctx_n = 0; }
     // A/B switch of the image term (tools/bench_ip_adapter.py; ladi_unet_set_ip_route): 0 = ip_attn_add, the shipped route on every level
     // (BASELINE.md "IP-Adapter"); 1 = flash_attn64 over the N image keys into a scratch tensor plus ip_scaled_add (two roundings)
@@ -548,12 +571,18 @@ struct VisionEncoder {
     DConv patch;                 // [hidden][3*ps*ps padded to 64] bias-free
     h16* posc = nullptr;         // [tokens][hidden]: position embedding, class embedding added to row 0
     DNorm pre_ln, post_ln; std::vector<TextLayer> layers;
+    h16* vproj = nullptr; int proj_dim = 0;   // visual_projection.weight [proj_dim][hidden], bias-free (CLIPVisionModelWithProjection); 0: not in the weights
     Arena arena;
     int tokens() const { return 1 + (cfg.image / cfg.patch) * (cfg.image / cfg.patch); }
     void load(const VisionCfg& c, const WeightStore& ws);
     // pixels [B][3][image][image] (fp32 or fp16, device); out_hidden fp16 [B][tokens][hidden] (encoder output, no post_layernorm);
     // out_pooled fp16 [B][hidden] = post_layernorm(out_hidden[:, 0]) or null
     int forward(const void* pixels, int in_f32, int B, h16* out_hidden, h16* out_pooled, hipStream_t st);
+    // the same with every output optional (null: not produced; what a missing output's readers need lives in the arena), plus out_penultimate fp16 [B][tokens][hidden] = the input of the last encoder layer (hidden_states[-2]; with one layer
+    // the pre_layrnorm output), written by its producer directly, and out_image_embeds fp16 [B][proj_dim] = visual_projection(pooled).
+    // out_image_embeds without a loaded projection is refused before anything is launched.  Shared outputs are forward()'s bit for bit
+    int forward_ex(const void* pixels, int in_f32, int B, h16* out_hidden, h16* out_pooled, h16* out_penultimate, h16* out_image_embeds,
+                   hipStream_t st);
 };
 
 // ---- fp32 path of the warping module (runtime_f32.cpp, f32path.hip): src/inference.py:253,264 call both networks on fp32 tensors
@@ -617,6 +646,8 @@ struct TryOnInputs {
 };
 enum { TRYON_PAG_WITH_CACHE = -12 };  // TryOn::run: a PAG table with a positive entry together with a feature-cache plan (LADI_TRYON_PAG_WITH_FEATURE_CACHE)
 enum { TRYON_IP_NO_ADAPTER = -13 };   // TryOn::run: image embeddings are set but the UNet has no IP-Adapter loaded (LADI_TRYON_IP_NO_ADAPTER)
+// TryOn::run: embeddings [B][E] are set but the loaded adapter is a Plus adapter, or hidden states [B][T][E] but it is a plain one
+enum { TRYON_IP_ADAPTER_KIND = -19 };
 // TryOn::run with self-attention guidance on (ladi_tryon_set_sag), refused before anything is launched (LADI_TRYON_SAG_*):
 enum {
     TRYON_SAG_WITH_CACHE = -14,    // together with a feature-cache plan: shallow evaluations do not run the mid block
@@ -738,7 +769,9 @@ struct TryOn {
     // run).  The caller's fp16 [B][E] embeddings (ip_neg null: zeros, diffusers' zeros_like) are assembled per run into the runtime-owned
     // ip_buf [groups * B][E] -- [neg ; pos], [neg ; pos ; pos] with PAG, [pos] without CFG -- on the run's stream, next to the prompt
     // embeddings, and become the UNet's image context right after set_context
-    const h16* ip_pos = nullptr; const h16* ip_neg = nullptr;
+    // ladi_tryon_set_ip_adapter_seq (the two setters replace each other): ip_T > 0, the pointers are hidden states fp16 [B][ip_T][E] of a
+    // Plus adapter, the rows assembled are ip_T * E halves wide and go through UNet::set_ip_context_seq (the Resampler); ip_T = 0: embeddings
+    const h16* ip_pos = nullptr; const h16* ip_neg = nullptr; int ip_T = 0;
     h16* ip_buf = nullptr; size_t ip_buf_cap = 0;
     int last_shallow = 0;     // evaluations of the last run that ran shallow, after promotion (ladi_tryon_shallow_evals)
     // preserve-unmasked (ladi_tryon_set_preserve, sticky; 0 = off: nothing below is allocated or launched).  Bit 0, latents: after every

@@ -219,6 +219,13 @@ int TryOn::plan(Run& r) {
         set_error("tryon: image embeddings are set (ladi_tryon_set_ip_adapter) but the UNet has no IP-Adapter loaded (ladi_unet_ip_adapter_load)");
         return TRYON_IP_NO_ADAPTER;
     }
+    if (ip_pos && (ip_T > 0) != (unet->ip_resampler != nullptr)) {
+        set_error(ip_T > 0 ? "tryon: hidden states are set (ladi_tryon_set_ip_adapter_seq) but the loaded IP-Adapter is a plain adapter, which takes one "
+                             "embedding per image (ladi_tryon_set_ip_adapter)"
+                           : "tryon: image embeddings are set (ladi_tryon_set_ip_adapter) but the loaded IP-Adapter is a Plus adapter, which takes hidden "
+                             "states (ladi_tryon_set_ip_adapter_seq)");
+        return TRYON_IP_ADAPTER_KIND;
+    }
     if (cfg_shaped(in.guidance, g_sched) && !in.negative_prompt_embeds) { set_error("tryon: negative_prompt_embeds required when guidance_scale > 1"); return -4; }
     // ---- scheduler tables (host)
     if (in.alphas_cumprod) r.ac.assign(in.alphas_cumprod, in.alphas_cumprod + 1000); else default_alphas_cumprod(r.ac);
@@ -287,7 +294,7 @@ int TryOn::grow_tables(Run& r) {
         }
     }
     if (ip_pos) {
-        const size_t need = (size_t)r.n * unet->ip_E;
+        const size_t need = (size_t)r.n * (ip_T > 0 ? ip_T : 1) * unet->ip_E;
         if (need > ip_buf_cap) {
             if (ip_buf) HIP_OK_RC(hipFree(ip_buf));
             ip_buf = nullptr; ip_buf_cap = 0;
@@ -378,7 +385,7 @@ void TryOn::encode(Run& r) {
         if (unet->set_context(ehs, n, L, st)) { r.rc = -6; return; }
         // image embeddings, the same groups: [neg ; pos], the perturbed group a copy of pos; a null negative is zeros
         if (ip_pos) {
-            const size_t ie = (size_t)B * unet->ip_E;
+            const size_t ie = (size_t)B * (ip_T > 0 ? ip_T : 1) * unet->ip_E;     // rows of E halves, or of T * E with a Plus adapter
             for (int g = 0; g < p.groups; ++g) {
                 h16* dst = ip_buf + (size_t)g * ie;
                 if (p.cfg && g == 0) {
@@ -386,7 +393,7 @@ void TryOn::encode(Run& r) {
                     else HIP_OK(hipMemsetAsync(dst, 0, ie * sizeof(h16), st));
                 } else HIP_OK(hipMemcpyAsync(dst, ip_pos, ie * sizeof(h16), hipMemcpyDeviceToDevice, st));
             }
-            if (unet->set_ip_context(ip_buf, n, st)) { r.rc = -6; return; }
+            if (ip_T > 0 ? unet->set_ip_context_seq(ip_buf, n, ip_T, st) : unet->set_ip_context(ip_buf, n, st)) { r.rc = -6; return; }
         }
     }
     // ---------------- 4. mask / masked image / pose (tryon_pipe.py:630-636)

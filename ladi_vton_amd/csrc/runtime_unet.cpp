@@ -269,8 +269,49 @@ int UNet::compute_temb(const float* ts_host, int count, hipStream_t st) {
 // ------------------------------------------------------------------------------------------------
 // IP-Adapter image prompt (runtime.h UNet; ip_adapter.hip)
 // ------------------------------------------------------------------------------------------------
-void UNet::ip_load(const WeightStore& ws) {
+// the weights of ip_load with a Resampler as image_proj.* (Plus): validated by Resampler::load, K/V weights as for the plain adapter
+static void ip_load_plus(UNet& u, const WeightStore& ws, int dim_head) {
+    const int D = u.cfg.cross_dim;
+    for (auto& kv : ws.m) {
+        const std::string& k = kv.first;
+        bool known = k.compare(0, 11, "image_proj.") == 0;
+        for (auto& b : u.xf)
+            known = known || k == b.prefix + ".transformer_blocks.0.attn2.processor.to_k_ip.weight" ||
+                    k == b.prefix + ".transformer_blocks.0.attn2.processor.to_v_ip.weight";
+        if (!known) throw std::runtime_error("unexpected key '" + k + "'");
+    }
+    for (auto& b : u.xf)
+        for (const char* nm : {"to_k_ip", "to_v_ip"}) {
+            const std::string k = b.prefix + ".transformer_blocks.0.attn2.processor." + nm + ".weight";
+            if (!ws.has(k)) throw std::runtime_error("'" + k + "' is missing");
+            const HostTensor& w = ws.get(k);
+            if (w.shape.size() != 2 || w.shape[0] != b.C || w.shape[1] != D)
+                throw std::runtime_error(k + " is not [" + std::to_string(b.C) + ", " + std::to_string(D) + "]");
+        }
+    std::unique_ptr<Resampler> rs(new Resampler());
+    rs->check(ws, "image_proj.", dim_head);       // host only; the device is touched after the last refusal
+    if (rs->out_dim != D)
+        throw std::runtime_error("the Resampler's output width " + std::to_string(rs->out_dim) + " is not the UNet's cross-attention width " + std::to_string(D));
+    rs->upload(ws, "image_proj.");
+    std::unique_ptr<DevPool> pool_(new DevPool());
+    std::vector<DConv> kv;
+    for (auto& b : u.xf) {
+        const std::string p = b.prefix + ".transformer_blocks.0.attn2.processor.";
+        kv.push_back(load_linear_cat(*pool_, ws, {p + "to_k_ip", p + "to_v_ip"}, false));
+    }
+    HIP_OK(hipDeviceSynchronize());
+    for (auto& b : u.xf) { b.ip_kv = kv[b.bit]; b.ip_scale = 1.f; }
+    u.ip_pool = std::move(pool_);
+    u.ip_proj_w = u.ip_proj_b = nullptr; u.ip_norm = DNorm();
+    u.ip_N = rs->N; u.ip_E = rs->E; u.ip_dim_head = dim_head;
+    u.ip_resampler = std::move(rs);
+    u.ip_loaded = true;
+    u.ip_ctx_n = 0;
+}
+
+void UNet::ip_load(const WeightStore& ws, int dim_head) {
     if (ip_loaded) throw std::runtime_error("an IP-Adapter is already loaded (ladi_unet_ip_adapter_unload first)");
+    if (ws.has("image_proj.latents")) { ip_load_plus(*this, ws, dim_head); return; }
     auto shape_str = [](const HostTensor& t) { std::string s = "["; for (size_t i = 0; i < t.shape.size(); ++i) s += (i ? ", " : "") + std::to_string(t.shape[i]); return s + "]"; };
     auto need = [&](const std::string& k) -> const HostTensor& {
         if (!ws.has(k)) throw std::runtime_error("'" + k + "' is missing");
@@ -333,6 +374,7 @@ void UNet::ip_unload() {
     ip_lin = ip_tok = nullptr;
     ip_ctx_pool.reset();
     ip_pool.reset();
+    ip_resampler.reset();
     ip_proj_w = ip_proj_b = nullptr; ip_norm = DNorm();
     ip_N = ip_E = 0; ip_loaded = false;
 }
@@ -379,12 +421,28 @@ static int ip_project_kv(UNet& u, const h16* tok, hipStream_t st) {
 
 int UNet::set_ip_context(const h16* embeds, int n, hipStream_t st) {
     if (!embeds) throw std::runtime_error("null image embeddings");
+    if (ip_resampler)
+        throw std::runtime_error("the loaded IP-Adapter is a Plus adapter (Resampler): it takes hidden states [n][T][" + std::to_string(ip_E) +
+                                 "] through ladi_unet_set_ip_context_seq, not one embedding per image");
     ip_reserve(n, ip_N);
     const int D = cfg.cross_dim;
     // tokens = LayerNorm(Linear(embeds)).reshape(n, N, cross_dim): the projection's output row [N * D] is N token rows of D
     int rc = ladi_launch_small_linear(embeds, 0, ip_E, ip_proj_w, ip_proj_b, nullptr, 0, n, ip_N * D, ip_E, LADI_ACT_NONE, 0, ip_lin, 0, ip_N * D, st);
     if (!rc) rc = ladi_launch_layernorm(ip_lin, D, ip_norm.g, ip_norm.b, 1e-5f, n * ip_N, D, ip_tok, D, st);
     if (rc) { ip_ctx_n = 0; set_error("set_ip_context image projection rc=" + std::to_string(rc)); return rc; }
+    return ip_project_kv(*this, ip_tok, st);
+}
+
+int UNet::set_ip_context_seq(const h16* hidden, int n, int T, hipStream_t st) {
+    if (!hidden) throw std::runtime_error("null hidden states");
+    if (!ip_loaded) throw std::runtime_error("no IP-Adapter is loaded (ladi_unet_ip_adapter_load)");
+    if (!ip_resampler)
+        throw std::runtime_error("the loaded IP-Adapter is a plain adapter (Linear + LayerNorm projection): it takes one embedding per image "
+                                 "through ladi_unet_set_ip_context, not a sequence of hidden states");
+    if (T < 1) throw std::runtime_error("hidden states of " + std::to_string(T) + " tokens: T >= 1");
+    ip_reserve(n, ip_N);
+    try { ip_resampler->forward(hidden, n, T, ip_tok, st); }
+    catch (...) { ip_ctx_n = 0; throw; }
     return ip_project_kv(*this, ip_tok, st);
 }
 

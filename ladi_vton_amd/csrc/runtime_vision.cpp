@@ -30,14 +30,39 @@ void VisionEncoder::load(const VisionCfg& c, const WeightStore& ws) {
     pre_ln = load_norm(pool, ws, pre + "pre_layrnorm");      // (sic: the key is misspelled upstream)
     post_ln = load_norm(pool, ws, pre + "post_layernorm");
     layers = load_clip_layers(pool, ws, pre + "encoder.layers.", c.layers);
+    if (ws.has("visual_projection.weight")) {                // CLIPVisionModelWithProjection: Linear(hidden -> projection_dim), no bias
+        const HostTensor& vp = ws.get("visual_projection.weight");
+        if (vp.shape.size() != 2 || vp.shape[1] != H || vp.shape[0] < 1)
+            throw std::runtime_error("vision encoder: visual_projection.weight is not [projection_dim, " + std::to_string(H) + "]");
+        if (ws.has("visual_projection.bias")) throw std::runtime_error("vision encoder: visual_projection has no bias");
+        vproj = pool.upload_h16(vp.data);
+        proj_dim = (int)vp.shape[0];
+    }
 }
 
 int VisionEncoder::forward(const void* pixels, int in_f32, int B, h16* out_hidden, h16* out_pooled, hipStream_t st) {
+    return forward_ex(pixels, in_f32, B, out_hidden, out_pooled, nullptr, nullptr, st);
+}
+
+int VisionEncoder::forward_ex(const void* pixels, int in_f32, int B, h16* out_hidden, h16* out_pooled, h16* out_pen, h16* out_embeds,
+                              hipStream_t st) {
     if (B <= 0) { set_error("vision encoder: bad batch"); return -1; }
-    const int H = cfg.hidden, T = tokens();
+    if (out_embeds && !vproj) {
+        set_error("vision encoder: image_embeds asked for, but the weights hold no visual_projection.weight");
+        return -1;
+    }
+    const int H = cfg.hidden, T = tokens(), nl = (int)layers.size();
+    const bool need_pooled = out_pooled || out_embeds;
+    if (!out_hidden && !need_pooled && !out_pen) return 0;
     run_planned(arena, st, [&](Ctx& c) {
         Act xa = c.new_act(B, T, 1, H), xb = c.new_act(B, T, 1, H);   // residual stream, ping-pong
+        // every call runs the whole encoder: an output the caller did not ask for lives in the arena
+        h16* hidden = out_hidden ? out_hidden : c.alloc_h16((size_t)B * T * H);
+        h16* pooled = out_pooled ? out_pooled : (need_pooled ? c.alloc_h16((size_t)B * H) : nullptr);
+        Act last = xa; last.p = hidden; last.ld = H;          // the last block writes straight into the caller's buffer
+        Act pen = xa; pen.p = out_pen; pen.ld = H;            // ... and so does the producer of the last block's input
         Act* cur = &xa; Act* nxt = &xb;
+        if (out_pen && nl == 1) cur = &pen;
         {   // embeddings: patch rows -> GEMM (+ position / class embeddings as the residual, shared by every image) -> pre_layrnorm
             const size_t mk = c.ar->mark();
             Act pr = c.new_act(B, T, 1, patch.cin_pad);
@@ -55,13 +80,17 @@ int VisionEncoder::forward(const void* pixels, int in_f32, int B, h16* out_hidde
             }
             c.ar->release(mk);
         }
-        Act last = xa; last.p = out_hidden; last.ld = H;      // the last block writes straight into the caller's buffer
-        for (const TextLayer& L : layers) {
-            clip_layer(c, L, *cur, &L == &layers.back() ? last : *nxt, cfg.heads, false, cfg.ln_eps);
-            std::swap(cur, nxt);
+        for (int i = 0; i < nl; ++i) {
+            Act* dst = i == nl - 1 ? &last : (i == nl - 2 && out_pen) ? &pen : nxt;
+            clip_layer(c, layers[i], *cur, *dst, cfg.heads, false, cfg.ln_eps);
+            if (dst == nxt) std::swap(cur, nxt);
+            else cur = dst;
         }
-        if (!c.dry() && out_pooled)
-            c.check(ladi_launch_layernorm(out_hidden, T * H, post_ln.g, post_ln.b, cfg.ln_eps, B, H, out_pooled, H, st), "post_layernorm");
+        if (!c.dry() && need_pooled)
+            c.check(ladi_launch_layernorm(hidden, T * H, post_ln.g, post_ln.b, cfg.ln_eps, B, H, pooled, H, st), "post_layernorm");
+        if (!c.dry() && out_embeds)
+            c.check(ladi_launch_small_linear(pooled, 0, H, vproj, nullptr, nullptr, 0, B, proj_dim, H, LADI_ACT_NONE, 0, out_embeds, 0, proj_dim, st),
+                    "visual_projection");
     });
     return 0;
 }

@@ -277,14 +277,16 @@ class NativeUNet(_Base):
         return out
 
     # ---- IP-Adapter image prompt (ip_adapter.py, include/ladi_native.h "IP-Adapter image prompt")
-    def load_ip_adapter(self, state_dict_or_path):
+    def load_ip_adapter(self, state_dict_or_path, image_proj_dim_head=64):
         """Load an IP-Adapter (diffusers' {"image_proj", "ip_adapter"} layout, nested or flat, numbered or module-named keys:
         ip_adapter.load_state).  Everything is checked before anything changes; one adapter per UNet.  Loading activates nothing: an image
-        term appears in a forward that is given ip_image_embeds= / ip_tokens=.  A new adapter starts with every scale 1.0."""
+        term appears in a forward that is given ip_image_embeds= / ip_tokens=.  A new adapter starts with every scale 1.0.
+        A Plus checkpoint (image_proj is a Resampler) is loaded with its Resampler, built with heads of image_proj_dim_head (the weights
+        do not record it; 64 in the released files); ip_image_embeds= then takes hidden states [n, T, E]."""
         from . import ip_adapter
         sd = ip_adapter.load_state(state_dict_or_path, self.cfg["layers_per_block"])
         with _Weights(sd) as w:
-            check(self.lib.ladi_unet_ip_adapter_load(self.h, w.h), "ladi_unet_ip_adapter_load")
+            check(self.lib.ladi_unet_ip_adapter_load_ex(self.h, w.h, int(image_proj_dim_head)), "ladi_unet_ip_adapter_load_ex")
         self._ip_key = self._ip_keepalive = None
 
     def unload_ip_adapter(self):
@@ -299,6 +301,14 @@ class NativeUNet(_Base):
         if rc < 0:
             raise NativeError("ladi_unet_ip_adapter_info failed: " + _lib.last_error())
         return (n.value, e.value) if rc else None
+
+    @property
+    def ip_adapter_is_plus(self):
+        """True when the loaded adapter's image projection is a Resampler (it reads hidden states [n, T, E], not one embedding per image)"""
+        rc = self.lib.ladi_unet_ip_adapter_is_plus(self.h)
+        if rc < 0:
+            raise NativeError("ladi_unet_ip_adapter_is_plus failed: " + _lib.last_error())
+        return bool(rc)
 
     def set_ip_adapter_scale(self, scale):
         """diffusers' set_ip_adapter_scale: a number (every transformer block), or a dict / list of (name, scale) in the block names of
@@ -318,8 +328,9 @@ class NativeUNet(_Base):
         return [float(out[i]) for i in range(n)]
 
     def set_ip_context(self, embeds=None, tokens=None):
-        """the image context of the following forwards: embeds [n, E] (or [n, 1, E]) through the adapter's projection, or finished tokens
-        [n, N, cross_dim]; both None: none.  The same tensor object passed again unmodified is not uploaded again."""
+        """the image context of the following forwards: embeds [n, E] (or [n, 1, E]) through the adapter's projection -- with a Plus adapter
+        hidden states [n, T, E] through its Resampler (ladi_unet_set_ip_context_seq) --, or finished tokens [n, N, cross_dim]; both None:
+        none.  The same tensor object passed again unmodified is not uploaded again."""
         if embeds is not None and tokens is not None:
             raise ValueError("`ip_image_embeds` and `ip_tokens` cannot both be given.")
         t = embeds if embeds is not None else tokens
@@ -334,7 +345,13 @@ class NativeUNet(_Base):
         key = (id(t), t._version, embeds is not None)
         if self._ip_key == key and self._ip_keepalive is not None and self._ip_keepalive[0] is t:
             return
-        if embeds is not None:
+        if embeds is not None and self.ip_adapter_is_plus:
+            if embeds.dim() != 3 or embeds.shape[1] < 1 or embeds.shape[2] != info[1]:
+                raise ValueError("ip_image_embeds has shape %s, but the loaded adapter is a Plus adapter: expected hidden states [n, T, %d] "
+                                 "(the image encoder's hidden_states[-2])" % (tuple(embeds.shape), info[1]))
+            e = embeds.to(device=self.device, dtype=torch.float16).contiguous()
+            check(self.lib.ladi_unet_set_ip_context_seq(self.h, ptr(e), e.shape[0], e.shape[1], stream_ptr()), "ladi_unet_set_ip_context_seq")
+        elif embeds is not None:
             e = embeds[:, 0] if embeds.dim() == 3 and embeds.shape[1] == 1 else embeds
             if e.dim() != 2 or e.shape[1] != info[1]:
                 raise ValueError("ip_image_embeds has shape %s, expected [n, %d] (the loaded adapter's embedding width)" % (tuple(embeds.shape), info[1]))

@@ -281,9 +281,10 @@ def numpy_to_pil(images):
 
 class StableDiffusionTryOnePipeline:
     def __init__(self, vae, text_encoder, tokenizer, unet, scheduler, safety_checker=None, feature_extractor=None,
-                 requires_safety_checker=False, emasc=None, emasc_int_layers=None):
+                 requires_safety_checker=False, emasc=None, emasc_int_layers=None, image_encoder=None):
         self.vae, self.text_encoder, self.tokenizer, self.unet, self.scheduler = vae, text_encoder, tokenizer, unet, scheduler
         self.emasc, self.emasc_int_layers = emasc, emasc_int_layers
+        self.image_encoder = image_encoder      # NativeCLIPVisionEncoder (or None): encodes `ip_adapter_image` (encode_image)
         if getattr(scheduler.config, "steps_offset", 1) != 1:
             scheduler.config.steps_offset = 1          # tryon_pipe.py:74-86
         if getattr(scheduler.config, "skip_prk_steps", True) is False:
@@ -393,10 +394,11 @@ class StableDiffusionTryOnePipeline:
             raise ValueError("`%s` needs the native UNet (NativeUNet), the pipeline holds %s." % (what, type(self.unet).__name__))
         return self.unet
 
-    def load_ip_adapter(self, state_dict_or_path):
-        """diffusers' pipe.load_ip_adapter for the plain adapter: a state dict in diffusers' {"image_proj", "ip_adapter"} layout or a path
-        to one (ip_adapter.load_state).  The picture itself is not encoded here: pass `ip_adapter_image_embeds` to the call."""
-        self._ip_unet("load_ip_adapter").load_ip_adapter(state_dict_or_path)
+    def load_ip_adapter(self, state_dict_or_path, image_proj_dim_head=64):
+        """diffusers' pipe.load_ip_adapter for the plain and the Plus adapter: a state dict in diffusers' {"image_proj", "ip_adapter"} layout
+        or a path to one (ip_adapter.load_state).  A Plus file's Resampler is loaded with it (heads of image_proj_dim_head).  The call then
+        takes the picture itself (`ip_adapter_image`, encoded by `pipe.image_encoder`) or `ip_adapter_image_embeds`."""
+        self._ip_unet("load_ip_adapter").load_ip_adapter(state_dict_or_path, image_proj_dim_head)
 
     def unload_ip_adapter(self):
         self._ip_unet("unload_ip_adapter").unload_ip_adapter()
@@ -404,6 +406,59 @@ class StableDiffusionTryOnePipeline:
     def set_ip_adapter_scale(self, scale):
         """a number, or per-block scales as a dict / list in the names of set_pag_applied_layers (NativeUNet.set_ip_adapter_scale)"""
         self._ip_unet("set_ip_adapter_scale").set_ip_adapter_scale(scale)
+
+    @property
+    def image_encoder(self):
+        """the vision encoder that turns `ip_adapter_image` into the adapter's input (NativeCLIPVisionEncoder; with `visual_projection.weight`
+        in its weights for a plain adapter).  Settable; a new encoder drops the cached unconditional hidden states."""
+        return getattr(self, "_image_encoder", None)
+
+    @image_encoder.setter
+    def image_encoder(self, enc):
+        self._image_encoder = enc
+        self._ip_uncond = None       # hidden_states[-2] of the zero pixel_values, one sample, computed on first use (encode_image)
+
+    @staticmethod
+    def _ip_image_tensor(image):
+        """[B, 3, H, W] in [-1, 1] as it is; a PIL image or a list of PIL images of one size -> that layout, float32 (host arithmetic only)"""
+        if isinstance(image, torch.Tensor):
+            if image.dim() != 4 or image.shape[1] != 3:
+                raise ValueError("`ip_adapter_image` has shape %s, expected [B, 3, H, W] in [-1, 1] (or PIL images)." % (tuple(image.shape),))
+            return image
+        import numpy as np
+        ims = list(image) if isinstance(image, (list, tuple)) else [image]
+        if not ims or not all(hasattr(im, "convert") for im in ims):
+            raise ValueError("`ip_adapter_image` has to be a [B, 3, H, W] tensor in [-1, 1], a PIL image or a list of PIL images.")
+        arr = [np.asarray(im.convert("RGB"), dtype=np.float32) for im in ims]
+        if any(a.shape != arr[0].shape for a in arr):
+            raise ValueError("the PIL images of `ip_adapter_image` have different sizes; resize them to one size first.")
+        return torch.from_numpy(np.stack(arr)).permute(0, 3, 1, 2) / 127.5 - 1.0
+
+    def encode_image(self, image, output_hidden_states=None):
+        """diffusers' encode_image: -> (cond, uncond), what `ip_adapter_image_embeds` / `negative_ip_adapter_image_embeds` take.
+        image: [B, 3, H, W] in [-1, 1] or PIL images.  It goes through warp.clip_preprocess at the encoder's image_size with the CLIP mean and
+        std: the whole picture is resized (antialiased) to the square -- the pre-processing the reference applies to the in-shop cloth for
+        the inversion adapter, NOT CLIPImageProcessor's shortest-edge resize plus centre crop.
+        output_hidden_states (default: the loaded adapter is a Plus adapter): False -> cond = image_embeds [B, projection_dim], uncond =
+        zeros_like (a plain adapter's input); True -> cond = hidden_states[-2] [B, T, hidden], uncond = hidden_states[-2] of zero
+        pixel_values, computed for one sample once per encoder, cached on the pipeline and broadcast (a Plus adapter's input)."""
+        enc = self.image_encoder
+        if enc is None:
+            raise ValueError("`encode_image` needs `pipe.image_encoder` (NativeCLIPVisionEncoder).")
+        if output_hidden_states is None:
+            output_hidden_states = bool(getattr(self.unet, "ip_adapter_is_plus", False))
+        if not output_hidden_states and not getattr(enc, "projection_dim", 0):
+            raise ValueError("`pipe.image_encoder` has no visual_projection (its weights lack visual_projection.weight): it cannot produce "
+                             "image_embeds for a plain IP-Adapter.")
+        from .warp import clip_preprocess
+        px = clip_preprocess(self._ip_image_tensor(image), enc.cfg["image_size"])
+        out = enc(px, output_hidden_states=bool(output_hidden_states))
+        if not output_hidden_states:
+            return out.image_embeds, torch.zeros_like(out.image_embeds)
+        if getattr(self, "_ip_uncond", None) is None:
+            self._ip_uncond = enc(torch.zeros_like(px[:1]), output_hidden_states=True).hidden_states[-2]
+        cond = out.hidden_states[-2]
+        return cond, self._ip_uncond.expand(cond.shape[0], -1, -1)
 
     @property
     def shallow_evals(self):
@@ -533,7 +588,7 @@ class StableDiffusionTryOnePipeline:
                  callback_steps=1, cloth_cond_rate=1.0, no_pose=False, cloth_input_type="warped", fused=True, noise=None,
                  use_graph=True, guidance_rescale=0.0, strength=1.0, init_image=None, init_latents=None, init_is_noisy=False,
                  feature_cache=None, preserve_unmasked=None, mask_feather=0.0, pag_scale=0.0, pag_adaptive_scale=0.0,
-                 ip_adapter_image_embeds=None, negative_ip_adapter_image_embeds=None, sag_scale=0.0):
+                 ip_adapter_image_embeds=None, negative_ip_adapter_image_embeds=None, sag_scale=0.0, ip_adapter_image=None):
         """tryon_pipe.py's __call__.  `guidance_scale`: a float, a sequence with one scale per evaluation (len(scheduler.timesteps); PNDM: steps
         + 1) or a callable f(i, n_evals) -- see guidance_interval.  Classifier-free guidance is on if any scale is > 1; an evaluation whose scale
         is <= 1 then runs the UNet over the conditional samples only.  `guidance_rescale` (rescale_noise_cfg's phi, [0, 1]) acts on the CFG
@@ -583,7 +638,11 @@ class StableDiffusionTryOnePipeline:
         `ip_adapter_image_embeds` is the image prompt of a loaded IP-Adapter (load_ip_adapter): [B, E] or [B, 1, E] image embeddings, or
         diffusers' one-element list holding [2B, 1, E] with the negatives first.  `negative_ip_adapter_image_embeds` defaults to zeros.  Every
         cross-attention then adds scale * softmax(q k_ip^T / 8) v_ip over the projected image tokens (set_ip_adapter_scale; fused and modular
-        path alike).  None is the plain run; a raw `ip_adapter_image` is not taken (this package's vision encoder has no visual_projection).
+        path alike).  With a Plus adapter the embeddings are hidden states of the image encoder, [B, T, E], or the one-element list holding
+        [2B, T, E] with the negatives first.  `ip_adapter_image` is the picture itself instead ([B, 3, H, W] in [-1, 1] or PIL images, one per
+        sample of the batch): `pipe.image_encoder` encodes it (encode_image: whole-picture resize, not a centre crop) into what the loaded
+        adapter takes -- image_embeds for a plain adapter, whose encoder needs a visual_projection of the adapter's width, hidden_states[-2]
+        for a Plus adapter.  It cannot be combined with `ip_adapter_image_embeds`.  None for both is the plain run.
 
         `sag_scale` > 0 is self-attention guidance (diffusers StableDiffusionSAGPipeline, whose default is 0.75): every evaluation reads the
         self-attention map of the mid block, blurs the regions of its own x0 estimate that receive more than average attention (9 x 9
@@ -652,14 +711,39 @@ class StableDiffusionTryOnePipeline:
         pe, neg = self._encode_prompt(prompt, device, num_images_per_prompt, do_cfg, negative_prompt, prompt_embeds, negative_prompt_embeds)
         B = pe.shape[0]
         ip = None
-        if ip_adapter_image_embeds is not None:
+        if ip_adapter_image is not None:
+            # every refusal comes before the encoder runs: nothing is launched for a call that is not going to happen
+            if ip_adapter_image_embeds is not None or negative_ip_adapter_image_embeds is not None:
+                raise ValueError("Cannot forward both `ip_adapter_image` and `ip_adapter_image_embeds` / `negative_ip_adapter_image_embeds`.")
+            ip_unet = self._ip_unet("ip_adapter_image")
+            info = ip_unet.ip_adapter_info
+            if info is None:
+                raise ValueError("`ip_adapter_image` needs a loaded IP-Adapter (load_ip_adapter).")
+            enc = self.image_encoder
+            if enc is None:
+                raise ValueError("`ip_adapter_image` needs `pipe.image_encoder` (NativeCLIPVisionEncoder) to encode the picture.")
+            plus = ip_unet.ip_adapter_is_plus
+            if plus and enc.cfg["hidden"] != info[1]:
+                raise ValueError("`pipe.image_encoder` has hidden states of width %d, the loaded Plus adapter takes %d." % (enc.cfg["hidden"], info[1]))
+            if not plus and not getattr(enc, "projection_dim", 0):
+                raise ValueError("`pipe.image_encoder` has no visual_projection (its weights lack visual_projection.weight), which the loaded "
+                                 "plain IP-Adapter needs: it takes image_embeds.")
+            if not plus and enc.projection_dim != info[1]:
+                raise ValueError("`pipe.image_encoder` projects to %d, the loaded adapter takes embeddings of width %d." % (enc.projection_dim, info[1]))
+            picture = self._ip_image_tensor(ip_adapter_image)
+            if picture.shape[0] != B:
+                raise ValueError("`ip_adapter_image` has batch %d, the prompt embeddings have %d." % (picture.shape[0], B))
+            ip = tuple(t.to(device=device, dtype=torch.float16).contiguous() for t in self.encode_image(picture, plus))
+        elif ip_adapter_image_embeds is not None:
             from . import ip_adapter
-            info = self._ip_unet("ip_adapter_image_embeds").ip_adapter_info
+            ip_unet = self._ip_unet("ip_adapter_image_embeds")
+            info = ip_unet.ip_adapter_info
             if info is None:
                 raise ValueError("`ip_adapter_image_embeds` needs a loaded IP-Adapter (load_ip_adapter).")
-            ip_pos, ip_neg = ip_adapter.split_embeds(ip_adapter_image_embeds, negative_ip_adapter_image_embeds, B, do_cfg)
-            if ip_pos.shape[1] != info[1]:
-                raise ValueError("`ip_adapter_image_embeds` has width %d, the loaded adapter takes %d." % (ip_pos.shape[1], info[1]))
+            ip_pos, ip_neg = ip_adapter.split_embeds(ip_adapter_image_embeds, negative_ip_adapter_image_embeds, B, do_cfg,
+                                                     seq=ip_unet.ip_adapter_is_plus)
+            if ip_pos.shape[-1] != info[1]:
+                raise ValueError("`ip_adapter_image_embeds` has width %d, the loaded adapter takes %d." % (ip_pos.shape[-1], info[1]))
             ip_pos = ip_pos.to(device=device, dtype=torch.float16).contiguous()
             ip_neg = ip_neg.to(device=device, dtype=torch.float16).contiguous() if ip_neg is not None else torch.zeros_like(ip_pos)
             ip = (ip_pos, ip_neg)
@@ -746,7 +830,8 @@ class StableDiffusionTryOnePipeline:
                    use_graph, return_device=False, out_uint8=False, lanes=None, step_noise=None, eta=0.0, callback=None, callback_steps=1,
                    guidance_table=None, guidance_rescale=0.0, init_latents=None, first_step=0, init_is_noisy=False, feature_cache=None,
                    preserve=None, pag_table=None, ip=None, sag_scale=0.0):
-        """ip: (embeds, negative embeds), fp16 [B, E] device tensors each (ladi_tryon_set_ip_adapter); None = no image prompt.
+        """ip: (embeds, negative embeds), fp16 [B, E] device tensors each (ladi_tryon_set_ip_adapter), or [B, T, E] hidden states for a Plus
+        adapter (ladi_tryon_set_ip_adapter_seq); None = no image prompt.
         return_device: hand back the device tensor (no host copy); out_uint8: the batch as uint8 [B,H,W,3] = numpy_to_pil's
         (images * 255).round() computed by the decode epilogue (ladi_tryon_run_u8); lanes: sample-group lanes of the UNet forward;
         step_noise: fp32 [steps, B, 4, h, w], the per-step noise of EulerAncestralDiscreteScheduler and of DDIM with eta > 0
@@ -858,9 +943,13 @@ class StableDiffusionTryOnePipeline:
         check(lib.ladi_tryon_set_preserve(self._tryon, int(p_bits), float(p_sigma)), "ladi_tryon_set_preserve")
         if ip is not None:
             for t in ip:
-                if t.dim() != 2 or t.shape[0] != B or t.dtype != torch.float16 or not t.is_contiguous():
-                    raise ValueError("image embeddings have shape %s (%s), expected a contiguous fp16 [%d, E]" % (tuple(t.shape), t.dtype, B))
-            check(lib.ladi_tryon_set_ip_adapter(self._tryon, ptr(ip[0]), ptr(ip[1])), "ladi_tryon_set_ip_adapter")
+                if t.dim() not in (2, 3) or t.shape != ip[0].shape or t.shape[0] != B or t.dtype != torch.float16 or not t.is_contiguous():
+                    raise ValueError("image embeddings have shape %s (%s), expected a contiguous fp16 [%d, E] (Plus adapter: [%d, T, E])"
+                                     % (tuple(t.shape), t.dtype, B, B))
+            if ip[0].dim() == 3:      # hidden states of a Plus adapter: the run puts them through the UNet's Resampler
+                check(lib.ladi_tryon_set_ip_adapter_seq(self._tryon, ptr(ip[0]), ptr(ip[1]), int(ip[0].shape[1])), "ladi_tryon_set_ip_adapter_seq")
+            else:
+                check(lib.ladi_tryon_set_ip_adapter(self._tryon, ptr(ip[0]), ptr(ip[1])), "ladi_tryon_set_ip_adapter")
         else:
             check(lib.ladi_tryon_set_ip_adapter(self._tryon, None, None), "ladi_tryon_set_ip_adapter")
         self._shallow_evals = None
